@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the I/Q STFT -> RGBA hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--no-cpu-baseline] [--rotate K]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
+                    [--no-cpu-baseline] [--rotate K]
 
 A "step" is one pass of the hot path (sp_plan_execute: ONE kernel, the frame loop, which also produces the side outputs) over one
 capture of synthetic I/Q that is already resident in HBM, producing the RGBA image, both histograms, the gauges and the dBfs range
@@ -12,7 +13,10 @@ own slice scheme, lib/spectroplot.js:1206-1228) and the per-slice histograms / d
 (an RCCL all-gather of the records per batch of renders + sp_merge_replies) inside the timed region; the RGBA strips stay resident on their GPUs (see DESIGN.md "Multi-GPU") and the
 gather of the strips to rank 0 is timed separately and reported as extra fields.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`);
+everything else this file measures or checks - the rocprofv3 child runs and the roofline, the steady-clock leg, the rotating-buffers
+and two-requests-in-flight legs, the histogram check, the CPU baseline, the Node drop-in leg, the strip gather of N > 1 - runs with
+--full only.  --dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs below).
 """
 import argparse
 import json
@@ -151,7 +155,7 @@ def rocprof_kernel_us(argv_config):
     try:
         env = dict(os.environ, TMPDIR="/tmp")
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "400", "--warmup", "100", "--no-cpu-baseline", "--no-e2e", "--no-rocprof", "--no-extras"] + argv_config
+               "--steps", "400", "--warmup", "100", "--full", "--no-cpu-baseline", "--no-e2e", "--no-rocprof", "--no-extras"] + argv_config
         # (its own process group: on a timeout the profiler AND the python below it go, nothing keeps the GPU busy behind our back)
         child_out = os.path.join(d, "child_stdout.txt")
         with open(child_out, "w") as fh:
@@ -221,7 +225,7 @@ def rocprof_hbm_bytes(argv_config):
         try:
             env = dict(os.environ, TMPDIR="/tmp")
             cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "40", "--warmup", "1000", "--no-cpu-baseline", "--no-e2e", "--no-rocprof", "--no-extras"] + argv_config
+                   "--steps", "40", "--warmup", "1000", "--full", "--no-cpu-baseline", "--no-e2e", "--no-rocprof", "--no-extras"] + argv_config
             child = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
                 child.wait(timeout=300)
@@ -289,6 +293,42 @@ def launch_ranks(argv, gpus):
     return subprocess.call(cmd)
 
 
+DUMP_RGBA_PIXELS = 2 << 20    # RGBA pixels drawn for --dump-outputs (fewer after de-duplication): 32 MiB of float32 + 16 MiB of indices
+DUMP_SEED = 0x5EED0D0D
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, rgba, gauges, record, L, W):
+    """--dump-outputs: the reply of one render as the caller of sp_plan_execute receives it, written as DIR/<name>.npy.
+
+    rgba (uint8 device tensor, None with --no-rgba) is sampled: `rgba_sample` [k, 4] float32 holds the pixels at `rgba_sample_index`
+    (float64, pixel index into the image in memory order), drawn by a fixed seed from the image's pixel count, so that two runs with
+    the same arguments compare pixel for pixel.  gauge_mins / gauge_maxs / gauge_amps [W] float32 from `gauges` (uint8 [3 W]); c_hist
+    [L], cB_hist [1000], dBfs_min [1], dBfs_max [1] float64 from `record` (int64 [L + 1000 + 2], the range as f64 bits)."""
+    import numpy as np
+    import torch
+    arrays = {}
+    if rgba is not None:
+        npix = rgba.numel() // 4
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, npix, DUMP_RGBA_PIXELS)) if npix > DUMP_RGBA_PIXELS else np.arange(npix)
+        pix = rgba.view(npix, 4)[torch.from_numpy(idx).to(rgba.device)]
+        arrays["rgba_sample"] = pix.float().cpu().numpy()
+        arrays["rgba_sample_index"] = idx.astype(np.float64)
+    g = gauges.cpu().numpy().astype(np.float32)
+    arrays.update(gauge_mins=g[:W], gauge_maxs=g[W:2 * W], gauge_amps=g[2 * W:3 * W])
+    rec = record.cpu()
+    arrays.update(c_hist=rec[:L].numpy().astype(np.float64), cB_hist=rec[L:L + 1000].numpy().astype(np.float64))
+    mm = rec[L + 1000:L + 1002].view(torch.float64).numpy()
+    arrays.update(dBfs_min=mm[:1].copy(), dBfs_max=mm[1:2].copy())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,7 +338,7 @@ def main():
                          "--steps steps right after --warmup steps of the fresh process, nothing in between)")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--gather", action="store_true", help="(default when N > 1) also time the RCCL gather of the RGBA strips to rank 0")
+    ap.add_argument("--gather", action="store_true", help="(default with --full when N > 1) also time the RCCL gather of the RGBA strips to rank 0")
     ap.add_argument("--no-gather", action="store_true", help="skip the strip gather")
     ap.add_argument("--no-e2e", action="store_true", help="skip the Node drop-in leg")
     ap.add_argument("--no-rocprof", action="store_true", help="skip the rocprofv3 child run that times the dominant kernel (N = 1)")
@@ -324,6 +364,12 @@ def main():
     ap.add_argument("--channel-mode", action="store_true", help="the reference's L/R split (channelMode: lib/fft_nayuki.js:103-119); not a BASELINE config")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure the kernel's HBM traffic (N = 1)")
     ap.add_argument("--no-extras", action="store_true", help="skip the rotating-buffers and two-requests-in-flight legs (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else: rocprofv3 child runs and roofline, steady-clock leg, rotating-buffers and "
+                         "two-in-flight legs, histogram check, CPU baseline, Node drop-in leg, strip gather (N > 1); the --no-* options "
+                         "leave out parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -331,7 +377,7 @@ def main():
 
     # dominant kernel's duration as rocprofv3 reports it: a short child run of this command, before this process touches the GPU
     prof = prof_rot = pmc = None
-    if args.gpus == 1 and not args.no_rocprof and "WORLD_SIZE" not in os.environ:
+    if args.full and args.gpus == 1 and not args.no_rocprof and "WORLD_SIZE" not in os.environ:
         shape = ["--config", args.config, "--kernel", args.kernel] + (["--waterfall"] if args.waterfall else []) + (["--no-rgba"] if args.no_rgba else []) + (["--channel-mode"] if args.channel_mode else [])
         prof = rocprof_kernel_us(shape + (["--rotate-all", "--rotate", str(args.rotate)] if args.rotate_all else []))
         if args.rotate >= 2 and not args.rotate_all and not args.no_extras:
@@ -488,6 +534,40 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    stride_eff = min((S - n) / (W - 1), n)
+    frames_per_s = world * W * args.steps / dt
+    head = {
+        "metric": "STFT frames/sec (N=1024 cf32) + IQ MSamples/s end-to-end to RGBA" if args.config == "cfg2"
+                  else "STFT frames/sec (%s)" % desc,
+        "value": frames_per_s, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "cold": cold,
+        "value_is": "--steps steps right after --warmup steps of a fresh process (%s --warmup %d), nothing in between"
+                    % ("the caller's" if warmup_given else "default", args.warmup),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": desc + ", gain 6, range 30, spectrogram layout, %d frames per GPU" % W + (", L/R split (channelMode)" if args.channel_mode else "")
+                               + (", %d capture / image sets in rotation" % len(rot_sets) if rot_sets else ""), "format": fmt, "n": n,
+                   "samples_per_gpu": S, "frames_per_gpu": W, "window": window, "cmap": cmap,
+                   "sharding": "contiguous time slice per GPU" if world > 1 else "single GPU",
+                   "butterfly_graph": "the reference's radix-2 DIT graph (lib/fft_nayuki.js:54-96) in f64 without fused multiply-adds, executed "
+                                      "as 16-point register passes with LDS / register re-distribution between them (not a Stockham "
+                                      "re-factorisation: any other factorisation changes the rounding and with it RGBA bytes)",
+                   "generator": "trinoise seed=0x%08X step=%d gshift=%d amp=%g namp=%g" % (GEN["seed"], GEN["step"], GEN["gshift"], GEN["amp"], GEN["namp"])},
+        "msamples_per_s": frames_per_s * stride_eff / 1e6,
+        "kernel": plan.kernel_name(),
+        "renders_per_collective": M if dist is not None else None,
+    }
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs (with --rotate-all: the set it rendered into), before anything below renders again
+        last_rgba = rot_sets[(rot_k[0] - 1) % len(rot_sets)][1] if rot_sets is not None else rgba
+        head["dumped_outputs"] = dump_outputs(args.dump_outputs, None if args.no_rgba else last_rgba, gauges, batcher.final_record(), L, W)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        plan.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # the steady figure (an extra): where the warm-up was shorter than the spin-up, the same --steps again after the rest of it
     dt_steady, steady_after, steady_leg = dt, args.warmup, False
     if args.warmup < spinup:
@@ -673,11 +753,9 @@ def main():
         ranks_seen = {"world_size": dist.get_world_size(), "backend": args.backend, "ranks": seen,
                       "distinct_devices": len({(r["pci_bus_id"], r["uuid"]) for r in seen})}
 
-    stride_eff = min((S - n) / (W - 1), n)
     bytes_per_frame = sw * stride_eff + 4 * n + 3                 # unique input bytes + RGBA + 3 gauge bytes
     algo_bytes = bytes_per_frame * W
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-    frames_per_s = world * W * args.steps / dt
 
     traffic, traffic_source = None, None
     if pmc:
@@ -699,29 +777,11 @@ def main():
     leans = bool(achieved_rot) and (rotating["ratio"] > 1.02 or rotating["step_ratio"] > 1.02) and not rot_sets
     achieved_head = achieved_rot if leans else achieved
     if rank == 0:
-        out = {
-            "metric": "STFT frames/sec (N=1024 cf32) + IQ MSamples/s end-to-end to RGBA" if args.config == "cfg2"
-                      else "STFT frames/sec (%s)" % desc,
-            "value": frames_per_s, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "cold": cold,
-            "value_is": "--steps steps right after --warmup steps of a fresh process (%s --warmup %d), nothing in between"
-                        % ("the caller's" if warmup_given else "default", args.warmup),
+        out = dict(head, **{
             "value_steady": world * W * args.steps / dt_steady, "ms_per_step_steady": dt_steady / args.steps * 1e3,
             "value_steady_note": ("the same --steps steps again once the process had run %d steps (the clock spin-up of this configuration: "
                                   "%d steps + 200): the shader clock no longer ramps" % (steady_after, spinup)) if steady_leg
                                  else "the warm-up covered the clock spin-up of this configuration (%d steps): value_steady is value" % spinup,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": desc + ", gain 6, range 30, spectrogram layout, %d frames per GPU" % W + (", L/R split (channelMode)" if args.channel_mode else "")
-                                   + (", %d capture / image sets in rotation" % len(rot_sets) if rot_sets else ""), "format": fmt, "n": n,
-                       "samples_per_gpu": S, "frames_per_gpu": W, "window": window, "cmap": cmap,
-                       "sharding": "contiguous time slice per GPU" if world > 1 else "single GPU",
-                       "butterfly_graph": "the reference's radix-2 DIT graph (lib/fft_nayuki.js:54-96) in f64 without fused multiply-adds, executed "
-                                          "as 16-point register passes with LDS / register re-distribution between them (not a Stockham "
-                                          "re-factorisation: any other factorisation changes the rounding and with it RGBA bytes)",
-                       "generator": "trinoise seed=0x%08X step=%d gshift=%d amp=%g namp=%g" % (GEN["seed"], GEN["step"], GEN["gshift"], GEN["amp"], GEN["namp"])},
-            "msamples_per_s": frames_per_s * stride_eff / 1e6,
-            "kernel": plan.kernel_name(),
             "roofline": {"bound": "hbm", "achieved": achieved_head, "peak": 8000.0, "unit": "GB/s", "frac": achieved_head / 8000.0, "traffic": traffic,
                          "traffic_source": traffic_source,
                          "frac_basis": ("kernel duration over %d capture / image sets in rotation (%.0f MiB: streams through HBM); the one-set loop "
@@ -742,9 +802,8 @@ def main():
             "value_two_in_flight": two_in_flight.get("value_two_in_flight") if two_in_flight else None,
             "two_in_flight": two_in_flight,
             "checks": {"c_hist_sum": hsum, "expected": world * W * n},
-            "renders_per_collective": M if dist is not None else None,
             "rccl_ranks_seen": ranks_seen,
-        }
+        })
         if gather_ms is not None:
             out["rgba_gather_ms"] = gather_ms
             out["rgba_gather_GBps"] = (world - 1) * rgba.numel() / (gather_ms * 1e-3) / 1e9

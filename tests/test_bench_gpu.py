@@ -1,5 +1,6 @@
-"""bench.py's own contract on the GPU box: one JSON line with the roofline object, and the N > 1 path (ranks sharing the one GPU of
-the test box, gloo for the collectives) with a batch size that does not divide the step count."""
+"""bench.py's own contract on an MI355X: a plain run prints the headline alone and --dump-outputs writes the last step's reply; with
+--full, one JSON line with the roofline object, and the N > 1 path (ranks sharing the one GPU of the test machine, gloo for the
+collectives) with a batch size that does not divide the step count."""
 import json
 import os
 import signal
@@ -38,7 +39,7 @@ def run_bench(*argv):
 
 
 def test_single_gpu_line_has_roofline_and_checks():
-    d = run_bench("--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-e2e")
+    d = run_bench("--full", "--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-e2e")
     assert d["n_gpus"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "f64" and d["kernel"] == "frames"
     assert d["checks"]["c_hist_sum"] == d["checks"]["expected"] == 16384 * 1024
     r = d["roofline"]
@@ -82,7 +83,7 @@ def test_single_gpu_line_has_roofline_and_checks():
 
 @pytest.mark.parametrize("merge_every,per_render", [(1, False), (3, False), (3, True)], ids=["every_render", "batches_of_3", "batches_of_3_merged_per_render"])
 def test_two_ranks_on_one_gpu_merge_every_render(merge_every, per_render):
-    d = run_bench("--gpus", "2", "--oversubscribe", "--backend", "gloo", "--steps", "20", "--warmup", "5", "--merge-every", str(merge_every),
+    d = run_bench("--full", "--gpus", "2", "--oversubscribe", "--backend", "gloo", "--steps", "20", "--warmup", "5", "--merge-every", str(merge_every),
                   *(["--merge-per-render"] if per_render else []))
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["renders_per_collective"] == merge_every
     assert d["checks"]["c_hist_sum"] == d["checks"]["expected"] == 2 * 16384 * 1024      # the LAST render's merged histogram
@@ -93,8 +94,28 @@ def test_two_ranks_on_one_gpu_merge_every_render(merge_every, per_render):
 
 def test_one_rank_rccl_group_runs_the_collectives():
     """The N > 1 path's collectives through the nccl backend (RCCL) with a one-rank group: all the box has is one GPU."""
-    d = run_bench("--force-dist", "--steps", "40", "--warmup", "5", "--merge-every", "16", "--no-cpu-baseline", "--no-e2e", "--no-rocprof")
+    d = run_bench("--full", "--force-dist", "--steps", "40", "--warmup", "5", "--merge-every", "16", "--no-cpu-baseline", "--no-e2e", "--no-rocprof")
     assert d["n_gpus"] == 1 and d["renders_per_collective"] == 16
     assert d["checks"]["c_hist_sum"] == d["checks"]["expected"] == 16384 * 1024
     assert d["rgba_gather_ms"] > 0
     assert d["rccl_ranks_seen"]["world_size"] == 1 and d["rccl_ranks_seen"]["backend"] == "nccl"
+
+
+@pytest.mark.parametrize("gpus", [1, 2], ids=["one_rank", "two_ranks_on_one_gpu"])
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path, gpus):
+    """Without --full: the headline alone, and --dump-outputs writes the last timed step's reply (the merged side outputs for N > 1)."""
+    import numpy as np
+    dump = str(tmp_path / "out")
+    extra = ["--gpus", "2", "--oversubscribe", "--backend", "gloo"] if gpus == 2 else []
+    d = run_bench(*extra, "--steps", "20", "--warmup", "5", "--dump-outputs", dump)
+    assert d["n_gpus"] == gpus and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "frames/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and abs(d["value"] - gpus * 16384 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "roofline_valu", "checks", "value_steady", "two_in_flight", "cpu_baseline", "e2e", "rgba_gather_ms"} & set(d)
+    names = sorted(f[:-4] for f in os.listdir(dump))
+    assert names == d["dumped_outputs"] and "rgba_sample" in names and "c_hist" in names
+    a = {k: np.load(os.path.join(dump, k + ".npy")) for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10**6
+    assert a["c_hist"].sum() == gpus * 16384 * 1024 and a["gauge_mins"].shape == (16384,)
+    assert a["rgba_sample"].shape[1] == 4 and a["rgba_sample"].min() >= 0 and a["rgba_sample"].max() <= 255
+    assert a["dBfs_min"][0] <= a["dBfs_max"][0]
