@@ -170,9 +170,7 @@ int sp_render_strip(sp_context *ctx, const sp_request *req, const uint8_t *bytes
  * inside the capture uploads the frames' own samples only, as rows of pitched copies into a packed device buffer; every other request
  * uploads the capture as it is.  SPECTROPLOT_HIP_NO_PACKED_UPLOAD=1 turns the packed upload off.
  * A large request (>= 16 MiB of samples + image, width >= 1024) is pipelined in chunks of frames: 4, from 64 MiB 6, of UNEVEN size -
- * each 0.65 of its neighbour, shrinking towards the end of the longer transfer's direction.  SPECTROPLOT_HIP_RENDER_CHUNKS=2..16
- * overrides the count and SPECTROPLOT_HIP_CHUNK_RATIO=0.2..1 the ratio (1 = equal chunks); both are read once per process and neither
- * applies below that gate (the count also needs width >= 32 per chunk).
+ * each 0.65 of its neighbour, shrinking towards the end of the longer transfer's direction.
  */
 int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbytes);
 /*

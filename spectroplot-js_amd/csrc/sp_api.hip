@@ -87,7 +87,7 @@ struct sp_context {
     HostBuffer host_small;
     // sp_render's copy streams and events: the image goes back to the host chunk by chunk while later chunks still arrive
     hipStream_t copy_in = nullptr, copy_out = nullptr;
-    static constexpr int kMaxChunks = 16;
+    static constexpr int kMaxChunks = 6;
     hipEvent_t ev_arrived[kMaxChunks] = {}, ev_rendered[kMaxChunks] = {};
     sp_plan *cached_plan = nullptr;
     // sp_render_named: the names and numbers the cached plan was built from (empty: the cached plan came from arrays)
@@ -909,7 +909,7 @@ extern "C" int sp_merge_replies(sp_context *ctx, const void *d_records, int32_t 
 {
     if (!ctx || !d_records || count < 1 || lut_len < 1 || lut_len > SP_MAX_LUT) return SP_ERR_INVALID_ARG;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    const int total = lut_len + SP_CB_HIST_SIZE + 2;
+    const int total = (int)sphost::ReplyRecord{(size_t)lut_len, 0}.words();
     hipLaunchKernelGGL(k_merge_replies, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const unsigned long long *)d_records, (int)count, (int)lut_len, (size_t)total, (unsigned long long *)d_c_hist,
                        (unsigned long long *)d_cb_hist, d_dbfs_minmax);
@@ -922,12 +922,13 @@ extern "C" int sp_merge_replies_batch(sp_context *ctx, const void *d_gathered, i
     if (!ctx || !d_gathered || !d_merged || ranks < 1 || renders < 1 || renders > 65535 || lut_len < 1 || lut_len > SP_MAX_LUT)
         return SP_ERR_INVALID_ARG;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    const int total = lut_len + SP_CB_HIST_SIZE + 2;
-    unsigned long long *const out = (unsigned long long *)d_merged;
+    const sphost::ReplyRecord rec{(size_t)lut_len, 0};
+    const int total = (int)rec.words();
     // the merged records keep the record layout [c_hist | cB_hist | min, max]: the three outputs are one block, `total` words per render
+    const sp_reply m = rec.view(d_merged);
     hipLaunchKernelGGL(k_merge_replies, dim3((unsigned)((total + 255) / 256), (unsigned)renders), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)d_gathered, (int)ranks, (int)lut_len, (size_t)renders * (size_t)total, out, out + lut_len,
-                       (double *)(out + lut_len + SP_CB_HIST_SIZE));
+                       (const unsigned long long *)d_gathered, (int)ranks, (int)lut_len, (size_t)renders * (size_t)total,
+                       (unsigned long long *)m.c_hist, (unsigned long long *)m.cb_hist, m.dbfs_minmax);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -978,17 +979,6 @@ extern "C" int sp_place_strips(sp_context *ctx, uint8_t *d_image, const uint8_t 
 }
 
 // ------------------------------------------------------------------------------------------------- host-buffer render
-
-static bool same_request(const sp_plan *p, const sp_request *r)
-{
-    const sp_request &q = p->req;
-    if (q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall
-        || q.lut_len != r->lut_len)
-        return false;
-    if (memcmp(&q.block_norm, &r->block_norm, 8) || memcmp(&q.gain, &r->gain, 8) || memcmp(&q.range, &r->range, 8)) return false;
-    if (memcmp(p->window.data(), r->windowc, sizeof(double) * (size_t)r->n)) return false;
-    return memcmp(p->lut.data(), r->lut_rgb, 3 * (size_t)r->lut_len) == 0;
-}
 
 // ---- sparse requests: upload only what the frames read --------------------------------------------------------------------------------
 // With stride > n the reference's loop touches n samples per frame and skips the rest (lib/worker.js:50, 70-75) - its interactive shape:
@@ -1118,44 +1108,59 @@ static hipError_t upload_packed_chunk(const PackedChunk &ch, int n, int sample_w
     return e;
 }
 
-// How [0, width) is cut into chunks of frames for a request that moves in_est bytes of samples in and rgba_bytes of image out.
-static void chunk_bounds(int32_t width, size_t in_est, size_t rgba_bytes, bool chunkable, std::vector<int32_t> &bounds)
+// How [0, width) is cut into chunks of frames for a request that moves in_est bytes of samples in and out_bytes of image out.
+static void chunk_bounds(int32_t width, size_t in_est, size_t out_bytes, bool chunkable, std::vector<int32_t> &bounds)
 {
     int chunks = 1;
-    // SPECTROPLOT_HIP_RENDER_CHUNKS=k overrides the count (2 .. 16), SPECTROPLOT_HIP_CHUNK_RATIO=r the size of a chunk relative to
-    // its neighbour (0.2 .. 1; 1 = equal chunks); both read once
-    static const int env_chunks = getenv("SPECTROPLOT_HIP_RENDER_CHUNKS") ? atoi(getenv("SPECTROPLOT_HIP_RENDER_CHUNKS")) : 0;
-    static const double env_ratio = getenv("SPECTROPLOT_HIP_CHUNK_RATIO") ? atof(getenv("SPECTROPLOT_HIP_CHUNK_RATIO")) : 0.0;
-    const double ratio = env_ratio >= 0.2 && env_ratio <= 1.0 ? env_ratio : 0.65;
-    const bool uneven = ratio < 1.0;
-    if (chunkable && width >= 1024 && in_est + rgba_bytes >= ((size_t)16 << 20)) {
-        chunks = in_est + rgba_bytes >= ((size_t)64 << 20) ? 6 : 4;
-        if (env_chunks >= 2 && env_chunks <= sp_context::kMaxChunks && width >= 32 * env_chunks) chunks = env_chunks;
-    }
+    if (chunkable && width >= 1024 && in_est + out_bytes >= ((size_t)16 << 20)) chunks = in_est + out_bytes >= ((size_t)64 << 20) ? 6 : 4;
     // The busier direction of the link never pauses; what does not overlap it is one chunk's way in the other direction plus its
     // render: the LAST chunk's image when the samples are the longer transfer, the FIRST chunk's samples when the image is.  So the
     // chunks shrink (or grow) geometrically towards that end - each 0.65 of its neighbour, which also keeps the shorter direction
     // from falling behind - instead of being equal (measured, config 2: 8 equal chunks 2.73 ms, pure two-way copy 2.37 ms; every
     // additional copy call costs the link ~13 us, so few chunks).  Chunks end on multiples of 32 frames.
+    const bool in_heavy = in_est >= out_bytes;
+    double w[sp_context::kMaxChunks], sum = 0, acc = 0;
+    for (int k = 0; k < chunks; k++) sum += (w[k] = std::pow(0.65, in_heavy ? k : chunks - 1 - k));
     bounds.assign(1, 0);
-    if (chunks > 1 && uneven) {
-        const bool in_heavy = in_est >= rgba_bytes;
-        double w[sp_context::kMaxChunks], sum = 0, acc = 0;
-        for (int k = 0; k < chunks; k++) sum += (w[k] = std::pow(ratio, in_heavy ? k : chunks - 1 - k));
-        for (int k = 0; k + 1 < chunks; k++) {
-            acc += w[k];
-            const int32_t x = (int32_t)((int64_t)((double)width * acc / sum) & ~(int64_t)31);
-            if (x > bounds.back() && x < width) bounds.push_back(x);
-        }
-        bounds.push_back(width);
-    } else {
-        for (int k = 0; k < chunks; k++) {
-            const int32_t x = k + 1 == chunks ? width : (int32_t)(((int64_t)width * (k + 1) / chunks) & ~(int64_t)31);
-            if (x > bounds.back()) bounds.push_back(x);
-        }
-        if (bounds.back() != width) bounds.push_back(width);
+    for (int k = 0; k + 1 < chunks; k++) {
+        acc += w[k];
+        const int32_t x = (int32_t)((int64_t)((double)width * acc / sum) & ~(int64_t)31);
+        if (x > bounds.back() && x < width) bounds.push_back(x);
     }
-    if (bounds.size() < 2) bounds.push_back(width);   // (width = 0: one empty chunk, so that the reply still gets its initial values)
+    bounds.push_back(width);   // (width = 0: one empty chunk, so that the reply still gets its initial values)
+}
+
+// How a request's samples travel to the device: [0, width) cut into chunks of frames and, for a sparse request, every chunk's packed
+// layout.  packable: the plan's kernel can read a packed chunk; chunkable: the request may be pipelined; out_bytes: the image that
+// comes back over the link.
+struct UploadPlan {
+    bool packed = false;
+    double stride = 0;                   // samples between two frames' starts (lib/worker.js:50)
+    std::vector<int32_t> bounds;         // chunk k: frames [bounds[k], bounds[k + 1])
+    std::vector<PackedChunk> chunks;     // packed: chunk k's layout
+    size_t dev_bytes = 0, link_bytes = 0;   // the staging buffer it needs; what crosses the link
+};
+
+static void plan_upload(const spfmt::Format &f, int n, size_t nbytes, int32_t width, bool packable, bool chunkable, size_t out_bytes,
+                        UploadPlan &u)
+{
+    const double sample_count = (double)nbytes / (double)f.width;
+    u.stride = width > 1 ? (sample_count - (double)n) / (double)(width - 1) : 0.0;
+    const bool stride_ok = u.stride >= 0.0 && std::isfinite(u.stride) && 0.5 + u.stride * (double)(width - 1) < 2147483000.0;
+    // a sparse request (stride > n, every frame inside the capture) is cut by the bytes its frames read; if it cannot be packed after
+    // all, it is cut again by the whole capture
+    bool sparse = packable && stride_ok && width >= 2 && u.stride > (double)n
+                  && (size_t)(spjs::to_int32(0.5 + u.stride * (double)(width - 1)) + (int64_t)n) * (size_t)f.width <= nbytes;
+    for (;; sparse = false) {
+        chunk_bounds(width, sparse ? (size_t)width * (size_t)n * (size_t)f.width : nbytes, out_bytes, chunkable && stride_ok, u.bounds);
+        u.packed = sparse && build_packed_chunks(n, f.width, nbytes, width, u.stride, u.bounds, u.chunks, &u.dev_bytes, &u.link_bytes)
+                   && u.chunks.size() + 1 == u.bounds.size();
+        if (u.packed || !sparse) break;
+    }
+    if (u.packed) return;
+    u.chunks.clear();
+    u.dev_bytes = nbytes + 16;
+    u.link_bytes = nbytes;
 }
 
 // (tests) The upload plan sp_render would use for a request of this shape - pure host arithmetic, no device.  out[]: packed (0 / 1),
@@ -1165,32 +1170,14 @@ extern "C" int sp_debug_upload_plan(int32_t format, int32_t n, size_t nbytes, in
                                     size_t *used)
 {
     if (format < 0 || format >= SP_FMT_COUNT || n < 2 || width < 1 || !out || !used) return SP_ERR_INVALID_ARG;
-    const spfmt::Format f = spfmt::describe(format);
-    const double sample_count = (double)nbytes / (double)f.width;
-    const double stride = width > 1 ? (sample_count - (double)n) / (double)(width - 1) : 0.0;
-    const bool stride_ok = stride >= 0.0 && std::isfinite(stride) && 0.5 + stride * (double)(width - 1) < 2147483000.0;
-    const size_t rgba_bytes = 4 * (size_t)width * (size_t)n;
-    bool sparse = stride_ok && width >= 2 && stride > (double)n
-                  && (size_t)(spjs::to_int32(0.5 + stride * (double)(width - 1)) + (int64_t)n) * (size_t)f.width <= nbytes;
-    std::vector<PackedChunk> packed;
-    std::vector<int32_t> bounds;
-    size_t dev = 0, link = nbytes;
-    for (int attempt = sparse ? 0 : 1; attempt < 2; attempt++) {
-        chunk_bounds(width, attempt == 0 ? (size_t)width * (size_t)n * (size_t)f.width : nbytes, rgba_bytes, want_image && stride_ok, bounds);
-        if (attempt == 0) {
-            sparse = build_packed_chunks(n, f.width, nbytes, width, stride, bounds, packed, &dev, &link) && packed.size() + 1 == bounds.size();
-            if (sparse) break;
-            packed.clear();
-            dev = 0;
-            link = nbytes;
-        }
-    }
-    std::vector<int64_t> v{sparse ? 1 : 0, (int64_t)bounds.size() - 1, (int64_t)dev, (int64_t)link};
-    for (size_t c = 0; c + 1 < bounds.size(); c++) {
-        v.push_back(bounds[c]);
-        v.push_back(bounds[c + 1]);
-        if (!sparse) continue;
-        const PackedChunk &ch = packed[c];
+    UploadPlan u;
+    plan_upload(spfmt::describe(format), n, nbytes, width, true, want_image != 0, 4 * (size_t)width * (size_t)n, u);
+    std::vector<int64_t> v{u.packed ? 1 : 0, (int64_t)u.bounds.size() - 1, u.packed ? (int64_t)u.dev_bytes : 0, (int64_t)u.link_bytes};
+    for (size_t c = 0; c + 1 < u.bounds.size(); c++) {
+        v.push_back(u.bounds[c]);
+        v.push_back(u.bounds[c + 1]);
+        if (!u.packed) continue;
+        const PackedChunk &ch = u.chunks[c];
         int64_t bits;
         memcpy(&bits, &ch.stride2, 8);
         for (int64_t x : {ch.first, ch.F, ch.P, (int64_t)ch.dev_off, ch.pos2_x0, ch.pos2_last, bits, (int64_t)ch.blocks.size()}) v.push_back(x);
@@ -1201,6 +1188,22 @@ extern "C" int sp_debug_upload_plan(int32_t format, int32_t n, size_t nbytes, in
     if (v.size() > capacity) return SP_ERR_INVALID_ARG;
     memcpy(out, v.data(), v.size() * 8);
     return SP_OK;
+}
+
+// Frames [x0, x1) of the device image (`width` frames, rows 4 * width bytes apart) into the caller's image (rows host_pitch bytes
+// apart) on `stream`: one copy where the band is contiguous on both sides (a waterfall band: rows width-1-x; the whole width of
+// equally wide images), a pitched copy of columns x0 .. x1-1 of every row otherwise.
+static hipError_t download_band(uint8_t *host, size_t host_pitch, const uint8_t *dev, int32_t width, size_t n, bool waterfall, int32_t x0,
+                                int32_t x1, hipStream_t stream)
+{
+    const size_t W = (size_t)width;
+    if (waterfall) {
+        const size_t off = 4 * n * (W - (size_t)x1);
+        return hipMemcpyAsync(host + off, dev + off, 4 * n * (size_t)(x1 - x0), hipMemcpyDeviceToHost, stream);
+    }
+    if (x0 == 0 && x1 == width && host_pitch == 4 * W) return hipMemcpyAsync(host, dev, 4 * W * n, hipMemcpyDeviceToHost, stream);
+    return hipMemcpy2DAsync(host + 4 * (size_t)x0, host_pitch, dev + 4 * (size_t)x0, 4 * W, 4 * (size_t)(x1 - x0), n, hipMemcpyDeviceToHost,
+                            stream);
 }
 
 // sp_render / sp_render_strip / sp_plan_execute_from_host: the capture comes from HOST memory, in chunks of frames that travel while
@@ -1216,181 +1219,106 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     const sp_request *req = &plan->req;
     hipStream_t s = ctx->stream;
 
-    const size_t W = (size_t)width, n = (size_t)req->n, L = (size_t)req->lut_len;
+    const size_t W = (size_t)width, n = (size_t)req->n;
     const size_t rgba_bytes = 4 * W * n;
     const size_t host_pitch = req->waterfall ? 4 * n : 4 * (size_t)image_width;   // bytes between rows of the caller's image
+    const sphost::ReplyRecord rec{(size_t)req->lut_len, W};   // the small outputs, side by side on the device
     int rc = SP_OK;
-    // small outputs: [c_hist L u64][cb_hist 1000 u64][minmax 2 f64][gauges 3*W u8]
-    const size_t small_u64 = L + SP_CB_HIST_SIZE + 2;
-    DeviceBuffer &small = ctx->render_small;
-    const size_t small_bytes = small_u64 * 8 + 3 * W;
     sp_reply d = *reply;
     if (!device_out) {
         rc = ctx->out_rgba.reserve(rgba_bytes + 16);
-        if (!rc) rc = small.reserve(small_bytes + 16);
-        if (!rc) rc = ctx->host_small.reserve(small_bytes + 16);
+        if (!rc) rc = ctx->render_small.reserve(rec.bytes() + 16);
+        if (!rc) rc = ctx->host_small.reserve(rec.bytes() + 16);
         if (rc) return fail(ctx, rc, "sp_render: out of memory");
-        uint64_t *d_c = (uint64_t *)small.p, *d_cb = d_c + L;
-        double *d_mm = (double *)(d_cb + SP_CB_HIST_SIZE);
-        uint8_t *d_g = (uint8_t *)(d_mm + 2);
+        d = rec.view(ctx->render_small.p);
         d.rgba = reply->rgba ? (uint8_t *)ctx->out_rgba.p : nullptr;
-        d.gauge_mins = d_g;
-        d.gauge_maxs = d_g + W;
-        d.gauge_amps = d_g + 2 * W;
-        d.c_hist = d_c;
-        d.cb_hist = d_cb;
-        d.dbfs_minmax = d_mm;
     }
 
-    // Large requests are rendered in chunks of frames: chunk k's samples travel to the device while chunk k-1 is rendered and
-    // chunk k-2's part of the image travels back (PCIe is full duplex; the kernels are a few per cent of the copies).  Chunks end
-    // on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.
+    // Large requests are rendered in chunks of frames: chunk k's samples travel to the device on copy_in while chunk k-1 is rendered
+    // and chunk k-2's part of the image travels back on copy_out (PCIe is full duplex; the kernels are a few per cent of the copies).
+    // Chunks end on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.  A
+    // request of one chunk does everything on the context's stream.  A sparse request (the frame-loop kernel) uploads only the
+    // samples its frames read.
     const spfmt::Format f = spfmt::describe(req->format);
-    const double sample_count = (double)nbytes / (double)f.width;
-    const double stride = width > 1 ? (sample_count - (double)req->n) / (double)(width - 1) : 0.0;
-    const bool stride_ok = stride >= 0.0 && std::isfinite(stride) && 0.5 + stride * (double)(width - 1) < 2147483000.0;
-    // a sparse request (stride > n, every frame inside the capture, the frame-loop kernel): only the frames' own samples are uploaded
-    bool sparse = stride_ok && width >= 2 && stride > (double)req->n && plan_kernel(plan) == 3 && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD")
-                  && (size_t)(spjs::to_int32(0.5 + stride * (double)(width - 1)) + (int64_t)req->n) * (size_t)f.width <= nbytes;
-    std::vector<PackedChunk> packed;
-    std::vector<int32_t> bounds;
-    int chunks = 1;
-    size_t packed_dev_bytes = 0, packed_link_bytes = 0;
-    for (int attempt = sparse ? 0 : 1; attempt < 2; attempt++) {
-        const size_t in_est = attempt == 0 ? W * n * (size_t)f.width : nbytes;
-        // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
-        chunk_bounds(width, in_est, device_out ? 0 : rgba_bytes, (device_out || reply->rgba != nullptr) && stride_ok, bounds);
-        chunks = (int)bounds.size() - 1;
-        if (attempt == 0) {
-            sparse = build_packed_chunks(req->n, f.width, nbytes, width, stride, bounds, packed, &packed_dev_bytes, &packed_link_bytes)
-                     && (int)packed.size() == chunks;
-            if (sparse) break;
-            packed.clear();
-        }
-    }
-    ctx->last_upload_bytes = sparse ? packed_link_bytes : nbytes;
-    rc = ctx->in_bytes.reserve(sparse ? packed_dev_bytes : nbytes + 16);
+    UploadPlan u;
+    // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
+    plan_upload(f, req->n, nbytes, width, plan_kernel(plan) == 3 && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"), device_out || reply->rgba,
+                device_out ? 0 : rgba_bytes, u);
+    const int chunks = (int)u.bounds.size() - 1;
+    const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
+    ctx->last_upload_bytes = u.link_bytes;
+    rc = ctx->in_bytes.reserve(u.dev_bytes);
     if (rc) return fail(ctx, rc, "sp_render: out of memory");
+    uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
     hipError_t e = hipSuccess;
-    if (chunks > 1) {
+    if (overlap) {
         if (!ctx->copy_in) e = hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking);
         if (e == hipSuccess && !ctx->copy_out) e = hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking);
         for (int k = 0; k < chunks && e == hipSuccess; k++) {
             if (!ctx->ev_arrived[k]) e = hipEventCreateWithFlags(&ctx->ev_arrived[k], hipEventDisableTiming);
             if (e == hipSuccess && !ctx->ev_rendered[k]) e = hipEventCreateWithFlags(&ctx->ev_rendered[k], hipEventDisableTiming);
         }
-        // device_out returns without waiting: whatever the stream still holds (an earlier request reading the staging buffer, the
-        // caller's own work) comes before this request's first copy
-        if (e == hipSuccess && device_out) {
-            e = hipEventRecord(ctx->ev_rendered[0], s);
-            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_rendered[0], 0);
-        }
-        if (e != hipSuccess) return hip_fail(ctx, e, "sp_render streams");
+        // whatever the stream still holds (an sp_plan_execute_from_host still reading the staging buffer, the caller's own work) comes
+        // before this request's first copy; an idle stream is not waited for (that wait alone costs config 2 ~3 %)
+        const bool busy = hipStreamQuery(s) != hipSuccess;
+        (void)hipGetLastError();   // (hipErrorNotReady: the stream is busy, nothing failed)
+        if (e == hipSuccess && busy) e = hipEventRecord(ctx->ev_rendered[0], s);
+        if (e == hipSuccess && busy) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_rendered[0], 0);
     }
-    // a packed chunk as the kernel sees it: (virtual) sample 0 of its layout, a length that covers its last frame and one spare sample
-    // (3-byte samples are fetched as dwords), its stride
-    auto packed_source = [&](const PackedChunk &ch) {
-        PackedSource ps;
-        ps.bytes = (const uint8_t *)ctx->in_bytes.p + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
-        ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
-        ps.nbytes -= ps.nbytes % (size_t)f.elem;
-        ps.stride = ch.stride2;
-        return ps;
-    };
+    hipStream_t in_s = overlap ? ctx->copy_in : s, out_s = overlap ? ctx->copy_out : s;
     // (nothing to clear: the kernels overwrite every histogram count, both range values and every gauge byte)
-    if (chunks == 1) {
-        if (sparse) {
-            e = upload_packed_chunk(packed[0], req->n, f.width, bytes, nbytes, (uint8_t *)ctx->in_bytes.p, s);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(s);
-                return hip_fail(ctx, e, "sp_render packed upload");
-            }
-            const PackedSource ps = packed_source(packed[0]);
-            rc = plan_execute_range(plan, ctx->in_bytes.p, nbytes, width, 0, width, true, true, &d, &ps);
+    size_t sent = 0;
+    for (int k = 0; k < chunks && e == hipSuccess; k++) {
+        const int32_t x0 = u.bounds[(size_t)k], x1 = u.bounds[(size_t)k + 1];
+        // a packed chunk as the kernel sees it: (virtual) sample 0 of its layout, a length that covers its last frame and one spare
+        // sample (3-byte samples are fetched as dwords), its stride
+        PackedSource ps{};
+        if (u.packed) {
+            const PackedChunk &ch = u.chunks[(size_t)k];
+            e = upload_packed_chunk(ch, req->n, f.width, bytes, nbytes, in, in_s);
+            ps.bytes = in + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
+            ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
+            ps.nbytes -= ps.nbytes % (size_t)f.elem;
+            ps.stride = ch.stride2;
         } else {
-            if (nbytes) e = hipMemcpyAsync(ctx->in_bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return hip_fail(ctx, e, "sp_render upload");
-            rc = sp_plan_execute(plan, ctx->in_bytes.p, nbytes, width, &d);
-        }
-        if (rc) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-    } else {
-        size_t sent = 0;
-        for (int k = 0; k < chunks; k++) {
-            const int32_t x0 = bounds[(size_t)k], x1 = bounds[(size_t)k + 1];
-            PackedSource ps{};
-            if (sparse) {
-                e = upload_packed_chunk(packed[(size_t)k], req->n, f.width, bytes, nbytes, (uint8_t *)ctx->in_bytes.p, ctx->copy_in);
-                ps = packed_source(packed[(size_t)k]);
-            } else {
-                size_t need = nbytes;
-                if (k + 1 < chunks) {
-                    const int64_t last_start = spjs::to_int32(0.5 + stride * (double)(x1 - 1));          // worker.js:72
-                    need = (size_t)(last_start + req->n) * (size_t)f.width;
-                    if (need > nbytes) need = nbytes;
-                }
-                if (need > sent) {
-                    e = hipMemcpyAsync((char *)ctx->in_bytes.p + sent, bytes + sent, need - sent, hipMemcpyHostToDevice, ctx->copy_in);
-                    sent = need;
-                }
+            size_t need = nbytes;
+            if (k + 1 < chunks) {
+                const int64_t last_start = spjs::to_int32(0.5 + u.stride * (double)(x1 - 1));          // worker.js:72
+                need = (size_t)(last_start + req->n) * (size_t)f.width;
+                if (need > nbytes) need = nbytes;
             }
-            if (e == hipSuccess) e = hipEventRecord(ctx->ev_arrived[k], ctx->copy_in);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
-            if (e != hipSuccess) break;
-            rc = plan_execute_range(plan, ctx->in_bytes.p, nbytes, width, x0, x1, k == 0, k + 1 == chunks, &d, sparse ? &ps : nullptr);
-            if (rc) break;
-            if (device_out) continue;
-            e = hipEventRecord(ctx->ev_rendered[k], s);
-            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_out, ctx->ev_rendered[k], 0);
-            if (e != hipSuccess) break;
-            if (x1 > x0) {
-                if (req->waterfall) {   // rows width-1-x: the chunk is one contiguous band of rows
-                    const size_t off = 4 * n * (size_t)(width - x1);
-                    e = hipMemcpyAsync(reply->rgba + off, (char *)ctx->out_rgba.p + off, 4 * n * (size_t)(x1 - x0), hipMemcpyDeviceToHost,
-                                       ctx->copy_out);
-                } else {                // columns x0 .. x1-1 of every row
-                    e = hipMemcpy2DAsync(reply->rgba + 4 * (size_t)x0, host_pitch, (char *)ctx->out_rgba.p + 4 * (size_t)x0, 4 * W,
-                                         4 * (size_t)(x1 - x0), n, hipMemcpyDeviceToHost, ctx->copy_out);
-                }
-                if (e != hipSuccess) break;
+            if (need > sent) {
+                e = hipMemcpyAsync(in + sent, bytes + sent, need - sent, hipMemcpyHostToDevice, in_s);
+                sent = need;
             }
         }
-        if (rc || e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->copy_in);
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(ctx->copy_out);
-            ctx->acc_dirty = true;
-            return rc ? rc : hip_fail(ctx, e, "sp_render chunk");
-        }
+        if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
+        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
+        if (e == hipSuccess) rc = plan_execute_range(plan, in, nbytes, width, x0, x1, k == 0, k + 1 == chunks, &d, u.packed ? &ps : nullptr);
+        if (rc || e != hipSuccess) break;
+        if (device_out) continue;
+        if (overlap) e = hipEventRecord(ctx->ev_rendered[k], s);
+        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(out_s, ctx->ev_rendered[k], 0);
+        if (e == hipSuccess && reply->rgba && x1 > x0)
+            e = download_band(reply->rgba, host_pitch, (const uint8_t *)ctx->out_rgba.p, width, n, req->waterfall, x0, x1, out_s);
+    }
+    if (!device_out && !rc && e == hipSuccess) {
+        // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
+        // (separate copies into pageable memory cost more than the kernels of a small request)
+        e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess && overlap) e = hipStreamSynchronize(out_s);
+    }
+    if (rc || e != hipSuccess) {   // the one way out of a failed request: nothing of it is left in flight
+        if (overlap && ctx->copy_in) (void)hipStreamSynchronize(ctx->copy_in);
+        (void)hipStreamSynchronize(s);
+        if (overlap && ctx->copy_out) (void)hipStreamSynchronize(ctx->copy_out);
+        ctx->acc_dirty = true;
+        return rc ? rc : hip_fail(ctx, e, "sp_render copies");
     }
     if (device_out) return SP_OK;
-    auto down = [&](void *dst, const void *src, size_t bytes_) {
-        if (dst && bytes_ && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes_, hipMemcpyDeviceToHost, s);
-    };
-    if (chunks == 1) {
-        if (req->waterfall || host_pitch == 4 * W) down(reply->rgba, ctx->out_rgba.p, rgba_bytes);
-        else if (reply->rgba && rgba_bytes && e == hipSuccess)   // a column band of a wider image
-            e = hipMemcpy2DAsync(reply->rgba, host_pitch, ctx->out_rgba.p, 4 * W, 4 * W, n, hipMemcpyDeviceToHost, s);
-    }
-    // the six small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
-    // (six separate copies into pageable memory cost more than the kernels of a small request)
-    down(ctx->host_small.p, small.p, small_bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (chunks > 1) {
-        const hipError_t e2 = hipStreamSynchronize(ctx->copy_out);
-        if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "sp_render download");
-    const uint8_t *h = (const uint8_t *)ctx->host_small.p;
-    const uint8_t *h_g = h + small_u64 * 8;
-    if (reply->c_hist) memcpy(reply->c_hist, h, L * 8);
-    if (reply->cb_hist) memcpy(reply->cb_hist, h + L * 8, SP_CB_HIST_SIZE * 8);
-    if (reply->dbfs_minmax) memcpy(reply->dbfs_minmax, h + (L + SP_CB_HIST_SIZE) * 8, 16);
-    if (reply->gauge_mins) memcpy(reply->gauge_mins, h_g, W);
-    if (reply->gauge_maxs) memcpy(reply->gauge_maxs, h_g + W, W);
-    if (reply->gauge_amps) memcpy(reply->gauge_amps, h_g + 2 * W, W);
+    rec.unpack_side(ctx->host_small.p, *reply);
+    rec.unpack_gauges(ctx->host_small.p, *reply);
     return SP_OK;
 }
 
@@ -1408,7 +1336,8 @@ static int render_host(sp_context *ctx, const sp_request *req, const uint8_t *by
         return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
     SP_HIP(ctx, hipSetDevice(ctx->device));
 
-    if (!ctx->cached_plan || !same_request(ctx->cached_plan, req)) {
+    const sp_plan *cp = ctx->cached_plan;
+    if (!cp || !sphost::same_request(cp->req, cp->window, cp->lut, req)) {
         if (ctx->cached_plan) sp_plan_destroy(ctx->cached_plan);
         ctx->cached_plan = nullptr;
         rc = sp_plan_create(ctx, req, &ctx->cached_plan);

@@ -26,6 +26,7 @@
 
 #include "../../include/spectroplot_hip.h"
 #include "sp_formats.h"
+#include "sp_host.h"
 
 namespace {
 
@@ -160,17 +161,6 @@ void add_note(sp_group *g, const std::string &msg)
     if (g->note.find(msg) != std::string::npos) return;
     if (!g->note.empty()) g->note += "; ";
     g->note += msg;
-}
-
-bool same_request(const sp_group *g, const sp_request *r)
-{
-    const sp_request &q = g->req;
-    if (!g->have_plan || q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall
-        || q.lut_len != r->lut_len)
-        return false;
-    if (memcmp(&q.block_norm, &r->block_norm, 8) || memcmp(&q.gain, &r->gain, 8) || memcmp(&q.range, &r->range, 8)) return false;
-    if (g->window.size() != (size_t)r->n || memcmp(g->window.data(), r->windowc, sizeof(double) * (size_t)r->n)) return false;
-    return g->lut.size() == 3 * (size_t)r->lut_len && memcmp(g->lut.data(), r->lut_rgb, g->lut.size()) == 0;
 }
 
 void drop_plans(sp_group *g)
@@ -492,7 +482,7 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     Member &root = g->m[0];
 
     // plans: one per member (its tables live on its device), kept while the request's constants repeat
-    if (!same_request(g, req)) {
+    if (!g->have_plan || !sphost::same_request(g->req, g->window, g->lut, req)) {
         drop_plans(g);
         for (Member &mb : g->m) {
             const int rc = sp_plan_create(mb.ctx, req, &mb.plan);
@@ -513,9 +503,8 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     const size_t n = (size_t)req->n, L = (size_t)req->lut_len, W = (size_t)width;
     const size_t sw = (size_t)(width / count);                          // sliceWidth = ~~(width / workers), lib/spectroplot.js:1208
     const size_t strip_bytes = 4 * sw * n;
-    const size_t rec_u64 = L + SP_CB_HIST_SIZE + 2;                     // [c_hist | cB_hist | dBfs_min, dBfs_max]
-    const size_t small_bytes = rec_u64 * 8 + 3 * sw;                    // ... followed by the slice's three gauge arrays
-    const size_t small_pitch = (small_bytes + 15) & ~(size_t)15;
+    const sphost::ReplyRecord rec{L, sw}, side{L, 0};                  // a member's record; its histograms and range (what is merged)
+    const size_t small_pitch = (rec.bytes() + 15) & ~(size_t)15;
     const bool want_image = reply->rgba && strip_bytes;
 
     // ---- every member: its slice to its device, rendered there (all members at once) -------------------------------------------
@@ -534,16 +523,8 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
         if (mb.status) return;
         hip(hipEventRecord(mb.started, mb.stream), "hipEventRecord");
         if (mb.status) return;
-        uint64_t *d_c = (uint64_t *)mb.small.p;
-        uint8_t *d_g = (uint8_t *)(d_c + rec_u64);
-        sp_reply d{};
+        sp_reply d = rec.view(mb.small.p);
         d.rgba = reply->rgba ? (uint8_t *)mb.strip.p : nullptr;
-        d.c_hist = d_c;
-        d.cb_hist = d_c + L;
-        d.dbfs_minmax = (double *)(d_c + L + SP_CB_HIST_SIZE);
-        d.gauge_mins = d_g;
-        d.gauge_maxs = d_g + sw;
-        d.gauge_amps = d_g + 2 * sw;
         // the slice travels in chunks of frames while earlier chunks are rendered (a sparse slice: only the samples its frames read)
         const int rc = sp_plan_execute_from_host(mb.plan, bytes + b0, b1 - b0, (int32_t)sw, &d);
         if (rc) {
@@ -595,7 +576,7 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     int rc = g->smalls.reserve(small_pitch * (size_t)count);
     if (!rc && staged) rc = g->staging.reserve(strip_bytes * staged + 16);
     if (!rc && reply->rgba) rc = g->image.reserve(4 * W * n + 16);
-    if (!rc) rc = g->merged.reserve(rec_u64 * 8 * ((size_t)count + 1));   // the records end to end, then the merged record
+    if (!rc) rc = g->merged.reserve(side.bytes() * ((size_t)count + 1));   // the records end to end, then the merged record
     if (rc) return gfail(g, rc, "group root: out of device memory");
 
     for_each_member(g, run_member);
@@ -711,11 +692,11 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     // records sit small_pitch apart: sp_merge_replies takes them end to end, so they are packed first (count small copies)
     DevBuf &packed = g->merged;   // [count records] then [merged record]
     for (int r = 0; r < count && e == hipSuccess; r++)
-        e = hipMemcpyAsync((char *)packed.p + rec_u64 * 8 * (size_t)r, (char *)g->smalls.p + small_pitch * (size_t)r, rec_u64 * 8,
+        e = hipMemcpyAsync((char *)packed.p + side.bytes() * (size_t)r, (char *)g->smalls.p + small_pitch * (size_t)r, side.bytes(),
                            hipMemcpyDeviceToDevice, root.stream);
-    uint64_t *d_merged = (uint64_t *)((char *)packed.p + rec_u64 * 8 * (size_t)count);
+    const sp_reply dm = side.view((char *)packed.p + side.bytes() * (size_t)count);
     if (e == hipSuccess) {
-        rc = sp_merge_replies(root.ctx, packed.p, count, (int32_t)L, d_merged, d_merged + L, (double *)(d_merged + L + SP_CB_HIST_SIZE));
+        rc = sp_merge_replies(root.ctx, packed.p, count, (int32_t)L, dm.c_hist, dm.cb_hist, dm.dbfs_minmax);
         if (rc) {
             drain(g);
             return gfail(g, rc, sp_last_error(root.ctx));
@@ -723,10 +704,10 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     }
     if (e == hipSuccess) e = hipEventRecord(g->gathered, root.stream);
     if (e == hipSuccess && reply->rgba && W && n) e = hipMemcpyAsync(reply->rgba, g->image.p, 4 * W * n, hipMemcpyDeviceToHost, root.stream);
-    g->host_small.resize(small_pitch * (size_t)count + rec_u64 * 8);
+    g->host_small.resize(small_pitch * (size_t)count + side.bytes());
     if (e == hipSuccess) e = hipMemcpyAsync(g->host_small.data(), g->smalls.p, small_pitch * (size_t)count, hipMemcpyDeviceToHost, root.stream);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(g->host_small.data() + small_pitch * (size_t)count, d_merged, rec_u64 * 8, hipMemcpyDeviceToHost, root.stream);
+        e = hipMemcpyAsync(g->host_small.data() + small_pitch * (size_t)count, dm.c_hist, side.bytes(), hipMemcpyDeviceToHost, root.stream);
     if (e == hipSuccess) e = hipEventRecord(g->downloaded, root.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(root.stream);
     for (int r = 1; r < count; r++) {   // (the senders' streams: their part of the exchange has long finished)
@@ -758,17 +739,11 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
         (void)hipGetLastError();
     }
 
-    const uint8_t *hm = g->host_small.data() + small_pitch * (size_t)count;
-    if (reply->c_hist) memcpy(reply->c_hist, hm, L * 8);
-    if (reply->cb_hist) memcpy(reply->cb_hist, hm + L * 8, SP_CB_HIST_SIZE * 8);
-    if (reply->dbfs_minmax) memcpy(reply->dbfs_minmax, hm + (L + SP_CB_HIST_SIZE) * 8, 16);
+    side.unpack_side(g->host_small.data() + small_pitch * (size_t)count, *reply);
     // gauges: slice r's at columns [r * sliceWidth, (r + 1) * sliceWidth), the rest clear
-    uint8_t *gs[3] = {reply->gauge_mins, reply->gauge_maxs, reply->gauge_amps};
-    for (int k = 0; k < 3; k++) {
-        if (!gs[k]) continue;
-        memset(gs[k], 0, W);
-        for (int r = 0; r < count; r++) memcpy(gs[k] + sw * (size_t)r, g->host_small.data() + small_pitch * (size_t)r + rec_u64 * 8 + sw * (size_t)k, sw);
-    }
+    for (uint8_t *gp : {reply->gauge_mins, reply->gauge_maxs, reply->gauge_amps})
+        if (gp) memset(gp, 0, W);
+    for (int r = 0; r < count; r++) rec.unpack_gauges(g->host_small.data() + small_pitch * (size_t)r, *reply, sw * (size_t)r);
     return SP_OK;
 }
 

@@ -339,4 +339,41 @@ Thresholds build_thresholds(const PixelMath &pm, int32_t lut_len)
     return t;
 }
 
+sp_reply ReplyRecord::view(void *base) const
+{
+    sp_reply r{};
+    r.c_hist = (uint64_t *)base;
+    r.cb_hist = r.c_hist + lut_len;
+    r.dbfs_minmax = (double *)(r.cb_hist + SP_CB_HIST_SIZE);
+    r.gauge_mins = (uint8_t *)(r.dbfs_minmax + 2);
+    r.gauge_maxs = r.gauge_mins + width;
+    r.gauge_amps = r.gauge_maxs + width;
+    return r;
+}
+
+void ReplyRecord::unpack_side(const void *base, const sp_reply &to) const
+{
+    const sp_reply h = view(const_cast<void *>(base));
+    if (to.c_hist) memcpy(to.c_hist, h.c_hist, lut_len * 8);
+    if (to.cb_hist) memcpy(to.cb_hist, h.cb_hist, SP_CB_HIST_SIZE * 8);
+    if (to.dbfs_minmax) memcpy(to.dbfs_minmax, h.dbfs_minmax, 16);
+}
+
+void ReplyRecord::unpack_gauges(const void *base, const sp_reply &to, size_t at) const
+{
+    const sp_reply h = view(const_cast<void *>(base));
+    if (to.gauge_mins) memcpy(to.gauge_mins + at, h.gauge_mins, width);
+    if (to.gauge_maxs) memcpy(to.gauge_maxs + at, h.gauge_maxs, width);
+    if (to.gauge_amps) memcpy(to.gauge_amps + at, h.gauge_amps, width);
+}
+
+bool same_request(const sp_request &q, const std::vector<double> &window, const std::vector<uint8_t> &lut, const sp_request *r)
+{
+    if (q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall || q.lut_len != r->lut_len)
+        return false;
+    if (memcmp(&q.block_norm, &r->block_norm, 8) || memcmp(&q.gain, &r->gain, 8) || memcmp(&q.range, &r->range, 8)) return false;
+    if (window.size() != (size_t)r->n || memcmp(window.data(), r->windowc, sizeof(double) * (size_t)r->n)) return false;
+    return lut.size() == 3 * (size_t)r->lut_len && memcmp(lut.data(), r->lut_rgb, lut.size()) == 0;
+}
+
 }  // namespace sphost

@@ -1,11 +1,12 @@
 // sp_host.h — host-side tables of a render plan: format names, tapers, twiddles and the exact threshold tables that
-// replace the per-pixel Math.log10 of the reference.
+// replace the per-pixel Math.log10 of the reference; the layout of a reply record and the test of a plan's request constants.
 #pragma once
 
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "../../include/spectroplot_hip.h"
 #include "sp_formats.h"
 
 namespace sphost {
@@ -73,5 +74,20 @@ struct Thresholds {
     int32_t cells;                   // lut_len + SP_CB_HIST_SIZE + 2 (the last two: special keys)
 };
 Thresholds build_thresholds(const PixelMath &pm, int32_t lut_len);
+
+// The side outputs of one render side by side, as the host-buffer render, a group member and sp_merge_replies keep them in memory:
+// [c_hist lut_len u64][cB_hist SP_CB_HIST_SIZE u64][dBfs min, max f64][gauge mins | maxs | amps, width u8 each].
+struct ReplyRecord {
+    size_t lut_len, width;
+    size_t words() const { return lut_len + SP_CB_HIST_SIZE + 2; }   // the 64-bit words: histograms and range
+    size_t bytes() const { return words() * 8 + 3 * width; }         // ... and the gauges
+    sp_reply view(void *base) const;                                  // pointers into the record at `base` (rgba: null)
+    // out of a host record into `to`'s non-null arrays: the histograms and the range; the gauges, at to.gauge_* + at
+    void unpack_side(const void *base, const sp_reply &to) const;
+    void unpack_gauges(const void *base, const sp_reply &to, size_t at = 0) const;
+};
+
+// Whether `r` has the constants a plan was built from (the kept request, its taper and its colour map): the plan can serve it.
+bool same_request(const sp_request &kept, const std::vector<double> &window, const std::vector<uint8_t> &lut, const sp_request *r);
 
 }  // namespace sphost

@@ -1,6 +1,8 @@
 """GPU parity tests: the HIP path, called through the C ABI, against the golden vectors of the real reference worker
 and against the C oracle on seeded inputs.  Bit-exact: RGBA bytes, histograms, gauges and the f64 dBfs range.
 Tolerance: none (every compared quantity is an integer, a byte, or an f64 that is required to be bit-identical)."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -610,6 +612,54 @@ def test_plan_execute_from_host_matches_the_oracle(pkg, ctx, fmt, n, lg, width, 
     _assert_same(got, want)
     del keep
     for p_ in ptrs:
+        ctx.free(p_)
+    plan.close()
+
+
+@pytest.mark.parametrize("fmt,n,lg,width,wf", FROM_HOST, ids=lambda v: str(v))
+def test_chunked_render_waits_for_a_queued_execute_from_host(pkg, ctx, fmt, n, lg, width, wf):
+    """sp_plan_execute_from_host returns with its copies and kernels still queued on the context's staging buffer; a chunked sp_render
+    on the same context, called WITHOUT a synchronisation in between, must not upload over them.  Both results against the oracle.
+    The capture sits in page-locked memory and the stream is kept busy before it, so that its copies really are still queued."""
+    S = (1 << lg) if lg else n + (width - 1) * 3 * n
+    data = siggen.generate(fmt, {"kind": "trinoise", "seed": 99 + n, "step": 7321, "gshift": 9, "amp": 0.5, "namp": 0.02}, S)
+    win, weight = pyoracle.window("blackmanHarris", n)
+    i = np.arange(256)
+    lut = np.stack([i, 255 - i, (i * 7) & 255], axis=1).astype(np.uint8)
+    want = pyoracle.render(fmt, data, n, win, 1.0 / weight, 6.0, 30.0, lut, width, False, wf)
+    # the render: a different capture, format and shape, large enough to be chunked (16 MiB of samples in, 8 MiB of image out)
+    r_fmt, r_n, r_width = "CF32", 1024, 2048
+    r_data = siggen.generate(r_fmt, {"kind": "trinoise", "seed": 321, "step": 7321, "gshift": 11, "amp": 0.5, "namp": 0.02}, 1 << 21)
+    r_win, r_weight = pyoracle.window("hann", r_n)
+    r_want = pyoracle.render(r_fmt, r_data, r_n, r_win, 1.0 / r_weight, 6.0, 30.0, lut, r_width)
+    plan = ctx.plan(fmt, n, win, 1.0 / weight, 6.0, 30.0, lut, False, wf)
+    W = width
+    sizes = [4 * W * n, W, W, W, 8 * 256, 8000, 16]
+    ptrs = [ctx.alloc(max(s_, 16)) for s_ in sizes]
+    L = ctx.lib.L
+    L.sp_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+    L.sp_host_free.argtypes = [ctypes.c_void_p]
+    h = ctypes.c_void_p()
+    assert L.sp_host_alloc(data.size, ctypes.byref(h)) == 0
+    pinned = np.ctypeslib.as_array(ctypes.cast(h, ctypes.POINTER(ctypes.c_uint8)), shape=(data.size,))
+    pinned[:] = data
+    busy = ctx.alloc(1 << 30)
+    # once before, so that nothing between the two calls below synchronises by itself (the render's plan, staging buffers, streams)
+    _assert_same(ctx.render(r_fmt, r_data, r_n, r_win, 1.0 / r_weight, 6.0, 30.0, lut, r_width), r_want)
+    for _ in range(16):                                  # a few ms of work ahead of the request on the context's stream
+        ctx.memset(busy, 0, 1 << 30)
+    plan.execute_from_host(pinned, W, *ptrs)
+    r_got = ctx.render(r_fmt, r_data, r_n, r_win, 1.0 / r_weight, 6.0, 30.0, lut, r_width)
+    ctx.synchronize()
+    got = {"rgba": ctx.download(ptrs[0], sizes[0]), "gauge_mins": ctx.download(ptrs[1], W), "gauge_maxs": ctx.download(ptrs[2], W),
+           "gauge_amps": ctx.download(ptrs[3], W), "c_hist": ctx.download(ptrs[4], 8 * 256, np.uint64),
+           "cB_hist": ctx.download(ptrs[5], 8000, np.uint64)}
+    mm = ctx.download(ptrs[6], 16, np.float64)
+    got["dBfs_min"], got["dBfs_max"] = float(mm[0]), float(mm[1])
+    _assert_same(got, want)
+    _assert_same(r_got, r_want)
+    L.sp_host_free(h)
+    for p_ in ptrs + [busy]:
         ctx.free(p_)
     plan.close()
 
