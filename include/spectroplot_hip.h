@@ -22,6 +22,10 @@
  *   sp_plan_execute          lib/worker.js:68-137       the frame loop, operands resident in HBM (benchmarks, multi-GPU)
  *   sp_plan_execute_from_host  lib/worker.js:68-137     the same with the capture in host memory (uploaded in chunks under the renders),
  *                                                        outputs resident in HBM: what a group member does with its slice
+ *   sp_plan_execute_batch    lib/worker.js:68-137 per item   many captures' frame loops with one plan in one launch, operands in HBM
+ *   sp_render_batch          lib/worker.js:23-156 per item + lib/easy.js:22-72 / lib/spectroplot.js:85-116   many instances' requests
+ *                                                        queued on one worker pool (one Spectroplot per dropped file), on host buffers
+ *   sp_debug_batch_plan      (none)                     (tests) the host's work list for a batch
  *   sp_merge_replies(_batch) lib/spectroplot.js:1229-1238   the caller's merge of the slices' histograms and dBfs range, on the device
  *   sp_place_strips          lib/spectroplot.js:1241-1244   the caller's putImageData of every slice's strip, on the device
  *   sp_group_render          lib/spectroplot.js:1206-1244, lib/samples.js:253-258   the caller's sliced render: one slice per device, the
@@ -313,6 +317,45 @@ int sp_group_rccl_info(const sp_group *group, char *text, size_t capacity);
 /* Device bytes the root member holds for the gather beyond its own strip (image + staging), after the last render. */
 int sp_group_root_bytes(const sp_group *group, size_t *image_bytes, size_t *staging_bytes);
 const char *sp_group_last_error(const sp_group *group);
+
+/*
+ * Batches: K captures rendered with ONE plan (format, n, taper, LUT, gain, range, channel mode and layout are the plan's).  Every item
+ * gets, byte for byte, the reply sp_plan_execute / sp_render of that item alone gives (RGBA, gauges, both histograms, dBfs range): each
+ * item is still one reference message (lib/worker.js:23-156).  Items have their own capture, byte length, width (so their own stride,
+ * lib/worker.js:50) and reply buffers.  The frames of all items are dealt into groups of one size chosen from the batch's total frame
+ * count, so small captures fill the chip (k_frames_batch, for 64 <= n <= 512; other plans render the items one by one, with the same
+ * results).
+ */
+typedef struct sp_batch_item {
+    const void *bytes;   /* the capture: host pointer (sp_render_batch) or device pointer, 16-byte aligned (sp_plan_execute_batch) */
+    size_t nbytes;
+    int32_t width;       /* frames of this item (0 and 1 allowed, with their single-request meaning) */
+    int32_t reserved;
+    sp_reply reply;      /* this item's outputs, host or device pointers as above; any may be NULL */
+} sp_batch_item;
+/*
+ * Device-resident batch, asynchronous on the context's stream.  A small kernel clears every item's histograms and range first, then one
+ * launch renders the items whose frames all lie inside their captures with the format's prefetching loader and one the others.  The
+ * context's single-request state is not touched: single requests and batches may be interleaved on one context.  count == 0 queues
+ * nothing; count < 0 or items == NULL with count > 0: SP_ERR_INVALID_ARG, as are misaligned reply arrays (see sp_plan_execute).  Not
+ * capturable into a hipGraph (SP_ERR_UNSUPPORTED on a capturing stream).
+ */
+int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, int32_t count);
+/*
+ * The same on host buffers, synchronously: the captures are uploaded WHOLE (no sparse packing) into one device buffer at 16-byte aligned
+ * offsets, the batch is rendered, each image comes back in one copy and the small outputs of all items in one.  A batch whose captures,
+ * images and reply records need more than 256 MiB of device memory is rendered in sub-batches of at most that much (an item larger
+ * than that alone).  Plans are cached as sp_render caches them; sp_context_last_upload_bytes reports the batch's upload total.
+ */
+int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_batch_item *items, int32_t count);
+/*
+ * (tests) The work list sp_plan_execute_batch builds for a frame-loop plan with these shapes, without a device: out[] receives int64
+ * words: frames per group, grid of the prefetching launch, grid of the generic launch, groups of each; then per item its launch
+ * (0 prefetching, 1 generic loaders, 2 one by one through sp_plan_execute's path, 3 nothing to render: width 0, reply cleared only),
+ * its first group in that launch and its group count.  *used = words needed (SP_ERR_INVALID_ARG if capacity is smaller).
+ */
+int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, int32_t cu_count, const size_t *nbytes, const int32_t *widths,
+                        int32_t count, int64_t *out, size_t capacity, size_t *used);
 
 /* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else). */
 const char *sp_plan_kernel_name(const sp_plan *plan);

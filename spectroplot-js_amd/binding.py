@@ -39,6 +39,10 @@ class _Reply(C.Structure):
                 ("c_hist", C.c_void_p), ("cb_hist", C.c_void_p), ("dbfs_minmax", C.c_void_p)]
 
 
+class _BatchItem(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("nbytes", C.c_size_t), ("width", C.c_int32), ("reserved", C.c_int32), ("reply", _Reply)]
+
+
 def lib_path():
     # Kernel experiments only (tools/build_variant.sh, tools/ab_variants.sh): with SP_EXPERIMENT_KNOBS=1 in the environment,
     # SP_LIB_VARIANT=<name> loads lib/variants/<name>.so, a copy of the library built with other compile-time options.
@@ -138,6 +142,9 @@ class Library:
         if hasattr(L, "sp_context_last_upload_bytes"):
             L.sp_context_last_upload_bytes.argtypes = [vp, C.POINTER(sz)]
         L.sp_context_get_stream.argtypes = [vp, C.POINTER(vp)]
+        L.sp_plan_execute_batch.argtypes = [vp, C.POINTER(_BatchItem), i32]
+        L.sp_render_batch.argtypes = [vp, C.POINTER(_Request), C.POINTER(_BatchItem), i32]
+        L.sp_debug_batch_plan.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -185,6 +192,21 @@ def twiddles(n):
     s = np.empty(max(n // 2, 1), dtype=np.float64)
     lib.check(lib.L.sp_twiddles(n, c.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)))
     return c[:n // 2], s[:n // 2]
+
+
+def debug_batch_plan(fmt, n, lut_len, cu_count, nbytes, widths):
+    """The work list of a batch (sp_debug_batch_plan): (frames per group, (grid0, grid1), (groups0, groups1), per-item rows of
+    (launch, first group, group count)).  Launch: 0 prefetching loader, 1 generic loaders, 2 one by one, 3 nothing to render."""
+    lib = Library.get()
+    fid = parse_format(fmt)[0] if isinstance(fmt, str) else int(fmt)
+    nb = np.ascontiguousarray(nbytes, dtype=np.uint64)
+    wd = np.ascontiguousarray(widths, dtype=np.int32)
+    cap = 5 + 3 * len(wd)
+    out = np.zeros(cap, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_batch_plan(fid, int(n), int(lut_len), int(cu_count), nb.ctypes.data_as(C.c_void_p),
+                                        wd.ctypes.data_as(C.c_void_p), len(wd), out.ctypes.data_as(C.c_void_p), cap, C.byref(used)))
+    return int(out[0]), (int(out[1]), int(out[2])), (int(out[3]), int(out[4])), out[5:used.value].reshape(-1, 3)
 
 
 def named_resolve(window, cmap):
@@ -322,6 +344,36 @@ class Context:
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
+    def render_batch(self, fmt, datas, n, windowc, block_norm, gain, rng, lut, widths, channel_mode=False, waterfall=False):
+        """sp_render_batch: every capture of `datas` (one width each) rendered with ONE plan; a list of dicts shaped as render()'s,
+        each byte for byte what render() of that capture alone returns."""
+        fid, _ = parse_format(fmt)
+        datas = [np.ascontiguousarray(d, dtype=np.uint8) for d in datas]
+        if len(widths) != len(datas):
+            raise ValueError("one width per capture")
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+        L = len(keep[1])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        outs, mms = [], []
+        items = (_BatchItem * max(len(datas), 1))()
+        for k, (d, w) in enumerate(zip(datas, widths)):
+            W = int(w)
+            out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
+                   "gauge_maxs": np.zeros(max(W, 0), np.uint8), "gauge_amps": np.zeros(max(W, 0), np.uint8),
+                   "c_hist": np.zeros(L, np.uint64), "cB_hist": np.zeros(SP_CB_HIST_SIZE, np.uint64)}
+            mm = np.array([0.0, -200.0])
+            items[k].bytes = d.ctypes.data
+            items[k].nbytes = d.size
+            items[k].width = W
+            items[k].reply = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
+                                    p(out["cB_hist"]), p(mm))
+            outs.append(out)
+            mms.append(mm)
+        self._chk(self.lib.L.sp_render_batch(self.h, C.byref(req), items, len(datas)))
+        for out, mm in zip(outs, mms):
+            out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
+        return outs
+
     def render_named(self, fmt, data, n, window, cmap, gain, rng, width, channel_mode=False, waterfall=False):
         """The request by option names, as the reference's caller assembles its message (lib/spectroplot.js:1113-1146): the library
         evaluates taper, block_norm and colour map (ends forced) itself and keeps the plan while names and numbers repeat."""
@@ -386,6 +438,18 @@ class Plan:
         rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
                      dbfs_minmax or None)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute(self.h, C.c_void_p(d_bytes), nbytes, int(width), C.byref(rep)))
+
+    def execute_batch(self, items):
+        """sp_plan_execute_batch: `items` = [(d_bytes, nbytes, width, {"rgba": addr, "gauge_mins": ..., "c_hist": ..., "cb_hist": ...,
+        "dbfs_minmax": ...}), ...], every address on the device (missing keys: output skipped).  Asynchronous on the context's stream."""
+        arr = (_BatchItem * max(len(items), 1))()
+        keys = ("rgba", "gauge_mins", "gauge_maxs", "gauge_amps", "c_hist", "cb_hist", "dbfs_minmax")
+        for k, (d_bytes, nbytes, width, outs) in enumerate(items):
+            arr[k].bytes = d_bytes or None
+            arr[k].nbytes = int(nbytes)
+            arr[k].width = int(width)
+            arr[k].reply = _Reply(*[outs.get(key) or None for key in keys])
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_batch(self.h, arr, len(items)))
 
     def execute_from_host(self, data, width, rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0, dbfs_minmax=0):
         """sp_plan_execute_from_host: `data` is the capture in HOST memory (numpy uint8; it must stay alive until the context has been

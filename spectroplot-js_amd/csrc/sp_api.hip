@@ -15,7 +15,7 @@
 
 #include "../../include/spectroplot_hip.h"
 #include "sp_host.h"
-#include "sp_kernel_frames.h"
+#include "sp_kernel_frames_batch.h"
 #include "sp_kernel_scratch.h"
 #include "sp_synth.h"
 #include "sp_cmap_tables.h"
@@ -101,6 +101,12 @@ struct sp_context {
     bool acc_dirty = false;      // a request failed between its launches: accumulators must be re-initialised
     size_t last_upload_bytes = 0; // what the last sp_render sent over the host link (a sparse request sends its frames only)
     uint32_t seq = 0;            // requests started on this context (k_frames publishes the number once the reply is cleared; never 0)
+    // sp_plan_execute_batch: the work list (item records, group -> item maps) on the device and its page-locked source, which is
+    // rewritten only once the event says the previous batch's copy has read it
+    DeviceBuffer batch_dev;
+    HostBuffer batch_host;
+    hipEvent_t ev_batch = nullptr;
+    hipEvent_t ev_batch_done = nullptr;   // behind the last batch's launches: the next table copy waits for it (on whatever stream)
     // timing
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -345,6 +351,10 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->out_rgba.release();
     ctx->render_small.release();
     ctx->host_small.release();
+    if (ctx->ev_batch) (void)hipEventDestroy(ctx->ev_batch);
+    if (ctx->ev_batch_done) (void)hipEventDestroy(ctx->ev_batch_done);
+    ctx->batch_dev.release();
+    ctx->batch_host.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int k = 0; k < sp_context::kMaxChunks; k++) {
@@ -662,6 +672,43 @@ struct PackedSource {
     double stride;         // frame x starts at sample ~~(0.5 + stride * x) of it
 };
 
+// The kernel arguments a plan fixes: sizes, layout, the device tables and the epilogue's constants.
+static void plan_frame_args(const sp_plan *plan, spk::FrameArgs &a)
+{
+    a.n = plan->req.n;
+    a.levels = plan->levels;
+    a.channel_mode = plan->req.channel_mode ? 1 : 0;
+    a.waterfall = plan->req.waterfall ? 1 : 0;
+    a.lut_len = plan->req.lut_len;
+    a.sample_width = plan->fmt.width;
+    a.window = plan->d_window;
+    a.cos_t = plan->d_cos;
+    a.sin_t = plan->d_sin;
+    a.gray_edge = plan->d_gray_edge;
+    a.cb_edge = plan->d_cb_edge;
+    a.lut_rgba = plan->d_lut;
+    a.gray_a = plan->gray_a;
+    a.gray_b = plan->gray_b;
+    a.cb_a = plan->cb_a;
+    a.cb_b = plan->cb_b;
+    a.g2_a = plan->th.g2_a;
+    a.g2_b = plan->th.g2_b;
+    a.g2_thr = plan->th.g2_thr;
+    a.g2_m = plan->th.g2_m;
+    a.c2_a = plan->th.c2_a;
+    a.c2_b = plan->th.c2_b;
+    a.c2_thr = plan->th.c2_thr;
+    a.c2_m = plan->th.c2_m;
+    a.c2_lo = plan->th.c2_lo;
+    a.c2_hi = plan->th.c2_hi;
+    a.block_norm_db = plan->block_norm_db;
+    a.gain = plan->req.gain;
+    a.range = plan->req.range;
+    a.cell_g = plan->d_cell_g;
+    a.cell_l = plan->d_cell_l;
+    a.cells = plan->th.cells;
+}
+
 static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, int32_t x_begin, int32_t x_end, bool first,
                               bool last, const sp_reply *out, const PackedSource *src = nullptr)
 {
@@ -746,40 +793,15 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     ctx->acc_dirty = true;   // until this request's last launch (k_frames) or its finish kernel (scratch path) has been queued
 
     spk::FrameArgs a{};
+    plan_frame_args(plan, a);
     a.bytes = (const uint8_t *)d_bytes;
     a.nbytes = (int64_t)nbytes;
     a.nelem = (int64_t)(nbytes / (size_t)f.elem);
     a.stride = width > 1 ? stride : 0.0;   // one frame: (S - n) / 0 is an infinity or a NaN and ~~(0.5 + it * 0) = 0, as with 0
-    a.n = n;
-    a.levels = plan->levels;
     a.width = width;
-    a.channel_mode = plan->req.channel_mode ? 1 : 0;
-    a.waterfall = plan->req.waterfall ? 1 : 0;
-    a.lut_len = plan->req.lut_len;
     a.in_bounds = in_bounds ? 1 : 0;
     a.frame0 = x_begin;
     a.x_end = x_end;
-    a.sample_width = f.width;
-    a.window = plan->d_window;
-    a.cos_t = plan->d_cos;
-    a.sin_t = plan->d_sin;
-    a.gray_edge = plan->d_gray_edge;
-    a.cb_edge = plan->d_cb_edge;
-    a.lut_rgba = plan->d_lut;
-    a.gray_a = plan->gray_a;
-    a.gray_b = plan->gray_b;
-    a.cb_a = plan->cb_a;
-    a.cb_b = plan->cb_b;
-    a.g2_a = plan->th.g2_a;
-    a.g2_b = plan->th.g2_b;
-    a.g2_thr = plan->th.g2_thr;
-    a.g2_m = plan->th.g2_m;
-    a.c2_a = plan->th.c2_a;
-    a.c2_b = plan->th.c2_b;
-    a.c2_thr = plan->th.c2_thr;
-    a.c2_m = plan->th.c2_m;
-    a.c2_lo = plan->th.c2_lo;
-    a.c2_hi = plan->th.c2_hi;
     a.rgba = out->rgba;
     a.frame_min = (double *)ctx->frame_minmax.p;
     a.frame_max = a.frame_min + width;
@@ -791,20 +813,14 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     a.gauge_mins = out->gauge_mins;
     a.gauge_maxs = out->gauge_maxs;
     a.gauge_amps = out->gauge_amps;
-    a.block_norm_db = plan->block_norm_db;
-    a.gain = plan->req.gain;
-    a.range = plan->req.range;
     a.out_c = (unsigned long long *)out->c_hist;
     a.out_cb = (unsigned long long *)out->cb_hist;
     a.out_minmax = out->dbfs_minmax;
-    a.cell_g = plan->d_cell_g;
-    a.cell_l = plan->d_cell_l;
 
     // the kernels count into the context's accumulators; the finish kernel moves the counts to the reply
     a.mm_acc = (unsigned long long *)((char *)ctx->partial.p + 16);
     a.c_hist = (unsigned long long *)((char *)ctx->partial.p + 64);
     a.cb_hist = a.c_hist + SP_MAX_LUT;
-    a.cells = plan->th.cells;
     a.rgba_fast = out->rgba && ((uintptr_t)out->rgba & 15) == 0 && (width & 3) == 0 && width < (1 << 24)
                   && (double)width * (double)n * 4.0 <= 4294967296.0;
 
@@ -1438,4 +1454,354 @@ extern "C" int sp_render_named(sp_context *ctx, const sp_named_request *nr, cons
     const int rc = sp_render(ctx, &r, bytes, nbytes, width, reply);
     if (rc) ctx->named_windowc.clear();
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------- batches of captures
+
+// How a batch is rendered with one plan: every item's frames in groups of one size, in one of two launches of k_frames_batch -
+// launch 0 with the format's prefetching loader (every frame of the item inside its capture: launch_frames' conditions, per item),
+// launch 1 with the generic loaders - or, for a plan k_frames does not cover, item by item through sp_plan_execute's path.
+enum BatchLaunch { kBatchPrefetch = 0, kBatchGeneric = 1, kBatchFallback = 2, kBatchEmpty = 3 };
+struct BatchWork {
+    int gf = 0;                        // frames per group
+    int groups[2] = {0, 0};            // groups of launch 0 / 1
+    std::vector<int> launch;           // per item: BatchLaunch (kBatchEmpty: width 0, the reply is only cleared)
+    std::vector<int32_t> first_group;  // per item: its first group in its launch
+    std::vector<int32_t> group_count;
+    std::vector<double> stride;        // per item: the kernel's stride (0 for one frame) and whether every frame is inside the capture
+    std::vector<int> in_bounds;
+};
+
+static void item_geometry(const spfmt::Format &f, int n, size_t nbytes, int32_t width, double *stride, bool *in_bounds)
+{
+    const double sample_count = (double)nbytes / (double)f.width;                 // samples.js:167
+    const double st = width > 1 ? (sample_count - (double)n) / (double)(width - 1) : 0.0;   // worker.js:50
+    bool ib = false;
+    if (width == 1) {
+        ib = (size_t)n * (size_t)f.width <= nbytes;
+    } else if (width > 1 && st >= 0.0 && std::isfinite(st) && 0.5 + st * (double)(width - 1) < 2147483647.0) {
+        const int64_t last = spjs::to_int32(0.5 + st * (double)(width - 1));
+        ib = (size_t)(last + n) * (size_t)f.width <= nbytes;
+    }
+    *stride = st;
+    *in_bounds = ib;
+}
+
+static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_plan, int cu_count, const size_t *nbytes, const int32_t *widths,
+                       int count, BatchWork &w)
+{
+    w.launch.assign((size_t)count, kBatchFallback);
+    w.first_group.assign((size_t)count, 0);
+    w.group_count.assign((size_t)count, 0);
+    w.stride.assign((size_t)count, 0.0);
+    w.in_bounds.assign((size_t)count, 0);
+    w.gf = 0;
+    w.groups[0] = w.groups[1] = 0;
+    int64_t total = 0;
+    for (int i = 0; i < count; i++) {
+        double st;
+        bool ib;
+        item_geometry(f, n, nbytes[i], widths[i], &st, &ib);
+        w.stride[(size_t)i] = st;
+        w.in_bounds[(size_t)i] = ib ? 1 : 0;
+        total += widths[i] > 0 ? widths[i] : 0;
+    }
+    if (!frames_plan || !spk2::frames_kernel_supports(n) || n > (1 << spk2::kBatchMaxLog2N) || lut_len < 2 || lut_len > spk::kLdsMaxLut)
+        return;
+    const int gf = spk2::batch_group_frames(n, total, cu_count);
+    if ((gf & (gf - 1)) || spk2::layout(n, lut_len, gf).total > 160 * 1024) return;
+    w.gf = gf;
+    for (int i = 0; i < count; i++) {
+        const int32_t W = widths[i];
+        if (W == 0) {
+            w.launch[(size_t)i] = kBatchEmpty;
+            continue;
+        }
+        // launch_frames: the prefetching loaders need every frame inside the capture, 3-byte samples a frame that starts past sample 0
+        bool pf = w.in_bounds[(size_t)i] && (f.width <= 4 || f.width == 8);
+        if (pf && f.width == 3 && !(W >= 2 && spk::frame_start(w.stride[(size_t)i], W - 1) >= 1)) pf = false;
+        const int l = pf ? kBatchPrefetch : kBatchGeneric;
+        w.launch[(size_t)i] = l;
+        w.first_group[(size_t)i] = w.groups[l];
+        w.group_count[(size_t)i] = (W + gf - 1) / gf;
+        w.groups[l] += w.group_count[(size_t)i];
+    }
+}
+
+static int batch_grid(int groups, int cu_count)
+{
+    if (groups <= 0) return 0;
+    const int g = groups < cu_count ? groups : cu_count;
+    return (g + 7) & ~7;
+}
+
+extern "C" int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, int32_t cu_count, const size_t *nbytes, const int32_t *widths,
+                                   int32_t count, int64_t *out, size_t capacity, size_t *used)
+{
+    if (format < 0 || format >= SP_FMT_COUNT || n < 2 || sphost::log2_exact(n) < 0 || lut_len < 1 || cu_count < 1 || count < 0 || !used
+        || (count > 0 && (!nbytes || !widths)))
+        return SP_ERR_INVALID_ARG;
+    for (int i = 0; i < count; i++)
+        if (widths[i] < 0) return SP_ERR_INVALID_ARG;
+    BatchWork w;
+    plan_batch(spfmt::describe(format), n, lut_len, true, cu_count, nbytes, widths, count, w);
+    std::vector<int64_t> v{w.gf, batch_grid(w.groups[0], cu_count), batch_grid(w.groups[1], cu_count), w.groups[0], w.groups[1]};
+    for (int i = 0; i < count; i++) {
+        v.push_back(w.launch[(size_t)i]);
+        v.push_back(w.first_group[(size_t)i]);
+        v.push_back(w.group_count[(size_t)i]);
+    }
+    *used = v.size();
+    if (v.size() > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v.data(), v.size() * 8);
+    return SP_OK;
+}
+
+// Clears the replies of a batch's items before its launches: histograms 0, dBfs range (0, -200) (worker.js:35-41).  One workgroup per item.
+__global__ void k_batch_clear(const spk2::BatchItem *items, int lut_len)
+{
+    const spk2::BatchItem &it = items[blockIdx.x];
+    for (int i = threadIdx.x; i < lut_len + SP_CB_HIST_SIZE + 2; i += blockDim.x) {
+        if (i < lut_len) {
+            if (it.out_c) it.out_c[i] = 0;
+        } else if (i < lut_len + SP_CB_HIST_SIZE) {
+            if (it.out_cb) it.out_cb[i - lut_len] = 0;
+        } else if (it.out_minmax) {
+            it.out_minmax[i - lut_len - SP_CB_HIST_SIZE] = i == lut_len + SP_CB_HIST_SIZE ? 0.0 : -200.0;
+        }
+    }
+}
+
+static int batch_check_items(sp_context *ctx, const spfmt::Format &f, int n, const sp_batch_item *items, int32_t count, bool device)
+{
+    for (int i = 0; i < count; i++) {
+        const sp_batch_item &it = items[i];
+        if (it.width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "batch item: width < 0");
+        if (it.nbytes && !it.bytes) return fail(ctx, SP_ERR_INVALID_ARG, "batch item: bytes is null");
+        if (it.nbytes % (size_t)f.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, "batch item: byte length is not a multiple of the element size");
+        if ((double)it.nbytes / (double)f.width >= 2147483648.0 - (double)n)
+            return fail(ctx, SP_ERR_UNSUPPORTED, "batch item: captures of 2^31 samples or more must be sliced (sample positions are int32)");
+        if ((double)it.width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, "batch item: image too large");
+        if (device && (((uintptr_t)it.reply.c_hist | (uintptr_t)it.reply.cb_hist | (uintptr_t)it.reply.dbfs_minmax) & 7) != 0)
+            return fail(ctx, SP_ERR_INVALID_ARG, "batch item: c_hist, cb_hist and dbfs_minmax must be 8-byte aligned");
+    }
+    return SP_OK;
+}
+
+static int no_context(void)
+{
+    int32_t c = 0;
+    return sp_device_count(&c) == SP_OK ? SP_ERR_INVALID_ARG : SP_ERR_NO_DEVICE;
+}
+
+extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, int32_t count)
+{
+    if (count < 0 || (!items && count > 0)) return SP_ERR_INVALID_ARG;
+    if (!plan) return no_context();
+    if (count == 0) return SP_OK;
+    sp_context *ctx = plan->ctx;
+    const int n = plan->req.n;
+    int rc = batch_check_items(ctx, plan->fmt, n, items, count, true);
+    if (rc) return rc;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+            return fail(ctx, SP_ERR_UNSUPPORTED, "sp_plan_execute_batch cannot be captured into a hipGraph");
+        (void)hipGetLastError();
+    }
+    std::vector<size_t> nb((size_t)count);
+    std::vector<int32_t> wd((size_t)count);
+    for (int i = 0; i < count; i++) {
+        nb[(size_t)i] = items[i].nbytes;
+        wd[(size_t)i] = items[i].width;
+    }
+    BatchWork w;
+    plan_batch(plan->fmt, n, plan->req.lut_len, plan_kernel(plan) == 3, ctx->cu_count, nb.data(), wd.data(), count, w);
+    if (w.gf == 0) {
+        // a plan outside k_frames: the items one by one, as sp_plan_execute renders them
+        for (int i = 0; i < count; i++) {
+            rc = plan_execute_range(plan, items[i].bytes, items[i].nbytes, items[i].width, 0, items[i].width, true, true, &items[i].reply);
+            if (rc) return rc;
+        }
+        return SP_OK;
+    }
+
+    // the work list: item records of launch 0, of launch 1, of the empty items (cleared only), then the group -> item maps
+    std::vector<int> order;
+    for (int l : {kBatchPrefetch, kBatchGeneric, kBatchEmpty})
+        for (int i = 0; i < count; i++)
+            if (w.launch[(size_t)i] == l) order.push_back(i);
+    const size_t nrec = order.size(), rec_bytes = nrec * sizeof(spk2::BatchItem);
+    const size_t map_off = (rec_bytes + 15) & ~(size_t)15;
+    const size_t total = map_off + ((size_t)w.groups[0] + (size_t)w.groups[1]) * sizeof(int32_t);
+    if (ctx->ev_batch) SP_HIP(ctx, hipEventSynchronize(ctx->ev_batch));   // the previous batch's copy has read the page-locked table
+    else SP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_batch, hipEventDisableTiming));
+    rc = ctx->batch_host.reserve(total);
+    if (!rc) rc = ctx->batch_dev.reserve(total);
+    if (rc) return fail(ctx, rc, "sp_plan_execute_batch: out of memory");
+    uint8_t *h = (uint8_t *)ctx->batch_host.p;
+    spk2::BatchItem *rec = (spk2::BatchItem *)h;
+    int32_t *map = (int32_t *)(h + map_off);
+    int rec_first[2] = {0, 0};   // the launch's first record
+    for (int i = 0; i < count; i++) rec_first[1] += w.launch[(size_t)i] == kBatchPrefetch ? 1 : 0;
+    for (size_t r = 0; r < nrec; r++) {
+        const int i = order[r];
+        const sp_batch_item &it = items[i];
+        const int l = w.launch[(size_t)i];
+        spk2::BatchItem &b = rec[r];
+        b = spk2::BatchItem{};
+        b.bytes = (const uint8_t *)it.bytes;
+        b.nbytes = (int64_t)it.nbytes;
+        b.nelem = (int64_t)(it.nbytes / (size_t)plan->fmt.elem);
+        b.stride = w.stride[(size_t)i];
+        b.rgba = it.reply.rgba;
+        b.gauge_mins = it.reply.gauge_mins;
+        b.gauge_maxs = it.reply.gauge_maxs;
+        b.gauge_amps = it.reply.gauge_amps;
+        b.out_c = (unsigned long long *)it.reply.c_hist;
+        b.out_cb = (unsigned long long *)it.reply.cb_hist;
+        b.out_minmax = it.reply.dbfs_minmax;
+        b.width = it.width;
+        b.in_bounds = w.in_bounds[(size_t)i];
+        b.rgba_fast = it.reply.rgba && ((uintptr_t)it.reply.rgba & 15) == 0 && (it.width & 3) == 0 && it.width < (1 << 24)
+                      && (double)it.width * (double)n * 4.0 <= 4294967296.0;
+        b.first_group = w.first_group[(size_t)i];
+        if (l == kBatchEmpty) continue;
+        // launch 1's map follows launch 0's; its records are indexed from the launch's own first record
+        int32_t *m = map + (l == kBatchGeneric ? w.groups[0] : 0);
+        const int32_t local = (int32_t)r - (l == kBatchGeneric ? rec_first[1] : 0);
+        for (int32_t g = 0; g < w.group_count[(size_t)i]; g++) m[b.first_group + g] = local;
+    }
+    uint8_t *d = (uint8_t *)ctx->batch_dev.p;
+    // the previous batch's kernels may still read the table - on another stream, if the caller has switched since
+    if (ctx->ev_batch_done) SP_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_batch_done, 0));
+    else SP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_batch_done, hipEventDisableTiming));
+    SP_HIP(ctx, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s));
+    SP_HIP(ctx, hipEventRecord(ctx->ev_batch, s));
+    const spk2::BatchItem *d_rec = (const spk2::BatchItem *)d;
+    const int32_t *d_map = (const int32_t *)(d + map_off);
+    hipLaunchKernelGGL(k_batch_clear, dim3((unsigned)nrec), dim3(256), 0, s, d_rec, plan->req.lut_len);
+    SP_HIP(ctx, hipGetLastError());
+
+    spk::FrameArgs a{};
+    plan_frame_args(plan, a);
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
+    for (int l = 0; l < 2; l++) {
+        if (!w.groups[l]) continue;
+        rc = spk2::launch_frames_batch(a, plan->req.format, plan->d_stage_tw, w.gf, w.groups[l], l == 0 ? plan->fmt.width : 0,
+                                       d_rec + rec_first[l], d_map + (l ? w.groups[0] : 0), ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, "k_frames_batch launch rejected the configuration");
+        SP_HIP(ctx, hipGetLastError());
+    }
+    SP_HIP(ctx, hipEventRecord(ctx->ev_batch_done, s));
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, s));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+// sp_render_batch's device memory per sub-batch (captures, images and reply records together); a larger batch is rendered in several
+// sub-batches, an item larger than this alone
+static constexpr size_t kBatchBudget = (size_t)256 << 20;
+
+extern "C" int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_batch_item *items, int32_t count)
+{
+    if (count < 0 || (!items && count > 0)) return SP_ERR_INVALID_ARG;
+    if (!ctx) return no_context();
+    int rc = validate_request(ctx, req);
+    if (rc) return rc;
+    const spfmt::Format f = spfmt::describe(req->format);
+    rc = batch_check_items(ctx, f, req->n, items, count, false);
+    if (rc) return rc;
+    if (count == 0) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const sp_plan *cp = ctx->cached_plan;
+    if (!cp || !sphost::same_request(cp->req, cp->window, cp->lut, req)) {
+        if (ctx->cached_plan) sp_plan_destroy(ctx->cached_plan);
+        ctx->cached_plan = nullptr;
+        rc = sp_plan_create(ctx, req, &ctx->cached_plan);
+        if (rc) return rc;
+    }
+    sp_plan *plan = ctx->cached_plan;
+    size_t uploaded = 0;
+    if (plan_kernel(plan) != 3) {
+        // a plan outside k_frames: item by item through sp_render's path
+        for (int i = 0; i < count; i++) {
+            rc = render_core(plan, (const uint8_t *)items[i].bytes, items[i].nbytes, items[i].width, &items[i].reply, items[i].width, false);
+            if (rc) return rc;
+            uploaded += ctx->last_upload_bytes;
+        }
+        ctx->last_upload_bytes = uploaded;
+        return SP_OK;
+    }
+    hipStream_t s = ctx->stream;
+    // the staging buffers below may be in use by work still queued (sp_plan_execute_from_host): this request starts behind it
+    SP_HIP(ctx, hipStreamSynchronize(s));
+    const size_t n = (size_t)req->n;
+    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    std::vector<sp_batch_item> dev((size_t)count);
+    std::vector<size_t> in_off((size_t)count), img_off((size_t)count), rec_off((size_t)count);
+    for (int i0 = 0; i0 < count;) {
+        // the sub-batch [i0, i1): captures, images and records side by side in the context's staging buffers
+        size_t in_sz = 0, img_sz = 0, rec_sz = 0;
+        int i1 = i0;
+        while (i1 < count) {
+            const sp_batch_item &it = items[i1];
+            const sphost::ReplyRecord rr{(size_t)req->lut_len, (size_t)it.width};
+            const size_t img = it.reply.rgba ? a16(4 * (size_t)it.width * n) : 0;
+            if (i1 > i0 && in_sz + img_sz + rec_sz + a16(it.nbytes) + img + a16(rr.bytes()) > kBatchBudget) break;
+            in_off[(size_t)i1] = in_sz;
+            img_off[(size_t)i1] = img_sz;
+            rec_off[(size_t)i1] = rec_sz;
+            in_sz += a16(it.nbytes);
+            img_sz += img;
+            rec_sz += a16(rr.bytes());
+            i1++;
+        }
+        rc = ctx->in_bytes.reserve(in_sz + 16);
+        if (!rc) rc = ctx->out_rgba.reserve(img_sz + 16);
+        if (!rc) rc = ctx->render_small.reserve(rec_sz + 16);
+        if (!rc) rc = ctx->host_small.reserve(rec_sz + 16);
+        if (rc) return fail(ctx, rc, "sp_render_batch: out of memory");
+        uint8_t *const din = (uint8_t *)ctx->in_bytes.p, *const dimg = (uint8_t *)ctx->out_rgba.p, *const drec = (uint8_t *)ctx->render_small.p;
+        hipError_t e = hipSuccess;
+        for (int i = i0; i < i1 && e == hipSuccess; i++) {
+            const sp_batch_item &it = items[i];
+            const sphost::ReplyRecord rr{(size_t)req->lut_len, (size_t)it.width};
+            sp_batch_item &di = dev[(size_t)i];
+            di = it;
+            di.bytes = din + in_off[(size_t)i];
+            di.reply = rr.view(drec + rec_off[(size_t)i]);
+            di.reply.rgba = it.reply.rgba ? dimg + img_off[(size_t)i] : nullptr;
+            if (it.nbytes) e = hipMemcpyAsync(din + in_off[(size_t)i], it.bytes, it.nbytes, hipMemcpyHostToDevice, s);
+            uploaded += it.nbytes;
+        }
+        if (e != hipSuccess) rc = hip_fail(ctx, e, "sp_render_batch upload");
+        if (!rc) rc = sp_plan_execute_batch(plan, dev.data() + i0, i1 - i0);
+        if (!rc) {
+            // the records of the sub-batch come back in one copy, each image in one
+            e = hipMemcpyAsync(ctx->host_small.p, drec, rec_sz, hipMemcpyDeviceToHost, s);
+            for (int i = i0; i < i1 && e == hipSuccess; i++)
+                if (items[i].reply.rgba && items[i].width)
+                    e = hipMemcpyAsync(items[i].reply.rgba, dimg + img_off[(size_t)i], 4 * (size_t)items[i].width * n, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = hip_fail(ctx, e, "sp_render_batch download");
+        }
+        if (rc) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        for (int i = i0; i < i1; i++) {
+            const sphost::ReplyRecord rr{(size_t)req->lut_len, (size_t)items[i].width};
+            const uint8_t *hb = (const uint8_t *)ctx->host_small.p + rec_off[(size_t)i];
+            rr.unpack_side(hb, items[i].reply);
+            rr.unpack_gauges(hb, items[i].reply);
+        }
+        i0 = i1;
+    }
+    ctx->last_upload_bytes = uploaded;
+    return SP_OK;
 }

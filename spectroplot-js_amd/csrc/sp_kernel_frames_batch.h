@@ -1,359 +1,161 @@
-// sp_kernel_frames.h — the frame-loop kernel for 64 <= n <= 8192 (gfx950).
+// sp_kernel_frames_batch.h — k_frames_batch: the frame loop of k_frames over the groups of MANY items in one launch (sp_plan_execute_batch).
 //
-// lib/worker.js:68-137 per frame (decode, taper, the butterfly graph of lib/fft_nayuki.js:54-96, |X|^2 -> dB -> indices -> RGBA, side
-// outputs), built from the parts of sp_frame_parts.h around what bounds it on MI355X.  tools/op_cost.hip (profiles/r02_op_cost.txt): an
-// f64 multiply or add costs 4.4-4.7 issue cycles per wave-instruction per SIMD whatever the occupancy, v_permlane32_swap 8, v_log_f32
-// 8.5, conversions / floor / fract / compares 4.4, 32-bit integer and f32 multiply-add 2.5; one wave alone reaches half of that, two
-// waves reach it.  The reference's unfused butterflies are 800 f64 wave-instructions per 1024-point frame, so the loop is bound by
-// VALU issue, not by HBM, LDS or latency, and the design moves work off the VALU or removes it:
-//   * first pass (stages 1-4): its eight twiddles cos / sin(2 pi k / 16) are the same doubles for every n >= 16 (the table
-//     index k*n/16 is scaled by a power of two before the division by n), so they are literals: no LDS reads, no registers;
-//     the butterflies whose twiddle is (1, 0) skip their products when the frame is finite (integer formats always; float
-//     frames after one f32 multiply-add per raw word), the ones whose sine is exactly 1 skip two products always;
-//   * the re-distribution between passes goes through a padded, wave-private LDS buffer; at n = 512 / 1024 the second one is a
-//     register transpose (v_permlane16_swap / v_permlane32_swap: what it costs the VALU the LDS round trip costs the LDS pipe);
-//   * input: the raw words of the NEXT frame are requested right after the current frame is decoded (1-, 2-, 3-, 4-, 8-byte samples).
-//     One rule follows from the chip completing a wave's vector-memory operations IN ORDER: whatever waits for a younger operation - a
-//     reload of a spilled register, a table load - waits for that prefetch too.  So no prefetching variant may spill inside the loop
-//     (tests/test_isa_checks.py); the variants that would (8-byte samples at n >= 2048; the L/R split at n >= 2048 and with 8-byte samples
-//     from n = 512) request a frame's samples when it starts; and the prologue requests the first frame BEHIND its table loads (n <= 1024);
-//   * epilogue: colour index and centi-bel level are floor(a + b*log2(|X|^2)) in f32; a lane is sent to the exact edge tables
-//     only if its f32 value lies within a proven error margin of an integer (a few lanes in ten thousand), so the common path has
-//     no LDS read and no f64 compare; one histogram atomic per pixel on the merged cell (colour index + level), which the
-//     workgroup turns back into the two histograms at its end; one colour byte per pixel into an LDS tile [frame][bin]; frame
-//     extremes of |X|^2 by LDS integer atomics on the bit patterns;
-//   * after a group of frames the workgroup writes the tile out through the RGBA LUT, in two slices around the passes of the next
-//     group's first frame: 16-byte stores, 128-byte row segments in spectrogram layout; in waterfall layout one tile dword per item as
-//     four dword stores, 256 contiguous bytes of an image row per wave and store instruction;
-//   * n >= 2048 (a frame spans several waves): the waves of a frame meet through an LDS counter, announced early and waited for
-//     late where the dataflow allows, instead of the workgroup barrier;
-//   * the workgroup's last write-out is split between the first and the second waves of the SIMDs (n = 1024): the first ones
-//     finish ~7 us earlier and write their half meanwhile;
-//   * the request's side outputs come from this kernel too - one launch per sp_plan_execute: the gauges of a group of frames are
-//     evaluated (the reference's software log10, three per frame) by two waves inside the next group, where the first waves of the
-//     SIMDs have slack; at its end every workgroup adds its own share of the two histograms and of the dBfs range to the reply with
-//     fire-and-forget atomics (workgroup 0 has cleared the reply and published the request's number), so no workgroup waits for
-//     another and nothing makes a dependent trip to memory (a last-workgroup ticket costs three: profiles/r04_experiments.txt).
-// Measured alternatives (three waves per SIMD, two workgroups per CU, LDS-DMA input, other batch / slice / chain counts) are recorded in
-// DESIGN.md section 6.2; the cost-attribution switches and per-wave clock stamps that produced profiles/ live in
-// tools/experiments/frames_instrumentation.patch (tools/build_variant.sh applies it), not here.
-// k_frames_batch (sp_kernel_frames_batch.h) carries a copy of this frame loop: keep the two in step.
+// The items of a batch share one plan (format, n, taper, LUT, gain, range, layout); each has its own capture, width, stride and reply.
+// The host deals every item's frames into groups of one size, chosen from the batch's total frame count with launch_frames' rule, so
+// small captures get full 32-frame groups and a full grid; a group never spans two items.  A table of item records and a group -> item
+// map travel to the device in one copy.  The loop is k_frames' (sp_kernel_frames.h) with these differences:
+//   * the workgroup reads its group's item record with scalar loads at group start;
+//   * when its next group belongs to another item, the current item's last group is written out, its gauges evaluated, and the
+//     workgroup's share of the item's histograms and dBfs range added to the item's reply (batch_flush); the LDS cells and range restart;
+//   * the next frame's samples are requested one frame ahead as in k_frames - from the next item's capture when that frame is the
+//     first of a group of another item;
+//   * no reply clearing and no request number: sp_plan_execute_batch queues a small clearing kernel ahead of the launch on the same
+//     stream, so no workgroup waits for another (dispatch order is undefined) and the context's single-request state is not touched.
+// The body is a copy of k_frames' rather than a shared template: routed through a common always-inline body, k_frames' own instruction
+// stream changed (every variant at n = 1024), and k_frames is the kernel the benchmark configurations run.
+// Every measured figure in the comments of the copied loop (microseconds, per cent, profiles/ files) was measured on k_frames, not on
+// this kernel.  A fix to the frame loop in sp_kernel_frames.h must be made here too.
 #pragma once
 
-#include <atomic>
-#include <cstdio>
-
-#include "sp_frame_parts.h"
+#include "sp_kernel_frames.h"
 
 namespace spk2 {
 
-using namespace spk;
+// k_frames_batch is built for n <= 512 only.  There its prefetching variants keep k_frames' register budget (no scratch, no spilled
+// VGPR); at n >= 1024 the item bookkeeping on top of the frame loop's peak cost them scratch and spills.  Larger plans render the items
+// of a batch one by one through k_frames: a capture of n >= 1024 fills the chip with far fewer frames, which is what batching buys.
+constexpr int kBatchMaxLog2N = 9;
 
-// cos / sin(2 pi k / 16), k = 0..7, as sphost::twiddles produces them for every n >= 16 (sp_api.hip checks it per plan).
-struct Tw16 {
-    double c, s;
+// k_frames_batch (sp_plan_execute_batch): one record per item of a batch, which shares the plan (the fields of FrameArgs that describe
+// a capture, an image and a reply are taken from here instead).  A group of frames never spans two items; an item's groups are
+// [first_group, first_group + ceil(width / group_frames)) of its launch.
+struct BatchItem {
+    const uint8_t *bytes;
+    int64_t nbytes, nelem;
+    double stride;
+    uint8_t *rgba, *gauge_mins, *gauge_maxs, *gauge_amps;
+    unsigned long long *out_c, *out_cb;
+    double *out_minmax;
+    int32_t width, in_bounds, rgba_fast, first_group;
 };
-__device__ constexpr Tw16 kTw16[8] = {
-    {0x1.0000000000000p+0, 0x0.0p+0},
-    {0x1.d906bcf328d46p-1, 0x1.87de2a6aea963p-2},
-    {0x1.6a09e667f3bcdp-1, 0x1.6a09e667f3bccp-1},
-    {0x1.87de2a6aea964p-2, 0x1.d906bcf328d46p-1},
-    {0x1.1a62633145c07p-54, 0x1.0000000000000p+0},
-    {-0x1.87de2a6aea962p-2, 0x1.d906bcf328d46p-1},
-    {-0x1.6a09e667f3bccp-1, 0x1.6a09e667f3bcdp-1},
-    {-0x1.d906bcf328d46p-1, 0x1.87de2a6aea965p-2},
-};
-inline constexpr Tw16 kTw16Host[8] = {
-    {0x1.0000000000000p+0, 0x0.0p+0},
-    {0x1.d906bcf328d46p-1, 0x1.87de2a6aea963p-2},
-    {0x1.6a09e667f3bcdp-1, 0x1.6a09e667f3bccp-1},
-    {0x1.87de2a6aea964p-2, 0x1.d906bcf328d46p-1},
-    {0x1.1a62633145c07p-54, 0x1.0000000000000p+0},
-    {-0x1.87de2a6aea962p-2, 0x1.d906bcf328d46p-1},
-    {-0x1.6a09e667f3bccp-1, 0x1.6a09e667f3bcdp-1},
-    {-0x1.d906bcf328d46p-1, 0x1.87de2a6aea965p-2},
-};
+typedef const __attribute__((address_space(4))) BatchItem *BatchItemK;   // scalar loads: the table is read-only for the launch
 
-// a group's row pieces are written with non-temporal stores from this many frames per group on (4 bytes per frame and row)
-#ifndef SP_NT_MIN_GROUP
-#define SP_NT_MIN_GROUP 32
-#endif
-
-constexpr int kMmSlotsMax = 4;
-constexpr int kMaxCells = kLdsMaxLut + SP_CB_HIST_SIZE + 2;   // merged histogram cells (sp_host.h Thresholds)
-
-__host__ __device__ inline constexpr int mm_slots(int n)
+// The item of group g, and an item's record behind an opaque copy of its address: the fields are fetched (s_load) where they are used
+// instead of being held in SGPRs through the frame loop (two records' worth of pointers, lengths and strides live across the loop
+// cost the prefetching variants scratch and spilled VGPRs).
+__device__ inline int group_item_of(const int32_t *group_item, int g)
 {
-    return lds_mm_slots(n) < kMmSlotsMax ? lds_mm_slots(n) : kMmSlotsMax;
+    return ((const __attribute__((address_space(4))) int32_t *)group_item)[g];
 }
-
-constexpr int kFrameThreads = 512;   // one workgroup per CU: eight waves, two per SIMD
-
-// 16 points per thread, whole frames per workgroup: 64 <= n <= 8192
-__host__ __device__ inline bool frames_kernel_supports(int n) { return frame_parts_support(n); }
-
-// n >= 2048: the twiddle tables of stages 1-9 only stay in LDS (stage 10 joins the later ones in L2: two more loads per thread and
-// frame), which makes room for a 64 KiB tile: 32 / 16 / 8 frames per group instead of 16 / 8 / 4, i.e. 128 / 64 / 32-byte pieces of
-// the image rows and half as many group barriers (config 5 wrote 2.1 x its image with 16-byte pieces; config 3: -0.7 %, cf32 at
-// n = 2048: -5 %, config 5: -5 %)
-__host__ __device__ inline constexpr int frames_tw_max_stage(int n) { return n >= 2048 ? 9 : kLdsTwMaxStage; }
-__host__ __device__ inline constexpr int frames_tw_entries(int n) { return n < (1 << frames_tw_max_stage(n)) ? n : (1 << frames_tw_max_stage(n)); }
-
-// frames per output group (tile height): a multiple of the frames per round and of 4 (the write-out handles frame quads)
-__host__ __device__ inline int group_frames_for(int n, int want)
+// (every index is wave-uniform: an item is a group's, and a slot's next frame leaves its group in the same round for every slot,
+// because group_frames is a multiple of the frames per round - readfirstlane tells the compiler so)
+__device__ inline BatchItemK item_rec(const BatchItem *items, int i)
 {
-    const int fpb = kFrameThreads * 16 / n;
-    int unit = fpb;
-    while (unit % 4) unit *= 2;          // lcm(fpb, 4) for fpb in {1, 2, 3, 6, 12, ...}
-    int cap = (n >= 2048 ? 65536 : 32768) / n;
-    if (cap > want) cap = want;
-    int f = cap / unit * unit;
-    if (f < unit) f = unit;
-    return f;
-}
-
-// n <= 1024: a group's side outputs are evaluated behind the SECOND barrier of the following group's first frame, which takes a second
-// set of frame-extreme slots (n >= 2048 has no LDS left for one: they are evaluated behind the first barrier there)
-__host__ __device__ inline constexpr bool late_side_outputs(int n) { return n <= 1024; }
-
-// The RGBA LUT and the merged histogram cells sit at FIXED LDS addresses in front of everything whose size depends on the request, so
-// that a pixel's LUT read and its histogram atomic are `ds_* vaddr offset:imm` with vaddr = index * 4 alone: one VALU instruction per
-// pixel for either address (v_lshlrev_b32_sdwa of a tile byte; v_add_lshl_u32 of colour index + level) instead of two.
-constexpr int kOffLut = 0;                                        // u32[kLdsMaxLut]
-constexpr int kOffCells = kOffLut + kLdsMaxLut * 4;               // u32[kMaxCells]: word c counts the pixels with colour index + level == c
-constexpr int kOffXch = (kOffCells + kMaxCells * 4 + 15) & ~15;   // exchange buffers, then the rest of Layout
-
-struct Layout {
-    int off_tw, off_gedge, off_cbedge, off_mm, off_tile, off_done, off_amp, off_win, total;
-};
-
-__host__ __device__ inline Layout layout(int n, int lut_len, int group_frames)
-{
-    Layout l;
-    const int fpb = kFrameThreads * 16 / n;
-    int o = kOffXch + fpb * (n + n / 16) * 8;                    // exchange buffers
-    l.off_tw = o;     o += frames_tw_entries(n) * 16;
-    l.off_gedge = o;  o += lut_len * 8;                          // exact edge tables (read by the few lanes the f32 test sends there)
-    l.off_cbedge = o; o += (SP_CB_HIST_SIZE + 1) * 8;
-    o = (o + 15) & ~15;
-    l.off_mm = o;     o += (late_side_outputs(n) ? 2 : 1) * group_frames * mm_slots(n) * 2 * 8;   // frame extremes (n <= 1024: by group parity)
-    l.off_tile = o;   o += (group_frames * (n + kTilePad) + 15) & ~15;
-    l.off_done = o;   o += 32;                                   // arrival counters: the two wave sets (last write-out), the frames' waves; [7]: "last workgroup"
-    o = (o + 15) & ~15;
-    l.off_amp = o;    o += 16 + 2 * group_frames * 16;           // the workgroup's extreme |X|^2 so far; raw centre samples of two groups' frames
-    l.off_win = o;    o += lds_win_in_lds(n) ? n * 8 : 0;
-    l.total = (o + 15) & ~15;
-    return l;
-}
-
-// v_min_f64 / v_max_f64 as single instructions: fmin() / fmax() first quiet a possible signalling NaN in each operand with a
-// v_max_f64 x, x, x of its own, three instructions per call.  The hardware minimum / maximum already ignores a (quiet) NaN
-// operand, which is all the frame extremes need (worker.js:102-103: comparisons with NaN are false).
-__device__ inline double min_raw(double a, double b)
-{
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ inline double max_raw(double a, double b)
-{
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// Fire-and-forget LDS minimum / maximum of doubles (no NaN operands here).  As instructions: the compiler's atomic optimiser turns
-// an atomic with a wave-uniform address into a loop over the active lanes, ~10 instructions per lane; the LDS serialises the lanes itself.
-__device__ inline void lds_min_f64(double *p, double v)
-{
-    asm volatile("ds_min_f64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) double *)p), "v"(v) : "memory");
-}
-__device__ inline void lds_max_f64(double *p, double v)
-{
-    asm volatile("ds_max_f64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) double *)p), "v"(v) : "memory");
-}
-
-// Inclusive prefix sum over the 64 lanes of a wave in the VALU: row shifts, then the two row broadcasts of the GFX9 family (a shuffle
-// scan is six dependent trips through the LDS crossbar).
-__device__ inline unsigned wave_scan_u32(unsigned x)
-{
-#define SP_DPP_ADD(ctrl, rows) x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rows, 0xf, false);
-    SP_DPP_ADD(0x111, 0xf)   // row_shr:1
-    SP_DPP_ADD(0x112, 0xf)   // row_shr:2
-    SP_DPP_ADD(0x114, 0xf)   // row_shr:4
-    SP_DPP_ADD(0x118, 0xf)   // row_shr:8
-    SP_DPP_ADD(0x142, 0xa)   // row_bcast:15 -> rows 1, 3
-    SP_DPP_ADD(0x143, 0xc)   // row_bcast:31 -> rows 2, 3
-#undef SP_DPP_ADD
-    return x;
-}
-
-// 16-byte non-temporal store (dst is 16-byte aligned)
-__device__ inline void store_nt(uint8_t *dst, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = {a, b, c, d};
-    __builtin_nontemporal_store(v, (u32x4 *)dst);
-}
-
-// 16-byte store at a wave-uniform base + a 32-bit lane offset: `global_store_dwordx4 voff, data, s[base]`.  From `base + off` the
-// compiler builds the 64-bit address in the VALU (a v_mov of the zero high half and a v_lshl_add_u64 per store).
-__device__ inline void store16_at(uint8_t *base, unsigned off, uint32_t a, uint32_t b, uint32_t c, uint32_t d, bool nt)
-{
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = {a, b, c, d};
-    if (nt) asm volatile("global_store_dwordx4 %0, %1, %2 nt" ::"v"(off), "v"(v), "s"(base) : "memory");
-    else asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
-}
-
-// LDS accesses at a compile-time offset plus a byte offset held in a VGPR, through a pointer made from the integer (the dynamic LDS
-// block starts at address 0: k_frames has no static LDS and checks it once): `ds_* vaddr offset:imm`.  Going through `smem + ...`
-// instead leaves a `v_add_u32 v, 0, v` per access behind - the block's address is only replaced by its value after the last folding pass.
-typedef __attribute__((address_space(3))) uint32_t *LdsU32;
-__device__ inline uint32_t lds_read_u32(int fixed_off, unsigned var_off) { return *(LdsU32)(uintptr_t)(unsigned)(fixed_off + var_off); }
-__device__ inline void lds_count(int fixed_off, unsigned var_off)
-{
-    __hip_atomic_fetch_add((LdsU32)(uintptr_t)(unsigned)(fixed_off + var_off), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// 4 * byte J of a dword in ONE instruction (sub-dword addressing): the LDS byte offset of a tile byte's LUT entry.
-template <int J>
-__device__ inline unsigned byte_times4(unsigned w)
-{
-    unsigned r;
-    if constexpr (J == 0) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(w));
-    else if constexpr (J == 1) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(w));
-    else if constexpr (J == 2) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(w));
-    else asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(w));
-    return r;
-}
-
-// Does any of the raw f32 words (lo[e], hi[e]: the two halves of one 64-bit load) hold an infinity or a NaN?  x*0 is NaN exactly for
-// those; v_pk_fma_f32 takes a sample's two words at once.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// The launch arguments as they lie in the kernel-argument segment (FrameArgs is k_frames' first parameter), behind an opaque copy of
-// the segment pointer: fields read through it are fetched (s_load) where they are used - the side outputs once per group, the
-// request's end - instead of sitting in SGPRs from the kernel's first instruction on (the compiler loads every field of a by-value
-// argument it can see at the entry; the two dozen that only the side outputs need cost as many spilled SGPRs in the frame loop).
-typedef const __attribute__((address_space(4))) FrameArgs *LateArgs;
-__device__ inline LateArgs late_args()
-{
-    LateArgs p = (LateArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    BatchItemK p = (BatchItemK)items + __builtin_amdgcn_readfirstlane(i);
     asm volatile("" : "+s"(p));
     return p;
 }
 
-// First register pass: stages 1-4 inside window [0, 4) with literal twiddles.
-template <bool TRIV>
-__device__ inline void fft_pass1(double (&re)[16], double (&im)[16])
+// The generic loaders of k_frames_batch: the format switch of the frame loop over the current item's capture.
+template <int LOG2N>
+__device__ inline void load_frame_item(int format, const BatchItemK c, int64_t start, int tl, const double (&win)[16], double (&re)[16],
+                                       double (&im)[16], double2 *centre)
 {
-#pragma unroll
-    for (int s = 1; s <= 4; s++) {
-        const int u = s - 1;
-#pragma unroll
-        for (int e0 = 0; e0 < 16; e0++) {
-            if (e0 & (1 << u)) continue;
-            const int e1 = e0 | (1 << u);
-            const int k = (e0 & ((1 << u) - 1)) << (4 - s);     // fft_nayuki.js:76-78: table index j * n / size, in units of n / 16
-            const double c = kTw16[k].c, sn = kTw16[k].s;
-            const double rl = re[e1], il = im[e1];
-            double tpre, tpim;                                   // fft_nayuki.js:80-81
-            if (TRIV && k == 0) {
-                // (1, 0): x*1 + y*0 == x bit for bit for finite x, y (only the sign of a zero can differ; nothing depends on it)
-                tpre = rl;
-                tpim = il;
-            } else if (k == 4) {
-                // sine exactly 1: y*1 == y for every y, NaN and infinities included
-                tpre = rl * c + il;
-                tpim = il * c - rl;
-            } else {
-                tpre = rl * c + il * sn;
-                tpim = il * c - rl * sn;
-            }
-            const double rj = re[e0], ij = im[e0];
-            re[e1] = rj - tpre;
-            im[e1] = ij - tpim;
-            re[e0] = rj + tpre;
-            im[e0] = ij + tpim;
-        }
+    constexpr int T = (1 << LOG2N) / 16;
+    FrameArgs fa{};
+    fa.bytes = c->bytes;
+    fa.in_bounds = c->in_bounds;
+    const spfmt::View view{c->bytes, c->nbytes, c->nelem};
+    switch (format) {
+#define SP_CASE(F) case F: load_frame<F>(fa, view, start, tl, T, LOG2N, win, re, im, centre); break;
+        SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
+        SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
+        SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32)
+#undef SP_CASE
+    default: load_frame<SP_FMT_CF64>(fa, view, start, tl, T, LOG2N, win, re, im, centre); break;
     }
 }
 
-template <int NHI>
-__device__ inline bool raw_f32_nonfinite(const uint32_t (&lo)[16], const uint32_t (&hi)[NHI])
+// k_frames_batch: the workgroup's share of one item's histograms and dBfs range goes to the item's reply (as at the end of k_frames,
+// without the request-number check: the reply was cleared by a kernel queued ahead), then the merged cells and the range restart for
+// the next item.  Every thread calls it, behind the item's last side outputs (their LDS minimum / maximum land before the first barrier).
+template <int kThreads>
+__device__ inline void batch_flush(const FrameArgs &a, unsigned char *smem, double *s_red, const BatchItemK it, const int tid)
 {
-    static_assert(NHI == 16, "8-byte samples: two f32 words each");
-    unsigned long long s = 0ull;
-    const unsigned long long zero = 0ull;
+    constexpr int kPer = 3;
+    unsigned int *const s_cells = (unsigned int *)(smem + kOffCells);
+    unsigned int *const s_pre = (unsigned int *)(smem + kOffXch);
+    unsigned int *const s_part = s_pre + kThreads * kPer + 4;
+    const int lane = tid & 63;
+    const LateArgs la = late_args();   // (lut_len, cells too: nothing of this is held through the frame loop)
+    const uint16_t *const cell_g = la->cell_g, *const cell_l = la->cell_l;
+    const int gi_c = tid < la->lut_len ? tid : 0;
+    const int cg_lo = cell_g[gi_c], cg_hi = cell_g[gi_c + 1];
+    int l_lo[2], l_hi[2];
 #pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const unsigned long long w = ((unsigned long long)hi[e] << 32) | lo[e];   // the register pair the 64-bit load filled
-        asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(s) : "v"(w), "v"(zero));
+    for (int u = 0; u < 2; u++) {
+        const int gi = tid + u * kThreads;
+        const int l_cb = gi < SP_CB_HIST_SIZE ? SP_CB_HIST_SIZE - 1 - gi : 0;
+        l_lo[u] = cell_l[l_cb];
+        l_hi[u] = cell_l[l_cb + 1];
     }
-    const float s0 = __uint_as_float((uint32_t)s), s1 = __uint_as_float((uint32_t)(s >> 32));
-    return __ballot(s0 != s0 || s1 != s1) != 0ull;
+    unsigned int v[kPer], run = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int c = tid * kPer + k;
+        v[k] = c < la->cells ? s_cells[c] : 0u;
+        run += v[k];
+    }
+    const unsigned int incl = wave_scan_u32(run);
+    if (lane == 63) s_part[tid >> 6] = incl;
+    lds_barrier();
+    for (int i = tid; i < la->cells; i += kThreads) s_cells[i] = 0;   // (read above: the next item counts from zero)
+    unsigned int base = incl - run;
+    {
+        const uint4 p0 = *(const uint4 *)s_part, p1 = *(const uint4 *)(s_part + 4);
+        const unsigned int part[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+        const int wave = tid >> 6;
+#pragma unroll
+        for (int w = 0; w < 7; w++) base += w < wave ? part[w] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        s_pre[tid * kPer + k] = base;
+        base += v[k];
+    }
+    if (tid == kThreads - 1) s_pre[kThreads * kPer] = base;
+    lds_barrier();
+    const int sp0 = la->cells - 2, sp1 = la->cells - 1;
+    const unsigned int n0 = s_pre[sp0 + 1] - s_pre[sp0], n1 = s_pre[sp1 + 1] - s_pre[sp1];
+    unsigned long long *const out_c = it->out_c, *const out_cb = it->out_cb;
+    if (tid < la->lut_len && out_c) {
+        const unsigned int cnt = s_pre[cg_hi] - s_pre[cg_lo] + (tid == 0 ? n0 : 0u) + (tid == la->lut_len - 1 ? n1 : 0u);
+        if (cnt) atomicAdd(&out_c[tid], (unsigned long long)cnt);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int gi = tid + u * kThreads;
+        if (gi < SP_CB_HIST_SIZE && out_cb) {
+            const unsigned int cnt = s_pre[l_hi[u]] - s_pre[l_lo[u]] + (gi == 0 ? n0 + n1 : 0u);
+            if (cnt) atomicAdd(&out_cb[gi], (unsigned long long)cnt);
+        }
+    }
+    double *const out_mm = it->out_minmax;
+    if (tid < 2) {
+        typedef __attribute__((address_space(1))) double *GlobalF64;
+        if (out_mm) {
+            if (tid == 0) __builtin_amdgcn_global_atomic_fmin_f64((GlobalF64)&out_mm[0], s_red[0]);
+            else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
+        }
+        s_red[tid] = tid ? -200.0 : 0.0;                                      // worker.js:35-36
+    }
+    lds_barrier();   // (the prefix's reads are done before the next frame's re-distribution writes over it)
 }
-
-
-// The waves that share a frame (n = 2048: two, n = 4096: four) meet through an LDS counter instead of the workgroup barrier, which
-// held every frame of a round to the pace of the slowest wave and kept all waves in the same phase (all in the VALU, then all in the
-// LDS).  Every LDS operation a wave has issued is ahead of its increment in the LDS queue (a wave's LDS operations execute in
-// order), so "my writes are visible" and "my reads are done" both hold once the partners see the count.
-template <bool COUNTER, bool BLOCK_SYNC>
-struct FrameMeet {
-    unsigned addr;     // LDS byte address of the frame's counter (wave-uniform)
-    unsigned target;   // the count once every wave of the frame has arrived the next time
-    unsigned step;     // waves per frame
-    // One asm block each (a C loop around an atomic splits the kernel's big basic blocks and costs the register allocator 60+ spilled
-    // VGPRs).  arrive(): lane 0 adds one.  wait(): the wave polls until every wave of the frame has arrived as often as itself.
-    // A wave alternates arrive and wait strictly, so no wave is ever two arrivals ahead and the count cannot be reached early.
-    __device__ inline void arrive()
-    {
-        if constexpr (COUNTER) {
-            unsigned long long save;
-            unsigned a_v, one_v;
-            asm volatile("v_mov_b32 %[a_v], %[addr]\n\t"
-                         "v_mov_b32 %[one_v], 1\n\t"
-                         "s_mov_b64 %[save], exec\n\t"
-                         "s_mov_b64 exec, 1\n\t"
-                         "ds_add_u32 %[a_v], %[one_v]\n\t"
-                         "s_mov_b64 exec, %[save]"
-                         : [save] "=&s"(save), [a_v] "=&v"(a_v), [one_v] "=&v"(one_v)
-                         : [addr] "s"(addr)
-                         : "memory");
-        }
-    }
-    __device__ inline void wait()
-    {
-        if constexpr (COUNTER) {
-            target = (unsigned)__builtin_amdgcn_readfirstlane((int)(target + step));   // wave-uniform, kept in an SGPR
-            unsigned a_v, got_v, got_s;
-            asm volatile("v_mov_b32 %[a_v], %[addr]\n"
-                         "L_sp_meet_%=:\n\t"
-                         "ds_read_b32 %[got_v], %[a_v]\n\t"
-                         "s_waitcnt lgkmcnt(0)\n\t"
-                         "v_readfirstlane_b32 %[got_s], %[got_v]\n\t"
-                         "s_sub_i32 %[got_s], %[got_s], %[target]\n\t"
-                         "s_cmp_lt_i32 %[got_s], 0\n\t"
-                         "s_cbranch_scc1 L_sp_meet_%="
-                         : [a_v] "=&v"(a_v), [got_v] "=&v"(got_v), [got_s] "=&s"(got_s)
-                         : [addr] "s"(addr), [target] "s"(target)
-                         : "memory", "scc");
-        } else {
-            spk::frame_sync<BLOCK_SYNC>();
-        }
-    }
-    __device__ inline void operator()()
-    {
-        arrive();
-        wait();
-    }
-};
 
 template <int LOG2N, bool CH, int PFB>
-__global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, const int format, const double2 *__restrict__ stage_tw,
-                                                       const int group_frames, const int groups)
+__global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameArgs a, const int format, const double2 *__restrict__ stage_tw,
+                                                             const int group_frames, const int groups, const BatchItem *__restrict__ bitems,
+                                                             const int32_t *__restrict__ bgroup)
 {
     constexpr int kThreads = kFrameThreads;   // eight waves, two per SIMD, one workgroup per CU
     constexpr int N = 1 << LOG2N;
@@ -406,6 +208,8 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     const int xcd = blockIdx.x & 7, lane_in_xcd = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
     const int chunk = (groups + 7) >> 3;
     const int g_end = min(groups, (xcd + 1) * chunk);
+    // the item of the workgroup's current group, the item of the frame requested next
+    int cur = group_item_of(bgroup, min(xcd * chunk + lane_in_xcd, groups - 1)), rq = cur;
 
     constexpr bool PF = PFB != 0;
     const int sidx_pf = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
@@ -415,12 +219,14 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     auto request = [&](int xq) {
         if constexpr (PF) {
             // (the prefetching variants only run when every frame lies inside the buffer: launch_frames)
-            const int xc = xq < a.x_end ? xq : a.x_end - 1;
+            const BatchItemK rr = item_rec(bitems, rq);
+            const int xe = rr->width;
+            const int xc = xq < xe ? xq : xe - 1;
             constexpr bool UNI = T >= 64;   // a frame per wave or more: its start is wave-uniform
-            const int sv = frame_start_in_bounds(a.stride, xc);
+            const int sv = frame_start_in_bounds(rr->stride, xc);
             const int64_t st = UNI ? __builtin_amdgcn_readfirstlane(sv) : sv;
-            if constexpr (PFB == 3) raw_back = (st + N) * 3 + 1 > a.nbytes ? 1 : 0;
-            issue_raw<PFB, UNI>(a.bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
+            if constexpr (PFB == 3) raw_back = (st + N) * 3 + 1 > rr->nbytes ? 1 : 0;
+            issue_raw<PFB, UNI>(rr->bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
         }
     };
     // n = 1024, 32-frame groups: the first / second waves of the SIMDs each take one half of a group's frames
@@ -430,10 +236,8 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     // are a quarter of the size and the taper goes to registers after them, the old order measures the same (n = 2048) or 1.3 % better
     // (n = 8192: the other order shifts the loop's register allocation)
     constexpr bool REQ_AFTER_TABLES = PF && !LATE_PF && LOG2N <= 10;
-    if (PF && !LATE_PF && !REQ_AFTER_TABLES && xcd * chunk + lane_in_xcd < g_end) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
+    if (PF && !LATE_PF && !REQ_AFTER_TABLES && xcd * chunk + lane_in_xcd < g_end) request((xcd * chunk + lane_in_xcd - item_rec(bitems, rq)->first_group) * group_frames + fs0);
 
-    // workgroup 0's first wave owns the reply's initial state in the first launch of a request (below)
-    const bool owner = blockIdx.x == 0 && __builtin_amdgcn_readfirstlane(tid >> 6) == 0 && a.first;   // (wave-uniform)
     constexpr bool WIN_LDS = lds_win_in_lds(N);   // taper in LDS for n <= 1024, in registers for the whole launch above
     double *s_win = (double *)(smem + lay.off_win);
     constexpr int MMS = mm_slots(N);
@@ -465,27 +269,10 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
             const int i = tid + k * kThreads;
             cb_r[k] = i <= SP_CB_HIST_SIZE ? a.cb_edge[i] : 0.0;
         }
-        // Workgroup 0 of a request's first launch clears the reply's histograms and sets its dBfs range to (0, -200): its first wave
-        // alone, so that the wave knows when the stores have landed (publish() below).  Fire-and-forget, behind the table loads.
-        if (owner) {
-            const LateArgs la = late_args();
-            unsigned long long *const out_c = la->out_c, *const out_cb = la->out_cb;
-            unsigned long long *const out_mm = (unsigned long long *)la->out_minmax;
-            constexpr int kClr = (kLdsMaxLut + SP_CB_HIST_SIZE + 63) / 64;
-#pragma unroll
-            for (int k = 0; k < kClr; k++) {
-                const int i = tid + 64 * k;
-                unsigned long long *const dst = i < kLdsMaxLut ? (out_c && i < a.lut_len ? out_c + i : nullptr)
-                                                               : (out_cb && i < kLdsMaxLut + SP_CB_HIST_SIZE ? out_cb + (i - kLdsMaxLut) : nullptr);
-                if (dst) __hip_atomic_store(dst, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 2 && out_mm)
-                __hip_atomic_store(out_mm + tid, tid ? 0xc069000000000000ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // -200.0, 0.0
-        }
         // The first frame's samples are requested BEHIND the table loads (vector-memory operations complete in order: requested ahead of
         // them, the wait for the tables - L2 hits - was a wait for the samples from HBM), and unconditionally (a frame past the end is
         // clamped), so that the compiler can count the 16 younger loads in that wait: s_waitcnt vmcnt(16).
-        if constexpr (REQ_AFTER_TABLES) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
+        if constexpr (REQ_AFTER_TABLES) request((xcd * chunk + lane_in_xcd - item_rec(bitems, rq)->first_group) * group_frames + fs0);
         // what needs no table is set up while the loads are in flight (a table load takes ~2.3 us at the start of a launch)
         for (int i = tid; i < a.cells; i += kThreads) s_cells[i] = 0;
         if (tid < 8) s_done[tid] = 0;
@@ -524,7 +311,6 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     }
     lds_barrier();
 
-    const spfmt::View view{a.bytes, a.nbytes, a.nelem};
     uint32_t pf_word = 0;
     // epilogue constants (sp_host.cpp build_thresholds): t = a + b*log2(|X|^2), already lowered by the margin
     const float g_a = a.g2_a, g_b = a.g2_b, g_m = a.g2_m;
@@ -554,8 +340,10 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         const LateArgs la = late_args();
         // three scalar loads, selected per lane below (the compiler turns a select between fields into ONE indexed vector load, whose
         // wait covers every outstanding vector-memory operation of the wave: the sample prefetch, ~2 us)
-        uint8_t *out_min = la->gauge_mins, *out_max = la->gauge_maxs, *out_amp = la->gauge_amps;
-        asm volatile("" : "+s"(out_min), "+s"(out_max), "+s"(out_amp));
+        const BatchItemK ir = item_rec(bitems, cur);
+        uint8_t *out_min = ir->gauge_mins, *out_max = ir->gauge_maxs, *out_amp = ir->gauge_amps;
+        int x_end = ir->width;
+        asm volatile("" : "+s"(out_min), "+s"(out_max), "+s"(out_amp), "+s"(x_end));
         const double gain = la->gain, range = la->range, bn_db = la->block_norm_db;
         if (tid >= 3 * group_frames) return;
         const int role = (tid >= group_frames ? 1 : 0) + (tid >= 2 * group_frames ? 1 : 0), f = tid - role * group_frames;
@@ -585,7 +373,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
             else lds_min_f64(&s_red[0], v);
         }
         uint8_t *const out = role == 0 ? out_min : role == 1 ? out_max : out_amp;
-        if (out && x0 + f < a.x_end) out[x0 + f] = clamp_u8(0.5 + (range + v) * 256 / range);   // worker.js:128-136
+        if (out && x0 + f < x_end) out[x0 + f] = clamp_u8(0.5 + (range + v) * 256 / range);   // worker.js:128-136
     };
     // write-out of tile rows [f0, f0 + fcount) by the threads [t0, t0 + dthreads), slice `part` of `nparts`
     auto drain_rows = [&](const int x0, const int part, const int nparts, const int f0, const int fcount, const int t0, const int dthreads,
@@ -595,8 +383,11 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         // (the image's address, width and layout are read from the argument segment here, once per write-out, instead of sitting in
         // SGPRs through every frame)
         const LateArgs la = late_args();
-        uint8_t *const img = la->rgba;
-        const int img_width = la->width, img_waterfall = la->waterfall, img_fast = la->rgba_fast;
+        const BatchItemK ir = item_rec(bitems, cur);
+        uint8_t *const img = ir->rgba;
+        const int img_width = ir->width, img_waterfall = la->waterfall;
+        const int img_fast = ir->rgba_fast;
+        const int x_end = img_width;
         if (img) {
             if (!img_waterfall) {
                 // spectrogram: image is n rows x width columns; row y holds bin (n/2 - y) mod n            worker.js:90,117
@@ -616,7 +407,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                         const int itc = it < items ? it : it0;
                         const int e4 = itc & 3, fq = (itc >> 2) & (quads - 1), tq = (itc >> 2) >> lq;   // tq: thread of the frame
                         i0v[u] = tq + 4 * e4 * T;
-                        xav[u] = it < items ? x0 + f0 + fq * 4 : a.x_end;
+                        xav[u] = it < items ? x0 + f0 + fq * 4 : x_end;
 #pragma unroll
                         for (int k = 0; k < 4; k++)
                             gb[u][k] = *(const uint32_t *)(s_tile + __umul24((unsigned)(f0 + fq * 4), (unsigned)tile_pitch) + k * tile_pitch + tq * 16 + e4 * 4);
@@ -638,7 +429,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
 #pragma unroll
                         for (int u = 0; u < 2; u++) {
                             const int xa = xav[u];
-                            if (xa >= a.x_end) continue;
+                            if (xa >= x_end) continue;
                             const unsigned y0 = (unsigned)(N / 2 - i0v[u]) & (N - 1);
 #pragma unroll
                             for (int j = 0; j < 4; j++) {
@@ -656,18 +447,18 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
 #pragma unroll
                     for (int u = 0; u < 2; u++) {
                         const int xa = xav[u];
-                        if (xa >= a.x_end) continue;
+                        if (xa >= x_end) continue;
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
                             const int i = i0v[u] + j * T;
                             const int y = (N / 2 - i) & (N - 1);
                             uint8_t *dst = img + ((size_t)y * (size_t)img_width + (size_t)xa) * 4;
-                            if (xa + 3 < a.x_end && (((size_t)dst & 15) == 0)) {
+                            if (xa + 3 < x_end && (((size_t)dst & 15) == 0)) {
                                 *(uint4 *)dst = make_uint4(px[u][j][0], px[u][j][1], px[u][j][2], px[u][j][3]);
                             } else {
 #pragma unroll
                                 for (int k = 0; k < 4; k++)
-                                    if (xa + k < a.x_end) ((uint32_t *)dst)[k] = px[u][j][k];
+                                    if (xa + k < x_end) ((uint32_t *)dst)[k] = px[u][j][k];
                             }
                         }
                     }
@@ -682,7 +473,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 for (int it = dt + part * dthreads; it < items; it += nparts * dthreads) {
                     const int tq = it % T, e4 = (it / T) & 3, f = f0 + it / (4 * T);
                     const int xa = x0 + f;
-                    if (xa >= a.x_end) continue;
+                    if (xa >= x_end) continue;
                     const uint32_t gb = *(const uint32_t *)(s_tile + f * tile_pitch + tq * 16 + e4 * 4);
                     // columns (i + n/2 - 1) mod n of bins i = tq + (4*e4 + j)*T: c0 + j*T without a wrap inside an item - except for
                     // the one item per frame whose first pixel is the row's last (bin n/2): its other three start the row
@@ -704,16 +495,33 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     int gpar = 0;   // parity of the workgroup's current group (s_amp)
     meet.arrive();   // the first re-distribution only waits (exchange<.., SECOND = false>)
     for (int g = xcd * chunk + lane_in_xcd; g < g_end; g += per_xcd) {
-        const int x0 = a.frame0 + g * group_frames;
+        {
+            // a group of another item: the current item's last group is written out and its shares go to its reply first (the
+            // samples of this group's first frame are already on their way, from the new item's capture: `rq` below)
+            const int gi = group_item_of(bgroup, g);
+            if (gi != cur) {
+                if (drain_x0 >= 0) {
+                    lds_barrier();
+                    drain(drain_x0, 0, 1);
+                    side_outputs(drain_x0, gpar ^ 1);
+                    batch_flush<kThreads>(a, smem, s_red, item_rec(bitems, cur), tid);
+                    drain_x0 = -1;
+                }
+                cur = gi;
+            }
+        }
+        const int x0 = (g - item_rec(bitems, cur)->first_group) * group_frames;
         for (int r = 0; r < rounds; r++) {
             // HALVES: the first waves of the SIMDs (slots 0 .. FPB/2-1) own the group's first half of the frames, the second waves the
             // other half, so that each set can write its half out by itself after the workgroup's last group
             const int fr = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + r * (FPB / 2) + fs % (FPB / 2) : r * FPB + fs;
             const int xr = x0 + fr;
             if (fr >= group_frames) continue;   // a slot without a frame in the group's last round (its next frame is already requested)
-            const bool live = xr < a.x_end;
-            const int x = live ? xr : a.x_end - 1;
-            const int64_t start = frame_start(a.stride, x);
+            const BatchItemK cr = item_rec(bitems, cur);
+            const int x_end = cr->width;
+            const bool live = xr < x_end;
+            const int x = live ? xr : x_end - 1;
+            const int64_t start = frame_start(cr->stride, x);
 
             double re[16], im[16];
             double win[16];
@@ -721,10 +529,16 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
             bool nonfinite = true;   // wave-uniform
 #pragma unroll
             for (int e = 0; e < 16; e++) win[e] = WIN_LDS ? wbase[e * T] : win_reg[WIN_LDS ? 0 : e];
-            // the frame this slot processes next: the same slot one round on, or its frame in the workgroup's next group
-            const int xn = (r + 1 < rounds && (HALVES || fr + FPB < group_frames)) ? xr + (HALVES ? FPB / 2 : FPB)
-                                                                         : (g + per_xcd < g_end ? a.frame0 + (g + per_xcd) * group_frames + fs0 : -1);
-            if constexpr (PF && LATE_PF) request(xr);
+            // the frame this slot processes next: the same slot one round on, or its frame in the workgroup's next group - whose item's
+            // record is read here, in the group's last round
+            const bool same_group = r + 1 < rounds && (HALVES || fr + FPB < group_frames);
+            rq = same_group || g + per_xcd >= g_end ? cur : group_item_of(bgroup, g + per_xcd);
+            const int xn = same_group ? xr + (HALVES ? FPB / 2 : FPB)
+                                      : (g + per_xcd < g_end ? (g + per_xcd - item_rec(bitems, rq)->first_group) * group_frames + fs0 : -1);
+            if constexpr (PF && LATE_PF) {
+                rq = cur;
+                request(xr);
+            }
             if constexpr (PF) {
                 if constexpr (PFB == 1) {
                     if (format == SP_FMT_CU4) nonfinite = decode_frame<SP_FMT_CU4, 1>(raw_lo, raw_hi, win, re, im, centre);
@@ -749,19 +563,13 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 if (!LATE_PF && xn >= 0) request(xn);           // in flight during this frame's butterflies
             } else {
                 asm volatile("" ::"v"(pf_word));
-                if (a.in_bounds && xn >= 0 && xn < a.x_end) {
+                const BatchItemK nr = item_rec(bitems, rq);
+                if (nr->in_bounds && xn >= 0 && xn < nr->width) {
                     const int lines = (N * a.sample_width + 127) >> 7;
-                    const int64_t nb = (int64_t)frame_start(a.stride, xn) * a.sample_width;
-                    for (int l = tl; l < lines; l += T) pf_word = *(const uint32_t *)(a.bytes + ((nb + (int64_t)l * 128) & ~(int64_t)3));
+                    const int64_t nb = (int64_t)frame_start(nr->stride, xn) * a.sample_width;
+                    for (int l = tl; l < lines; l += T) pf_word = *(const uint32_t *)(nr->bytes + ((nb + (int64_t)l * 128) & ~(int64_t)3));
                 }
-                switch (format) {
-#define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                    SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
-                    SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
-                    SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32)
-#undef SP_CASE
-                default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                }
+                load_frame_item<LOG2N>(format, cr, start, tl, win, re, im, centre);
             }
 
             unsigned tw_off = 0;
@@ -1023,157 +831,55 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 atomicMin(slot, (unsigned long long)__double_as_longlong(mn));
                 atomicMax(slot + 1, (unsigned long long)__double_as_longlong(mx));
             }
-            // Workgroup 0's first wave publishes the request's number once its clearing stores have landed: after its first frame (group 0
-            // is workgroup 0's, and every slot has a frame in a group's first round), when they long have.
-            if (g == 0 && r == 0 && a.first && __builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const LateArgs la = late_args();
-                if (tid == 0) __hip_atomic_store(la->flag, la->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
         }
         drain_x0 = x0;
         gpar ^= 1;
     }
-
-    // ---- end of the workgroup's frames: last write-out and side outputs, the workgroup's share of histograms and dBfs range ----------
-    const LateArgs la = late_args();
-    // requested now, used behind the last barrier: the cell ranges of this thread's histogram outputs and the request's number as
-    // workgroup 0 published it
-    const uint16_t *const cell_g = la->cell_g, *const cell_l = la->cell_l;
-    const int gi_c = tid < a.lut_len ? tid : 0;
-    const int cg_lo = cell_g[gi_c], cg_hi = cell_g[gi_c + 1];
-    int l_lo[2], l_hi[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int gi = tid + u * kThreads;
-        const int l_cb = gi < SP_CB_HIST_SIZE ? SP_CB_HIST_SIZE - 1 - gi : 0;              // bin gi counts level 999 - gi
-        l_lo[u] = cell_l[l_cb];
-        l_hi[u] = cell_l[l_cb + 1];
-    }
-    const unsigned int seen = __hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (HALVES && drain_x0 >= 0 && a.rgba) {
-        // The workgroup's last write-out overlaps nothing.  The first waves of the SIMDs reach it ~7 us before the second ones (config 2;
-        // issue arbitration favours the older wave, s_setprio does not change that - tools/stamps.py) and would wait at the barrier:
-        // each set of four waves meets by itself and writes its own half of the group, 64-byte pieces of the image rows, so half of the
-        // chip's last stores are under way while the second waves still compute.
-        const int half = tid >> 8;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_fetch_add(&s_done[half], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        while (__hip_atomic_load(&s_done[half], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 4u) __builtin_amdgcn_s_sleep(2);
-        // (non-temporal: left in L2, the 64-byte pieces are written back when the kernel ends, +1.2 us instead of -1.1 us; the first
-        // set also taking half of the second set's rows once those are ready: no further gain)
-        drain_rows(drain_x0, 0, 1, half * (group_frames / 2), group_frames / 2, half * (kThreads / 2), kThreads / 2, true);
-    }
-    lds_barrier();
-    if (drain_x0 >= 0 && !(HALVES && a.rgba)) drain(drain_x0, 0, 1);
-    // ---- the workgroup's share of the request's histograms and dBfs range (worker.js:105-113, 124-125, 140-155) ----------------------
-    // No workgroup finishes for the others (that costs the last one three dependent trips to memory, 6 us): every workgroup turns its
-    // own merged cells into histogram counts and adds them to the reply itself, with fire-and-forget atomics the launch's end waits
-    // for anyway.  Workgroup 0 has zeroed the reply's histograms and set its dBfs range to (0, -200) at the start of the request's
-    // first launch and published the request's number behind that (below); everybody checks the number before its first add.
-    {
-        // cells -> prefix sums: every count is a difference of two prefix sums over the cells (sp_host.h Thresholds).  A thread takes
-        // kPer consecutive cells, the workgroup scans the 512 partial sums (in each wave with shuffles, the eight wave totals through
-        // LDS).  The exchange buffers are idle by now and hold the prefix.  (Counts of one workgroup fit 32 bits, as s_cells does.)
-        constexpr int kPer = 3;
-        static_assert(kThreads * kPer >= kMaxCells, "every cell needs a thread");
-        unsigned int *const s_pre = (unsigned int *)(smem + kOffXch);         // [kThreads * kPer + 1]: s_pre[c] = sum of the cells [0, c)
-        unsigned int *const s_part = s_pre + kThreads * kPer + 4;             // [kThreads / 64] wave totals
-        unsigned int v[kPer], run = 0;
-#pragma unroll
-        for (int k = 0; k < kPer; k++) {
-            const int c = tid * kPer + k;
-            v[k] = c < a.cells ? s_cells[c] : 0u;
-            run += v[k];
-        }
-        const unsigned int incl = wave_scan_u32(run);
-        if (lane == 63) s_part[tid >> 6] = incl;
+    // the last item's last group and shares; no request number to wait for (sp_plan_execute_batch clears the replies first)
+    if (drain_x0 >= 0) {
         lds_barrier();
-        unsigned int base = incl - run;                                       // sum of the cells below this thread's first
-        {
-            const uint4 p0 = *(const uint4 *)s_part, p1 = *(const uint4 *)(s_part + 4);   // (one batch of reads, not one per wave below)
-            const unsigned int part[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-            const int wave = tid >> 6;
-#pragma unroll
-            for (int w = 0; w < 7; w++) base += w < wave ? part[w] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; k++) {
-            s_pre[tid * kPer + k] = base;
-            base += v[k];
-        }
-        if (tid == kThreads - 1) s_pre[kThreads * kPer] = base;
-        lds_barrier();
-        if (seen != la->seq) {
-            // (never in practice: workgroup 0 - dispatched first: the lowest workgroup number - published the number tens of microseconds
-            // ago.  The wait is bounded: ~2 s of polling end in a trap, i.e. a failed launch, instead of a hung device.)
-            unsigned polls = 0;
-            while (__hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != la->seq) {
-                __builtin_amdgcn_s_sleep(32);
-                if (++polls > (1u << 22)) __builtin_trap();
-            }
-        }
-        const int sp0 = a.cells - 2, sp1 = a.cells - 1;                       // -inf / NaN dB (colour 0, bin 0); +inf dB (last colour, bin 0)
-        const unsigned int n0 = s_pre[sp0 + 1] - s_pre[sp0], n1 = s_pre[sp1 + 1] - s_pre[sp1];
-        unsigned long long *const out_c = la->out_c, *const out_cb = la->out_cb;
-        if (tid < a.lut_len && out_c) {
-            const unsigned int cnt = s_pre[cg_hi] - s_pre[cg_lo] + (tid == 0 ? n0 : 0u) + (tid == a.lut_len - 1 ? n1 : 0u);
-            if (cnt) atomicAdd(&out_c[tid], (unsigned long long)cnt);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int gi = tid + u * kThreads;
-            if (gi < SP_CB_HIST_SIZE && out_cb) {
-                const unsigned int cnt = s_pre[l_hi[u]] - s_pre[l_lo[u]] + (gi == 0 ? n0 + n1 : 0u);
-                if (cnt) atomicAdd(&out_cb[gi], (unsigned long long)cnt);
-            }
-        }
-        // The last group's gauges come behind the adds (two waves, one software log10: ~1 us during which everybody's adds and stores
-        // are on their way), and behind them the workgroup's share of the dBfs range.
-        if (drain_x0 >= 0) side_outputs(drain_x0, gpar ^ 1);
-        lds_barrier();
-        double *const out_mm = la->out_minmax;
-        if (tid < 2 && out_mm) {
-            typedef __attribute__((address_space(1))) double *GlobalF64;
-            if (tid == 0) __builtin_amdgcn_global_atomic_fmin_f64((GlobalF64)&out_mm[0], s_red[0]);
-            else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
-        }
+        drain(drain_x0, 0, 1);
+        side_outputs(drain_x0, gpar ^ 1);
+        batch_flush<kThreads>(a, smem, s_red, item_rec(bitems, cur), tid);
     }
 }
 
-// Per-n launchers, one translation unit each (sp_inst_frames.hip is compiled once per LOG2N).
 template <int L>
-int launch_frames_n(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int prefetch,
-                    int device, hipStream_t stream);
+int launch_frames_batch_n(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int prefetch,
+                          const BatchItem *items, const int32_t *group_item, int device, hipStream_t stream);
 #define SP_DECL(L)                                                                                                              \
     template <>                                                                                                                 \
-    int launch_frames_n<L>(const FrameArgs &, int, const double2 *, int, int, int, int, int, int, hipStream_t);
+    int launch_frames_batch_n<L>(const FrameArgs &, int, const double2 *, int, int, int, int, int, const BatchItem *, const int32_t *, int, \
+                                 hipStream_t);
 SP_DECL(6) SP_DECL(7) SP_DECL(8) SP_DECL(9) SP_DECL(10) SP_DECL(11) SP_DECL(12) SP_DECL(13)
 #undef SP_DECL
 
 #ifdef SP_INST_FRAMES_LOG2N
-// per-device, per-variant opt-in to the full LDS (function attributes belong to the device's code object)
 template <int L, bool C, int P>
-inline int launch_variant(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int device,
-                          hipStream_t stream)
+inline int launch_batch_variant(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups,
+                                const BatchItem *items, const int32_t *group_item, int device, hipStream_t stream)
 {
-    // (contexts of several devices render on different threads: the flags are atomic, and setting the attribute twice is harmless)
     static std::atomic<bool> attr_set[kMaxDevices];
     if (device < 0 || device >= kMaxDevices || !attr_set[device].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void *)k_frames<L, C, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)k_frames_batch<L, C, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return SP_ERR_HIP;
         if (device >= 0 && device < kMaxDevices) attr_set[device].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((k_frames<L, C, P>), dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, a, format, stage_tw, gf, groups);
+    hipLaunchKernelGGL((k_frames_batch<L, C, P>), dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, a, format, stage_tw, gf,
+                       groups, items, group_item);
     return SP_OK;
 }
 
 template <>
-int launch_frames_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups,
-                                   int prefetch, int device, hipStream_t stream)
+int launch_frames_batch_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf,
+                                                int groups, int prefetch, const BatchItem *items, const int32_t *group_item, int device,
+                                                hipStream_t stream)
 {
     constexpr int L = SP_INST_FRAMES_LOG2N;
-#define SP_V(C, P) return launch_variant<L, C, P>(a, format, stage_tw, grid, lds_bytes, gf, groups, device, stream);
+    if constexpr (L > kBatchMaxLog2N) {
+        return SP_ERR_UNSUPPORTED;   // (not instantiated: plan_batch renders these items one by one)
+    } else {
+#define SP_V(C, P) return launch_batch_variant<L, C, P>(a, format, stage_tw, grid, lds_bytes, gf, groups, items, group_item, device, stream);
 #define SP_CH(C)                                                                                              \
     switch (prefetch) {                                                                                       \
     case 8: SP_V(C, 8) case 4: SP_V(C, 4) case 3: SP_V(C, 3) case 2: SP_V(C, 2) case 1: SP_V(C, 1) default: SP_V(C, 0) \
@@ -1181,27 +887,30 @@ int launch_frames_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const 
     if (a.channel_mode) { SP_CH(true) } else { SP_CH(false) }
 #undef SP_V
 #undef SP_CH
+    }
 }
 #endif
 
-// Host-side launch.  Returns SP_OK or SP_ERR_UNSUPPORTED.
-inline int launch_frames(const FrameArgs &a, int format, const double2 *stage_tw, int cu_count, int device, hipStream_t stream)
+// The batch's group size: launch_frames' rule applied to the frames of every item the batch kernel renders (both of its launches).
+inline int batch_group_frames(int n, int64_t total_frames, int cu_count)
 {
-    int prefetch = (a.in_bounds && (a.sample_width <= 4 || a.sample_width == 8)) ? a.sample_width : 0;
-    if (prefetch == 3 && !(a.width >= 2 && frame_start(a.stride, a.width - 1) >= 1)) prefetch = 0;
-    if (!frames_kernel_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2) return SP_ERR_UNSUPPORTED;
-    const int n = a.n;
     int want = 32;
-    while (want > 4 && (a.x_end - a.frame0 + want - 1) / want < 2 * cu_count) want >>= 1;
-    const int gf = group_frames_for(n, want);
-    if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;   // (the write-out splits item numbers with shifts; every n in range gives a power of two)
-    const int groups = (a.x_end - a.frame0 + gf - 1) / gf;
-    const Layout lay = layout(n, a.lut_len, gf);
+    while (want > 4 && (total_frames + want - 1) / want < 2 * (int64_t)cu_count) want >>= 1;
+    return group_frames_for(n, want);
+}
+
+// One launch of k_frames_batch over `groups` groups (the caller's work list: items[], group_item[] on the device).
+inline int launch_frames_batch(const FrameArgs &a, int format, const double2 *stage_tw, int gf, int groups, int prefetch, const BatchItem *items,
+                               const int32_t *group_item, int cu_count, int device, hipStream_t stream)
+{
+    if (!frames_kernel_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2 || groups < 1) return SP_ERR_UNSUPPORTED;
+    if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;
+    const Layout lay = layout(a.n, a.lut_len, gf);
     if (lay.total > 160 * 1024) return SP_ERR_UNSUPPORTED;
     int grid = groups < cu_count ? groups : cu_count;
     grid = (grid + 7) & ~7;
     switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, device, stream);
+#define SP_L(L) case L: return launch_frames_batch_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, items, group_item, device, stream);
         SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)
 #undef SP_L
     default: return SP_ERR_UNSUPPORTED;

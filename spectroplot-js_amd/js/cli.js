@@ -7,6 +7,11 @@
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr]
  *        [--full] --out image.ppm
+ *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
+ *
+ * Batch mode (--out-dir): one image per capture, DIR/<capture's file name>.ppm (or .rgba with --rgba), the same bytes a single-file
+ * run writes for it.  Captures are grouped by format (each file's extension, or --format) and every group is rendered with ONE native
+ * call (renderMany -> sp_render_batch).  --full is for single-file runs.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -15,18 +20,66 @@
  * only the text labels need a canvas.
  */
 const fs = require('fs')
-const { renderSliced, parseFormat, parseFreqRate, HipWorker, composePlot, cmapByName } = require('./index.js')
+const path = require('path')
+const { renderSliced, renderMany, parseFormat, parseFreqRate, HipWorker, composePlot, cmapByName } = require('./index.js')
+
+function writeImage(img, out) {
+    if (out.endsWith('.rgba')) {
+        fs.writeFileSync(out, Buffer.from(img.data.buffer, img.data.byteOffset, img.data.byteLength))
+        return
+    }
+    const rgb = Buffer.alloc(img.width * img.height * 3)
+    for (let p = 0, q = 0; p < img.data.length; p += 4) { rgb[q++] = img.data[p]; rgb[q++] = img.data[p + 1]; rgb[q++] = img.data[p + 2] }
+    fs.writeFileSync(out, Buffer.concat([Buffer.from(`P6\n${img.width} ${img.height}\n255\n`), rgb]))
+}
+
+function readCapture(file) {
+    const bytes = fs.readFileSync(file)
+    return bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength)
+}
+
+// --out-dir: the captures grouped by format, each group in one batch; the option names resolve as the single-file run's do
+function mainBatch(files, opt) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const n = parseInt(opt.n, 10), width = parseInt(opt.width, 10)
+    const resolved = native.namedResolve(String(opt.window), String(opt.cmap))   // lookup rules of lib/utils.js:25-40, with the defaults
+    const cmap = cmapByName(String(opt.cmap))
+    fs.mkdirSync(opt['out-dir'], { recursive: true })
+    const groups = new Map()
+    for (const file of files) {
+        const format = opt.format || parseFormat(file)
+        if (!groups.has(format)) groups.set(format, [])
+        groups.get(format).push(file)
+    }
+    let chain = Promise.resolve()
+    for (const [format, group] of groups) {
+        chain = chain.then(() => renderMany({ buffers: group.map(readCapture), format, n, width, window: resolved.window, cmap,
+            gain: parseFloat(opt.gain), range: parseFloat(opt.range), channelMode: !!opt.channelMode, waterfall: !!opt.waterfall }))
+            .then(imgs => imgs.forEach((img, k) => {
+                const out = path.join(opt['out-dir'], path.basename(group[k]) + (opt.rgba ? '.rgba' : '.ppm'))
+                writeImage(img, out)
+                console.log(`${group[k]}: ${format} -> ${out} (${img.width} x ${img.height}), dBfs ${img.dBfs_min.toFixed(2)} .. ${img.dBfs_max.toFixed(2)}`)
+            }))
+    }
+    return chain
+}
 
 function main(argv) {
     const opt = { n: 512, width: 1024, window: 'blackmanHarris', cmap: 'cube1', gain: 6, range: 30, out: 'spectrogram.ppm' }
     let file = null
+    const files = []
     for (let i = 0; i < argv.length; i++) {
         const a = argv[i]
         if (a === '--waterfall') opt.waterfall = true
         else if (a === '--full') opt.full = true
         else if (a === '--lr') opt.channelMode = true
+        else if (a === '--rgba') opt.rgba = true
         else if (a.startsWith('--')) opt[a.slice(2)] = argv[++i]
-        else file = a
+        else { file = a; files.push(a) }
+    }
+    if (opt['out-dir'] !== undefined) {
+        if (!files.length) { console.error('usage: cli.js <capture> ... --n N --width W [options] --out-dir DIR'); process.exit(2) }
+        return mainBatch(files, opt)
     }
     if (!file) { console.error('usage: cli.js <capture> --n N --width W [options] --out image.ppm'); process.exit(2) }
     const bytes = fs.readFileSync(file)
@@ -46,12 +99,8 @@ function main(argv) {
                 if (opt.out.endsWith('.rgba')) fs.writeFileSync(opt.out, Buffer.from(plot.surface.data.buffer))
                 else fs.writeFileSync(opt.out, plot.surface.toPPM())
                 img = { width: plot.surface.width, height: plot.surface.height, dBfs_min: img.dBfs_min, dBfs_max: img.dBfs_max }
-            } else if (opt.out.endsWith('.rgba')) {
-                fs.writeFileSync(opt.out, Buffer.from(img.data.buffer))
             } else {
-                const rgb = Buffer.alloc(img.width * img.height * 3)
-                for (let p = 0, q = 0; p < img.data.length; p += 4) { rgb[q++] = img.data[p]; rgb[q++] = img.data[p + 1]; rgb[q++] = img.data[p + 2] }
-                fs.writeFileSync(opt.out, Buffer.concat([Buffer.from(`P6\n${img.width} ${img.height}\n255\n`), rgb]))
+                writeImage(img, opt.out)
             }
             console.log(`${file}: ${format}, centre ${fr.freq} Hz, rate ${fr.rate} Hz -> ${opt.out} (${img.width} x ${img.height}), ` +
                 `dBfs ${img.dBfs_min.toFixed(2)} .. ${img.dBfs_max.toFixed(2)}, ${Date.now() - t0} ms`)

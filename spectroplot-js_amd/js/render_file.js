@@ -148,4 +148,52 @@ function stripPlacement(reply, o) {
     return o.waterfall ? [0, o.width - o.sliceWidth - reply.offset, w, h] : [reply.offset, 0, w, h]
 }
 
-module.exports = { renderSliced, stripPlacement }
+/**
+ * Many captures with ONE set of options in one native call (sp_render_batch: one frame-loop launch for all of them).  Names resolve as
+ * renderSliced's evaluated-array path resolves them: the taper from window(name, n) (or a {window, weight} object), the colour map with
+ * its ends forced to black / white (lib/spectroplot.js:1116, 1129-1130).  All buffers share the plan: format, n, taper, colour map,
+ * gain, range and layout - group captures by those first (js/cli.js groups by format).  Each result is shaped as renderSliced's for that
+ * buffer alone (with one worker), byte for byte, plus its gauges.
+ * @param {{buffers: ArrayBuffer[], format: string, n: number, width?: number, widths?: number[], window?: string|{window, weight},
+ *          cmap: number[][], gain?: number, range?: number, channelMode?: boolean, waterfall?: boolean}} o
+ * @param {number} [device] GPU index (default 0)
+ * @returns {Promise<Array<{data: Uint8ClampedArray, width, height, c_hist, cB_hist, dBfs_min, dBfs_max, gauge_mins, gauge_maxs,
+ *          gauge_amps}>>}
+ */
+function renderMany(o, device) {
+    const a = native()
+    if (!o || !Array.isArray(o.buffers)) throw new TypeError('renderMany: buffers must be an array of ArrayBuffers')
+    const n = o.n
+    const widths = o.widths !== undefined ? o.widths : o.buffers.map(() => o.width)
+    if (!Array.isArray(widths) || widths.length !== o.buffers.length) throw new TypeError('renderMany: one width per buffer')
+    widths.forEach((w, k) => {
+        if (typeof w !== 'number' || !Number.isInteger(w) || w < 0) throw new TypeError(`renderMany: width of item ${k} is not a frame count`)
+    })
+    o.buffers.forEach((b, k) => { if (!(b instanceof ArrayBuffer)) throw new TypeError(`renderMany: item ${k} has no ArrayBuffer`) })
+    if (!Array.isArray(o.cmap)) throw new TypeError('renderMany: cmap must be an array of [r, g, b]')
+    const w = typeof o.window === 'object' && o.window ? o.window : a.window(o.window || 'blackmanHarris', n)
+    const cmap = o.cmap.map(c => c.slice())
+    cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                // spectroplot.js:1129-1130
+    const gain = o.gain === undefined ? 6 : o.gain, range = o.range === undefined ? 30 : o.range
+    const fmt = a.parseFormat(o.format)
+    const req = { format: fmt.id, n, windowc: w.window instanceof Float64Array ? w.window : new Float64Array(w.window),
+        block_norm: 1.0 / w.weight, gain, range, lut: packLut(cmap), channelMode: !!o.channelMode, waterfall: !!o.waterfall }
+    // each buffer as renderSliced's one worker gets it: SampleView.slice's whole samples (lib/samples.js:253-258)
+    const items = o.buffers.map((buffer, k) => {
+        const [b0, b1] = a.sliceBounds(buffer.byteLength, fmt.sampleWidth, 0, 1)
+        return { buffer: b0 === 0 && b1 === buffer.byteLength ? buffer : buffer.slice(b0, b1), width: widths[k] }
+    })
+    const handle = a.createContext(device || 0)
+    return new Promise((resolve, reject) => {
+        a.renderBatch(handle, req, items, (err, replies) => {
+            a.destroyContext(handle)
+            if (err) { reject(err); return }
+            resolve(replies.map((r, k) => ({ data: new Uint8ClampedArray(r.rgba), width: o.waterfall ? n : widths[k],
+                height: o.waterfall ? widths[k] : n, c_hist: plainArray(r.c_hist), cB_hist: plainArray(r.cB_hist), dBfs_min: r.dBfs_min,
+                dBfs_max: r.dBfs_max, gauge_mins: new Uint8ClampedArray(r.gauge_mins), gauge_maxs: new Uint8ClampedArray(r.gauge_maxs),
+                gauge_amps: new Uint8ClampedArray(r.gauge_amps) })))
+        })
+    })
+}
+
+module.exports = { renderSliced, renderMany, stripPlacement }

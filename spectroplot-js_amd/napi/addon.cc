@@ -35,6 +35,8 @@
 //       sp_group_render - the caller's sliced render (lib/spectroplot.js:1206-1244) with the strips gathered device to device (RCCL or
 //       peer copies) and merged on the root; the reply is the merged result (rgba = the whole image, gauges [width]) plus
 //       {sliceWidth, members, transport: 'none' | 'rccl' | 'peer'}
+//   renderBatch(handle, req, items, cb) / renderBatchSync(handle, req, items)   req as for render without buffer and width; items =
+//       [{buffer: ArrayBuffer, width}]: sp_render_batch, one reply per item shaped as render's
 // One render at a time per handle: a second render on a handle whose first is still in flight throws (HipWorker serialises its own).
 #include <node_api.h>
 
@@ -576,6 +578,275 @@ napi_value render_async(napi_env env, napi_callback_info info, bool named)
 napi_value Render(napi_env env, napi_callback_info info) { return render_async(env, info, false); }
 napi_value RenderNamed(napi_env env, napi_callback_info info) { return render_async(env, info, true); }
 
+// ---- batches: renderBatch(handle, req, [{buffer, width}], cb) / renderBatchSync(handle, req, items) -------------------------------
+// req is render's request without buffer and width; every item gets its own reply, shaped as render's (sp_render_batch).  Every
+// value is read with its status checked: a missing or non-numeric field throws instead of leaving a stale value behind.
+struct BatchJob {
+    Ctx *owner = nullptr;
+    sp_request req{};
+    std::vector<double> window;
+    std::vector<uint8_t> lut;
+    std::vector<Job *> items;
+    int status = SP_OK;
+    std::string error;
+    napi_async_work work = nullptr;
+    napi_ref cb_ref = nullptr, ctx_ref = nullptr, items_ref = nullptr;
+};
+
+bool checked_number(napi_env env, napi_value obj, const char *name, double *out)
+{
+    napi_value v;
+    napi_valuetype t;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok || t != napi_number
+        || napi_get_value_double(env, v, out) != napi_ok) {
+        napi_throw_type_error(env, nullptr, (std::string(name) + " must be a number").c_str());
+        return false;
+    }
+    return true;
+}
+
+bool checked_int32(napi_env env, napi_value obj, const char *name, int32_t *out)
+{
+    double d = 0;
+    if (!checked_number(env, obj, name, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0) || d != (double)(int32_t)d) {
+        napi_throw_range_error(env, nullptr, (std::string(name) + " must be a 32-bit integer").c_str());
+        return false;
+    }
+    *out = (int32_t)d;
+    return true;
+}
+
+bool checked_bool(napi_env env, napi_value obj, const char *name, int32_t *out)
+{
+    napi_value v, b;
+    bool r = false;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok || napi_coerce_to_bool(env, v, &b) != napi_ok
+        || napi_get_value_bool(env, b, &r) != napi_ok) {
+        napi_throw_type_error(env, nullptr, (std::string(name) + " must be a boolean").c_str());
+        return false;
+    }
+    *out = r ? 1 : 0;
+    return true;
+}
+
+void free_batch(napi_env env, BatchJob *b)
+{
+    for (Job *j : b->items) free_job(env, j);
+    if (b->cb_ref) napi_delete_reference(env, b->cb_ref);
+    if (b->ctx_ref) napi_delete_reference(env, b->ctx_ref);
+    if (b->items_ref) napi_delete_reference(env, b->items_ref);
+    if (b->work) napi_delete_async_work(env, b->work);
+    delete b;
+}
+
+bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value items, BatchJob *b)
+{
+    void *p = nullptr;
+    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
+        napi_throw_type_error(env, nullptr, "context handle expected");
+        return false;
+    }
+    b->owner = (Ctx *)p;
+    if (b->owner->closed || !b->owner->c) {
+        napi_throw_error(env, nullptr, b->owner->g ? "renderBatch takes a context handle, not a group" : "context has been destroyed");
+        return false;
+    }
+    double d = 0;
+    if (!checked_int32(env, req, "format", &b->req.format) || !checked_int32(env, req, "n", &b->req.n)) return false;
+    if (!checked_bool(env, req, "channelMode", &b->req.channel_mode) || !checked_bool(env, req, "waterfall", &b->req.waterfall)) return false;
+    if (!checked_number(env, req, "block_norm", &b->req.block_norm) || !checked_number(env, req, "gain", &b->req.gain)) return false;
+    if (!checked_number(env, req, "range", &d)) return false;
+    b->req.range = d;
+    napi_value v, ab;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void *data = nullptr;
+    if (napi_get_named_property(env, req, "windowc", &v) != napi_ok
+        || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_float64_array) {
+        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
+        return false;
+    }
+    if (b->req.n > 0 && len < (size_t)b->req.n) {
+        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
+        return false;
+    }
+    b->window.assign((const double *)data, (const double *)data + len);
+    if (napi_get_named_property(env, req, "lut", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
+        || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
+        napi_throw_type_error(env, nullptr, "lut must be a Uint8Array");
+        return false;
+    }
+    b->lut.assign((const uint8_t *)data, (const uint8_t *)data + len);
+    b->req.lut_len = (int32_t)(len / 3);
+    b->req.windowc = b->window.data();
+    b->req.lut_rgb = b->lut.data();
+    bool is_array = false;
+    uint32_t count = 0;
+    if (napi_is_array(env, items, &is_array) != napi_ok || !is_array || napi_get_array_length(env, items, &count) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "items must be an array of {buffer, width}");
+        return false;
+    }
+    for (uint32_t k = 0; k < count; k++) {
+        napi_value it, buf;
+        napi_valuetype t;
+        if (napi_get_element(env, items, k, &it) != napi_ok || napi_typeof(env, it, &t) != napi_ok || t != napi_object) {
+            napi_throw_type_error(env, nullptr, "items must be an array of {buffer, width}");
+            return false;
+        }
+        Job *j = new Job;
+        b->items.push_back(j);
+        j->owner = b->owner;
+        j->ctx = b->owner->c;
+        j->req = b->req;
+        if (!checked_int32(env, it, "width", &j->width)) return false;
+        if (j->width < 0) {
+            napi_throw_range_error(env, nullptr, "width must not be negative");
+            return false;
+        }
+        if (napi_get_named_property(env, it, "buffer", &buf) != napi_ok || napi_get_arraybuffer_info(env, buf, &data, &len) != napi_ok) {
+            napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
+            return false;
+        }
+        j->bytes = (const uint8_t *)data;
+        j->nbytes = len;
+    }
+    return true;
+}
+
+void run_batch(BatchJob *b)
+{
+    std::vector<sp_batch_item> items(b->items.size());
+    for (size_t k = 0; k < b->items.size(); k++) {
+        Job *j = b->items[k];
+        const size_t W = (size_t)j->width, n = (size_t)j->req.n;
+        j->rgba_size = 4 * W * n + 1;
+        j->rgba = (uint8_t *)g_pool.take(j->rgba_size, &j->rgba_pin);
+        j->gmin = (uint8_t *)calloc(W + 1, 1);
+        j->gmax = (uint8_t *)calloc(W + 1, 1);
+        j->gamp = (uint8_t *)calloc(W + 1, 1);
+        j->c_hist.assign(j->req.lut_len > 0 ? (size_t)j->req.lut_len : 0, 0);
+        j->cb_hist.assign(SP_CB_HIST_SIZE, 0);
+        if (!j->rgba || !j->gmin || !j->gmax || !j->gamp) {
+            b->status = SP_ERR_NOMEM;
+            b->error = "out of host memory";
+            return;
+        }
+        sp_batch_item &it = items[k];
+        it.bytes = j->bytes;
+        it.nbytes = j->nbytes;
+        it.width = j->width;
+        it.reply.rgba = j->rgba; it.reply.gauge_mins = j->gmin; it.reply.gauge_maxs = j->gmax; it.reply.gauge_amps = j->gamp;
+        it.reply.c_hist = j->c_hist.data(); it.reply.cb_hist = j->cb_hist.data(); it.reply.dbfs_minmax = j->minmax;
+    }
+    b->status = sp_render_batch(b->owner->c, &b->req, items.data(), (int32_t)items.size());
+    if (b->status != SP_OK) b->error = sp_last_error(b->owner->c);
+}
+
+napi_value batch_result(napi_env env, BatchJob *b)
+{
+    if (b->status != SP_OK) {
+        Job e;
+        e.status = b->status;
+        e.error = b->error;
+        return make_error(env, &e);
+    }
+    napi_value arr;
+    if (napi_create_array_with_length(env, b->items.size(), &arr) != napi_ok) return nullptr;
+    for (size_t k = 0; k < b->items.size(); k++) {
+        napi_value r = make_reply(env, b->items[k]);
+        if (!r || napi_set_element(env, arr, (uint32_t)k, r) != napi_ok) return nullptr;
+    }
+    return arr;
+}
+
+napi_value RenderBatchSync(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 3) {
+        napi_throw_type_error(env, nullptr, "renderBatchSync(handle, request, items)");
+        return nullptr;
+    }
+    BatchJob *b = new BatchJob;
+    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_batch(env, b); return nullptr; }
+    if (b->owner->inflight > 0) {
+        free_batch(env, b);
+        napi_throw_error(env, nullptr, "a render is already in flight on this context");
+        return nullptr;
+    }
+    b->owner->inflight++;
+    run_batch(b);
+    b->owner->inflight--;
+    ctx_release(b->owner);
+    napi_value out = batch_result(env, b);
+    if (b->status != SP_OK) {
+        napi_throw(env, out);
+        out = nullptr;
+    }
+    free_batch(env, b);
+    return out;
+}
+
+void batch_exec_cb(napi_env, void *data) { run_batch((BatchJob *)data); }
+
+void batch_done_cb(napi_env env, napi_status, void *data)
+{
+    BatchJob *b = (BatchJob *)data;
+    b->owner->inflight--;
+    ctx_release(b->owner);
+    napi_value cb, global, argv[2], ignored;
+    napi_get_reference_value(env, b->cb_ref, &cb);
+    napi_get_global(env, &global);
+    if (b->status != SP_OK) {
+        argv[0] = batch_result(env, b);
+        napi_get_undefined(env, &argv[1]);
+    } else {
+        napi_get_null(env, &argv[0]);
+        argv[1] = batch_result(env, b);
+    }
+    napi_call_function(env, global, cb, 2, argv, &ignored);
+    free_batch(env, b);
+}
+
+napi_value RenderBatch(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    napi_valuetype t = napi_undefined;
+    if (argc < 4 || napi_typeof(env, argv[3], &t) != napi_ok || t != napi_function) {
+        napi_throw_type_error(env, nullptr, "renderBatch(handle, request, items, callback)");
+        return nullptr;
+    }
+    BatchJob *b = new BatchJob;
+    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_batch(env, b); return nullptr; }
+    if (b->owner->inflight > 0) {
+        free_batch(env, b);
+        napi_throw_error(env, nullptr, "a render is already in flight on this context");
+        return nullptr;
+    }
+    napi_value name;
+    bool ok = napi_create_reference(env, argv[2], 1, &b->items_ref) == napi_ok;   // the items (and their buffers) stay alive
+    ok = ok && napi_create_reference(env, argv[3], 1, &b->cb_ref) == napi_ok;
+    ok = ok && napi_create_reference(env, argv[0], 1, &b->ctx_ref) == napi_ok;
+    ok = ok && napi_create_string_utf8(env, "spectroplot_hip.renderBatch", NAPI_AUTO_LENGTH, &name) == napi_ok;
+    ok = ok && napi_create_async_work(env, nullptr, name, batch_exec_cb, batch_done_cb, b, &b->work) == napi_ok;
+    if (ok) {
+        b->owner->inflight++;
+        if (napi_queue_async_work(env, b->work) != napi_ok) {
+            b->owner->inflight--;
+            ok = false;
+        }
+    }
+    if (!ok) {
+        free_batch(env, b);
+        napi_throw_error(env, nullptr, "could not queue the batch");
+    }
+    return nullptr;
+}
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -867,6 +1138,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderSync", nullptr, RenderSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderNamed", nullptr, RenderNamed, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderNamedSync", nullptr, RenderNamedSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderBatch", nullptr, RenderBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"createGroup", nullptr, CreateGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
