@@ -1508,7 +1508,7 @@ static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_p
     }
     if (!frames_plan || !spk2::frames_kernel_supports(n) || n > (1 << spk2::kBatchMaxLog2N) || lut_len < 2 || lut_len > spk::kLdsMaxLut)
         return;
-    const int gf = spk2::batch_group_frames(n, total, cu_count);
+    const int gf = spk2::frames_group_frames(n, total, cu_count);
     if ((gf & (gf - 1)) || spk2::layout(n, lut_len, gf).total > 160 * 1024) return;
     w.gf = gf;
     for (int i = 0; i < count; i++) {
@@ -1517,22 +1517,12 @@ static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_p
             w.launch[(size_t)i] = kBatchEmpty;
             continue;
         }
-        // launch_frames: the prefetching loaders need every frame inside the capture, 3-byte samples a frame that starts past sample 0
-        bool pf = w.in_bounds[(size_t)i] && (f.width <= 4 || f.width == 8);
-        if (pf && f.width == 3 && !(W >= 2 && spk::frame_start(w.stride[(size_t)i], W - 1) >= 1)) pf = false;
-        const int l = pf ? kBatchPrefetch : kBatchGeneric;
+        const int l = spk2::frames_prefetch_width(f.width, w.in_bounds[(size_t)i], w.stride[(size_t)i], W) ? kBatchPrefetch : kBatchGeneric;
         w.launch[(size_t)i] = l;
         w.first_group[(size_t)i] = w.groups[l];
         w.group_count[(size_t)i] = (W + gf - 1) / gf;
         w.groups[l] += w.group_count[(size_t)i];
     }
-}
-
-static int batch_grid(int groups, int cu_count)
-{
-    if (groups <= 0) return 0;
-    const int g = groups < cu_count ? groups : cu_count;
-    return (g + 7) & ~7;
 }
 
 extern "C" int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, int32_t cu_count, const size_t *nbytes, const int32_t *widths,
@@ -1545,7 +1535,7 @@ extern "C" int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, i
         if (widths[i] < 0) return SP_ERR_INVALID_ARG;
     BatchWork w;
     plan_batch(spfmt::describe(format), n, lut_len, true, cu_count, nbytes, widths, count, w);
-    std::vector<int64_t> v{w.gf, batch_grid(w.groups[0], cu_count), batch_grid(w.groups[1], cu_count), w.groups[0], w.groups[1]};
+    std::vector<int64_t> v{w.gf, spk2::frames_grid(w.groups[0], cu_count), spk2::frames_grid(w.groups[1], cu_count), w.groups[0], w.groups[1]};
     for (int i = 0; i < count; i++) {
         v.push_back(w.launch[(size_t)i]);
         v.push_back(w.first_group[(size_t)i]);

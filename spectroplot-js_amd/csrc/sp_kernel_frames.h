@@ -37,7 +37,12 @@
 // Measured alternatives (three waves per SIMD, two workgroups per CU, LDS-DMA input, other batch / slice / chain counts) are recorded in
 // DESIGN.md section 6.2; the cost-attribution switches and per-wave clock stamps that produced profiles/ live in
 // tools/experiments/frames_instrumentation.patch (tools/build_variant.sh applies it), not here.
-// k_frames_batch (sp_kernel_frames_batch.h) carries a copy of this frame loop: keep the two in step.
+// The stages this kernel shares with k_frames_batch (sp_kernel_frames_batch.h) are fragment files, sp_frames_*.inc.h, #included inside
+// both kernel bodies.  The inclusion is textual on purpose: the compiler sees the tokens it saw when each kernel spelled the stages out,
+// so neither kernel's code moves (a shared function, even a local alias, moved k_frames' instruction streams).  A fragment's first
+// comment lists the names it expects in scope; an expression that differs between the kernels is a macro (SP_X_END, ...) that each
+// kernel defines around the include.  tests/test_batch_cpu.py compares every k_frames and k_frames_batch instruction stream with a
+// reference build.
 #pragma once
 
 #include <atomic>
@@ -355,57 +360,7 @@ template <int LOG2N, bool CH, int PFB>
 __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, const int format, const double2 *__restrict__ stage_tw,
                                                        const int group_frames, const int groups)
 {
-    constexpr int kThreads = kFrameThreads;   // eight waves, two per SIMD, one workgroup per CU
-    constexpr int N = 1 << LOG2N;
-    constexpr int T = N / 16;                       // threads per frame
-    constexpr int FPB = kThreads / T;               // frames per round
-    constexpr bool BLOCK_SYNC = T > 64;
-    constexpr int TWMAX = frames_tw_max_stage(N);
-    constexpr int NPASS = (LOG2N + 3) / 4;
-    constexpr bool PERMLANE_MID = LOG2N == 13;
-    constexpr bool STAGED = PFB == 0;   // the generic loaders leave no registers for a whole pass's twiddles: read stage by stage
-    // 8-byte samples at n >= 2048: a frame's samples are requested when it starts, not one frame ahead (the prefetch registers of
-    // the next frame were what spilled there: cf32, n = 2048: 411 -> 358 us per 32 768 frames); its partner wave covers the latency
-    // The L/R split at n >= 2048 likewise (its 16 partner values on top of a frame's 32 spill ~32 registers with the prefetch kept): a
-    // spill reload waits for every vector-memory operation issued before it - in-order completion - i.e. for the prefetch itself.
-    // Requested at frame start, 12 spilled registers are left and configs 3 / 5 in channel mode take 12 % less time (1.39 -> 1.22 ms,
-    // 3.41 -> 2.96 ms).  (The taper from L2 per frame instead of registers: no spills at all, and slower than either.)
-    // (8-byte samples with the split at n = 1024: 22 spilled registers -> 0, 90.1 -> 88.0 us at config 2's shape; n = 512: 14 -> 0,
-    // 81.6 -> 77.8 us per 2^24 samples; n = 256, 6 spilled registers, is 2 % faster with the prefetch and keeps it)
-    constexpr bool LATE_PF = ((PFB == 8 || (CH && PFB != 0)) && LOG2N >= 11) || (CH && PFB == 8 && LOG2N >= 9);
-
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Layout lay = layout(N, a.lut_len, group_frames);
-    double *s_xch = (double *)(smem + kOffXch);
-    double2 *s_tw = (double2 *)(smem + lay.off_tw);
-    const double *edge_g = (const double *)(smem + lay.off_gedge);
-    const double *edge_cb = (const double *)(smem + lay.off_cbedge);
-    unsigned long long *s_mm = (unsigned long long *)(smem + lay.off_mm);
-    unsigned char *s_tile = smem + lay.off_tile;
-    unsigned int *const s_lut = (unsigned int *)(smem + kOffLut);
-    unsigned int *const s_cells = (unsigned int *)(smem + kOffCells);
-    [[maybe_unused]] unsigned int *s_done = (unsigned int *)(smem + lay.off_done);
-    double *s_red = (double *)(smem + lay.off_amp);                           // the workgroup's share of dBfs_min / dBfs_max so far
-    double2 *s_amp = (double2 *)(smem + lay.off_amp + 16);                    // [2][group_frames] (I, Q) of sample n/2, by group parity
-
-    // (lds_read_u32 / lds_count address the dynamic LDS block from 0)
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem != 0u) __builtin_trap();
-    const int tid = threadIdx.x;
-    [[maybe_unused]] const int lane = tid & 63;
-    const int fs = tid / T;                         // frame slot within a round
-    const int tl = tid % T;                         // thread within the frame
-    double *xbuf = s_xch + fs * (N + N / 16);
-    constexpr bool COUNTER_SYNC = BLOCK_SYNC && T < kThreads;   // a frame's waves are not the whole workgroup (n = 2048, 4096)
-    FrameMeet<COUNTER_SYNC, BLOCK_SYNC> meet{
-        (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) unsigned int *)(s_done + 2 + fs)),
-        0u, (unsigned)(T / 64)};
-    const int tile_pitch = N + kTilePad;
-    const int cmax = a.lut_len - 1;
-
-    // groups are dealt so that workgroups sharing an XCD (blockIdx % 8) own neighbouring groups
-    const int xcd = blockIdx.x & 7, lane_in_xcd = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-    const int chunk = (groups + 7) >> 3;
-    const int g_end = min(groups, (xcd + 1) * chunk);
+#include "sp_frames_setup.inc.h"
 
     constexpr bool PF = PFB != 0;
     const int sidx_pf = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
@@ -439,32 +394,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     constexpr int MMS = mm_slots(N);
     constexpr bool LATE_SIDE = late_side_outputs(N);
     {
-        // tables -> LDS: every global load is issued before the first LDS store (one memory latency for the prologue)
-        constexpr int WINK = WIN_LDS ? (N + kThreads - 1) / kThreads : 1;
-        double win_r[WINK];
-        if constexpr (WIN_LDS) {
-#pragma unroll
-            for (int k = 0; k < WINK; k++) {
-                const int i = tid + k * kThreads, e = i / T, t = i % T;
-                win_r[k] = i < N ? a.window[rev4(e) * T + (int)(__brev((unsigned)t) >> (32 - (LOG2N - 4)))] : 0.0;
-            }
-        }
-        constexpr int NTW = frames_tw_entries(N);
-        constexpr int TWK = (NTW + kThreads - 1) / kThreads;
-        double2 tw_r[TWK > 0 ? TWK : 1];
-#pragma unroll
-        for (int k = 0; k < TWK; k++) {
-            const int i = tid + k * kThreads;
-            tw_r[k] = i < NTW ? stage_tw[i] : make_double2(0.0, 0.0);
-        }
-        const unsigned int lut_r = tid < a.lut_len ? a.lut_rgba[tid] : 0u;       // lut_len <= 256 < kThreads
-        double cb_r[(SP_CB_HIST_SIZE + kThreads) / kThreads];
-        const double ge_r = tid < a.lut_len ? a.gray_edge[tid] : 0.0;
-#pragma unroll
-        for (int k = 0; k < (SP_CB_HIST_SIZE + kThreads) / kThreads; k++) {
-            const int i = tid + k * kThreads;
-            cb_r[k] = i <= SP_CB_HIST_SIZE ? a.cb_edge[i] : 0.0;
-        }
+#include "sp_frames_table_loads.inc.h"
         // Workgroup 0 of a request's first launch clears the reply's histograms and sets its dBfs range to (0, -200): its first wave
         // alone, so that the wave knows when the stores have landed (publish() below).  Fire-and-forget, behind the table loads.
         if (owner) {
@@ -486,33 +416,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         // them, the wait for the tables - L2 hits - was a wait for the samples from HBM), and unconditionally (a frame past the end is
         // clamped), so that the compiler can count the 16 younger loads in that wait: s_waitcnt vmcnt(16).
         if constexpr (REQ_AFTER_TABLES) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
-        // what needs no table is set up while the loads are in flight (a table load takes ~2.3 us at the start of a launch)
-        for (int i = tid; i < a.cells; i += kThreads) s_cells[i] = 0;
-        if (tid < 8) s_done[tid] = 0;
-        if (tid < 2) s_red[tid] = tid ? -200.0 : 0.0;                             // worker.js:35-36
-        for (int i = tid; i < (LATE_SIDE ? 2 : 1) * group_frames * MMS; i += kThreads) {
-            s_mm[2 * i] = 0x7ff0000000000000ull;
-            s_mm[2 * i + 1] = 0ull;
-        }
-#pragma unroll
-        for (int k = 0; k < TWK; k++) {
-            const int i = tid + k * kThreads;
-            if (i < NTW) s_tw[i] = tw_r[k];
-        }
-        if (tid < a.lut_len) s_lut[tid] = lut_r;
-        if (tid < a.lut_len) ((double *)(smem + lay.off_gedge))[tid] = ge_r;
-#pragma unroll
-        for (int k = 0; k < (SP_CB_HIST_SIZE + kThreads) / kThreads; k++) {
-            const int i = tid + k * kThreads;
-            if (i <= SP_CB_HIST_SIZE) ((double *)(smem + lay.off_cbedge))[i] = cb_r[k];
-        }
-        if constexpr (WIN_LDS) {
-#pragma unroll
-            for (int k = 0; k < WINK; k++) {
-                const int i = tid + k * kThreads;
-                if (i < N) s_win[i] = win_r[k];
-            }
-        }
+#include "sp_frames_table_stores.inc.h"
     }
 
     const double *const wbase = s_win + tl;   // stored as the threads read it: entry e*T + tl = taper[rev4(e)*T + rev(tl)]
@@ -526,29 +430,13 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
 
     const spfmt::View view{a.bytes, a.nbytes, a.nelem};
     uint32_t pf_word = 0;
-    // epilogue constants (sp_host.cpp build_thresholds): t = a + b*log2(|X|^2), already lowered by the margin
-    const float g_a = a.g2_a, g_b = a.g2_b, g_m = a.g2_m;
-    const float c_a = a.c2_a, c_b = a.c2_b, c_m = a.c2_m, c_lo = a.c2_lo, c_hi = a.c2_hi;
-    const float thr = fminf(a.g2_thr, a.c2_thr);
-    // A VALU instruction reads ONE scalar register: with both coefficients of a scale in SGPRs the compiler copies one of them into a
-    // VGPR again for every batch of bins (24 v_mov per frame).  The addends and the upper clamp bound live in VGPRs instead.
-    // (n <= 1024, where registers are left: above, the loop sits at the 256-VGPR limit and three more spill)
-    float g_a_v = g_a, c_a_v = c_a, c_hi_v = c_hi;
-    constexpr bool COEF_VGPR = LOG2N <= 10 && !CH && !(PFB == 8 && LOG2N < 9);
-    if constexpr (COEF_VGPR) asm volatile("" : "+v"(g_a_v), "+v"(c_a_v), "+v"(c_hi_v));
-    // ... and, at n = 1024, both scales of a batch's two bins as packed pairs (below that size the loop measures the same with and
-    // without, and the launch-bound config 1 pays 1 % for the longer set-up: profiles/r05_experiments.txt)
-    constexpr bool PK_SCALES = COEF_VGPR && LOG2N == 10;
-    [[maybe_unused]] f32x2 g_b2 = {g_b, g_b}, g_a2 = {g_a, g_a}, c_b2 = {c_b, c_b}, c_a2 = {c_a, c_a};
-    if constexpr (PK_SCALES) asm volatile("" : "+v"(g_b2), "+v"(g_a2), "+v"(c_b2), "+v"(c_a2));
-    // clamp bounds of the colour value: clipped pixels sit in the middle of the first / last step, far from the risky zone
-    const float g_lo = 0.5f, g_hi = (float)cmax + 0.5f;
-    const int cell_sp0 = a.cells - 2;   // -inf / NaN dB (colour 0, bin 0), +inf dB is the next one (last colour, bin 0)
+#include "sp_frames_epilogue_consts.inc.h"
 
     // Side outputs of a finished group of frames (worker.js:124-136), by the workgroup's first 3 * group_frames threads: gauge_mins and
     // gauge_maxs from the frame's extreme |X|^2 (d is monotone in |X|^2, so the frame's extreme d belong to them), gauge_amps from its
     // raw centre sample: one software log10 per output.  The frame's clamped extremes are also its share of the request's dBfs range
     // (worker.js:124-125): they are folded into the workgroup's; the frame's slots are reset.
+#define SP_X_END a.x_end
     auto side_outputs = [&](const int x0, const int par) {
         if (__builtin_amdgcn_readfirstlane(tid) >= 3 * group_frames) return;   // (wave-uniform: the waves that hold none of those threads)
         const LateArgs la = late_args();
@@ -556,36 +444,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         // wait covers every outstanding vector-memory operation of the wave: the sample prefetch, ~2 us)
         uint8_t *out_min = la->gauge_mins, *out_max = la->gauge_maxs, *out_amp = la->gauge_amps;
         asm volatile("" : "+s"(out_min), "+s"(out_max), "+s"(out_amp));
-        const double gain = la->gain, range = la->range, bn_db = la->block_norm_db;
-        if (tid >= 3 * group_frames) return;
-        const int role = (tid >= group_frames ? 1 : 0) + (tid >= 2 * group_frames ? 1 : 0), f = tid - role * group_frames;
-        double arg;
-        if (role < 2) {
-            unsigned long long ext = role ? 0ull : 0x7ff0000000000000ull;
-#pragma unroll
-            for (int k = 0; k < MMS; k++) {
-                unsigned long long *slot = s_mm + 2 * (((LATE_SIDE ? par : 0) * group_frames + f) * MMS + k) + role;
-                const unsigned long long v = *slot;
-                ext = role ? (v > ext ? v : ext) : (v < ext ? v : ext);
-                *slot = role ? 0ull : 0x7ff0000000000000ull;
-            }
-            arg = __longlong_as_double((long long)ext);
-        } else {
-            const double2 c = s_amp[par * group_frames + f];
-            arg = c.x * c.x + c.y * c.y;                                                       // worker.js:130-131
-        }
-        const double l5 = 5 * spjs::log10(arg);
-        double v;
-        if (role == 2) {
-            v = l5 + gain;
-        } else {
-            const double d = (l5 + bn_db + gain) - gain;                                       // dBfs - gain, worker.js:100
-            v = role ? (d > -200.0 ? d : -200.0) : (d < 0.0 ? d : 0.0);                        // worker.js:82-83, 102-103
-            if (role) lds_max_f64(&s_red[1], v);
-            else lds_min_f64(&s_red[0], v);
-        }
-        uint8_t *const out = role == 0 ? out_min : role == 1 ? out_max : out_amp;
-        if (out && x0 + f < a.x_end) out[x0 + f] = clamp_u8(0.5 + (range + v) * 256 / range);   // worker.js:128-136
+#include "sp_frames_side_outputs.inc.h"
     };
     // write-out of tile rows [f0, f0 + fcount) by the threads [t0, t0 + dthreads), slice `part` of `nparts`
     auto drain_rows = [&](const int x0, const int part, const int nparts, const int f0, const int fcount, const int t0, const int dthreads,
@@ -597,107 +456,9 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         const LateArgs la = late_args();
         uint8_t *const img = la->rgba;
         const int img_width = la->width, img_waterfall = la->waterfall, img_fast = la->rgba_fast;
-        if (img) {
-            if (!img_waterfall) {
-                // spectrogram: image is n rows x width columns; row y holds bin (n/2 - y) mod n            worker.js:90,117
-                // The tile keeps a frame as the epilogue leaves it: 16 bytes per thread, byte e = bin tl + e*T.  A write-out item is
-                // one of a thread's four dwords (bins tl + (4*e4 + j)*T, j = 0..3) of 4 consecutive frames: four 16-byte stores in four
-                // rows; the items of a row segment (8 frame quads) sit in lanes 4 apart, and a wave's dword reads are conflict-free
-                // (tile pitch = 1 dword mod 8).
-                const int quads = fcount / 4;                     // a power of two (launch_frames)
-                const int lq = 31 - __builtin_clz((unsigned)quads);
-                const int items = (N / 4) * quads;
-                for (int it0 = dt + part * 2 * dthreads; it0 < items; it0 += nparts * 2 * dthreads) {
-                    uint32_t gb[2][4];
-                    int i0v[2], xav[2];
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const int it = it0 + u * dthreads;
-                        const int itc = it < items ? it : it0;
-                        const int e4 = itc & 3, fq = (itc >> 2) & (quads - 1), tq = (itc >> 2) >> lq;   // tq: thread of the frame
-                        i0v[u] = tq + 4 * e4 * T;
-                        xav[u] = it < items ? x0 + f0 + fq * 4 : a.x_end;
-#pragma unroll
-                        for (int k = 0; k < 4; k++)
-                            gb[u][k] = *(const uint32_t *)(s_tile + __umul24((unsigned)(f0 + fq * 4), (unsigned)tile_pitch) + k * tile_pitch + tq * 16 + e4 * 4);
-                    }
-                    uint32_t px[2][4][4];
-                    const auto lut_at = [&](unsigned off4) { return lds_read_u32(kOffLut, off4); };
-#pragma unroll
-                    for (int u = 0; u < 2; u++)
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            px[u][0][k] = lut_at(byte_times4<0>(gb[u][k]));
-                            px[u][1][k] = lut_at(byte_times4<1>(gb[u][k]));
-                            px[u][2][k] = lut_at(byte_times4<2>(gb[u][k]));
-                            px[u][3][k] = lut_at(byte_times4<3>(gb[u][k]));
-                        }
-                    if (img_fast) {
-                        // rows are 16-byte aligned, the width is a multiple of 4 and the image is below 4 GiB: 32-bit offsets from the
-                        // uniform base (24-bit multiplies), no per-store checks
-#pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            const int xa = xav[u];
-                            if (xa >= a.x_end) continue;
-                            const unsigned y0 = (unsigned)(N / 2 - i0v[u]) & (N - 1);
-#pragma unroll
-                            for (int j = 0; j < 4; j++) {
-                                const unsigned y = (y0 - (unsigned)(j * T)) & (N - 1);
-                                const unsigned off = (__umul24(y, (unsigned)img_width) + (unsigned)xa) * 4u;
-                                // written once, never read by this kernel: non-temporal where a group's row segments are whole
-                                // 128-byte lines, so that the image does not displace the capture's lines in L2 (measured: 2.5 % of the
-                                // kernel at n = 1024); shorter segments (large n) are pieces of lines that L2 has to merge with the
-                                // neighbouring groups' pieces (non-temporal there doubled the HBM traffic)
-                                store16_at(img, off, px[u][j][0], px[u][j][1], px[u][j][2], px[u][j][3], nt_rows);
-                            }
-                        }
-                        continue;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const int xa = xav[u];
-                        if (xa >= a.x_end) continue;
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const int i = i0v[u] + j * T;
-                            const int y = (N / 2 - i) & (N - 1);
-                            uint8_t *dst = img + ((size_t)y * (size_t)img_width + (size_t)xa) * 4;
-                            if (xa + 3 < a.x_end && (((size_t)dst & 15) == 0)) {
-                                *(uint4 *)dst = make_uint4(px[u][j][0], px[u][j][1], px[u][j][2], px[u][j][3]);
-                            } else {
-#pragma unroll
-                                for (int k = 0; k < 4; k++)
-                                    if (xa + k < a.x_end) ((uint32_t *)dst)[k] = px[u][j][k];
-                            }
-                        }
-                    }
-                }
-            } else {
-                // waterfall: image is width rows x n columns; frame x is row width-1-x, bin i is column (i + n/2 - 1) mod n
-                // An item is one dword of the tile - the colour bytes of bins t + (4*e4 + j)*T, j = 0..3, of one frame - read once and
-                // stored as four pixels T columns apart; consecutive lanes take consecutive t, so each of a wave's four store
-                // instructions covers 64 consecutive pixels of an image row.  (Four consecutive COLUMNS per item - one 16-byte store,
-                // but four byte reads from four tile columns - took 6 ... 14 % more of the kernel than the spectrogram layout.)
-                const int items = fcount * (N / 4);
-                for (int it = dt + part * dthreads; it < items; it += nparts * dthreads) {
-                    const int tq = it % T, e4 = (it / T) & 3, f = f0 + it / (4 * T);
-                    const int xa = x0 + f;
-                    if (xa >= a.x_end) continue;
-                    const uint32_t gb = *(const uint32_t *)(s_tile + f * tile_pitch + tq * 16 + e4 * 4);
-                    // columns (i + n/2 - 1) mod n of bins i = tq + (4*e4 + j)*T: c0 + j*T without a wrap inside an item - except for
-                    // the one item per frame whose first pixel is the row's last (bin n/2): its other three start the row
-                    const int c0 = (tq + 4 * e4 * T + N / 2 - 1) & (N - 1);
-                    uint32_t *const row = (uint32_t *)(img + (size_t)(img_width - 1 - xa) * N * 4);
-                    uint32_t *const p = row + (c0 == N - 1 ? -1 : c0);
-                    const auto lut_at = [&](unsigned off4) { return lds_read_u32(kOffLut, off4); };
-                    __builtin_nontemporal_store(lut_at(byte_times4<0>(gb)), row + c0);
-                    __builtin_nontemporal_store(lut_at(byte_times4<1>(gb)), p + 1 * T);
-                    __builtin_nontemporal_store(lut_at(byte_times4<2>(gb)), p + 2 * T);
-                    __builtin_nontemporal_store(lut_at(byte_times4<3>(gb)), p + 3 * T);
-                }
-            }
-        }
+#include "sp_frames_drain_rows.inc.h"
     };
+#undef SP_X_END
     // non-temporal stores where a group's row pieces are whole 128-byte lines (below)
     auto drain = [&](const int x0, const int part, const int nparts) { drain_rows(x0, part, nparts, 0, group_frames, 0, kThreads, group_frames >= SP_NT_MIN_GROUP); };
     int drain_x0 = -1;
@@ -726,26 +487,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                                                                          : (g + per_xcd < g_end ? a.frame0 + (g + per_xcd) * group_frames + fs0 : -1);
             if constexpr (PF && LATE_PF) request(xr);
             if constexpr (PF) {
-                if constexpr (PFB == 1) {
-                    if (format == SP_FMT_CU4) nonfinite = decode_frame<SP_FMT_CU4, 1>(raw_lo, raw_hi, win, re, im, centre);
-                    else nonfinite = decode_frame<SP_FMT_CS4, 1>(raw_lo, raw_hi, win, re, im, centre);
-                } else if constexpr (PFB == 3) {
-                    if (format == SP_FMT_CU12) nonfinite = decode_frame<SP_FMT_CU12, 1>(raw_lo, raw_hi, win, re, im, centre, 8 * raw_back);
-                    else nonfinite = decode_frame<SP_FMT_CS12, 1>(raw_lo, raw_hi, win, re, im, centre, 8 * raw_back);
-                } else if constexpr (PFB == 2) {
-                    if (format == SP_FMT_CU8) nonfinite = decode_frame<SP_FMT_CU8, 1>(raw_lo, raw_hi, win, re, im, centre);
-                    else nonfinite = decode_frame<SP_FMT_CS8, 1>(raw_lo, raw_hi, win, re, im, centre);
-                } else if constexpr (PFB == 4) {
-                    if (format == SP_FMT_CU16) nonfinite = decode_frame<SP_FMT_CU16, 1>(raw_lo, raw_hi, win, re, im, centre);
-                    else nonfinite = decode_frame<SP_FMT_CS16, 1>(raw_lo, raw_hi, win, re, im, centre);
-                } else {
-                    if (format == SP_FMT_CU32) nonfinite = decode_frame<SP_FMT_CU32, 16>(raw_lo, raw_hi, win, re, im, centre);
-                    else if (format == SP_FMT_CS32) nonfinite = decode_frame<SP_FMT_CS32, 16>(raw_lo, raw_hi, win, re, im, centre);
-                    else {
-                        decode_frame<SP_FMT_CF32, 16>(raw_lo, raw_hi, win, re, im, centre);
-                        nonfinite = raw_f32_nonfinite<16>(raw_lo, raw_hi);
-                    }
-                }
+#include "sp_frames_decode_pf.inc.h"
                 if (!LATE_PF && xn >= 0) request(xn);           // in flight during this frame's butterflies
             } else {
                 asm volatile("" ::"v"(pf_word));
@@ -773,127 +515,9 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 if constexpr (!LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
                 drain(drain_x0, 0, 2);
             }
-            // ---- first pass: literal twiddles ------------------------------------------------------------------------------
-            if constexpr (PFB == 0) {
-                fft_pass1<false>(re, im);            // frames may leave the buffer (NaN samples), 16-byte formats
-            } else if constexpr (PFB == 8) {
-                if (nonfinite) fft_pass1<false>(re, im);
-                else fft_pass1<true>(re, im);
-            } else {
-                fft_pass1<true>(re, im);             // integer samples times a finite taper (sp_api.hip: plan_frames_capable)
-            }
-            if constexpr (NPASS >= 2) {
-                constexpr int WS1 = LOG2N >= 8 ? 4 : LOG2N - 4;
-                constexpr int E1 = LOG2N >= 8 ? 8 : LOG2N;
-                double *const b0 = xbuf + pad_idx(win_pos(tl, 0, 0)), *const b1 = xbuf + pad_idx(win_pos(tl, 0, WS1));
-                PassTw<WS1, 5, STAGED ? 4 : E1, TWMAX> tw1;
-                if constexpr (!STAGED) load_pass_tw(tw1, tl, s_tw, tw);
-                // The first re-distribution never leaves a wave, whatever n: under window 0 as under window [4,8) the 64 threads of a
-                // wave hold exactly the positions [1024 w, 1024 w + 1023] of their frame.  So the waves of a frame (n >= 2048) only
-                // wait, before its first writes, for the partners' last reads of the frame before; between its writes and reads the
-                // LDS's in-order execution of a wave's operations is all that is needed, as at n <= 1024.
-                meet.wait();
-                exchange<0, WS1, false, false>(re, b0, b1);
-                exchange<0, WS1, false, true>(im, b0, b1);
-                exchange_wait(re, im);
-                if constexpr (STAGED) fft_pass_staged<WS1, 5, E1, TWMAX>(re, im, tl, s_tw, tw);
-                else fft_pass<WS1, 5, E1>(re, im, tw1);
-                if constexpr (PERMLANE_MID) {
-                    // n = 8192: the second re-distribution stays inside the wave too - the register transpose of the 1024-point
-                    // layout (window [4,8) -> [6,10) of the wave's block), two stages there, and only then the one re-distribution
-                    // that crosses waves, to window [9,13) for the last three stages.  Four workgroup barriers per frame instead of
-                    // eight; the swaps cost the VALU, which has the time at this size.
-                    PassTw<6, 9, STAGED ? 8 : 10, TWMAX> tw2;
-                    if constexpr (!STAGED) load_pass_tw(tw2, tl, s_tw, tw);
-                    exchange_permlane<10>(re);
-                    exchange_permlane<10>(im);
-                    if constexpr (STAGED) fft_pass_staged<6, 9, 10, TWMAX>(re, im, tl, s_tw, tw);
-                    else fft_pass<6, 9, 10>(re, im, tw2);
-                    constexpr int WS3 = LOG2N - 4;
-                    double *const b2 = xbuf + pad_idx(win_pos(tl, 0, 6)), *const b3 = xbuf + pad_idx(win_pos(tl, 0, WS3));
-                    PassTw<WS3, 11, STAGED ? 10 : LOG2N, TWMAX> tw3;
-                    if constexpr (!STAGED) load_pass_tw(tw3, tl, s_tw, tw);
-                    exchange<6, WS3, BLOCK_SYNC, false, decltype(meet) &, false>(re, b2, b3, meet);
-                    exchange<6, WS3, BLOCK_SYNC, true>(im, b2, b3, meet);
-                    exchange_wait(re, im);
-                    if constexpr (STAGED) fft_pass_staged<WS3, 11, LOG2N, TWMAX>(re, im, tl, s_tw, tw);
-                    else fft_pass<WS3, 11, LOG2N>(re, im, tw3);
-                } else if constexpr (NPASS >= 3) {
-                    constexpr int WS2 = LOG2N >= 12 ? 8 : LOG2N - 4;
-                    constexpr int E2 = LOG2N >= 12 ? 12 : LOG2N;
-                    double *const b2 = xbuf + pad_idx(win_pos(tl, 0, WS2));
-                    PassTw<WS2, 9, STAGED ? 8 : E2, TWMAX> tw2;
-                    if constexpr (!STAGED) load_pass_tw(tw2, tl, s_tw, tw);
-                    if constexpr (LOG2N == 9 || LOG2N == 10) {
-                        // two register bits against lane bits 4 / 5: v_permlane16_swap / v_permlane32_swap.  The swaps cost the VALU
-                        // about what the LDS round trip costs the LDS pipe (measured: 1.2 % of the kernel in favour of the swaps)
-                        exchange_permlane<LOG2N>(re);
-                        exchange_permlane<LOG2N>(im);
-                    } else {
-                        // (writes the positions the wave itself read last: no wait before them)
-                        exchange<WS1, WS2, BLOCK_SYNC, false, decltype(meet) &, false>(re, b1, b2, meet);
-                        exchange<WS1, WS2, BLOCK_SYNC, true>(im, b1, b2, meet);
-                        exchange_wait(re, im);
-                    }
-                    if constexpr (STAGED) fft_pass_staged<WS2, 9, E2, TWMAX>(re, im, tl, s_tw, tw);
-                    else fft_pass<WS2, 9, E2>(re, im, tw2);
-                    static_assert(NPASS <= 3, "four passes (n = 8192) take the register-transpose branch above");
-                }
-            }
-            // now register e of thread tl holds bin i = tl + e*T
+#include "sp_frames_fft.inc.h"
 
-            if constexpr (CH) {   // fft_nayuki.js:103-119, partner bin n-i fetched through LDS
-                // (the partner values eight at a time where registers are short, n >= 2048: two LDS waits per component instead of one,
-                // and 16 registers fewer at the frame's register peak)
-                constexpr int PH = LOG2N >= 11 ? 8 : 16;
-                double pp[PH];
-                meet.wait();   // (announced after the last re-distribution's reads)
-#pragma unroll
-                for (int e = 0; e < 16; e++) xbuf[pad_idx(tl + e * T)] = re[e];
-                meet();
-#pragma unroll
-                for (int h = 0; h < 16; h += PH) {
-#pragma unroll
-                    for (int k = 0; k < PH; k++) pp[k] = xbuf[pad_idx((N - (tl + (h + k) * T)) & (N - 1))];
-#pragma unroll
-                    for (int k = 0; k < PH; k++) {
-                        const int e = h + k, i = tl + e * T;
-                        const double orr = re[e];
-                        if (i == 0) {
-                        } else if (i == N / 2) {
-                            re[e] = 0.0;
-                        } else if (i < N / 2) {
-                            re[e] = 0.5 * (orr + pp[k]);
-                        } else {
-                            re[e] = 0.5 * (-pp[k] + orr);
-                        }
-                    }
-                    if (PH < 16) asm volatile("" ::: "memory");   // the second half's reads stay behind the first half's arithmetic
-                }
-                meet();
-#pragma unroll
-                for (int e = 0; e < 16; e++) xbuf[pad_idx(tl + e * T)] = im[e];
-                meet();
-#pragma unroll
-                for (int h = 0; h < 16; h += PH) {
-#pragma unroll
-                    for (int k = 0; k < PH; k++) pp[k] = xbuf[pad_idx((N - (tl + (h + k) * T)) & (N - 1))];
-#pragma unroll
-                    for (int k = 0; k < PH; k++) {
-                        const int e = h + k, i = tl + e * T;
-                        const double oi = im[e];
-                        if (i == 0 || i == N / 2) {
-                            im[e] = 0.0;
-                        } else if (i < N / 2) {
-                            im[e] = 0.5 * (oi - pp[k]);
-                        } else {
-                            im[e] = 0.5 * (pp[k] + oi);
-                        }
-                    }
-                    if (PH < 16) asm volatile("" ::: "memory");
-                }
-                meet.arrive();   // for the next frame's first re-distribution
-            }
+#include "sp_frames_lr_split.inc.h"
 
             if (drain_x0 >= 0) {
                 drain(drain_x0, 1, 2);
@@ -904,125 +528,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 if constexpr (LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
                 drain_x0 = -1;
             }
-            // ---- |X|^2 -> colour index, centi-bel level ---------------------------------------------------------------------
-            // t = a + b*log2((float)|X|^2) in f32 is within the margin m of the real-valued position of |X|^2 on the index
-            // scale (sp_host.cpp); a and the clamp bounds are lowered by m, so floor(t) is exact unless fract(t) >= 1 - 2m.
-            // Lanes past that threshold (and centi-bel values at or beyond the ends of the scale, +-inf and NaN among them, whose
-            // clamp bounds lie past it by construction) take the exact edge compare.
-            // four independent min / max chains: a dependent f64 operation waits several issue slots
-            double mn4[4] = {spjs::inf(), spjs::inf(), spjs::inf(), spjs::inf()}, mx4[4] = {0.0, 0.0, 0.0, 0.0};
-            uint32_t *trow = (uint32_t *)(s_tile + fr * tile_pitch + tl * 16);
-            if (live) {
-                constexpr int EB = 2;   // bins per batch
-                [[maybe_unused]] uint32_t tile_word = 0;          // four colour bytes per tile dword
-                constexpr bool TILE_BYTES = LOG2N >= 10;         // (n <= 512: no gain measured; n = 2048: neutral; n = 8192: -0.6 %)
-                [[maybe_unused]] const unsigned trow_addr = (unsigned)(size_t)(__attribute__((address_space(3))) uint32_t *)trow;
-                // a batch of bins at a time: independent chains for the VALU, one branch per batch, four colour bytes per tile dword
-#pragma unroll
-                for (int q = 0; q < 16 / EB; q++) {
-                    double abs2[EB];
-                    float tg[EB], tc[EB];
-                    int gi[EB], cell[EB];
-                    unsigned cell4[EB];              // 4 * (colour index + level): the byte offset of the pixel's merged cell
-                    float worst = 0.0f;   // largest fractional part of the batch, either scale
-                    // written stage by stage: the four chains are independent, and every step of a chain waits on the one before
-                    float l2[EB];
-#pragma unroll
-                    for (int k = 0; k < EB; k++) abs2[k] = re[EB * q + k] * re[EB * q + k] + im[EB * q + k] * im[EB * q + k];   // worker.js:92
-#pragma unroll
-                    for (int k = 0; k < EB; k++) l2[k] = (float)abs2[k];
-#pragma unroll
-                    for (int k = 0; k < EB; k++) l2[k] = __log2f(l2[k]);
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        mn4[k & 3] = min_raw(mn4[k & 3], abs2[k]);
-                        mx4[k & 3] = max_raw(mx4[k & 3], abs2[k]);
-                    }
-                    if constexpr (PK_SCALES) {
-                        // one v_pk_fma_f32 per scale for the batch's two bins (4.7 issue cycles instead of 2 x 3.5, one instruction
-                        // fewer per bin); each half rounds like v_fma_f32
-                        static_assert(EB == 2, "a packed fma takes the batch's two bins");
-                        const f32x2 lp = {l2[0], l2[1]};
-                        const f32x2 tgp = __builtin_elementwise_fma(g_b2, lp, g_a2), tcp = __builtin_elementwise_fma(c_b2, lp, c_a2);
-                        tg[0] = tgp.x; tg[1] = tgp.y;
-                        tc[0] = tcp.x; tc[1] = tcp.y;
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < EB; k++) {
-                            tg[k] = fmaf(g_b, l2[k], g_a_v);
-                            tc[k] = fmaf(c_b, l2[k], c_a_v);
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        tg[k] = __builtin_amdgcn_fmed3f(tg[k], g_lo, g_hi);
-                        tc[k] = __builtin_amdgcn_fmed3f(tc[k], c_lo, c_hi_v);
-                    }
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        gi[k] = floor_to_int(tg[k]);                                   // colour index
-                        cell[k] = floor_to_int(tc[k]);                                 // level (= 999 - centi-bel bin)
-                    }
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        // (the clamps have turned a NaN into a bound, so the fractional parts are numbers; one threshold, the
-                        // smaller of the two, serves both scales)
-                        worst = fmaxf(fmaxf(worst, __builtin_amdgcn_fractf(tg[k])), __builtin_amdgcn_fractf(tc[k]));   // one v_max3_f32
-                    }
-                    if (__builtin_expect(__ballot(!(worst < thr)) != 0ull, 0)) {
-                        // Rare (one batch in eleven), and nearly always for ONE lane on ONE bin and ONE scale: each (bin, scale) is
-                        // decided on its own - the nearest edge of that scale for every lane (one LDS read, one exact comparison),
-                        // only the risky lanes keep the result (edges: sp_host.h Thresholds) - so a typical visit costs a quarter
-                        // of deciding everything for the whole batch.
-#pragma unroll
-                        for (int k = 0; k < EB; k++) {
-                            const bool rgk = !(__builtin_amdgcn_fractf(tg[k]) < thr), rck = !(__builtin_amdgcn_fractf(tc[k]) < thr);
-                            int lev = cell[k];
-                            if (__ballot(rgk) != 0ull) {
-                                const int r = min(max((int)rintf(tg[k] + g_m), 1), cmax);
-                                const int g = abs2[k] >= edge_g[r] ? r : r - 1;
-                                gi[k] = rgk ? g : gi[k];
-                            }
-                            if (__ballot(rck) != 0ull) {
-                                const int r = min(max((int)rintf(tc[k] + c_m), 1), SP_CB_HIST_SIZE);
-                                const int l = abs2[k] >= edge_cb[r] ? r : r - 1;
-                                // -inf / NaN dB: colour 0; +inf dB: last colour; all three: ToInt32 gives key 0 = bin 0      worker.js:105,111
-                                // (the clamp bounds of the level scale are risky by construction, so these lanes always come here)
-                                // (their cells lie behind the regular ones: the level is set so that colour index + level names them)
-                                const bool dark = !(abs2[k] > 0.0), bright = abs2[k] == spjs::inf();
-                                gi[k] = rck && dark ? 0 : gi[k];
-                                lev = rck ? (dark ? cell_sp0 : bright ? cell_sp0 + 1 - gi[k] : l) : lev;
-                            }
-                            cell[k] = lev;
-                        }
-                    }
-                    // the merged cell's byte offset, 4 * (colour index + level), as ONE instruction (left to the compiler it becomes an
-                    // add on one side of the branch above and a shift on the other)
-#pragma unroll
-                    for (int k = 0; k < EB; k++) asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(cell4[k]) : "v"(gi[k]), "v"(cell[k]));
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        const int e = EB * q + k;                 // compile-time after unrolling
-                        if constexpr (TILE_BYTES) {
-                            // one ds_write_b8 per bin (base + immediate): packing four indices into a dword first costs three
-                            // v_lshl_or_b32 per dword, and every VALU instruction costs what an f64 operation costs; the LDS pipe has room
-                            asm volatile("ds_write_b8 %0, %1 offset:%2" ::"v"(trow_addr), "v"(gi[k]), "n"(e) : "memory");
-                        } else {
-                            tile_word = (e & 3) == 0 ? (uint32_t)gi[k] : tile_word | ((uint32_t)gi[k] << (8 * (e & 3)));
-                            if ((e & 3) == 3) trow[e >> 2] = tile_word;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < EB; k++) {
-                        lds_count(kOffCells, cell4[k]);
-                    }
-                }
-                const double mn = min_raw(min_raw(mn4[0], mn4[1]), min_raw(mn4[2], mn4[3]));
-                const double mx = max_raw(max_raw(mx4[0], mx4[1]), max_raw(mx4[2], mx4[3]));
-                unsigned long long *slot = s_mm + 2 * (((LATE_SIDE ? gpar : 0) * group_frames + fr) * MMS + (tl & (MMS - 1)));
-                atomicMin(slot, (unsigned long long)__double_as_longlong(mn));
-                atomicMax(slot + 1, (unsigned long long)__double_as_longlong(mx));
-            }
+#include "sp_frames_pixels.inc.h"
             // Workgroup 0's first wave publishes the request's number once its clearing stores have landed: after its first frame (group 0
             // is workgroup 0's, and every slot has a frame in a group's first round), when they long have.
             if (g == 0 && r == 0 && a.first && __builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
@@ -1039,17 +545,11 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     const LateArgs la = late_args();
     // requested now, used behind the last barrier: the cell ranges of this thread's histogram outputs and the request's number as
     // workgroup 0 published it
-    const uint16_t *const cell_g = la->cell_g, *const cell_l = la->cell_l;
-    const int gi_c = tid < a.lut_len ? tid : 0;
-    const int cg_lo = cell_g[gi_c], cg_hi = cell_g[gi_c + 1];
-    int l_lo[2], l_hi[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int gi = tid + u * kThreads;
-        const int l_cb = gi < SP_CB_HIST_SIZE ? SP_CB_HIST_SIZE - 1 - gi : 0;              // bin gi counts level 999 - gi
-        l_lo[u] = cell_l[l_cb];
-        l_hi[u] = cell_l[l_cb + 1];
-    }
+#define SP_LUT_LEN a.lut_len
+#define SP_CELLS a.cells
+#define SP_REPLY la
+#define SP_AFTER_CELLS_READ
+#include "sp_frames_hist_ranges.inc.h"
     const unsigned int seen = __hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (HALVES && drain_x0 >= 0 && a.rgba) {
         // The workgroup's last write-out overlaps nothing.  The first waves of the SIMDs reach it ~7 us before the second ones (config 2;
@@ -1079,31 +579,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
         static_assert(kThreads * kPer >= kMaxCells, "every cell needs a thread");
         unsigned int *const s_pre = (unsigned int *)(smem + kOffXch);         // [kThreads * kPer + 1]: s_pre[c] = sum of the cells [0, c)
         unsigned int *const s_part = s_pre + kThreads * kPer + 4;             // [kThreads / 64] wave totals
-        unsigned int v[kPer], run = 0;
-#pragma unroll
-        for (int k = 0; k < kPer; k++) {
-            const int c = tid * kPer + k;
-            v[k] = c < a.cells ? s_cells[c] : 0u;
-            run += v[k];
-        }
-        const unsigned int incl = wave_scan_u32(run);
-        if (lane == 63) s_part[tid >> 6] = incl;
-        lds_barrier();
-        unsigned int base = incl - run;                                       // sum of the cells below this thread's first
-        {
-            const uint4 p0 = *(const uint4 *)s_part, p1 = *(const uint4 *)(s_part + 4);   // (one batch of reads, not one per wave below)
-            const unsigned int part[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-            const int wave = tid >> 6;
-#pragma unroll
-            for (int w = 0; w < 7; w++) base += w < wave ? part[w] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; k++) {
-            s_pre[tid * kPer + k] = base;
-            base += v[k];
-        }
-        if (tid == kThreads - 1) s_pre[kThreads * kPer] = base;
-        lds_barrier();
+#include "sp_frames_hist_scan.inc.h"
         if (seen != la->seq) {
             // (never in practice: workgroup 0 - dispatched first: the lowest workgroup number - published the number tens of microseconds
             // ago.  The wait is bounded: ~2 s of polling end in a trap, i.e. a failed launch, instead of a hung device.)
@@ -1113,21 +589,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 if (++polls > (1u << 22)) __builtin_trap();
             }
         }
-        const int sp0 = a.cells - 2, sp1 = a.cells - 1;                       // -inf / NaN dB (colour 0, bin 0); +inf dB (last colour, bin 0)
-        const unsigned int n0 = s_pre[sp0 + 1] - s_pre[sp0], n1 = s_pre[sp1 + 1] - s_pre[sp1];
-        unsigned long long *const out_c = la->out_c, *const out_cb = la->out_cb;
-        if (tid < a.lut_len && out_c) {
-            const unsigned int cnt = s_pre[cg_hi] - s_pre[cg_lo] + (tid == 0 ? n0 : 0u) + (tid == a.lut_len - 1 ? n1 : 0u);
-            if (cnt) atomicAdd(&out_c[tid], (unsigned long long)cnt);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int gi = tid + u * kThreads;
-            if (gi < SP_CB_HIST_SIZE && out_cb) {
-                const unsigned int cnt = s_pre[l_hi[u]] - s_pre[l_lo[u]] + (gi == 0 ? n0 + n1 : 0u);
-                if (cnt) atomicAdd(&out_cb[gi], (unsigned long long)cnt);
-            }
-        }
+#include "sp_frames_hist_adds.inc.h"
         // The last group's gauges come behind the adds (two waves, one software log10: ~1 us during which everybody's adds and stores
         // are on their way), and behind them the workgroup's share of the dBfs range.
         if (drain_x0 >= 0) side_outputs(drain_x0, gpar ^ 1);
@@ -1139,6 +601,10 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
             else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
         }
     }
+#undef SP_LUT_LEN
+#undef SP_CELLS
+#undef SP_REPLY
+#undef SP_AFTER_CELLS_READ
 }
 
 // Per-n launchers, one translation unit each (sp_inst_frames.hip is compiled once per LOG2N).
@@ -1152,19 +618,19 @@ SP_DECL(6) SP_DECL(7) SP_DECL(8) SP_DECL(9) SP_DECL(10) SP_DECL(11) SP_DECL(12) 
 #undef SP_DECL
 
 #ifdef SP_INST_FRAMES_LOG2N
-// per-device, per-variant opt-in to the full LDS (function attributes belong to the device's code object)
-template <int L, bool C, int P>
-inline int launch_variant(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int device,
-                          hipStream_t stream)
+// One launch of a variant of k_frames or k_frames_batch, behind its per-device opt-in to the full LDS (function attributes belong to the
+// device's code object).  (Contexts of several devices render on different threads: the flags are atomic, and setting the attribute
+// twice is harmless.)
+template <auto Kernel, typename... Args>
+inline int launch_full_lds(int grid, int lds_bytes, int device, hipStream_t stream, const Args &...args)
 {
-    // (contexts of several devices render on different threads: the flags are atomic, and setting the attribute twice is harmless)
     static std::atomic<bool> attr_set[kMaxDevices];
     if (device < 0 || device >= kMaxDevices || !attr_set[device].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void *)k_frames<L, C, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return SP_ERR_HIP;
         if (device >= 0 && device < kMaxDevices) attr_set[device].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((k_frames<L, C, P>), dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, a, format, stage_tw, gf, groups);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, args...);
     return SP_OK;
 }
 
@@ -1173,7 +639,7 @@ int launch_frames_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const 
                                    int prefetch, int device, hipStream_t stream)
 {
     constexpr int L = SP_INST_FRAMES_LOG2N;
-#define SP_V(C, P) return launch_variant<L, C, P>(a, format, stage_tw, grid, lds_bytes, gf, groups, device, stream);
+#define SP_V(C, P) return launch_full_lds<k_frames<L, C, P>>(grid, lds_bytes, device, stream, a, format, stage_tw, gf, groups);
 #define SP_CH(C)                                                                                              \
     switch (prefetch) {                                                                                       \
     case 8: SP_V(C, 8) case 4: SP_V(C, 4) case 3: SP_V(C, 3) case 2: SP_V(C, 2) case 1: SP_V(C, 1) default: SP_V(C, 0) \
@@ -1184,22 +650,42 @@ int launch_frames_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const 
 }
 #endif
 
+// The launch rules of k_frames and k_frames_batch (sp_api.hip's batch plan follows them too).
+// Frames per group for a launch over total_frames frames: 32, or fewer while that leaves less than two groups per CU.
+inline int frames_group_frames(int n, int64_t total_frames, int cu_count)
+{
+    int want = 32;
+    while (want > 4 && (total_frames + want - 1) / want < 2 * (int64_t)cu_count) want >>= 1;
+    return group_frames_for(n, want);
+}
+
+// Workgroups: at most one per CU, a multiple of the eight XCDs.
+inline int frames_grid(int groups, int cu_count)
+{
+    const int g = groups < cu_count ? groups : cu_count;
+    return (g + 7) & ~7;
+}
+
+// The prefetching loader of a capture (its sample width), or 0 for the generic loaders: every frame must lie inside the capture, and
+// with 3-byte samples the last frame must start past sample 0.
+inline int frames_prefetch_width(int sample_width, bool in_bounds, double stride, int width)
+{
+    const int p = in_bounds && (sample_width <= 4 || sample_width == 8) ? sample_width : 0;
+    return p == 3 && !(width >= 2 && frame_start(stride, width - 1) >= 1) ? 0 : p;
+}
+
 // Host-side launch.  Returns SP_OK or SP_ERR_UNSUPPORTED.
 inline int launch_frames(const FrameArgs &a, int format, const double2 *stage_tw, int cu_count, int device, hipStream_t stream)
 {
-    int prefetch = (a.in_bounds && (a.sample_width <= 4 || a.sample_width == 8)) ? a.sample_width : 0;
-    if (prefetch == 3 && !(a.width >= 2 && frame_start(a.stride, a.width - 1) >= 1)) prefetch = 0;
+    const int prefetch = frames_prefetch_width(a.sample_width, a.in_bounds, a.stride, a.width);
     if (!frames_kernel_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2) return SP_ERR_UNSUPPORTED;
     const int n = a.n;
-    int want = 32;
-    while (want > 4 && (a.x_end - a.frame0 + want - 1) / want < 2 * cu_count) want >>= 1;
-    const int gf = group_frames_for(n, want);
+    const int gf = frames_group_frames(n, a.x_end - a.frame0, cu_count);
     if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;   // (the write-out splits item numbers with shifts; every n in range gives a power of two)
     const int groups = (a.x_end - a.frame0 + gf - 1) / gf;
     const Layout lay = layout(n, a.lut_len, gf);
     if (lay.total > 160 * 1024) return SP_ERR_UNSUPPORTED;
-    int grid = groups < cu_count ? groups : cu_count;
-    grid = (grid + 7) & ~7;
+    const int grid = frames_grid(groups, cu_count);
     switch (a.levels) {
 #define SP_L(L) case L: return launch_frames_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, device, stream);
         SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)

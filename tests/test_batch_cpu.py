@@ -171,7 +171,7 @@ def test_batch_kernels_prefetching_iq_variants_use_no_scratch_memory():
     assert seen == 4 * 5           # four sizes x five prefetch widths
 
 
-def _k_frames_streams(objs):
+def _k_frames_streams(objs, prefix="_ZN4spk28k_framesI"):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_lds_reads as c
     out = {}
@@ -180,7 +180,7 @@ def _k_frames_streams(objs):
         for ln in c.disassemble(o):
             h = re.match(r"^[0-9a-f]+ <(.*)>:", ln)
             if h:
-                cur = h.group(1) if h.group(1).startswith("_ZN4spk28k_framesI") else None
+                cur = h.group(1) if h.group(1).startswith(prefix) else None
                 if cur:
                     out[cur] = []
                 continue
@@ -218,5 +218,35 @@ def test_k_frames_instruction_streams_match_the_parent_commit():
         finally:
             git("worktree", "remove", "--force", wt)
     assert len(theirs) == 96 and set(mine) == set(theirs)
+    differ = [k for k in theirs if mine[k] != theirs[k]]
+    assert not differ, differ[:5]
+
+
+def test_k_frames_batch_instruction_streams_match_the_commit_that_added_them():
+    """Every k_frames_batch<L, C, P> of this tree (n = 64 ... 512) has the instruction stream (addresses stripped) of the commit that added
+    sp_kernel_frames_batch.h: sharing the frame loop's stages with k_frames (the sp_frames_*.inc.h fragments) must not move the batch
+    kernel either.  This guards that change only: a later commit that changes k_frames_batch on purpose replaces the reference below with
+    its own parent (HEAD^ of the commit that last touched the batch kernel's loop)."""
+    if shutil.which("git") is None or not os.path.isdir(os.path.join(ROOT, ".git")):
+        pytest.skip("no git history here to build the reference commit from")
+    git = lambda *a: subprocess.run(["git", "-C", ROOT] + list(a), capture_output=True, text=True)  # noqa: E731
+    added = git("log", "--diff-filter=A", "--format=%H", "--", "spectroplot-js_amd/csrc/sp_kernel_frames_batch.h").stdout.split()
+    ref = added[-1] if added else "HEAD"
+    if git("rev-parse", "--verify", "-q", ref).returncode:
+        pytest.skip("the reference commit is not in this clone's history")
+    prefix = "_ZN4spk214k_frames_batchI"
+    mine = _k_frames_streams(_frame_objs(), prefix)
+    with tempfile.TemporaryDirectory() as t:
+        wt = os.path.join(t, "reference")
+        r = git("worktree", "add", "--detach", wt, ref)
+        if r.returncode:
+            pytest.skip("git worktree failed: " + r.stderr[-200:])
+        try:
+            subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(wt, "spectroplot-js_amd")]
+                                  + ["build/frames_%d.o" % lg for lg in range(6, 14)])
+            theirs = _k_frames_streams(sorted(glob.glob(os.path.join(wt, "spectroplot-js_amd", "build", "frames_*.o"))), prefix)
+        finally:
+            git("worktree", "remove", "--force", wt)
+    assert len(theirs) == 48 and set(mine) == set(theirs)
     differ = [k for k in theirs if mine[k] != theirs[k]]
     assert not differ, differ[:5]
