@@ -77,6 +77,20 @@ enum sp_format {
     SP_FMT_CU32, SP_FMT_CS32, SP_FMT_CU64, SP_FMT_CS64, SP_FMT_CF32, SP_FMT_CF64, SP_FMT_COUNT
 };
 
+/*
+ * What a column of a sparse request shows (stride = (sampleCount - n) / (width - 1) of lib/worker.js:50 at 2n or more).
+ * SP_DETECTOR_SAMPLE is the reference: the column's one frame, the samples up to the next column's frame are skipped (worker.js:68-75).
+ * SP_DETECTOR_PEAK is a spectrum analyser's max hold: with M = floor(stride / n) (M = 1 unless width >= 2 and stride is finite and
+ * >= 2n), sub-frame j < M of column x starts j * n samples behind the column's frame p(x) = ~~(0.5 + stride * x) and exists if j == 0 or
+ * p(x) + (j + 1) * n <= sampleCount; every existing sub-frame is tapered, transformed and split like a frame, and per bin the column keeps
+ * the largest |X|^2 of them in order of j (a NaN only if every sub-frame gives NaN: v_max_f64 / fmax).  From that value on the column is
+ * the reference's (worker.js:93-136): colour index, both histograms (one count per pixel), dBfs range, gauge_mins / gauge_maxs;
+ * gauge_amps stays the centre sample of sub-frame 0.  A request with M == 1 is the sample detector, byte for byte and kernel for kernel.
+ * The detector is part of a plan.  Peak plans run through sp_plan_execute, sp_plan_execute_from_host, sp_render, sp_render_strip and
+ * sp_render_named_ex; batches and groups (sp_plan_execute_batch, sp_render_batch, sp_group_render(_ex)) return SP_ERR_UNSUPPORTED.
+ */
+enum sp_detector { SP_DETECTOR_SAMPLE = 0, SP_DETECTOR_PEAK = 1 };
+
 typedef struct sp_context sp_context;
 typedef struct sp_plan sp_plan;
 
@@ -87,7 +101,7 @@ typedef struct sp_request {
     int32_t channel_mode;    /* 0 = I/Q, 1 = L/R split (lib/fft_nayuki.js:103-119) */
     int32_t waterfall;       /* 0 = spectrogram (n rows x width cols), 1 = waterfall (width rows x n cols) */
     int32_t lut_len;         /* colour map entries, 1 .. SP_MAX_LUT */
-    int32_t reserved;
+    int32_t detector;        /* enum sp_detector: 0 = sample (the reference: a column shows one frame), 1 = peak hold (below) */
     double block_norm;       /* 1 / sum(taper) */
     double gain;             /* dB */
     double range;            /* dB, finite and > 0 */
@@ -141,6 +155,12 @@ int sp_cmap_generate(const char *key, int32_t stops, uint8_t *rgb);
 int sp_twiddles(int32_t n, double *cos_table, double *sin_table);
 /* The engine's Math.log10 as restated by this library (exposed so tests can pin it). */
 double sp_js_log10(double x);
+/*
+ * The peak detector's sub-frame rule for a request of this shape (enum sp_detector): *subframes = M, the sub-frames per column (1: the
+ * request is the sample detector's), *last_column_count = how many of them exist in column width - 1 (every other column has all M
+ * whenever M >= 2).  width 0 gives (1, 0).  Either output may be NULL.
+ */
+int sp_peak_subframes(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t *subframes, int32_t *last_column_count);
 
 /* ---- device ------------------------------------------------------------------------------------------- */
 
@@ -204,6 +224,9 @@ typedef struct sp_named_request {
     double gain, range;
 } sp_named_request;
 int sp_render_named(sp_context *ctx, const sp_named_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply);
+/* The same with a detector (enum sp_detector; sp_render_named is detector = SP_DETECTOR_SAMPLE).  The named request's layout is unchanged. */
+int sp_render_named_ex(sp_context *ctx, const sp_named_request *req, int32_t detector, const uint8_t *bytes, size_t nbytes, int32_t width,
+                       const sp_reply *reply);
 /*
  * What the two option names of a named request resolve to (no device needed): the taper's plain name as sp_window takes it, the
  * colour map's key and its entry count (the caller sizes the reply's c_hist with it).  Any output may be NULL.
@@ -357,9 +380,18 @@ int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_batch_item 
 int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, int32_t cu_count, const size_t *nbytes, const int32_t *widths,
                         int32_t count, int64_t *out, size_t capacity, size_t *used);
 
-/* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else). */
+/* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else).
+ * A peak plan answers what its M >= 2 requests take: "frames_peak" (64 <= n <= 1024 and what "frames" asks for) or "scratch_radix2". */
 const char *sp_plan_kernel_name(const sp_plan *plan);
-/* Forces a kernel (tests compare the two device paths): 0 automatic, 1 scratch_radix2, 3 frames (2: removed, SP_ERR_UNSUPPORTED). */
+/*
+ * The same for a request of this shape: a peak plan answers "frames_peak" where k_frames_peak renders it (M >= 2, 64 <= n <= 1024 and
+ * everything "frames" asks for), "scratch_radix2" for its other M >= 2 requests (the portable kernel holds the peak too), and what
+ * sp_plan_kernel_name answers when M == 1.  A sample plan answers sp_plan_kernel_name's.
+ */
+const char *sp_plan_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+/* Forces a kernel (tests compare the two device paths): 0 automatic, 1 scratch_radix2, 3 frames (2: removed, SP_ERR_UNSUPPORTED).
+ * On a peak plan 3 means frames for M == 1 requests and frames_peak for M >= 2 requests where it covers the plan's n (64 ... 1024);
+ * the plan's other M >= 2 requests take scratch_radix2 (sp_plan_kernel_name_for tells). */
 int sp_plan_force_kernel(sp_plan *plan, int32_t which);
 
 /*

@@ -15,6 +15,16 @@ SP_ERR_NOT_POW2 = -2
 SP_ERR_BYTE_LENGTH = -3
 SP_ERR_UNSUPPORTED = -4
 SP_ERR_NO_DEVICE = -5
+SP_ERR_INVALID_ARG = -1
+
+DETECTORS = {"sample": 0, "peak": 1}       # enum sp_detector
+
+
+def detector_id(detector):
+    """enum sp_detector of "sample" / "peak"; anything else is an error here, never a different image."""
+    if detector not in DETECTORS:
+        raise SpectroplotError(SP_ERR_INVALID_ARG, "detector must be 'sample' or 'peak', not %r" % (detector,))
+    return DETECTORS[detector]
 
 
 class SpectroplotError(RuntimeError):
@@ -25,7 +35,7 @@ class SpectroplotError(RuntimeError):
 
 class _Request(C.Structure):
     _fields_ = [("format", C.c_int32), ("n", C.c_int32), ("channel_mode", C.c_int32), ("waterfall", C.c_int32),
-                ("lut_len", C.c_int32), ("reserved", C.c_int32), ("block_norm", C.c_double), ("gain", C.c_double),
+                ("lut_len", C.c_int32), ("detector", C.c_int32), ("block_norm", C.c_double), ("gain", C.c_double),
                 ("range", C.c_double), ("windowc", C.c_void_p), ("lut_rgb", C.c_void_p)]
 
 
@@ -145,6 +155,10 @@ class Library:
         L.sp_plan_execute_batch.argtypes = [vp, C.POINTER(_BatchItem), i32]
         L.sp_render_batch.argtypes = [vp, C.POINTER(_Request), C.POINTER(_BatchItem), i32]
         L.sp_debug_batch_plan.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, sz, C.POINTER(sz)]
+        L.sp_peak_subframes.argtypes = [i32, i32, sz, i32, C.POINTER(i32), C.POINTER(i32)]
+        L.sp_render_named_ex.argtypes = [vp, C.POINTER(_NamedRequest), i32, vp, sz, i32, C.POINTER(_Reply)]
+        L.sp_plan_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_kernel_name_for.argtypes = [vp, sz, i32]
 
     @classmethod
     def get(cls):
@@ -209,6 +223,16 @@ def debug_batch_plan(fmt, n, lut_len, cu_count, nbytes, widths):
     return int(out[0]), (int(out[1]), int(out[2])), (int(out[3]), int(out[4])), out[5:used.value].reshape(-1, 3)
 
 
+def peak_subframes(fmt, n, nbytes, width):
+    """The peak detector's sub-frame rule for a request of this shape (sp_peak_subframes): (M sub-frames per column, how many of them
+    the last column has).  M == 1: the request is the sample detector's."""
+    lib = Library.get()
+    fid = parse_format(fmt)[0] if isinstance(fmt, str) else int(fmt)
+    m, last = C.c_int32(), C.c_int32()
+    lib.check(lib.L.sp_peak_subframes(fid, int(n), int(nbytes), int(width), C.byref(m), C.byref(last)))
+    return m.value, last.value
+
+
 def named_resolve(window, cmap):
     """(taper name as sp_window takes it, colour-map key, entry count) for two option names, defaults included
     (lib/spectroplot.js:238-264, lib/utils.js:25-40)."""
@@ -218,10 +242,10 @@ def named_resolve(window, cmap):
     return w.value.decode(), k.value.decode(), n.value
 
 
-def _make_request(fmt_id, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall):
+def _make_request(fmt_id, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector="sample"):
     windowc = np.ascontiguousarray(windowc, dtype=np.float64)
     lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
-    req = _Request(fmt_id, int(n), int(bool(channel_mode)), int(bool(waterfall)), len(lut), 0, float(block_norm), float(gain),
+    req = _Request(fmt_id, int(n), int(bool(channel_mode)), int(bool(waterfall)), len(lut), detector_id(detector), float(block_norm), float(gain),
                    float(rng), windowc.ctypes.data_as(C.c_void_p), lut.ctypes.data_as(C.c_void_p))
     return req, (windowc, lut)
 
@@ -326,11 +350,12 @@ class Context:
         self._chk(self.lib.L.sp_synth_trinoise(self.h, C.c_void_p(d_ptr), fid, t0, count, seed, step, gshift, amp, namp))
 
     # -- renderFft on host buffers -------------------------------------------------------------------
-    def render(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False):
-        """Same argument meaning as the reference message; returns the reply fields as numpy arrays."""
+    def render(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False, detector="sample"):
+        """Same argument meaning as the reference message; returns the reply fields as numpy arrays.  detector: "sample" (the
+        reference) or "peak" (max hold over the sub-frames between two columns, include/spectroplot_hip.h enum sp_detector)."""
         fid, _ = parse_format(fmt)
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
         W = int(width)
         L = len(keep[1])
         out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
@@ -344,14 +369,15 @@ class Context:
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
-    def render_batch(self, fmt, datas, n, windowc, block_norm, gain, rng, lut, widths, channel_mode=False, waterfall=False):
+    def render_batch(self, fmt, datas, n, windowc, block_norm, gain, rng, lut, widths, channel_mode=False, waterfall=False,
+                     detector="sample"):
         """sp_render_batch: every capture of `datas` (one width each) rendered with ONE plan; a list of dicts shaped as render()'s,
         each byte for byte what render() of that capture alone returns."""
         fid, _ = parse_format(fmt)
         datas = [np.ascontiguousarray(d, dtype=np.uint8) for d in datas]
         if len(widths) != len(datas):
             raise ValueError("one width per capture")
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)   # (peak: refused)
         L = len(keep[1])
         p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         outs, mms = [], []
@@ -374,7 +400,7 @@ class Context:
             out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return outs
 
-    def render_named(self, fmt, data, n, window, cmap, gain, rng, width, channel_mode=False, waterfall=False):
+    def render_named(self, fmt, data, n, window, cmap, gain, rng, width, channel_mode=False, waterfall=False, detector="sample"):
         """The request by option names, as the reference's caller assembles its message (lib/spectroplot.js:1113-1146): the library
         evaluates taper, block_norm and colour map (ends forced) itself and keeps the plan while names and numbers repeat."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -389,7 +415,7 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         rep = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
                      p(out["cB_hist"]), p(mm))
-        self._chk(self.lib.L.sp_render_named(self.h, C.byref(req), p(data), data.size, W, C.byref(rep)))
+        self._chk(self.lib.L.sp_render_named_ex(self.h, C.byref(req), detector_id(detector), p(data), data.size, W, C.byref(rep)))
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
@@ -398,18 +424,19 @@ class Context:
         self._chk(self.lib.L.sp_context_plan_creations(self.h, C.byref(n)))
         return n.value
 
-    def plan(self, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode=False, waterfall=False):
-        return Plan(self, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+    def plan(self, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode=False, waterfall=False, detector="sample"):
+        return Plan(self, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
 
 
 class Plan:
     """Request constants resident on the device; execute() runs the frame loop on device-resident operands."""
 
-    def __init__(self, ctx, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode=False, waterfall=False):
+    def __init__(self, ctx, fmt, n, windowc, block_norm, gain, rng, lut, channel_mode=False, waterfall=False, detector="sample"):
         self.ctx = ctx
+        self.detector = detector
         self.n = int(n)
         self.fid, self.sample_width = parse_format(fmt)
-        req, keep = _make_request(self.fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+        req, keep = _make_request(self.fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
         self.lut_len = len(keep[1])
         h = C.c_void_p()
         ctx._chk(ctx.lib.L.sp_plan_create(ctx.h, C.byref(req), C.byref(h)))
@@ -427,8 +454,12 @@ class Plan:
         except Exception:
             pass
 
-    def kernel_name(self):
-        return self.ctx.lib.L.sp_plan_kernel_name(self.h).decode()
+    def kernel_name(self, nbytes=None, width=None):
+        """The kernel execute() launches; with a request's shape, the one that request takes (a peak plan renders requests with one
+        sub-frame per column through the sample detector's kernels)."""
+        if nbytes is None:
+            return self.ctx.lib.L.sp_plan_kernel_name(self.h).decode()
+        return self.ctx.lib.L.sp_plan_kernel_name_for(self.h, int(nbytes), int(width)).decode()
 
     def force_kernel(self, which):
         self.ctx._chk(self.ctx.lib.L.sp_plan_force_kernel(self.h, {"auto": 0, "scratch": 1, "frames": 3}[which]))
@@ -511,14 +542,14 @@ class Group:
         return a.value, b.value
 
     def render(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False, gather="device",
-               dirty=None):
+               dirty=None, detector="sample"):
         """Same argument meaning as Context.render; the reply is the caller's MERGED result (`rgba` the whole image, histograms and
         dBfs range over all slices, gauges with slice r's at [r * slice_width, (r + 1) * slice_width)).  gather: "device" (strips meet
         in the root's HBM: RCCL / peer copies) or "host" (every member writes its band of the host image over its own link).
         dirty: a byte value the output buffers are pre-filled with (tests: what no slice draws must come back cleared)."""
         fid, _ = parse_format(fmt)
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)   # (peak: refused)
         W = int(width)
         L = len(keep[1])
         out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),

@@ -16,6 +16,7 @@
 #include "../../include/spectroplot_hip.h"
 #include "sp_host.h"
 #include "sp_kernel_frames_batch.h"
+#include "sp_kernel_frames_peak.h"
 #include "sp_kernel_scratch.h"
 #include "sp_synth.h"
 #include "sp_cmap_tables.h"
@@ -177,7 +178,33 @@ int validate_request(sp_context *ctx, const sp_request *r)
     if (!r->windowc || !r->lut_rgb) return fail(ctx, SP_ERR_INVALID_ARG, "windowc / lut_rgb is null");
     if (!(r->range > 0) || !std::isfinite(r->range)) return fail(ctx, SP_ERR_UNSUPPORTED, "range must be finite and > 0");
     if (!std::isfinite(r->gain)) return fail(ctx, SP_ERR_UNSUPPORTED, "gain must be finite");
+    if (r->detector != SP_DETECTOR_SAMPLE && r->detector != SP_DETECTOR_PEAK)
+        return fail(ctx, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
     return SP_OK;
+}
+
+// The peak detector's sub-frame rule (include/spectroplot_hip.h, enum sp_detector) in the reference's arithmetic: M sub-frames per
+// column, how many of them the last column has, and floor(sampleCount), which every sub-frame j >= 1 must end at or before.
+struct PeakShape {
+    int32_t m = 1, last_count = 0;
+    int64_t nsamp = 0;
+};
+
+PeakShape peak_shape(const spfmt::Format &f, int n, size_t nbytes, int32_t width)
+{
+    PeakShape ps;
+    const double sample_count = (double)nbytes / (double)f.width;                 // samples.js:167
+    ps.nsamp = (int64_t)std::floor(sample_count);
+    if (width < 1) return ps;
+    ps.last_count = 1;
+    if (width < 2) return ps;
+    const double stride = (sample_count - (double)n) / (double)(width - 1);       // worker.js:50
+    if (!std::isfinite(stride) || !(stride >= 2.0 * (double)n)) return ps;
+    const double m = std::floor(stride / (double)n);
+    ps.m = m < 2147483647.0 ? (int32_t)m : 2147483647;
+    const int64_t p = spjs::to_int32(0.5 + stride * (double)(width - 1));         // worker.js:72
+    for (int32_t j = 1; j < ps.m && (double)(p + ((int64_t)j + 1) * n) <= sample_count; j++) ps.last_count = j + 1;
+    return ps;
 }
 
 }  // namespace
@@ -242,6 +269,15 @@ extern "C" int sp_twiddles(int32_t n, double *cos_table, double *sin_table)
 }
 
 extern "C" double sp_js_log10(double x) { return spjs::log10(x); }
+
+extern "C" int sp_peak_subframes(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t *subframes, int32_t *last_column_count)
+{
+    if (format < 0 || format >= SP_FMT_COUNT || n < 1 || width < 0) return SP_ERR_INVALID_ARG;
+    const PeakShape ps = peak_shape(spfmt::describe(format), n, nbytes, width);
+    if (subframes) *subframes = ps.m;
+    if (last_column_count) *last_column_count = ps.last_count;
+    return SP_OK;
+}
 
 extern "C" int sp_cmap_count(void) { return spcmap::kCount; }
 
@@ -641,6 +677,15 @@ static int plan_kernel(const sp_plan *plan)
     return 1;
 }
 
+// The kernel of one request of a plan: plan_kernel's, or for a peak plan's request with M >= 2 sub-frames per column 4 = frames_peak
+// where k_frames_peak covers the plan, else 1 (the scratch kernel holds the peak too).  M == 1 is the sample detector: the same kernels.
+static int request_kernel(const sp_plan *plan, int32_t peak_m)
+{
+    const int k = plan_kernel(plan);
+    if (plan->req.detector != SP_DETECTOR_PEAK || peak_m < 2) return k;
+    return k == 3 && spk2::frames_peak_supports(plan->req.n) ? 4 : 1;
+}
+
 extern "C" int sp_plan_force_kernel(sp_plan *plan, int32_t which)
 {
     if (!plan || which < 0 || which > 3) return SP_ERR_INVALID_ARG;
@@ -653,7 +698,18 @@ extern "C" int sp_plan_force_kernel(sp_plan *plan, int32_t which)
 extern "C" const char *sp_plan_kernel_name(const sp_plan *plan)
 {
     if (!plan) return "";
-    switch (plan_kernel(plan)) {
+    switch (request_kernel(plan, 2)) {
+    case 4: return "frames_peak";
+    case 3: return "frames";
+    default: return "scratch_radix2";
+    }
+}
+
+extern "C" const char *sp_plan_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    if (!plan) return "";
+    switch (request_kernel(plan, peak_shape(plan->fmt, plan->req.n, nbytes, width).m)) {
+    case 4: return "frames_peak";
     case 3: return "frames";
     default: return "scratch_radix2";
     }
@@ -767,9 +823,11 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
         }
     }
 
-    const int which = plan_kernel(plan);
+    // the peak detector's sub-frames per column (1: the request is the sample detector's, kernels included)
+    const PeakShape peak = plan->req.detector == SP_DETECTOR_PEAK ? peak_shape(f, n, nbytes, width) : PeakShape{};
+    const int which = request_kernel(plan, peak.m);
     if (src && which != 3) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    int rc = which == 3 ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
+    int rc = which >= 3 ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
     if (rc) return fail(ctx, rc, "workspace: out of device memory");
     int finish_blocks = 3 * ((width + spk::kFinishThreads - 1) / spk::kFinishThreads);   // three roles per 256 frames
     {
@@ -825,21 +883,30 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
                   && (double)width * (double)n * 4.0 <= 4294967296.0;
 
     if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
+    const int32_t peak_nsamp = (int32_t)(peak.nsamp < 2147483647 ? peak.nsamp : 2147483647);
     if (which == 3) {
         rc = spk2::launch_frames(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames launch rejected the configuration");
+    } else if (which == 4) {
+        rc = spk2::launch_frames_peak(a, plan->req.format, plan->d_stage_tw, peak.m, peak_nsamp, ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, "k_frames_peak launch rejected the configuration");
     } else {
         // scratch slabs: one per workgroup, capped at 256 MiB
-        long long blocks = (256ll << 20) / (16ll * n);
+        const bool hold = peak.m >= 2;   // a third slab per workgroup: the largest |X|^2 per bin over the column's sub-frames
+        long long blocks = (256ll << 20) / ((hold ? 24ll : 16ll) * n);
         if (blocks > x_end - x_begin) blocks = x_end - x_begin;
         if (blocks > 4 * ctx->cu_count) blocks = 4 * ctx->cu_count;
         if (blocks < 1) blocks = 1;
-        rc = ctx->scratch.reserve((size_t)blocks * 2 * (size_t)n * sizeof(double));
+        rc = ctx->scratch.reserve((size_t)blocks * (hold ? 3 : 2) * (size_t)n * sizeof(double));
         if (rc) return fail(ctx, rc, "scratch: out of device memory");
         a.scratch = (double *)ctx->scratch.p;
         rc = dispatch_format(plan->req.format, [&](auto F) {
-            if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_radix2<decltype(F)::value, true>), dim3((unsigned)blocks), dim3(spk::kScratchThreads), 0, s, a);
-            else hipLaunchKernelGGL((spk::k_scratch_radix2<decltype(F)::value, false>), dim3((unsigned)blocks), dim3(spk::kScratchThreads), 0, s, a);
+            constexpr int FMT = decltype(F)::value;
+            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
+            if (hold && n >= 4096) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, true, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
+            else if (hold) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, false, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
+            else if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, true, false>), grid, block, 0, s, a, 1, peak_nsamp);
+            else hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, false, false>), grid, block, 0, s, a, 1, peak_nsamp);
             return SP_OK;
         });
         if (rc) return fail(ctx, rc, "bad format");
@@ -851,7 +918,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     }
 
     if (!last) return SP_OK;
-    if (which == 3) {   // k_frames has finished the request itself
+    if (which >= 3) {   // k_frames / k_frames_peak has finished the request itself
         ctx->acc_dirty = false;
         return SP_OK;
     }
@@ -1258,8 +1325,10 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     const spfmt::Format f = spfmt::describe(req->format);
     UploadPlan u;
     // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
-    plan_upload(f, req->n, nbytes, width, plan_kernel(plan) == 3 && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"), device_out || reply->rgba,
-                device_out ? 0 : rgba_bytes, u);
+    // (a peak request with M >= 2 sub-frames per column reads more than half of the capture: the contiguous upload, chunked by columns)
+    const int32_t peak_m = req->detector == SP_DETECTOR_PEAK ? peak_shape(f, req->n, nbytes, width).m : 1;
+    plan_upload(f, req->n, nbytes, width, request_kernel(plan, peak_m) == 3 && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"),
+                device_out || reply->rgba, device_out ? 0 : rgba_bytes, u);
     const int chunks = (int)u.bounds.size() - 1;
     const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
     ctx->last_upload_bytes = u.link_bytes;
@@ -1300,7 +1369,7 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
             size_t need = nbytes;
             if (k + 1 < chunks) {
                 const int64_t last_start = spjs::to_int32(0.5 + u.stride * (double)(x1 - 1));          // worker.js:72
-                need = (size_t)(last_start + req->n) * (size_t)f.width;
+                need = (size_t)(last_start + (int64_t)peak_m * req->n) * (size_t)f.width;   // (the column's last sub-frame)
                 if (need > nbytes) need = nbytes;
             }
             if (need > sent) {
@@ -1407,7 +1476,15 @@ extern "C" int sp_named_resolve(const char *window, const char *cmap, const char
 extern "C" int sp_render_named(sp_context *ctx, const sp_named_request *nr, const uint8_t *bytes, size_t nbytes, int32_t width,
                                const sp_reply *reply)
 {
+    return sp_render_named_ex(ctx, nr, SP_DETECTOR_SAMPLE, bytes, nbytes, width, reply);
+}
+
+extern "C" int sp_render_named_ex(sp_context *ctx, const sp_named_request *nr, int32_t detector, const uint8_t *bytes, size_t nbytes,
+                                  int32_t width, const sp_reply *reply)
+{
     if (!ctx || !nr || !reply) return SP_ERR_INVALID_ARG;
+    if (detector != SP_DETECTOR_SAMPLE && detector != SP_DETECTOR_PEAK)
+        return fail(ctx, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
     if (nr->n < 1 || sphost::log2_exact(nr->n) < 0) return fail(ctx, SP_ERR_NOT_POW2, "Length is not a power of 2");
     if (nr->n > SP_MAX_N) return fail(ctx, SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
     const std::string f = nr->format ? nr->format : "", w = nr->window ? nr->window : "", c = nr->cmap ? nr->cmap : "";
@@ -1445,6 +1522,7 @@ extern "C" int sp_render_named(sp_context *ctx, const sp_named_request *nr, cons
     r.channel_mode = nr->channel_mode;
     r.waterfall = nr->waterfall;
     r.lut_len = (int32_t)(ctx->named_lut.size() / 3);
+    r.detector = detector;
     r.block_norm = ctx->named_block_norm;
     r.gain = nr->gain;
     r.range = nr->range;
@@ -1590,6 +1668,8 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
     if (!plan) return no_context();
     if (count == 0) return SP_OK;
     sp_context *ctx = plan->ctx;
+    if (plan->req.detector != SP_DETECTOR_SAMPLE)
+        return fail(ctx, SP_ERR_UNSUPPORTED, "sp_plan_execute_batch: the peak detector is not supported in batches (render the items one by one)");
     const int n = plan->req.n;
     int rc = batch_check_items(ctx, plan->fmt, n, items, count, true);
     if (rc) return rc;
@@ -1703,6 +1783,8 @@ extern "C" int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_
     if (!ctx) return no_context();
     int rc = validate_request(ctx, req);
     if (rc) return rc;
+    if (req->detector != SP_DETECTOR_SAMPLE)
+        return fail(ctx, SP_ERR_UNSUPPORTED, "sp_render_batch: the peak detector is not supported in batches (render the items one by one)");
     const spfmt::Format f = spfmt::describe(req->format);
     rc = batch_check_items(ctx, f, req->n, items, count, false);
     if (rc) return rc;

@@ -1,6 +1,12 @@
 // Frame-loop fragment: |X|^2 -> colour index and level, the tile byte and the merged-cell count per bin, the frame's extremes.
 // Expects in scope: re, im, tl, fr, live, gpar, group_frames, s_tile, tile_pitch, s_mm, edge_g, edge_cb, cmax, cell_sp0, LOG2N, MMS,
 // LATE_SIDE, and the constants of sp_frames_epilogue_consts.inc.h.
+// SP_ABS2(e): the value bin e of the thread is drawn from; the frame's own |X|^2 unless the including kernel defines it (k_frames_peak:
+// the largest |X|^2 of the column's sub-frames).
+#ifndef SP_ABS2
+#define SP_ABS2(e) (re[e] * re[e] + im[e] * im[e])   // worker.js:92
+#define SP_ABS2_DEFAULT
+#endif
             // ---- |X|^2 -> colour index, centi-bel level ---------------------------------------------------------------------
             // t = a + b*log2((float)|X|^2) in f32 is within the margin m of the real-valued position of |X|^2 on the index
             // scale (sp_host.cpp); a and the clamp bounds are lowered by m, so floor(t) is exact unless fract(t) >= 1 - 2m.
@@ -25,7 +31,7 @@
                     // written stage by stage: the four chains are independent, and every step of a chain waits on the one before
                     float l2[EB];
 #pragma unroll
-                    for (int k = 0; k < EB; k++) abs2[k] = re[EB * q + k] * re[EB * q + k] + im[EB * q + k] * im[EB * q + k];   // worker.js:92
+                    for (int k = 0; k < EB; k++) abs2[k] = SP_ABS2(EB * q + k);
 #pragma unroll
                     for (int k = 0; k < EB; k++) l2[k] = (float)abs2[k];
 #pragma unroll
@@ -120,3 +126,7 @@
                 atomicMin(slot, (unsigned long long)__double_as_longlong(mn));
                 atomicMax(slot + 1, (unsigned long long)__double_as_longlong(mx));
             }
+#ifdef SP_ABS2_DEFAULT
+#undef SP_ABS2
+#undef SP_ABS2_DEFAULT
+#endif

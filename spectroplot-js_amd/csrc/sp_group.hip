@@ -474,6 +474,10 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
     if (req->n > SP_MAX_N) return gfail(g, SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
     if (req->lut_len < 1 || req->lut_len > SP_MAX_LUT) return gfail(g, SP_ERR_UNSUPPORTED, "lut_len must be 1..SP_MAX_LUT");
     if (!req->windowc || !req->lut_rgb) return gfail(g, SP_ERR_INVALID_ARG, "windowc / lut_rgb is null");
+    if (req->detector != SP_DETECTOR_SAMPLE && req->detector != SP_DETECTOR_PEAK)
+        return gfail(g, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
+    // (a slice is its own request with its own stride, hence its own sub-frame count: not built here)
+    if (req->detector != SP_DETECTOR_SAMPLE) return gfail(g, SP_ERR_UNSUPPORTED, "the peak detector is not supported in group renders");
     const int count = (int)g->m.size();
     const spfmt::Format f = spfmt::describe(req->format);
     // the reference constructs its typed view over the whole buffer before it slices (lib/spectroplot.js:1096-1100)

@@ -369,7 +369,8 @@ void ReplyRecord::unpack_gauges(const void *base, const sp_reply &to, size_t at)
 
 bool same_request(const sp_request &q, const std::vector<double> &window, const std::vector<uint8_t> &lut, const sp_request *r)
 {
-    if (q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall || q.lut_len != r->lut_len)
+    if (q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall || q.lut_len != r->lut_len
+        || q.detector != r->detector)
         return false;
     if (memcmp(&q.block_norm, &r->block_norm, 8) || memcmp(&q.gain, &r->gain, 8) || memcmp(&q.range, &r->range, 8)) return false;
     if (window.size() != (size_t)r->n || memcmp(window.data(), r->windowc, sizeof(double) * (size_t)r->n)) return false;

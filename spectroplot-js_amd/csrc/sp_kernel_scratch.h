@@ -60,8 +60,11 @@ __device__ inline void scratch_stages(double *re, double *im, const double *__re
 // WIDE: four stages per barrier (n >= 4096, where every thread still has an item); the narrow instance keeps the plain one-stage
 // loop and its small register footprint (the latency-bound small sizes need the occupancy: n = 32 ran 1.8 x slower in one kernel
 // with the 16-point items).
-template <int FMT, bool WIDE>
-__global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameArgs a)
+// PEAK (the peak detector, include/spectroplot_hip.h enum sp_detector): the workgroup owns a column and loops over its sub-frames -
+// peak_m per column, sub-frame j >= 1 only if it ends at or before sample peak_nsamp = floor(sampleCount) - keeping the largest |X|^2
+// per bin in a third slab (a thread meets the same bins in every sub-frame); the last sub-frame draws the held values.
+template <int FMT, bool WIDE, bool PEAK>
+__global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameArgs a, const int peak_m, const int peak_nsamp)
 {
     __shared__ unsigned int s_c_hist[SP_MAX_LUT];
     __shared__ unsigned int s_cb_hist[SP_CB_HIST_SIZE];
@@ -69,8 +72,9 @@ __global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameA
 
     const int tid = threadIdx.x;
     const int n = a.n;
-    double *re = a.scratch + (size_t)blockIdx.x * 2 * (size_t)n;
+    double *re = a.scratch + (size_t)blockIdx.x * (PEAK ? 3 : 2) * (size_t)n;
     double *im = re + n;
+    [[maybe_unused]] double *hold = im + n;
     const spfmt::View view{a.bytes, a.nbytes, a.nelem};
 
     for (int i = tid; i < a.lut_len; i += kScratchThreads) s_c_hist[i] = 0;
@@ -79,84 +83,107 @@ __global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameA
 
     double blk_mn = spjs::inf(), blk_mx = 0.0;   // thread 0: over this workgroup's frames
     for (int x = a.frame0 + blockIdx.x; x < a.x_end; x += gridDim.x) {
-        const int64_t start = frame_start(a.stride, x);
-
-        // decode + taper, stored in bit-reversed order (fft_nayuki.js:57-69)            worker.js:70-75
-        for (int k = tid; k < n; k += kScratchThreads) {
-            double vi, vq;
-            if (a.in_bounds) {
-                spfmt::sample_fast<FMT>(a.bytes, start + k, vi, vq);
-            } else {
-                vi = spfmt::sample_checked<FMT>(view, start + k, 0);
-                vq = spfmt::sample_checked<FMT>(view, start + k, 1);
-            }
-            const double w = a.window[k];
-            const uint32_t j = a.levels ? bit_reverse((uint32_t)k, a.levels) : 0;
-            re[j] = w * vi;
-            im[j] = w * vq;
+        const int64_t start0 = frame_start(a.stride, x);
+        int subs = 1;   // the column's sub-frames that exist
+        if constexpr (PEAK) {
+            const int64_t c = ((int64_t)peak_nsamp - start0) / n;
+            subs = c < 1 ? 1 : (c > peak_m ? peak_m : (int)c);
         }
-        __syncthreads();
+        double mn = spjs::inf(), mx = 0.0;
+        for (int sub = 0; sub < subs; sub++) {
+            const int64_t start = start0 + (int64_t)sub * n;
 
-        // radix-2 decimation in time, same butterfly arithmetic as fft_nayuki.js:72-88, up to four stages between barriers
-        if constexpr (!WIDE) {
-            for (int s = 1; s <= a.levels; s++) {
-                const int half = 1 << (s - 1);
-                for (int b = tid; b < (n >> 1); b += kScratchThreads) {
-                    const int lowbits = b & (half - 1);
-                    const int j = ((b >> (s - 1)) << s) | lowbits;
-                    const int l = j + half;
-                    const int k = lowbits << (a.levels - s);
-                    const double c = a.cos_t[k], sn = a.sin_t[k];
-                    const double rl = re[l], il = im[l];
-                    const double tpre = rl * c + il * sn;
-                    const double tpim = -rl * sn + il * c;
-                    const double rj = re[j], ij = im[j];
-                    re[l] = rj - tpre;
-                    im[l] = ij - tpim;
-                    re[j] = rj + tpre;
-                    im[j] = ij + tpim;
+            // decode + taper, stored in bit-reversed order (fft_nayuki.js:57-69)            worker.js:70-75
+            for (int k = tid; k < n; k += kScratchThreads) {
+                double vi, vq;
+                if (a.in_bounds) {
+                    spfmt::sample_fast<FMT>(a.bytes, start + k, vi, vq);
+                } else {
+                    vi = spfmt::sample_checked<FMT>(view, start + k, 0);
+                    vq = spfmt::sample_checked<FMT>(view, start + k, 1);
+                }
+                const double w = a.window[k];
+                const uint32_t j = a.levels ? bit_reverse((uint32_t)k, a.levels) : 0;
+                re[j] = w * vi;
+                im[j] = w * vq;
+            }
+            __syncthreads();
+
+            // radix-2 decimation in time, same butterfly arithmetic as fft_nayuki.js:72-88, up to four stages between barriers
+            if constexpr (!WIDE) {
+                for (int s = 1; s <= a.levels; s++) {
+                    const int half = 1 << (s - 1);
+                    for (int b = tid; b < (n >> 1); b += kScratchThreads) {
+                        const int lowbits = b & (half - 1);
+                        const int j = ((b >> (s - 1)) << s) | lowbits;
+                        const int l = j + half;
+                        const int k = lowbits << (a.levels - s);
+                        const double c = a.cos_t[k], sn = a.sin_t[k];
+                        const double rl = re[l], il = im[l];
+                        const double tpre = rl * c + il * sn;
+                        const double tpim = -rl * sn + il * c;
+                        const double rj = re[j], ij = im[j];
+                        re[l] = rj - tpre;
+                        im[l] = ij - tpim;
+                        re[j] = rj + tpre;
+                        im[j] = ij + tpim;
+                    }
+                    __syncthreads();
+                }
+            } else {
+                for (int s = 1; s <= a.levels; s += 4) {
+                    const int left = a.levels - s + 1;
+                    if (left >= 4) scratch_stages<4>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+                    else if (left == 3) scratch_stages<3>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+                    else if (left == 2) scratch_stages<2>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+                    else scratch_stages<1>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+                    __syncthreads();
+                }
+            }
+
+            if (a.channel_mode) {   // fft_nayuki.js:103-119
+                for (int i = 1 + tid; i < (n >> 1); i += kScratchThreads) {
+                    const double ra = re[i], rb = re[n - i], ia = im[i], ib = im[n - i];
+                    re[i] = 0.5 * (ra + rb);
+                    im[i] = 0.5 * (ia - ib);
+                    re[n - i] = 0.5 * (ia + ib);
+                    im[n - i] = 0.5 * (-ra + rb);
+                }
+                if (tid == 0) {
+                    im[0] = 0.0;
+                    re[n >> 1] = 0.0;   // = imag[0], already zeroed in the reference
+                    im[n >> 1] = 0.0;
                 }
                 __syncthreads();
             }
-        } else {
-            for (int s = 1; s <= a.levels; s += 4) {
-                const int left = a.levels - s + 1;
-                if (left >= 4) scratch_stages<4>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                else if (left == 3) scratch_stages<3>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                else if (left == 2) scratch_stages<2>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                else scratch_stages<1>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                __syncthreads();
-            }
-        }
 
-        if (a.channel_mode) {   // fft_nayuki.js:103-119
-            for (int i = 1 + tid; i < (n >> 1); i += kScratchThreads) {
-                const double ra = re[i], rb = re[n - i], ia = im[i], ib = im[n - i];
-                re[i] = 0.5 * (ra + rb);
-                im[i] = 0.5 * (ia - ib);
-                re[n - i] = 0.5 * (ia + ib);
-                im[n - i] = 0.5 * (-ra + rb);
+            if constexpr (PEAK) {
+                if (sub + 1 < subs) {
+                    // held = abs2 of sub-frame 0, then the larger one; a NaN gives way to a number (fmax)
+                    for (int i = tid; i < n; i += kScratchThreads) {
+                        const double r = re[i], q = im[i];
+                        const double abs2 = r * r + q * q;
+                        hold[i] = sub == 0 ? abs2 : fmax(hold[i], abs2);
+                    }
+                    __syncthreads();   // the slab is written again by the next sub-frame
+                    continue;
+                }
             }
-            if (tid == 0) {
-                im[0] = 0.0;
-                re[n >> 1] = 0.0;   // = imag[0], already zeroed in the reference
-                im[n >> 1] = 0.0;
+            // |X|^2 -> indices -> histograms -> RGBA                                          worker.js:85-122
+            for (int i = tid; i < n; i += kScratchThreads) {
+                const double r = re[i], q = im[i];
+                double abs2 = r * r + q * q;
+                if constexpr (PEAK) {
+                    if (sub > 0) abs2 = fmax(hold[i], abs2);
+                }
+                mn = min_nn(mn, abs2);
+                mx = max_nn(mx, abs2);
+                const int gray = gray_exact(a.gray_edge, a.lut_len, abs2);
+                const int bin = cb_bin_exact(a.cb_edge, abs2);
+                atomicAdd(&s_c_hist[gray], 1u);
+                if (bin >= 0) atomicAdd(&s_cb_hist[bin], 1u);
+                if (a.rgba) *(uint32_t *)(a.rgba + pixel_offset(n, a.width, a.waterfall, x, i)) = a.lut_rgba[gray];
             }
-            __syncthreads();
-        }
-
-        // |X|^2 -> indices -> histograms -> RGBA                                          worker.js:85-122
-        double mn = spjs::inf(), mx = 0.0;
-        for (int i = tid; i < n; i += kScratchThreads) {
-            const double r = re[i], q = im[i];
-            const double abs2 = r * r + q * q;
-            mn = min_nn(mn, abs2);
-            mx = max_nn(mx, abs2);
-            const int gray = gray_exact(a.gray_edge, a.lut_len, abs2);
-            const int bin = cb_bin_exact(a.cb_edge, abs2);
-            atomicAdd(&s_c_hist[gray], 1u);
-            if (bin >= 0) atomicAdd(&s_cb_hist[bin], 1u);
-            if (a.rgba) *(uint32_t *)(a.rgba + pixel_offset(n, a.width, a.waterfall, x, i)) = a.lut_rgba[gray];
         }
         for (int off = 32; off > 0; off >>= 1) {
             mn = min_nn(mn, __shfl_xor(mn, off));

@@ -5,7 +5,7 @@
  * (lib/spectroplot.js:1096-1285) without a browser:
  *
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
- *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr]
+ *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
  *        [--full] --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
@@ -54,7 +54,8 @@ function mainBatch(files, opt) {
     let chain = Promise.resolve()
     for (const [format, group] of groups) {
         chain = chain.then(() => renderMany({ buffers: group.map(readCapture), format, n, width, window: resolved.window, cmap,
-            gain: parseFloat(opt.gain), range: parseFloat(opt.range), channelMode: !!opt.channelMode, waterfall: !!opt.waterfall }))
+            gain: parseFloat(opt.gain), range: parseFloat(opt.range), channelMode: !!opt.channelMode, waterfall: !!opt.waterfall,
+            detector: opt.detector }))                                  // (batches refuse 'peak')
             .then(imgs => imgs.forEach((img, k) => {
                 const out = path.join(opt['out-dir'], path.basename(group[k]) + (opt.rgba ? '.rgba' : '.ppm'))
                 writeImage(img, out)
@@ -90,7 +91,8 @@ function main(argv) {
     const t0 = Date.now()
     return renderSliced({ buffer, format, n, width, workers: opt.workers ? parseInt(opt.workers, 10) : HipWorker.deviceCount(),
         // the option names travel as they are: the library resolves them as the reference's caller does (sp_render_named)
-        byName: true, window: String(opt.window), cmap: String(opt.cmap), gain: parseFloat(opt.gain), range: parseFloat(opt.range), channelMode: !!opt.channelMode, waterfall: !!opt.waterfall })
+        byName: true, window: String(opt.window), cmap: String(opt.cmap), gain: parseFloat(opt.gain), range: parseFloat(opt.range), channelMode: !!opt.channelMode, waterfall: !!opt.waterfall,
+        detector: opt.detector })                                       // 'peak': max hold between columns; anything unknown is an error
         .then(img => {
             if (opt.full) {
                 const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())

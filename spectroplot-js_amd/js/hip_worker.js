@@ -50,6 +50,16 @@ function plainArray(t) {
     return a
 }
 
+/**
+ * `detector` of a message or named request -> enum sp_detector: absent / 'sample' = the reference (a column shows one frame), 'peak' =
+ * max hold over the sub-frames up to the next column.  Anything else is an error (status -1), never a different image.
+ */
+function detectorId(d) {
+    if (d === undefined || d === null || d === 'sample') return 0
+    if (d === 'peak') return 1
+    throw Object.assign(new Error(`detector must be 'sample' or 'peak', not ${JSON.stringify(d) || String(d)}`), { status: -1 })
+}
+
 class HipWorker {
     /** @param {{device?: number}} [options] — device index; default: round-robin over the visible GPUs. */
     constructor(options) {
@@ -96,7 +106,7 @@ class HipWorker {
         let buffer = m.buffer
         if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
         return { format: fmt.id, buffer, n, windowc, block_norm: m.block_norm, gain: m.gain, range: m.range,
-            lut: packLut(m.cmap), width: m.width, channelMode: !!m.channelMode, waterfall: !!m.waterfall }
+            lut: packLut(m.cmap), width: m.width, channelMode: !!m.channelMode, waterfall: !!m.waterfall, detector: detectorId(m.detector) }
     }
 
     _wrap(m, r) {
@@ -125,7 +135,7 @@ class HipWorker {
      * `window` and `cmap` with the reference's lookup rules and defaults (lib/utils.js:25-40, lib/spectroplot.js:238-264), evaluates
      * taper, block_norm and the end-forced colour map itself (:1113-1130) and keeps the device tables while names and numbers repeat.
      * @param {{buffer: ArrayBuffer, format: string, window: string, cmap: string, n: number, width: number, gain?: number,
-     *          range?: number, channelMode?: boolean, waterfall?: boolean, offset?: number}} o
+     *          range?: number, channelMode?: boolean, waterfall?: boolean, offset?: number, detector?: 'sample'|'peak'}} o
      * @returns {Promise<object>} the reply, fields as in a worker reply; runs in the instance's request order
      */
     renderNamed(o) {
@@ -145,7 +155,7 @@ class HipWorker {
         if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
         return { format: String(o.format), window: String(o.window === undefined ? '' : o.window), cmap: String(o.cmap === undefined ? '' : o.cmap),
             buffer, n: o.n, width: o.width, gain: o.gain === undefined ? 6 : o.gain, range: o.range === undefined ? 30 : o.range,
-            channelMode: !!o.channelMode, waterfall: !!o.waterfall }
+            channelMode: !!o.channelMode, waterfall: !!o.waterfall, detector: detectorId(o.detector) }
     }
 
     /** Synchronous form of renderNamed (tests). */
@@ -173,6 +183,8 @@ class HipWorker {
 /** A constructor bound to one device, for `workerOrUrl: HipWorker.onDevice(3)`. */
 HipWorker.onDevice = (device) => class extends HipWorker { constructor() { super({ device }) } }
 HipWorker.deviceCount = () => addon().deviceCount()
+/** The peak detector's sub-frame rule for a request's shape (sp_peak_subframes): {subframes: M, lastColumnCount}. */
+HipWorker.peakSubframes = (format, n, nbytes, width) => addon().peakSubframes(addon().parseFormat(String(format)).id, n, nbytes, width)
 /**
  * An ArrayBuffer in page-locked host memory.  A message whose `buffer` is one of these is copied to the GPU at the full rate of
  * the host link (pageable memory goes through the runtime's staging copies at less than half of it); js/render_file.js cuts its
@@ -180,4 +192,4 @@ HipWorker.deviceCount = () => addon().deviceCount()
  */
 HipWorker.allocBuffer = (nbytes) => addon().allocBuffer(nbytes)
 
-module.exports = { HipWorker, packLut, plainArray }
+module.exports = { HipWorker, packLut, plainArray, detectorId }

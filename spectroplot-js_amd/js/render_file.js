@@ -6,7 +6,7 @@
  * Un-rendered columns stay zero, as on the reference's canvas.
  */
 const path = require('path')
-const { HipWorker, packLut, plainArray } = require('./hip_worker.js')
+const { HipWorker, packLut, plainArray, detectorId } = require('./hip_worker.js')
 
 function native() { return require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node')) }
 
@@ -25,6 +25,8 @@ function native() { return require(path.join(__dirname, '..', 'lib', 'spectroplo
  * host buffers), `transport` names what moved the strips ('none' | 'rccl' | 'peer' | 'host'), `transportNote` why it was not the first
  * choice (an RCCL failure ends in peer copies, never in a failed render) and `timings` the phases' milliseconds.  Groups are kept per
  * worker count (renderSliced.closeGroups() releases them).
+ * `detector: 'peak'` (max hold, include/spectroplot_hip.h) goes to every slice on the worker-pool route: a slice is its own request
+ * with its own stride, hence its own sub-frame count M.  `device: true` refuses it (groups do not support the peak detector).
  * With `merge: false` the strips are not copied into one image (`data` is null; `replies` hold them): an image of 2^31 bytes or more -
  * BASELINE config 5 is exactly 2^31 - is beyond what one typed array can hold under Node 12, as it is beyond one canvas.
  * @param {{buffer: ArrayBuffer, format: string, n: number, width: number, workers?: number, window?: string|{window, weight},
@@ -44,6 +46,9 @@ function renderSliced(o, pool) {
     const gain = o.gain === undefined ? 6 : o.gain, range = o.range === undefined ? 30 : o.range
     const fmt = a.parseFormat(o.format)
     const width = o.width, sliceWidth = ~~(width / workers)             // spectroplot.js:1208
+    const detector = o.detector
+    const peak = detectorId(detector) !== 0                             // (an unknown detector throws here, before anything is rendered)
+    if (o.device && peak) throw Object.assign(new Error('renderSliced: device: true does not support the peak detector'), { status: -4 })
     if (o.device) {
         if (byName) throw new Error('renderSliced: device: true takes evaluated arrays (window, cmap), not names')
         return renderOnGroup(a, o, { workers, n, w, block_norm, cmap, gain, range, fmt, width, sliceWidth })
@@ -71,11 +76,11 @@ function renderSliced(o, pool) {
         const k = i % pool.length
         if (byName) {
             jobs.push(pool[k].renderNamed({ buffer: slice, format: o.format, window: o.window, cmap: o.cmap, n, width: sliceWidth,
-                offset: i * sliceWidth, gain, range, channelMode: !!o.channelMode, waterfall: !!o.waterfall }))
+                offset: i * sliceWidth, gain, range, channelMode: !!o.channelMode, waterfall: !!o.waterfall, detector }))
             continue
         }
         const message = { block_norm, gain, range, cmap, n, windowc: w.window, width: sliceWidth, offset: i * sliceWidth,
-            buffer: slice, format: o.format, channelMode: !!o.channelMode, waterfall: !!o.waterfall }
+            buffer: slice, format: o.format, channelMode: !!o.channelMode, waterfall: !!o.waterfall, detector }
         jobs.push(new Promise((resolve, reject) => {
             pending[k].push({ resolve, reject })
             pool[k].postMessage(message, [message.buffer])
@@ -171,6 +176,7 @@ function renderMany(o, device) {
     })
     o.buffers.forEach((b, k) => { if (!(b instanceof ArrayBuffer)) throw new TypeError(`renderMany: item ${k} has no ArrayBuffer`) })
     if (!Array.isArray(o.cmap)) throw new TypeError('renderMany: cmap must be an array of [r, g, b]')
+    if (detectorId(o.detector) !== 0) throw Object.assign(new Error('renderMany: batches do not support the peak detector'), { status: -4 })
     const w = typeof o.window === 'object' && o.window ? o.window : a.window(o.window || 'blackmanHarris', n)
     const cmap = o.cmap.map(c => c.slice())
     cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                // spectroplot.js:1129-1130

@@ -41,6 +41,7 @@
 #include <node_api.h>
 
 #include <chrono>
+#include <cmath>
 
 #include <cstdint>
 #include <cstdlib>
@@ -274,6 +275,33 @@ std::string get_string(napi_env env, napi_value obj, const char *name)
     return out;
 }
 
+// `detector` of a request object: absent / undefined = SP_DETECTOR_SAMPLE; otherwise the number 0 or 1 (the JS layer maps the names).
+// Read with every status checked - anything else throws, so no request ever renders with a value left over from elsewhere.
+bool read_detector(napi_env env, napi_value req, int32_t *out)
+{
+    *out = SP_DETECTOR_SAMPLE;
+    bool has = false;
+    napi_value v;
+    napi_valuetype t;
+    if (napi_has_named_property(env, req, "detector", &has) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "request must be an object");
+        return false;
+    }
+    if (!has) return true;
+    if (napi_get_named_property(env, req, "detector", &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "detector could not be read");
+        return false;
+    }
+    if (t == napi_undefined) return true;
+    double d = -1;
+    if (t != napi_number || napi_get_value_double(env, v, &d) != napi_ok || !(d == SP_DETECTOR_SAMPLE || d == SP_DETECTOR_PEAK)) {
+        napi_throw_range_error(env, nullptr, "detector must be 0 (sample) or 1 (peak)");
+        return false;
+    }
+    *out = (int32_t)d;
+    return true;
+}
+
 bool parse_request(napi_env env, napi_value handle, napi_value req, Job *j, bool named = false)
 {
     void *p = nullptr;
@@ -303,6 +331,7 @@ bool parse_request(napi_env env, napi_value handle, napi_value req, Job *j, bool
     if (j->group && get_string(env, req, "gather") == "host") j->gather = SP_GROUP_GATHER_HOST;
     j->req.channel_mode = get_bool(env, req, "channelMode");
     j->req.waterfall = get_bool(env, req, "waterfall");
+    if (!read_detector(env, req, &j->req.detector)) return false;
     j->req.block_norm = get_double(env, req, "block_norm");
     j->req.gain = get_double(env, req, "gain");
     j->req.range = get_double(env, req, "range");
@@ -400,7 +429,7 @@ void run_job_inner(Job *j)
         nr.waterfall = j->req.waterfall;
         nr.gain = j->req.gain;
         nr.range = j->req.range;
-        j->status = sp_render_named(j->ctx, &nr, j->bytes, j->nbytes, j->width, &r);
+        j->status = sp_render_named_ex(j->ctx, &nr, j->req.detector, j->bytes, j->nbytes, j->width, &r);
     } else {
         j->status = sp_render(j->ctx, &j->req, j->bytes, j->nbytes, j->width, &r);
     }
@@ -655,6 +684,7 @@ bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value ite
     double d = 0;
     if (!checked_int32(env, req, "format", &b->req.format) || !checked_int32(env, req, "n", &b->req.n)) return false;
     if (!checked_bool(env, req, "channelMode", &b->req.channel_mode) || !checked_bool(env, req, "waterfall", &b->req.waterfall)) return false;
+    if (!read_detector(env, req, &b->req.detector)) return false;   // (a peak batch is refused by the library: SP_ERR_UNSUPPORTED)
     if (!checked_number(env, req, "block_norm", &b->req.block_norm) || !checked_number(env, req, "gain", &b->req.gain)) return false;
     if (!checked_number(env, req, "range", &d)) return false;
     b->req.range = d;
@@ -1083,6 +1113,31 @@ napi_value NamedResolve(napi_env env, napi_callback_info info)
     return out;
 }
 
+// peakSubframes(formatId, n, nbytes, width) -> {subframes, lastColumnCount}: sp_peak_subframes, every argument checked
+napi_value PeakSubframes(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4], out, v;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    double a[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; k++) {
+        napi_valuetype t;
+        if (argc < 4 || napi_typeof(env, argv[k], &t) != napi_ok || t != napi_number || napi_get_value_double(env, argv[k], &a[k]) != napi_ok
+            || !(a[k] >= 0 && a[k] <= 9007199254740992.0) || a[k] != std::floor(a[k])) {
+            napi_throw_type_error(env, nullptr, "peakSubframes(formatId, n, nbytes, width): non-negative integers expected");
+            return nullptr;
+        }
+    }
+    if (a[0] > 2147483647.0 || a[1] > 2147483647.0 || a[3] > 2147483647.0) return throw_status(env, SP_ERR_INVALID_ARG, nullptr);
+    int32_t m = 1, last = 0;
+    const int rc = sp_peak_subframes((int32_t)a[0], (int32_t)a[1], (size_t)a[2], (int32_t)a[3], &m, &last);
+    if (rc) return throw_status(env, rc, nullptr);
+    NAPI_OK(env, napi_create_object(env, &out));
+    napi_create_int32(env, m, &v); napi_set_named_property(env, out, "subframes", v);
+    napi_create_int32(env, last, &v); napi_set_named_property(env, out, "lastColumnCount", v);
+    return out;
+}
+
 napi_value PlanCreations(napi_env env, napi_callback_info info)
 {
     size_t argc = 1;
@@ -1141,6 +1196,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderBatch", nullptr, RenderBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"peakSubframes", nullptr, PeakSubframes, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"createGroup", nullptr, CreateGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"destroyGroup", nullptr, DestroyContext, nullptr, nullptr, nullptr, napi_default, nullptr},

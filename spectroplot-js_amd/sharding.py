@@ -197,6 +197,9 @@ def render_sharded_device(plan, d_slice, width, waterfall=False, dst=0, group=No
 
     Returns device tensors: {"image": uint8 [4 * width * n] on dst (None elsewhere), "record": int64 [L + 1000 + 2] merged side outputs
     (every rank), "strip", "gauges": uint8 [3 * slice_width] (this rank's gauge_mins | gauge_maxs | gauge_amps), "slice_width"}."""
+    if getattr(plan, "detector", "sample") != "sample":
+        # (a slice is its own request with its own stride, so its own sub-frame count: not built here, and never rendered as "sample")
+        raise binding.SpectroplotError(binding.SP_ERR_UNSUPPORTED, "render_sharded_device: the peak detector is not supported across ranks")
     ctx, n, L = plan.ctx, plan.n, plan.lut_len
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     dev = d_slice.device

@@ -44,7 +44,8 @@ class HipWorker:
     def render(self, m):
         data = np.frombuffer(m["buffer"], dtype=np.uint8) if not isinstance(m["buffer"], np.ndarray) else m["buffer"]
         r = self.ctx.render(m["format"], data, m["n"], m["windowc"], m["block_norm"], m["gain"], m["range"], _lut_bytes(m["cmap"]),
-                            m["width"], bool(m.get("channelMode")), bool(m.get("waterfall")))
+                            m["width"], bool(m.get("channelMode")), bool(m.get("waterfall")),
+                            detector="sample" if m.get("detector") is None else m["detector"])   # (unknown: SpectroplotError, status -1)
         return {"cB_hist": r["cB_hist"], "c_hist": r["c_hist"], "dBfs_min": r["dBfs_min"], "dBfs_max": r["dBfs_max"],
                 "offset": m.get("offset"), "gauge_mins": r["gauge_mins"], "gauge_maxs": r["gauge_maxs"],
                 "gauge_amps": r["gauge_amps"], "imageData": {"data": r["rgba"]}}
