@@ -453,64 +453,28 @@ def test_pixels_straddling_every_index_edge(pkg, ctx):
     """k_frames decides colour index and centi-bel bin from an f32 value and sends only the lanes within a proven error margin of
     a step to the exact edge tables (sp_host.cpp).  This test puts |X|^2 onto both sides of EVERY step of both scales, a few ulps
     apart: a frame whose only non-zero sample is (x, 0) under a rectangular taper has |X|^2 = x*x in all its bins, exactly, and
-    x runs over the doubles around the square root of every edge.  The edges are located with the oracle's own log10."""
-    import ctypes
+    x runs over the doubles around the square root of every edge.  The edges are located with the oracle's own log10
+    (tests/edgeref.py; tests/test_edges_gpu.py runs the same construction over the rest of the accepted domain and every kernel)."""
+    import edgeref
     n, fmt = 64, "CF64"
-    gain, rng, L = 6.0, 30.0, 256
-    block_norm = 1.0 / n
-    log10 = pyoracle.lib().spo_log10
-    bndb = 10 * log10(block_norm)
-    cmax, color_norm = L - 1, L / -rng
-
-    def gray(a2):
-        u = cmax - (5 * log10(a2) + bndb + gain) * color_norm
-        return int(0.5 + (0 if u < 0 else cmax if u > cmax else u))
-
-    def cbin(a2):
-        v = 0.5 + ((5 * log10(a2) + bndb + gain) - gain) * -10
-        return min(int(v), 999) if v > -1 else -1 if int(v) < 0 else 0
-
-    def edges(f, lo, hi):
-        """smallest doubles in [lo, hi] at which f changes, by bisection over bit patterns (f is monotone there)"""
-        out = []
-        a, b = np.float64(lo).view(np.uint64), np.float64(hi).view(np.uint64)
-
-        def rec(a, fa, b, fb):
-            if fa == fb:
-                return
-            if b - a == 1:
-                out.append(np.uint64(b).view(np.float64))
-                return
-            m = a + (b - a) // 2
-            fm = f(float(np.uint64(m).view(np.float64)))
-            rec(a, fa, m, fm)
-            rec(m, fm, b, fb)
-        rec(int(a), f(float(lo)), int(b), f(float(hi)))
-        return out
-
-    es = edges(gray, 1e-18, 1e5) + edges(cbin, 1e-18, 1e5)
+    ps = edgeref.DEFAULT
+    assert (ps.gain, ps.rng, ps.lut_len, ps.block_norm) == (6.0, 30.0, 256, 1.0 / n)
+    es = edgeref.all_index_edges(ps)
     assert len(es) > 1200
-    xs = []
-    for e in es:
-        r = np.sqrt(np.float64(e))
-        for k in range(-2, 3):
-            xs.append(np.uint64(int(r.view(np.uint64)) + k).view(np.float64))
-    xs = np.array(xs, dtype=np.float64)
-    W = len(xs)
-    cap = np.zeros((W, n, 2), dtype=np.float64)
-    cap[:, 0, 0] = xs
-    data = cap.reshape(-1).view(np.uint8)
+    data, W, xs = edgeref.straddle_capture(es, n, (-2, -1, 0, 1, 2))
+    assert edgeref.straddles(xs, es).all()
     win = np.ones(n, dtype=np.float64)
-    i = np.arange(L)
-    lut = np.stack([i, 255 - i, (i * 7) & 255], axis=1).astype(np.uint8)
-    want = pyoracle.render(fmt, data, n, win, block_norm, gain, rng, lut, W)
+    lut = edgeref.lut(ps.lut_len)
+    want = pyoracle.render(fmt, data, n, win, ps.block_norm, ps.gain, ps.rng, lut, W)
     for kernel in ("frames", "scratch"):
-        got = _plan_render(pkg, ctx, kernel, fmt, data, n, win, block_norm, gain, rng, lut, W, False, False)
+        got = _plan_render(pkg, ctx, kernel, fmt, data, n, win, ps.block_norm, ps.gain, ps.rng, lut, W, False, False)
         assert got is not None and got["kernel"] == {"frames": "frames", "scratch": "scratch_radix2"}[kernel]
-        assert np.array_equal(got["rgba"], want["rgba"]), kernel
+        for k in ("rgba", "gauge_mins", "gauge_maxs", "gauge_amps"):
+            assert np.array_equal(got[k], want[k]), (kernel, k)
         assert np.array_equal(got["c_hist"].astype(np.int64), want["c_hist"]), kernel
         assert np.array_equal(got["cB_hist"].astype(np.int64), want["cB_hist"]), kernel
-        assert np.float64(got["dBfs_min"]).view(np.uint64) == np.float64(want["dBfs_min"]).view(np.uint64), kernel
+        for k in ("dBfs_min", "dBfs_max"):
+            assert np.float64(got[k]).view(np.uint64) == np.float64(want[k]).view(np.uint64), (kernel, k)
     # the squares really fall on both sides of the steps: both colours of most edges occur
     assert len(np.unique(want["rgba"].reshape(-1, 4)[:, 0])) > 250
 
