@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/spectroplot_hip.h"
+#include "sp_geometry.h"
 #include "sp_host.h"
 #include "sp_kernel_frames_batch.h"
 #include "sp_kernel_frames_peak.h"
@@ -71,6 +72,24 @@ struct HostBuffer {
     }
 };
 
+// sp_render_named: the names and numbers of the last request and the arrays built from them (windowc empty: none is remembered - the
+// cached plan came from arrays, or the render failed)
+struct NamedRequest {
+    std::string format, window, cmap;
+    int32_t n = 0, channel_mode = 0, waterfall = 0;
+    double gain = 0, range = 0;   // compared bit by bit
+    std::vector<double> windowc;
+    std::vector<uint8_t> lut;
+    double block_norm = 0;
+    static std::string str(const char *s) { return s ? s : ""; }
+    bool same(const sp_named_request &r) const
+    {
+        return !windowc.empty() && format == str(r.format) && window == str(r.window) && cmap == str(r.cmap) && n == r.n
+               && channel_mode == (r.channel_mode ? 1 : 0) && waterfall == (r.waterfall ? 1 : 0) && !memcmp(&gain, &r.gain, 8)
+               && !memcmp(&range, &r.range, 8);
+    }
+};
+
 }  // namespace
 
 struct sp_context {
@@ -88,16 +107,9 @@ struct sp_context {
     HostBuffer host_small;
     // sp_render's copy streams and events: the image goes back to the host chunk by chunk while later chunks still arrive
     hipStream_t copy_in = nullptr, copy_out = nullptr;
-    static constexpr int kMaxChunks = 6;
-    hipEvent_t ev_arrived[kMaxChunks] = {}, ev_rendered[kMaxChunks] = {};
+    hipEvent_t ev_arrived[spgeo::kMaxChunks] = {}, ev_rendered[spgeo::kMaxChunks] = {};
     sp_plan *cached_plan = nullptr;
-    // sp_render_named: the names and numbers the cached plan was built from (empty: the cached plan came from arrays)
-    std::string named_format, named_window, named_cmap;
-    int32_t named_n = 0, named_ch = 0, named_wf = 0;
-    double named_gain = 0, named_range = 0;
-    std::vector<double> named_windowc;
-    std::vector<uint8_t> named_lut;
-    double named_block_norm = 0;
+    NamedRequest named;          // sp_render_named: what the cached plan was built from
     long long plans_created = 0; // sp_context_plan_creations: how many plans (table sets on the device) this context has built
     bool acc_dirty = false;      // a request failed between its launches: accumulators must be re-initialised
     size_t last_upload_bytes = 0; // what the last sp_render sent over the host link (a sparse request sends its frames only)
@@ -113,6 +125,17 @@ struct sp_context {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
 };
+
+// The kernels of a request.  The values are public: sp_plan_force_kernel and SP_FORCE_KERNEL take them.
+enum Kernel {
+    kKernelAuto = 0,         // (sp_plan_force_kernel: the library chooses)
+    kKernelScratch = 1,      // k_scratch_radix2
+    kKernelLdsR16 = 2,       // k_lds_r16, round 1's frame loop: removed in round 3
+    kKernelFrames = 3,       // k_frames
+    kKernelFramesPeak = 4,   // k_frames_peak
+};
+// a frame-loop kernel finishes the request itself (histograms, dBfs range, gauges); behind the scratch kernel a finish kernel is queued
+static bool finishes_request(int kernel) { return kernel == kKernelFrames || kernel == kKernelFramesPeak; }
 
 struct sp_plan {
     sp_context *ctx = nullptr;
@@ -132,7 +155,7 @@ struct sp_plan {
     const uint32_t *d_lut = nullptr;
     const uint16_t *d_cell_g = nullptr, *d_cell_l = nullptr;   // merged-cell ranges per colour index / level (k_frames)
     const double2 *d_stage_tw = nullptr;   // per-stage twiddle tables for k_frames
-    int force_kernel = 0;           // 0 auto, 1 scratch, 3 frames
+    int force_kernel = kKernelAuto;
 };
 
 namespace {
@@ -181,30 +204,6 @@ int validate_request(sp_context *ctx, const sp_request *r)
     if (r->detector != SP_DETECTOR_SAMPLE && r->detector != SP_DETECTOR_PEAK)
         return fail(ctx, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
     return SP_OK;
-}
-
-// The peak detector's sub-frame rule (include/spectroplot_hip.h, enum sp_detector) in the reference's arithmetic: M sub-frames per
-// column, how many of them the last column has, and floor(sampleCount), which every sub-frame j >= 1 must end at or before.
-struct PeakShape {
-    int32_t m = 1, last_count = 0;
-    int64_t nsamp = 0;
-};
-
-PeakShape peak_shape(const spfmt::Format &f, int n, size_t nbytes, int32_t width)
-{
-    PeakShape ps;
-    const double sample_count = (double)nbytes / (double)f.width;                 // samples.js:167
-    ps.nsamp = (int64_t)std::floor(sample_count);
-    if (width < 1) return ps;
-    ps.last_count = 1;
-    if (width < 2) return ps;
-    const double stride = (sample_count - (double)n) / (double)(width - 1);       // worker.js:50
-    if (!std::isfinite(stride) || !(stride >= 2.0 * (double)n)) return ps;
-    const double m = std::floor(stride / (double)n);
-    ps.m = m < 2147483647.0 ? (int32_t)m : 2147483647;
-    const int64_t p = spjs::to_int32(0.5 + stride * (double)(width - 1));         // worker.js:72
-    for (int32_t j = 1; j < ps.m && (double)(p + ((int64_t)j + 1) * n) <= sample_count; j++) ps.last_count = j + 1;
-    return ps;
 }
 
 }  // namespace
@@ -269,15 +268,6 @@ extern "C" int sp_twiddles(int32_t n, double *cos_table, double *sin_table)
 }
 
 extern "C" double sp_js_log10(double x) { return spjs::log10(x); }
-
-extern "C" int sp_peak_subframes(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t *subframes, int32_t *last_column_count)
-{
-    if (format < 0 || format >= SP_FMT_COUNT || n < 1 || width < 0) return SP_ERR_INVALID_ARG;
-    const PeakShape ps = peak_shape(spfmt::describe(format), n, nbytes, width);
-    if (subframes) *subframes = ps.m;
-    if (last_column_count) *last_column_count = ps.last_count;
-    return SP_OK;
-}
 
 extern "C" int sp_cmap_count(void) { return spcmap::kCount; }
 
@@ -393,7 +383,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->batch_host.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (int k = 0; k < sp_context::kMaxChunks; k++) {
+    for (int k = 0; k < spgeo::kMaxChunks; k++) {
         if (ctx->ev_arrived[k]) (void)hipEventDestroy(ctx->ev_arrived[k]);
         if (ctx->ev_rendered[k]) (void)hipEventDestroy(ctx->ev_rendered[k]);
     }
@@ -663,65 +653,56 @@ static bool plan_frames_capable(const sp_plan *plan)
            && plan->gray_b <= spk::kLdsMaxGrayB && plan->edges_in_f32 && plan->taper_finite && plan->th.frames_ok && plan->tw16_ok;
 }
 
-// 1 = scratch_radix2, 3 = frames (2 was k_lds_r16, round 1's frame loop: removed in round 3)
 static int plan_kernel(const sp_plan *plan)
 {
     if (plan->force_kernel) return plan->force_kernel;
 #ifdef SP_EXPERIMENT_KNOBS
     static const int env_kernel = getenv("SP_FORCE_KERNEL") ? atoi(getenv("SP_FORCE_KERNEL")) : 0;
-    if (env_kernel == 3 && plan_frames_capable(plan)) return 3;
-    if (env_kernel == 1) return 1;
+    if (env_kernel == kKernelFrames && plan_frames_capable(plan)) return kKernelFrames;
+    if (env_kernel == kKernelScratch) return kKernelScratch;
 #endif
     // k_frames is the fast path; the scratch kernel covers every request it does not
-    if (plan_frames_capable(plan)) return 3;
-    return 1;
+    return plan_frames_capable(plan) ? kKernelFrames : kKernelScratch;
 }
 
-// The kernel of one request of a plan: plan_kernel's, or for a peak plan's request with M >= 2 sub-frames per column 4 = frames_peak
-// where k_frames_peak covers the plan, else 1 (the scratch kernel holds the peak too).  M == 1 is the sample detector: the same kernels.
+// The kernel of one request of a plan: plan_kernel's, or for a peak plan's request with M >= 2 sub-frames per column k_frames_peak
+// where it covers the plan, else the scratch kernel (it holds the peak too).  M == 1 is the sample detector: the same kernels.
 static int request_kernel(const sp_plan *plan, int32_t peak_m)
 {
     const int k = plan_kernel(plan);
     if (plan->req.detector != SP_DETECTOR_PEAK || peak_m < 2) return k;
-    return k == 3 && spk2::frames_peak_supports(plan->req.n) ? 4 : 1;
+    return k == kKernelFrames && spk2::frames_peak_supports(plan->req.n) ? kKernelFramesPeak : kKernelScratch;
 }
 
 extern "C" int sp_plan_force_kernel(sp_plan *plan, int32_t which)
 {
-    if (!plan || which < 0 || which > 3) return SP_ERR_INVALID_ARG;
-    if (which == 2) return fail(plan->ctx, SP_ERR_UNSUPPORTED, "k_lds_r16 is no longer part of the library");
-    if (which == 3 && !plan_frames_capable(plan)) return fail(plan->ctx, SP_ERR_UNSUPPORTED, "k_frames does not cover this request");
+    if (!plan || which < kKernelAuto || which > kKernelFrames) return SP_ERR_INVALID_ARG;
+    if (which == kKernelLdsR16) return fail(plan->ctx, SP_ERR_UNSUPPORTED, "k_lds_r16 is no longer part of the library");
+    if (which == kKernelFrames && !plan_frames_capable(plan)) return fail(plan->ctx, SP_ERR_UNSUPPORTED, "k_frames does not cover this request");
     plan->force_kernel = which;
     return SP_OK;
 }
 
-extern "C" const char *sp_plan_kernel_name(const sp_plan *plan)
+static const char *kernel_name(int kernel)
 {
-    if (!plan) return "";
-    switch (request_kernel(plan, 2)) {
-    case 4: return "frames_peak";
-    case 3: return "frames";
-    default: return "scratch_radix2";
-    }
+    return kernel == kKernelFramesPeak ? "frames_peak" : kernel == kKernelFrames ? "frames" : "scratch_radix2";
 }
+
+extern "C" const char *sp_plan_kernel_name(const sp_plan *plan) { return plan ? kernel_name(request_kernel(plan, 2)) : ""; }
 
 extern "C" const char *sp_plan_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
 {
-    if (!plan) return "";
-    switch (request_kernel(plan, peak_shape(plan->fmt, plan->req.n, nbytes, width).m)) {
-    case 4: return "frames_peak";
-    case 3: return "frames";
-    default: return "scratch_radix2";
-    }
+    return plan ? kernel_name(request_kernel(plan, spgeo::peak_shape(spgeo::geometry(plan->fmt, plan->req.n, nbytes, width)).m)) : "";
 }
 
 // The frame loop over frames [x_begin, x_end) of a width-frame image.  `first` prepares the context's workspace and accumulators,
 // `last` ends the request: k_frames then produces histograms and dBfs range itself (its last workgroup; the gauges it writes group by
 // group in every launch), behind the scratch kernel a finish kernel is queued.  sp_plan_execute is the whole range in one launch - ONE
 // kernel for every request k_frames covers; sp_render walks the image in chunks so that the copies to and from the host overlap.
+// `shape`: the request's geometry and peak shape, computed once per request from its own nbytes and width (request_shape).
 // `src` (sp_render's packed upload, below): the frames [x_begin, x_end) do not lie in the capture at d_bytes but in a packed copy of it;
 // the kernel is handed that copy's address, length and stride instead (every frame inside it), everything else - image geometry, frame
-// numbers, reply - stays the request's.
+// numbers, peak shape, kernel choice, reply - stays the request's.
 struct PackedSource {
     const void *bytes;     // address of (virtual) sample 0 of the packed layout
     size_t nbytes;         // its (virtual) length
@@ -765,33 +746,66 @@ static void plan_frame_args(const sp_plan *plan, spk::FrameArgs &a)
     a.cells = plan->th.cells;
 }
 
-static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, int32_t x_begin, int32_t x_end, bool first,
+struct RequestShape {
+    spgeo::Geometry g;
+    spgeo::PeakShape peak;   // the peak detector's sub-frames per column (m = 1: the request is the sample detector's, kernels included)
+};
+
+static RequestShape request_shape(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    return {g, plan->req.detector == SP_DETECTOR_PEAK ? spgeo::peak_shape(g) : spgeo::PeakShape{}};
+}
+
+// The limits of one capture and its image.  `reply`: device pointers the kernels add to with 64-bit atomics (null: none to check);
+// `who`: "" for a request, "batch item: " for an item of a batch.
+static int check_capture(sp_context *ctx, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                         const std::string &who)
+{
+    const bool item = !who.empty();
+    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, who + "width < 0");
+    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, who + (item ? "bytes is null" : "d_bytes is null"));
+    if (nbytes % (size_t)f.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, who + "byte length is not a multiple of the element size");
+    if ((double)nbytes / (double)f.width >= 2147483648.0 - (double)n)                 // samples.js:167
+        return fail(ctx, SP_ERR_UNSUPPORTED, who + "captures of 2^31 samples or more must be sliced (sample positions are int32)");
+    if ((double)width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, who + "image too large");
+    if (reply && (((uintptr_t)reply->c_hist | (uintptr_t)reply->cb_hist | (uintptr_t)reply->dbfs_minmax) & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, (item ? who : "reply: ") + "c_hist, cb_hist and dbfs_minmax must be 8-byte aligned");
+    return SP_OK;
+}
+
+// The request's number travels in the kernel arguments, and the frame loop's workgroups wait for workgroup 0 to publish it (the reply is
+// cleared first): a captured launch replayed from a hipGraph would find the number already there.  Refused.
+static int refuse_capture(sp_context *ctx, hipStream_t s, const char *message)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return fail(ctx, SP_ERR_UNSUPPORTED, message);
+    (void)hipGetLastError();
+    return SP_OK;
+}
+
+// the write-out may store an image in 16-byte pieces with 32-bit offsets
+static bool rgba_fast(const uint8_t *rgba, int32_t width, int n)
+{
+    return rgba && ((uintptr_t)rgba & 15) == 0 && (width & 3) == 0 && width < (1 << 24) && (double)width * (double)n * 4.0 <= 4294967296.0;
+}
+
+static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestShape &shape, int32_t x_begin, int32_t x_end, bool first,
                               bool last, const sp_reply *out, const PackedSource *src = nullptr)
 {
     if (!plan || !out) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
-    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
-    if (nbytes && !d_bytes) return fail(ctx, SP_ERR_INVALID_ARG, "d_bytes is null");
+    const spgeo::Geometry &g = shape.g;
+    const spgeo::PeakShape &peak = shape.peak;
     const spfmt::Format f = plan->fmt;
-    if (nbytes % (size_t)f.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
     const int n = plan->req.n;
-    const double sample_count = (double)nbytes / (double)f.width;                 // samples.js:167
-    if (sample_count >= 2147483648.0 - (double)n)
-        return fail(ctx, SP_ERR_UNSUPPORTED, "captures of 2^31 samples or more must be sliced (sample positions are int32)");
-    if ((double)width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large");
-    // (the kernels add to these with 64-bit device atomics)
-    if ((((uintptr_t)out->c_hist | (uintptr_t)out->cb_hist | (uintptr_t)out->dbfs_minmax) & 7) != 0)
-        return fail(ctx, SP_ERR_INVALID_ARG, "reply: c_hist, cb_hist and dbfs_minmax must be 8-byte aligned");
+    const int32_t width = g.width;
+    int rc = check_capture(ctx, f, n, d_bytes, g.nbytes, width, out, "");
+    if (rc) return rc;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    {
-        // The request's number travels in the kernel arguments, and the frame loop's workgroups wait for workgroup 0 to publish it (the
-        // reply is cleared first): a captured launch replayed from a hipGraph would find the number already there.  Refused.
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(ctx, SP_ERR_UNSUPPORTED, "sp_plan_execute cannot be captured into a hipGraph (every launch carries its request's number)");
-        (void)hipGetLastError();
-    }
+    rc = refuse_capture(ctx, s, "sp_plan_execute cannot be captured into a hipGraph (every launch carries its request's number)");
+    if (rc) return rc;
 
     if (width == 0) {
         // nothing to draw; the reply keeps the loop's initial values (worker.js:35-36)
@@ -805,29 +819,14 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
         return SP_OK;
     }
 
-    double stride = (sample_count - (double)n) / (double)(width - 1);              // worker.js:50
-    // do all frames lie inside the buffer?
-    bool in_bounds = false;
-    if (src) {
-        d_bytes = src->bytes;
-        nbytes = src->nbytes;
-        stride = src->stride;
-        in_bounds = true;
-    } else {
-        const double last_d = 0.5 + stride * (double)(width - 1);
-        if (width == 1) {
-            in_bounds = (size_t)n * (size_t)f.width <= nbytes;
-        } else if (stride >= 0.0 && std::isfinite(stride) && last_d < 2147483647.0) {
-            const int64_t last = spjs::to_int32(last_d);
-            in_bounds = (size_t)(last + n) * (size_t)f.width <= nbytes;
-        }
-    }
-
-    // the peak detector's sub-frames per column (1: the request is the sample detector's, kernels included)
-    const PeakShape peak = plan->req.detector == SP_DETECTOR_PEAK ? peak_shape(f, n, nbytes, width) : PeakShape{};
     const int which = request_kernel(plan, peak.m);
-    if (src && which != 3) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    int rc = which >= 3 ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
+    if (src && which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
+    // what the kernel reads: the capture with the request's stride, or a packed copy of this range's frames with its own
+    if (src) d_bytes = src->bytes;
+    const size_t nbytes = src ? src->nbytes : g.nbytes;
+    const double stride = src ? src->stride : g.stride;
+    const bool in_bounds = src ? true : g.in_bounds;
+    rc = finishes_request(which) ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
     if (rc) return fail(ctx, rc, "workspace: out of device memory");
     int finish_blocks = 3 * ((width + spk::kFinishThreads - 1) / spk::kFinishThreads);   // three roles per 256 frames
     {
@@ -855,7 +854,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     a.bytes = (const uint8_t *)d_bytes;
     a.nbytes = (int64_t)nbytes;
     a.nelem = (int64_t)(nbytes / (size_t)f.elem);
-    a.stride = width > 1 ? stride : 0.0;   // one frame: (S - n) / 0 is an infinity or a NaN and ~~(0.5 + it * 0) = 0, as with 0
+    a.stride = stride;
     a.width = width;
     a.in_bounds = in_bounds ? 1 : 0;
     a.frame0 = x_begin;
@@ -879,15 +878,14 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     a.mm_acc = (unsigned long long *)((char *)ctx->partial.p + 16);
     a.c_hist = (unsigned long long *)((char *)ctx->partial.p + 64);
     a.cb_hist = a.c_hist + SP_MAX_LUT;
-    a.rgba_fast = out->rgba && ((uintptr_t)out->rgba & 15) == 0 && (width & 3) == 0 && width < (1 << 24)
-                  && (double)width * (double)n * 4.0 <= 4294967296.0;
+    a.rgba_fast = rgba_fast(out->rgba, width, n);
 
     if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
     const int32_t peak_nsamp = (int32_t)(peak.nsamp < 2147483647 ? peak.nsamp : 2147483647);
-    if (which == 3) {
+    if (which == kKernelFrames) {
         rc = spk2::launch_frames(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames launch rejected the configuration");
-    } else if (which == 4) {
+    } else if (which == kKernelFramesPeak) {
         rc = spk2::launch_frames_peak(a, plan->req.format, plan->d_stage_tw, peak.m, peak_nsamp, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames_peak launch rejected the configuration");
     } else {
@@ -918,7 +916,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
     }
 
     if (!last) return SP_OK;
-    if (which >= 3) {   // k_frames / k_frames_peak has finished the request itself
+    if (finishes_request(which)) {   // k_frames / k_frames_peak has finished the request itself
         ctx->acc_dirty = false;
         return SP_OK;
     }
@@ -954,7 +952,8 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, size_t nbytes,
 
 extern "C" int sp_plan_execute(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const sp_reply *out)
 {
-    return plan_execute_range(plan, d_bytes, nbytes, width, 0, width < 0 ? 0 : width, true, true, out);
+    if (!plan) return SP_ERR_INVALID_ARG;
+    return plan_execute_range(plan, d_bytes, request_shape(plan, nbytes, width), 0, width < 0 ? 0 : width, true, true, out);
 }
 
 // ------------------------------------------------------------------------------------------------- merge of slice replies
@@ -1063,113 +1062,13 @@ extern "C" int sp_place_strips(sp_context *ctx, uint8_t *d_image, const uint8_t 
 
 // ------------------------------------------------------------------------------------------------- host-buffer render
 
-// ---- sparse requests: upload only what the frames read --------------------------------------------------------------------------------
-// With stride > n the reference's loop touches n samples per frame and skips the rest (lib/worker.js:50, 70-75) - its interactive shape:
-// a long capture at a screen-wide `width`.  Copying the capture contiguously moves stride / n times the bytes any frame reads.  Instead
-// a chunk's frames travel as the rows of pitched copies (hipMemcpy2DAsync: source rows floor(stride) samples apart) into a packed device
-// buffer whose rows are P samples apart, and the kernel is launched on that buffer with the stride P + frac(stride): frame x then
-// starts at ~~(0.5 + (P + frac) x) = P x + floor(0.5 + frac x), which is where the pitched copy put it, because the capture has it at
-// floor(stride) x + floor(0.5 + frac x).  The identity holds in exact arithmetic; the two sides round differently in f64, so the host
-// evaluates both for EVERY frame and takes the contiguous path if a single one disagrees.  The start's fractional drift within a chunk
-// (d_j = start_j - start_0 - j floor(stride), 0 <= d_j <= j) is what a pitched copy cannot follow row by row: it covers a run of rows
-// whose drifts differ by at most `span` samples and brings that many samples more per row (span: a few hundred samples, at most n/2,
-// chosen below to balance the cost of a copy call against the extra bytes); P = n + the widest run's range.
-// A frame's centre sample (gauge_amps) lies inside the frame, and nothing else of the path depends on where a frame came from.
-struct PackedBlock {
-    int32_t j0, j1;        // rows of the chunk (frame x0 + j)
-    int32_t dmin, dmax;    // their drifts lie in [dmin, dmax]
-};
-struct PackedChunk {
-    int32_t x0 = 0, x1 = 0;
-    int64_t first = 0;     // the capture's sample where frame x0 starts
-    int64_t F = 0;         // samples between the capture's rows: floor(stride)
-    int64_t P = 0;         // samples between the device rows
-    size_t dev_off = 0;    // the chunk's byte offset in the staging buffer
-    double stride2 = 0;    // P + frac(stride): the kernel's stride
-    int64_t pos2_x0 = 0;   // ~~(0.5 + stride2 * x0): the kernel's start of frame x0
-    int64_t pos2_last = 0; // ... and of frame x1 - 1
-    std::vector<PackedBlock> blocks;
-    std::vector<int32_t> drift;   // d_j per row
-};
-
-// Cuts [0, width) at `bounds` and lays every chunk out; false = this request is not worth packing or cannot be (then nothing is used).
-static bool build_packed_chunks(int n, int sample_width, size_t nbytes, int32_t width, double stride, const std::vector<int32_t> &bounds,
-                                std::vector<PackedChunk> &out, size_t *dev_bytes, size_t *link_bytes)
-{
-    out.clear();
-    if (width < 2 || !(stride > (double)n) || !std::isfinite(stride) || !(0.5 + stride * (double)(width - 1) < 2147483000.0)) return false;
-    const int64_t F = (int64_t)std::floor(stride);
-    const double frac = stride - (double)F;
-    size_t off = 256, moved = 0;
-    for (size_t c = 0; c + 1 < bounds.size(); c++) {
-        PackedChunk ch;
-        ch.x0 = bounds[c];
-        ch.x1 = bounds[c + 1];
-        if (ch.x1 <= ch.x0) continue;
-        ch.first = spjs::to_int32(0.5 + stride * (double)ch.x0);                       // worker.js:72
-        ch.F = F;
-        const int rows = ch.x1 - ch.x0;
-        ch.drift.resize((size_t)rows);
-        for (int j = 0; j < rows; j++) {
-            const int64_t d = (int64_t)spjs::to_int32(0.5 + stride * (double)(ch.x0 + j)) - ch.first - (int64_t)j * F;
-            if (d < 0 || d > (int64_t)rows) return false;       // (0 <= d_j <= j in exact arithmetic)
-            ch.drift[(size_t)j] = (int32_t)d;
-        }
-        // the frame must also END inside the capture (the caller established in_bounds for the request as a whole)
-        if ((size_t)(ch.first + (int64_t)(rows - 1) * F + ch.drift[(size_t)rows - 1] + n) * (size_t)sample_width > nbytes) return false;
-        // runs of rows whose drifts stay within `span` samples of each other: one pitched copy each, its rows widened by the run's drift
-        // range.  A copy call costs the link ~11 us (tools/pcie_probe.hip: 17 MiB in 16 pitched copies 0.49 ms, in one 0.32 ms), a
-        // widened row span / 2 samples on average: rows * frac / span calls against rows * span / 2 samples at ~55 GB/s balance at
-        // span = sqrt(2 * 11 us * frac * 55 GB/s / bytes per sample) - 275 samples for cf32 at frac = 0.5 - kept within [16, n/2].
-        int32_t span = (int32_t)std::sqrt(2.0 * 11e-6 * (frac > 1e-3 ? frac : 1e-3) * 55e9 / (double)sample_width);
-        span = span > n / 2 ? n / 2 : span;
-        span = span < 16 ? 16 : span;
-        int32_t widest = 0;
-        for (int j = 0; j < rows;) {
-            PackedBlock b{j, j + 1, ch.drift[(size_t)j], ch.drift[(size_t)j]};
-            while (b.j1 < rows) {
-                const int32_t d = ch.drift[(size_t)b.j1];
-                const int32_t lo = d < b.dmin ? d : b.dmin, hi = d > b.dmax ? d : b.dmax;
-                if (hi - lo > span) break;
-                b.dmin = lo;
-                b.dmax = hi;
-                b.j1++;
-            }
-            moved += (size_t)(b.j1 - b.j0) * (size_t)(n + b.dmax - b.dmin) * (size_t)sample_width;
-            if (b.dmax - b.dmin > widest) widest = b.dmax - b.dmin;
-            ch.blocks.push_back(b);
-            j = b.j1;
-        }
-        // device rows P apart: wide enough that a widened row ends where the next one begins (row j of a run lands at j P + dmin and is
-        // n + dmax - dmin long); the frames themselves sit at j P + d_j, their drift accumulating as it does in the capture
-        ch.P = (int64_t)n + widest;
-        ch.stride2 = (double)ch.P + frac;
-        if (!((double)(ch.P + 1) * (double)width < 2147483000.0)) return false;       // the kernel's positions are int32
-        ch.pos2_x0 = spjs::to_int32(0.5 + ch.stride2 * (double)ch.x0);
-        for (int j = 0; j < rows; j++) {
-            const int64_t pos2 = spjs::to_int32(0.5 + ch.stride2 * (double)(ch.x0 + j));
-            if (pos2 - ch.pos2_x0 != (int64_t)j * ch.P + ch.drift[(size_t)j]) return false;   // the two sides of the identity rounded apart
-            if (j == rows - 1) ch.pos2_last = pos2;
-        }
-        ch.dev_off = off;
-        off += ((size_t)((int64_t)rows * ch.P + ch.drift[(size_t)rows - 1] + widest) * (size_t)sample_width + 255) & ~(size_t)255;
-        out.push_back(std::move(ch));
-    }
-    *dev_bytes = off + 256;
-    *link_bytes = moved;
-    // worth it only if clearly fewer bytes cross the link, and not in a hail of small copies
-    size_t copies = 0;
-    for (const PackedChunk &ch : out) copies += ch.blocks.size();
-    return !out.empty() && moved <= nbytes / 4 * 3 && copies <= 512;
-}
-
 // The pitched copies of one chunk, on `stream`.
-static hipError_t upload_packed_chunk(const PackedChunk &ch, int n, int sample_width, const uint8_t *bytes, size_t nbytes, uint8_t *stage,
+static hipError_t upload_packed_chunk(const spgeo::PackedChunk &ch, int n, int sample_width, const uint8_t *bytes, size_t nbytes, uint8_t *stage,
                                       hipStream_t stream)
 {
     const size_t sw = (size_t)sample_width;
     hipError_t e = hipSuccess;
-    for (const PackedBlock &b : ch.blocks) {
+    for (const spgeo::PackedBlock &b : ch.blocks) {
         int32_t j1 = b.j1;
         // the widened rows may reach past the capture's end in the request's very last rows: those travel one by one, exactly
         while (j1 > b.j0 && (size_t)(ch.first + (int64_t)(j1 - 1) * ch.F + b.dmax + n) * sw > nbytes) j1--;
@@ -1189,88 +1088,6 @@ static hipError_t upload_packed_chunk(const PackedChunk &ch, int n, int sample_w
         }
     }
     return e;
-}
-
-// How [0, width) is cut into chunks of frames for a request that moves in_est bytes of samples in and out_bytes of image out.
-static void chunk_bounds(int32_t width, size_t in_est, size_t out_bytes, bool chunkable, std::vector<int32_t> &bounds)
-{
-    int chunks = 1;
-    if (chunkable && width >= 1024 && in_est + out_bytes >= ((size_t)16 << 20)) chunks = in_est + out_bytes >= ((size_t)64 << 20) ? 6 : 4;
-    // The busier direction of the link never pauses; what does not overlap it is one chunk's way in the other direction plus its
-    // render: the LAST chunk's image when the samples are the longer transfer, the FIRST chunk's samples when the image is.  So the
-    // chunks shrink (or grow) geometrically towards that end - each 0.65 of its neighbour, which also keeps the shorter direction
-    // from falling behind - instead of being equal (measured, config 2: 8 equal chunks 2.73 ms, pure two-way copy 2.37 ms; every
-    // additional copy call costs the link ~13 us, so few chunks).  Chunks end on multiples of 32 frames.
-    const bool in_heavy = in_est >= out_bytes;
-    double w[sp_context::kMaxChunks], sum = 0, acc = 0;
-    for (int k = 0; k < chunks; k++) sum += (w[k] = std::pow(0.65, in_heavy ? k : chunks - 1 - k));
-    bounds.assign(1, 0);
-    for (int k = 0; k + 1 < chunks; k++) {
-        acc += w[k];
-        const int32_t x = (int32_t)((int64_t)((double)width * acc / sum) & ~(int64_t)31);
-        if (x > bounds.back() && x < width) bounds.push_back(x);
-    }
-    bounds.push_back(width);   // (width = 0: one empty chunk, so that the reply still gets its initial values)
-}
-
-// How a request's samples travel to the device: [0, width) cut into chunks of frames and, for a sparse request, every chunk's packed
-// layout.  packable: the plan's kernel can read a packed chunk; chunkable: the request may be pipelined; out_bytes: the image that
-// comes back over the link.
-struct UploadPlan {
-    bool packed = false;
-    double stride = 0;                   // samples between two frames' starts (lib/worker.js:50)
-    std::vector<int32_t> bounds;         // chunk k: frames [bounds[k], bounds[k + 1])
-    std::vector<PackedChunk> chunks;     // packed: chunk k's layout
-    size_t dev_bytes = 0, link_bytes = 0;   // the staging buffer it needs; what crosses the link
-};
-
-static void plan_upload(const spfmt::Format &f, int n, size_t nbytes, int32_t width, bool packable, bool chunkable, size_t out_bytes,
-                        UploadPlan &u)
-{
-    const double sample_count = (double)nbytes / (double)f.width;
-    u.stride = width > 1 ? (sample_count - (double)n) / (double)(width - 1) : 0.0;
-    const bool stride_ok = u.stride >= 0.0 && std::isfinite(u.stride) && 0.5 + u.stride * (double)(width - 1) < 2147483000.0;
-    // a sparse request (stride > n, every frame inside the capture) is cut by the bytes its frames read; if it cannot be packed after
-    // all, it is cut again by the whole capture
-    bool sparse = packable && stride_ok && width >= 2 && u.stride > (double)n
-                  && (size_t)(spjs::to_int32(0.5 + u.stride * (double)(width - 1)) + (int64_t)n) * (size_t)f.width <= nbytes;
-    for (;; sparse = false) {
-        chunk_bounds(width, sparse ? (size_t)width * (size_t)n * (size_t)f.width : nbytes, out_bytes, chunkable && stride_ok, u.bounds);
-        u.packed = sparse && build_packed_chunks(n, f.width, nbytes, width, u.stride, u.bounds, u.chunks, &u.dev_bytes, &u.link_bytes)
-                   && u.chunks.size() + 1 == u.bounds.size();
-        if (u.packed || !sparse) break;
-    }
-    if (u.packed) return;
-    u.chunks.clear();
-    u.dev_bytes = nbytes + 16;
-    u.link_bytes = nbytes;
-}
-
-// (tests) The upload plan sp_render would use for a request of this shape - pure host arithmetic, no device.  out[]: packed (0 / 1),
-// chunks, device bytes, link bytes; per chunk x0, x1 and, if packed, first, F, P, dev_off, pos2_x0, pos2_last, the bits of stride2,
-// blocks, then j0, j1, dmin, dmax per block.
-extern "C" int sp_debug_upload_plan(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t want_image, int64_t *out, size_t capacity,
-                                    size_t *used)
-{
-    if (format < 0 || format >= SP_FMT_COUNT || n < 2 || width < 1 || !out || !used) return SP_ERR_INVALID_ARG;
-    UploadPlan u;
-    plan_upload(spfmt::describe(format), n, nbytes, width, true, want_image != 0, 4 * (size_t)width * (size_t)n, u);
-    std::vector<int64_t> v{u.packed ? 1 : 0, (int64_t)u.bounds.size() - 1, u.packed ? (int64_t)u.dev_bytes : 0, (int64_t)u.link_bytes};
-    for (size_t c = 0; c + 1 < u.bounds.size(); c++) {
-        v.push_back(u.bounds[c]);
-        v.push_back(u.bounds[c + 1]);
-        if (!u.packed) continue;
-        const PackedChunk &ch = u.chunks[c];
-        int64_t bits;
-        memcpy(&bits, &ch.stride2, 8);
-        for (int64_t x : {ch.first, ch.F, ch.P, (int64_t)ch.dev_off, ch.pos2_x0, ch.pos2_last, bits, (int64_t)ch.blocks.size()}) v.push_back(x);
-        for (const PackedBlock &b : ch.blocks)
-            for (int64_t x : {(int64_t)b.j0, (int64_t)b.j1, (int64_t)b.dmin, (int64_t)b.dmax}) v.push_back(x);
-    }
-    *used = v.size();
-    if (v.size() > capacity) return SP_ERR_INVALID_ARG;
-    memcpy(out, v.data(), v.size() * 8);
-    return SP_OK;
 }
 
 // Frames [x0, x1) of the device image (`width` frames, rows 4 * width bytes apart) into the caller's image (rows host_pitch bytes
@@ -1322,13 +1139,13 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     // Chunks end on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.  A
     // request of one chunk does everything on the context's stream.  A sparse request (the frame-loop kernel) uploads only the
     // samples its frames read.
-    const spfmt::Format f = spfmt::describe(req->format);
-    UploadPlan u;
+    const spfmt::Format f = plan->fmt;
+    const RequestShape shape = request_shape(plan, nbytes, width);   // once, for the upload plan and every chunk's launch
+    spgeo::UploadPlan u;
     // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
     // (a peak request with M >= 2 sub-frames per column reads more than half of the capture: the contiguous upload, chunked by columns)
-    const int32_t peak_m = req->detector == SP_DETECTOR_PEAK ? peak_shape(f, req->n, nbytes, width).m : 1;
-    plan_upload(f, req->n, nbytes, width, request_kernel(plan, peak_m) == 3 && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"),
-                device_out || reply->rgba, device_out ? 0 : rgba_bytes, u);
+    spgeo::plan_upload(shape.g, request_kernel(plan, shape.peak.m) == kKernelFrames && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"),
+                       device_out || reply->rgba, device_out ? 0 : rgba_bytes, u);
     const int chunks = (int)u.bounds.size() - 1;
     const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
     ctx->last_upload_bytes = u.link_bytes;
@@ -1359,7 +1176,7 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
         // sample (3-byte samples are fetched as dwords), its stride
         PackedSource ps{};
         if (u.packed) {
-            const PackedChunk &ch = u.chunks[(size_t)k];
+            const spgeo::PackedChunk &ch = u.chunks[(size_t)k];
             e = upload_packed_chunk(ch, req->n, f.width, bytes, nbytes, in, in_s);
             ps.bytes = in + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
             ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
@@ -1368,8 +1185,7 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
         } else {
             size_t need = nbytes;
             if (k + 1 < chunks) {
-                const int64_t last_start = spjs::to_int32(0.5 + u.stride * (double)(x1 - 1));          // worker.js:72
-                need = (size_t)(last_start + (int64_t)peak_m * req->n) * (size_t)f.width;   // (the column's last sub-frame)
+                need = (size_t)(shape.g.start(x1 - 1) + (int64_t)shape.peak.m * req->n) * (size_t)f.width;   // (the column's last sub-frame)
                 if (need > nbytes) need = nbytes;
             }
             if (need > sent) {
@@ -1379,7 +1195,7 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
         }
         if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
         if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
-        if (e == hipSuccess) rc = plan_execute_range(plan, in, nbytes, width, x0, x1, k == 0, k + 1 == chunks, &d, u.packed ? &ps : nullptr);
+        if (e == hipSuccess) rc = plan_execute_range(plan, in, shape, x0, x1, k == 0, k + 1 == chunks, &d, u.packed ? &ps : nullptr);
         if (rc || e != hipSuccess) break;
         if (device_out) continue;
         if (overlap) e = hipEventRecord(ctx->ev_rendered[k], s);
@@ -1407,6 +1223,20 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     return SP_OK;
 }
 
+// The context's cached plan if it serves `req`, else a new one in its place.
+static int cached_plan_for(sp_context *ctx, const sp_request *req, sp_plan **plan)
+{
+    const sp_plan *cp = ctx->cached_plan;
+    if (!cp || !sphost::same_request(cp->req, cp->window, cp->lut, req)) {
+        if (ctx->cached_plan) sp_plan_destroy(ctx->cached_plan);
+        ctx->cached_plan = nullptr;
+        const int rc = sp_plan_create(ctx, req, &ctx->cached_plan);
+        if (rc) return rc;
+    }
+    *plan = ctx->cached_plan;
+    return SP_OK;
+}
+
 static int render_host(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
                        int32_t image_width)
 {
@@ -1421,14 +1251,10 @@ static int render_host(sp_context *ctx, const sp_request *req, const uint8_t *by
         return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
     SP_HIP(ctx, hipSetDevice(ctx->device));
 
-    const sp_plan *cp = ctx->cached_plan;
-    if (!cp || !sphost::same_request(cp->req, cp->window, cp->lut, req)) {
-        if (ctx->cached_plan) sp_plan_destroy(ctx->cached_plan);
-        ctx->cached_plan = nullptr;
-        rc = sp_plan_create(ctx, req, &ctx->cached_plan);
-        if (rc) return rc;
-    }
-    return render_core(ctx->cached_plan, bytes, nbytes, width, reply, image_width, false);
+    sp_plan *plan = nullptr;
+    rc = cached_plan_for(ctx, req, &plan);
+    if (rc) return rc;
+    return render_core(plan, bytes, nbytes, width, reply, image_width, false);
 }
 
 extern "C" int sp_render(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply)
@@ -1487,50 +1313,47 @@ extern "C" int sp_render_named_ex(sp_context *ctx, const sp_named_request *nr, i
         return fail(ctx, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
     if (nr->n < 1 || sphost::log2_exact(nr->n) < 0) return fail(ctx, SP_ERR_NOT_POW2, "Length is not a power of 2");
     if (nr->n > SP_MAX_N) return fail(ctx, SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
-    const std::string f = nr->format ? nr->format : "", w = nr->window ? nr->window : "", c = nr->cmap ? nr->cmap : "";
-    const bool same = ctx->cached_plan && !ctx->named_windowc.empty() && ctx->named_format == f && ctx->named_window == w && ctx->named_cmap == c
-                      && ctx->named_n == nr->n && ctx->named_ch == (nr->channel_mode ? 1 : 0) && ctx->named_wf == (nr->waterfall ? 1 : 0)
-                      && !memcmp(&ctx->named_gain, &nr->gain, 8) && !memcmp(&ctx->named_range, &nr->range, 8);
-    if (!same) {
+    NamedRequest &nm = ctx->named;
+    if (!ctx->cached_plan || !nm.same(*nr)) {
         // the caller's message assembly (lib/spectroplot.js:1113-1146)
-        ctx->named_windowc.assign((size_t)nr->n, 0.0);
+        nm.windowc.assign((size_t)nr->n, 0.0);
         double weight = 0.0;
-        if (!sphost::window(sphost::window_by_name(w.c_str()), nr->n, ctx->named_windowc.data(), &weight))
+        if (!sphost::window(sphost::window_by_name(NamedRequest::str(nr->window).c_str()), nr->n, nm.windowc.data(), &weight))
             return fail(ctx, SP_ERR_INVALID_ARG, "window");
-        ctx->named_block_norm = 1.0 / weight;
-        int ci = cmap_index(c.c_str());
+        nm.block_norm = 1.0 / weight;
+        int ci = cmap_index(NamedRequest::str(nr->cmap).c_str());
         if (ci < 0) ci = 0;                                              // cube1 (lib/spectroplot.js:252-264)
         const spcmap::Entry &e = spcmap::kEntries[ci];
-        ctx->named_lut.assign(3 * (size_t)e.length, 0);
-        cmap_bytes(ci, ctx->named_lut.data());
+        nm.lut.assign(3 * (size_t)e.length, 0);
+        cmap_bytes(ci, nm.lut.data());
         for (int k = 0; k < 3; k++) {                                    // ends forced to black / white (:1129-1130)
-            ctx->named_lut[(size_t)k] = 0;
-            ctx->named_lut[3 * (size_t)(e.length - 1) + (size_t)k] = 255;
+            nm.lut[(size_t)k] = 0;
+            nm.lut[3 * (size_t)(e.length - 1) + (size_t)k] = 255;
         }
-        ctx->named_format = f;
-        ctx->named_window = w;
-        ctx->named_cmap = c;
-        ctx->named_n = nr->n;
-        ctx->named_ch = nr->channel_mode ? 1 : 0;
-        ctx->named_wf = nr->waterfall ? 1 : 0;
-        ctx->named_gain = nr->gain;
-        ctx->named_range = nr->range;
+        nm.format = NamedRequest::str(nr->format);
+        nm.window = NamedRequest::str(nr->window);
+        nm.cmap = NamedRequest::str(nr->cmap);
+        nm.n = nr->n;
+        nm.channel_mode = nr->channel_mode ? 1 : 0;
+        nm.waterfall = nr->waterfall ? 1 : 0;
+        nm.gain = nr->gain;
+        nm.range = nr->range;
     }
     sp_request r{};
-    r.format = sphost::parse_format(f.c_str());
+    r.format = sphost::parse_format(nm.format.c_str());
     r.n = nr->n;
     r.channel_mode = nr->channel_mode;
     r.waterfall = nr->waterfall;
-    r.lut_len = (int32_t)(ctx->named_lut.size() / 3);
+    r.lut_len = (int32_t)(nm.lut.size() / 3);
     r.detector = detector;
-    r.block_norm = ctx->named_block_norm;
+    r.block_norm = nm.block_norm;
     r.gain = nr->gain;
     r.range = nr->range;
-    r.windowc = ctx->named_windowc.data();
-    r.lut_rgb = ctx->named_lut.data();
+    r.windowc = nm.windowc.data();
+    r.lut_rgb = nm.lut.data();
     // same names and numbers: sp_render finds the cached plan by value (same arrays), nothing is rebuilt or uploaded
     const int rc = sp_render(ctx, &r, bytes, nbytes, width, reply);
-    if (rc) ctx->named_windowc.clear();
+    if (rc) nm.windowc.clear();   // a failed render forgets the identity
     return rc;
 }
 
@@ -1550,21 +1373,6 @@ struct BatchWork {
     std::vector<int> in_bounds;
 };
 
-static void item_geometry(const spfmt::Format &f, int n, size_t nbytes, int32_t width, double *stride, bool *in_bounds)
-{
-    const double sample_count = (double)nbytes / (double)f.width;                 // samples.js:167
-    const double st = width > 1 ? (sample_count - (double)n) / (double)(width - 1) : 0.0;   // worker.js:50
-    bool ib = false;
-    if (width == 1) {
-        ib = (size_t)n * (size_t)f.width <= nbytes;
-    } else if (width > 1 && st >= 0.0 && std::isfinite(st) && 0.5 + st * (double)(width - 1) < 2147483647.0) {
-        const int64_t last = spjs::to_int32(0.5 + st * (double)(width - 1));
-        ib = (size_t)(last + n) * (size_t)f.width <= nbytes;
-    }
-    *stride = st;
-    *in_bounds = ib;
-}
-
 static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_plan, int cu_count, const size_t *nbytes, const int32_t *widths,
                        int count, BatchWork &w)
 {
@@ -1577,11 +1385,9 @@ static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_p
     w.groups[0] = w.groups[1] = 0;
     int64_t total = 0;
     for (int i = 0; i < count; i++) {
-        double st;
-        bool ib;
-        item_geometry(f, n, nbytes[i], widths[i], &st, &ib);
-        w.stride[(size_t)i] = st;
-        w.in_bounds[(size_t)i] = ib ? 1 : 0;
+        const spgeo::Geometry g = spgeo::geometry(f, n, nbytes[i], widths[i]);
+        w.stride[(size_t)i] = g.stride;
+        w.in_bounds[(size_t)i] = g.in_bounds ? 1 : 0;
         total += widths[i] > 0 ? widths[i] : 0;
     }
     if (!frames_plan || !spk2::frames_kernel_supports(n) || n > (1 << spk2::kBatchMaxLog2N) || lut_len < 2 || lut_len > spk::kLdsMaxLut)
@@ -1643,15 +1449,8 @@ __global__ void k_batch_clear(const spk2::BatchItem *items, int lut_len)
 static int batch_check_items(sp_context *ctx, const spfmt::Format &f, int n, const sp_batch_item *items, int32_t count, bool device)
 {
     for (int i = 0; i < count; i++) {
-        const sp_batch_item &it = items[i];
-        if (it.width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "batch item: width < 0");
-        if (it.nbytes && !it.bytes) return fail(ctx, SP_ERR_INVALID_ARG, "batch item: bytes is null");
-        if (it.nbytes % (size_t)f.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, "batch item: byte length is not a multiple of the element size");
-        if ((double)it.nbytes / (double)f.width >= 2147483648.0 - (double)n)
-            return fail(ctx, SP_ERR_UNSUPPORTED, "batch item: captures of 2^31 samples or more must be sliced (sample positions are int32)");
-        if ((double)it.width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, "batch item: image too large");
-        if (device && (((uintptr_t)it.reply.c_hist | (uintptr_t)it.reply.cb_hist | (uintptr_t)it.reply.dbfs_minmax) & 7) != 0)
-            return fail(ctx, SP_ERR_INVALID_ARG, "batch item: c_hist, cb_hist and dbfs_minmax must be 8-byte aligned");
+        const int rc = check_capture(ctx, f, n, items[i].bytes, items[i].nbytes, items[i].width, device ? &items[i].reply : nullptr, "batch item: ");
+        if (rc) return rc;
     }
     return SP_OK;
 }
@@ -1675,12 +1474,8 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
     if (rc) return rc;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(ctx, SP_ERR_UNSUPPORTED, "sp_plan_execute_batch cannot be captured into a hipGraph");
-        (void)hipGetLastError();
-    }
+    rc = refuse_capture(ctx, s, "sp_plan_execute_batch cannot be captured into a hipGraph");
+    if (rc) return rc;
     std::vector<size_t> nb((size_t)count);
     std::vector<int32_t> wd((size_t)count);
     for (int i = 0; i < count; i++) {
@@ -1688,11 +1483,12 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
         wd[(size_t)i] = items[i].width;
     }
     BatchWork w;
-    plan_batch(plan->fmt, n, plan->req.lut_len, plan_kernel(plan) == 3, ctx->cu_count, nb.data(), wd.data(), count, w);
+    plan_batch(plan->fmt, n, plan->req.lut_len, plan_kernel(plan) == kKernelFrames, ctx->cu_count, nb.data(), wd.data(), count, w);
     if (w.gf == 0) {
         // a plan outside k_frames: the items one by one, as sp_plan_execute renders them
         for (int i = 0; i < count; i++) {
-            rc = plan_execute_range(plan, items[i].bytes, items[i].nbytes, items[i].width, 0, items[i].width, true, true, &items[i].reply);
+            rc = plan_execute_range(plan, items[i].bytes, request_shape(plan, items[i].nbytes, items[i].width), 0, items[i].width, true, true,
+                                    &items[i].reply);
             if (rc) return rc;
         }
         return SP_OK;
@@ -1735,8 +1531,7 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
         b.out_minmax = it.reply.dbfs_minmax;
         b.width = it.width;
         b.in_bounds = w.in_bounds[(size_t)i];
-        b.rgba_fast = it.reply.rgba && ((uintptr_t)it.reply.rgba & 15) == 0 && (it.width & 3) == 0 && it.width < (1 << 24)
-                      && (double)it.width * (double)n * 4.0 <= 4294967296.0;
+        b.rgba_fast = rgba_fast(it.reply.rgba, it.width, n);
         b.first_group = w.first_group[(size_t)i];
         if (l == kBatchEmpty) continue;
         // launch 1's map follows launch 0's; its records are indexed from the launch's own first record
@@ -1790,16 +1585,11 @@ extern "C" int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_
     if (rc) return rc;
     if (count == 0) return SP_OK;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    const sp_plan *cp = ctx->cached_plan;
-    if (!cp || !sphost::same_request(cp->req, cp->window, cp->lut, req)) {
-        if (ctx->cached_plan) sp_plan_destroy(ctx->cached_plan);
-        ctx->cached_plan = nullptr;
-        rc = sp_plan_create(ctx, req, &ctx->cached_plan);
-        if (rc) return rc;
-    }
-    sp_plan *plan = ctx->cached_plan;
+    sp_plan *plan = nullptr;
+    rc = cached_plan_for(ctx, req, &plan);
+    if (rc) return rc;
     size_t uploaded = 0;
-    if (plan_kernel(plan) != 3) {
+    if (plan_kernel(plan) != kKernelFrames) {
         // a plan outside k_frames: item by item through sp_render's path
         for (int i = 0; i < count; i++) {
             rc = render_core(plan, (const uint8_t *)items[i].bytes, items[i].nbytes, items[i].width, &items[i].reply, items[i].width, false);
