@@ -182,9 +182,7 @@ int dispatch_format(int32_t fmt, F &&f)
 {
     switch (fmt) {
 #define SP_CASE(X) case X: return f(std::integral_constant<int, X>{});
-        SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
-        SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
-        SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32) SP_CASE(SP_FMT_CF64)
+        SP_FORMATS_BUT_CF64(SP_CASE) SP_CASE(SP_FMT_CF64)
 #undef SP_CASE
     default: return SP_ERR_INVALID_ARG;
     }
@@ -1390,11 +1388,9 @@ static void plan_batch(const spfmt::Format &f, int n, int lut_len, bool frames_p
         w.in_bounds[(size_t)i] = g.in_bounds ? 1 : 0;
         total += widths[i] > 0 ? widths[i] : 0;
     }
-    if (!frames_plan || !spk2::frames_kernel_supports(n) || n > (1 << spk2::kBatchMaxLog2N) || lut_len < 2 || lut_len > spk::kLdsMaxLut)
-        return;
-    const int gf = spk2::frames_group_frames(n, total, cu_count);
-    if ((gf & (gf - 1)) || spk2::layout(n, lut_len, gf).total > 160 * 1024) return;
-    w.gf = gf;
+    spk2::FramesLaunch fl;   // (only the group size: the groups are dealt per item and launch below)
+    if (!frames_plan || n > (1 << spk2::kBatchMaxLog2N) || spk2::frames_launch_rule(n, lut_len, total, cu_count, 0, fl)) return;
+    const int gf = w.gf = fl.gf;
     for (int i = 0; i < count; i++) {
         const int32_t W = widths[i];
         if (W == 0) {

@@ -13,6 +13,11 @@
 #include "../../include/spectroplot_hip.h"
 #include "sp_jsmath.h"
 
+// The formats other than SP_FMT_CF64, which the switches over a format id keep as their `default:` (X-macro: X(id) per format).
+#define SP_FORMATS_BUT_CF64(X)                                                                                \
+    X(SP_FMT_CU4) X(SP_FMT_CS4) X(SP_FMT_CU8) X(SP_FMT_CS8) X(SP_FMT_CU12) X(SP_FMT_CS12) X(SP_FMT_CU16) \
+    X(SP_FMT_CS16) X(SP_FMT_CU32) X(SP_FMT_CS32) X(SP_FMT_CU64) X(SP_FMT_CS64) X(SP_FMT_CF32)
+
 namespace spfmt {
 
 struct Format {

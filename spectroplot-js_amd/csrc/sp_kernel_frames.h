@@ -41,8 +41,16 @@
 // both kernel bodies.  The inclusion is textual on purpose: the compiler sees the tokens it saw when each kernel spelled the stages out,
 // so neither kernel's code moves (a shared function, even a local alias, moved k_frames' instruction streams).  A fragment's first
 // comment lists the names it expects in scope; an expression that differs between the kernels is a macro (SP_X_END, ...) that each
-// kernel defines around the include.  tests/test_batch_cpu.py compares every k_frames and k_frames_batch instruction stream with a
-// reference build.
+// kernel defines around the include.  tests/test_isa_checks.py compares every k_frames, k_frames_batch and k_frames_peak instruction
+// stream with a reference build.  Who includes what (F = k_frames, B = k_frames_batch, P = k_frames_peak, sp_kernel_frames_peak.h):
+//   * F B P  the stages: setup, raw_regs, table_loads, table_stores, epilogue_consts, decode_pf, fft, lr_split, pixels (P defines
+//            SP_ABS2); the bodies side_outputs and drain_rows (inside each kernel's lambdas); hist_ranges, hist_scan, hist_adds and
+//            range_atomics (F and P through finale, B in batch_flush);
+//   * F P    the shell of a single request's loop: reply_clear (workgroup 0 clears the reply), publish (the request's number), writeout
+//            (the lambdas side_outputs, drain_rows, drain), finale (everything behind the group loop: split last write-out, scan, the
+//            bounded poll for the request's number, adds, last side outputs, dBfs range).  B keeps its own lambdas and batch_flush:
+//            they read the item record, and its replies are cleared by a kernel queued ahead, so it has no handshake.
+// The switches over a format id expand SP_FORMATS_BUT_CF64 (sp_formats.h).
 #pragma once
 
 #include <atomic>
@@ -362,11 +370,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
 {
 #include "sp_frames_setup.inc.h"
 
-    constexpr bool PF = PFB != 0;
-    const int sidx_pf = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
-    const int rounds = (group_frames + FPB - 1) / FPB;
-    uint32_t raw_lo[PF ? 16 : 1], raw_hi[PFB == 8 ? 16 : 1];
-    int raw_back = 0;
+#include "sp_frames_raw_regs.inc.h"
     auto request = [&](int xq) {
         if constexpr (PF) {
             // (the prefetching variants only run when every frame lies inside the buffer: launch_frames)
@@ -395,23 +399,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     constexpr bool LATE_SIDE = late_side_outputs(N);
     {
 #include "sp_frames_table_loads.inc.h"
-        // Workgroup 0 of a request's first launch clears the reply's histograms and sets its dBfs range to (0, -200): its first wave
-        // alone, so that the wave knows when the stores have landed (publish() below).  Fire-and-forget, behind the table loads.
-        if (owner) {
-            const LateArgs la = late_args();
-            unsigned long long *const out_c = la->out_c, *const out_cb = la->out_cb;
-            unsigned long long *const out_mm = (unsigned long long *)la->out_minmax;
-            constexpr int kClr = (kLdsMaxLut + SP_CB_HIST_SIZE + 63) / 64;
-#pragma unroll
-            for (int k = 0; k < kClr; k++) {
-                const int i = tid + 64 * k;
-                unsigned long long *const dst = i < kLdsMaxLut ? (out_c && i < a.lut_len ? out_c + i : nullptr)
-                                                               : (out_cb && i < kLdsMaxLut + SP_CB_HIST_SIZE ? out_cb + (i - kLdsMaxLut) : nullptr);
-                if (dst) __hip_atomic_store(dst, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 2 && out_mm)
-                __hip_atomic_store(out_mm + tid, tid ? 0xc069000000000000ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // -200.0, 0.0
-        }
+#include "sp_frames_reply_clear.inc.h"
         // The first frame's samples are requested BEHIND the table loads (vector-memory operations complete in order: requested ahead of
         // them, the wait for the tables - L2 hits - was a wait for the samples from HBM), and unconditionally (a frame past the end is
         // clamped), so that the compiler can count the 16 younger loads in that wait: s_waitcnt vmcnt(16).
@@ -432,35 +420,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
     uint32_t pf_word = 0;
 #include "sp_frames_epilogue_consts.inc.h"
 
-    // Side outputs of a finished group of frames (worker.js:124-136), by the workgroup's first 3 * group_frames threads: gauge_mins and
-    // gauge_maxs from the frame's extreme |X|^2 (d is monotone in |X|^2, so the frame's extreme d belong to them), gauge_amps from its
-    // raw centre sample: one software log10 per output.  The frame's clamped extremes are also its share of the request's dBfs range
-    // (worker.js:124-125): they are folded into the workgroup's; the frame's slots are reset.
-#define SP_X_END a.x_end
-    auto side_outputs = [&](const int x0, const int par) {
-        if (__builtin_amdgcn_readfirstlane(tid) >= 3 * group_frames) return;   // (wave-uniform: the waves that hold none of those threads)
-        const LateArgs la = late_args();
-        // three scalar loads, selected per lane below (the compiler turns a select between fields into ONE indexed vector load, whose
-        // wait covers every outstanding vector-memory operation of the wave: the sample prefetch, ~2 us)
-        uint8_t *out_min = la->gauge_mins, *out_max = la->gauge_maxs, *out_amp = la->gauge_amps;
-        asm volatile("" : "+s"(out_min), "+s"(out_max), "+s"(out_amp));
-#include "sp_frames_side_outputs.inc.h"
-    };
-    // write-out of tile rows [f0, f0 + fcount) by the threads [t0, t0 + dthreads), slice `part` of `nparts`
-    auto drain_rows = [&](const int x0, const int part, const int nparts, const int f0, const int fcount, const int t0, const int dthreads,
-                          const bool nt_rows) {
-        const int dt = tid - t0;
-        if (dt < 0) return;
-        // (the image's address, width and layout are read from the argument segment here, once per write-out, instead of sitting in
-        // SGPRs through every frame)
-        const LateArgs la = late_args();
-        uint8_t *const img = la->rgba;
-        const int img_width = la->width, img_waterfall = la->waterfall, img_fast = la->rgba_fast;
-#include "sp_frames_drain_rows.inc.h"
-    };
-#undef SP_X_END
-    // non-temporal stores where a group's row pieces are whole 128-byte lines (below)
-    auto drain = [&](const int x0, const int part, const int nparts) { drain_rows(x0, part, nparts, 0, group_frames, 0, kThreads, group_frames >= SP_NT_MIN_GROUP); };
+#include "sp_frames_writeout.inc.h"
     int drain_x0 = -1;
     int gpar = 0;   // parity of the workgroup's current group (s_amp)
     meet.arrive();   // the first re-distribution only waits (exchange<.., SECOND = false>)
@@ -498,9 +458,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 }
                 switch (format) {
 #define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                    SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
-                    SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
-                    SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32)
+                    SP_FORMATS_BUT_CF64(SP_CASE)
 #undef SP_CASE
                 default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
                 }
@@ -529,128 +487,16 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, 
                 drain_x0 = -1;
             }
 #include "sp_frames_pixels.inc.h"
-            // Workgroup 0's first wave publishes the request's number once its clearing stores have landed: after its first frame (group 0
-            // is workgroup 0's, and every slot has a frame in a group's first round), when they long have.
-            if (g == 0 && r == 0 && a.first && __builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const LateArgs la = late_args();
-                if (tid == 0) __hip_atomic_store(la->flag, la->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+#include "sp_frames_publish.inc.h"
         }
         drain_x0 = x0;
         gpar ^= 1;
     }
 
-    // ---- end of the workgroup's frames: last write-out and side outputs, the workgroup's share of histograms and dBfs range ----------
-    const LateArgs la = late_args();
-    // requested now, used behind the last barrier: the cell ranges of this thread's histogram outputs and the request's number as
-    // workgroup 0 published it
-#define SP_LUT_LEN a.lut_len
-#define SP_CELLS a.cells
-#define SP_REPLY la
-#define SP_AFTER_CELLS_READ
-#include "sp_frames_hist_ranges.inc.h"
-    const unsigned int seen = __hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (HALVES && drain_x0 >= 0 && a.rgba) {
-        // The workgroup's last write-out overlaps nothing.  The first waves of the SIMDs reach it ~7 us before the second ones (config 2;
-        // issue arbitration favours the older wave, s_setprio does not change that - tools/stamps.py) and would wait at the barrier:
-        // each set of four waves meets by itself and writes its own half of the group, 64-byte pieces of the image rows, so half of the
-        // chip's last stores are under way while the second waves still compute.
-        const int half = tid >> 8;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_fetch_add(&s_done[half], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        while (__hip_atomic_load(&s_done[half], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 4u) __builtin_amdgcn_s_sleep(2);
-        // (non-temporal: left in L2, the 64-byte pieces are written back when the kernel ends, +1.2 us instead of -1.1 us; the first
-        // set also taking half of the second set's rows once those are ready: no further gain)
-        drain_rows(drain_x0, 0, 1, half * (group_frames / 2), group_frames / 2, half * (kThreads / 2), kThreads / 2, true);
-    }
-    lds_barrier();
-    if (drain_x0 >= 0 && !(HALVES && a.rgba)) drain(drain_x0, 0, 1);
-    // ---- the workgroup's share of the request's histograms and dBfs range (worker.js:105-113, 124-125, 140-155) ----------------------
-    // No workgroup finishes for the others (that costs the last one three dependent trips to memory, 6 us): every workgroup turns its
-    // own merged cells into histogram counts and adds them to the reply itself, with fire-and-forget atomics the launch's end waits
-    // for anyway.  Workgroup 0 has zeroed the reply's histograms and set its dBfs range to (0, -200) at the start of the request's
-    // first launch and published the request's number behind that (below); everybody checks the number before its first add.
-    {
-        // cells -> prefix sums: every count is a difference of two prefix sums over the cells (sp_host.h Thresholds).  A thread takes
-        // kPer consecutive cells, the workgroup scans the 512 partial sums (in each wave with shuffles, the eight wave totals through
-        // LDS).  The exchange buffers are idle by now and hold the prefix.  (Counts of one workgroup fit 32 bits, as s_cells does.)
-        constexpr int kPer = 3;
-        static_assert(kThreads * kPer >= kMaxCells, "every cell needs a thread");
-        unsigned int *const s_pre = (unsigned int *)(smem + kOffXch);         // [kThreads * kPer + 1]: s_pre[c] = sum of the cells [0, c)
-        unsigned int *const s_part = s_pre + kThreads * kPer + 4;             // [kThreads / 64] wave totals
-#include "sp_frames_hist_scan.inc.h"
-        if (seen != la->seq) {
-            // (never in practice: workgroup 0 - dispatched first: the lowest workgroup number - published the number tens of microseconds
-            // ago.  The wait is bounded: ~2 s of polling end in a trap, i.e. a failed launch, instead of a hung device.)
-            unsigned polls = 0;
-            while (__hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != la->seq) {
-                __builtin_amdgcn_s_sleep(32);
-                if (++polls > (1u << 22)) __builtin_trap();
-            }
-        }
-#include "sp_frames_hist_adds.inc.h"
-        // The last group's gauges come behind the adds (two waves, one software log10: ~1 us during which everybody's adds and stores
-        // are on their way), and behind them the workgroup's share of the dBfs range.
-        if (drain_x0 >= 0) side_outputs(drain_x0, gpar ^ 1);
-        lds_barrier();
-        double *const out_mm = la->out_minmax;
-        if (tid < 2 && out_mm) {
-            typedef __attribute__((address_space(1))) double *GlobalF64;
-            if (tid == 0) __builtin_amdgcn_global_atomic_fmin_f64((GlobalF64)&out_mm[0], s_red[0]);
-            else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
-        }
-    }
-#undef SP_LUT_LEN
-#undef SP_CELLS
-#undef SP_REPLY
-#undef SP_AFTER_CELLS_READ
+#include "sp_frames_finale.inc.h"
 }
 
-// Per-n launchers, one translation unit each (sp_inst_frames.hip is compiled once per LOG2N).
-template <int L>
-int launch_frames_n(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int prefetch,
-                    int device, hipStream_t stream);
-#define SP_DECL(L)                                                                                                              \
-    template <>                                                                                                                 \
-    int launch_frames_n<L>(const FrameArgs &, int, const double2 *, int, int, int, int, int, int, hipStream_t);
-SP_DECL(6) SP_DECL(7) SP_DECL(8) SP_DECL(9) SP_DECL(10) SP_DECL(11) SP_DECL(12) SP_DECL(13)
-#undef SP_DECL
-
-#ifdef SP_INST_FRAMES_LOG2N
-// One launch of a variant of k_frames or k_frames_batch, behind its per-device opt-in to the full LDS (function attributes belong to the
-// device's code object).  (Contexts of several devices render on different threads: the flags are atomic, and setting the attribute
-// twice is harmless.)
-template <auto Kernel, typename... Args>
-inline int launch_full_lds(int grid, int lds_bytes, int device, hipStream_t stream, const Args &...args)
-{
-    static std::atomic<bool> attr_set[kMaxDevices];
-    if (device < 0 || device >= kMaxDevices || !attr_set[device].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SP_ERR_HIP;
-        if (device >= 0 && device < kMaxDevices) attr_set[device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, args...);
-    return SP_OK;
-}
-
-template <>
-int launch_frames_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups,
-                                   int prefetch, int device, hipStream_t stream)
-{
-    constexpr int L = SP_INST_FRAMES_LOG2N;
-#define SP_V(C, P) return launch_full_lds<k_frames<L, C, P>>(grid, lds_bytes, device, stream, a, format, stage_tw, gf, groups);
-#define SP_CH(C)                                                                                              \
-    switch (prefetch) {                                                                                       \
-    case 8: SP_V(C, 8) case 4: SP_V(C, 4) case 3: SP_V(C, 3) case 2: SP_V(C, 2) case 1: SP_V(C, 1) default: SP_V(C, 0) \
-    }
-    if (a.channel_mode) { SP_CH(true) } else { SP_CH(false) }
-#undef SP_V
-#undef SP_CH
-}
-#endif
-
-// The launch rules of k_frames and k_frames_batch (sp_api.hip's batch plan follows them too).
+// The launch rules of the three frame-loop kernels (sp_api.hip's batch plan follows them too).
 // Frames per group for a launch over total_frames frames: 32, or fewer while that leaves less than two groups per CU.
 inline int frames_group_frames(int n, int64_t total_frames, int cu_count)
 {
@@ -674,20 +520,92 @@ inline int frames_prefetch_width(int sample_width, bool in_bounds, double stride
     return p == 3 && !(width >= 2 && frame_start(stride, width - 1) >= 1) ? 0 : p;
 }
 
+// The shape of one launch: frames per group, groups, workgroups, dynamic LDS bytes.
+struct FramesLaunch {
+    int gf, groups, grid, lds_bytes;
+};
+
+// The one launch rule.  `count` frames (k_frames) or columns (k_frames_peak) are dealt into groups by frames_group_frames; with
+// gf_fixed > 0 (k_frames_batch) the caller has dealt its items into `count` groups of gf_fixed frames already.  Returns SP_OK and the
+// launch's shape, or SP_ERR_UNSUPPORTED.
+inline int frames_launch_rule(int n, int lut_len, int64_t count, int cu_count, int gf_fixed, FramesLaunch &fl)
+{
+    if (!frames_kernel_supports(n) || lut_len > kLdsMaxLut || lut_len < 2) return SP_ERR_UNSUPPORTED;
+    fl.gf = gf_fixed > 0 ? gf_fixed : frames_group_frames(n, count, cu_count);
+    if (fl.gf & (fl.gf - 1)) return SP_ERR_UNSUPPORTED;   // (the write-out splits item numbers with shifts; every n in range gives a power of two)
+    fl.groups = (int)(gf_fixed > 0 ? count : (count + fl.gf - 1) / fl.gf);
+    fl.lds_bytes = layout(n, lut_len, fl.gf).total;
+    if (fl.lds_bytes > 160 * 1024) return SP_ERR_UNSUPPORTED;
+    fl.grid = frames_grid(fl.groups, cu_count);
+    return SP_OK;
+}
+
+// One launch of a variant of a frame-loop kernel, behind its per-device opt-in to the full LDS (function attributes belong to the
+// device's code object).  (Contexts of several devices render on different threads: the flags are atomic, and setting the attribute
+// twice is harmless.)
+template <auto Kernel, typename... Args>
+inline int launch_full_lds(int grid, int lds_bytes, int device, hipStream_t stream, const Args &...args)
+{
+    static std::atomic<bool> attr_set[kMaxDevices];
+    if (device < 0 || device >= kMaxDevices || !attr_set[device].load(std::memory_order_acquire)) {
+        if (hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return SP_ERR_HIP;
+        if (device >= 0 && device < kMaxDevices) attr_set[device].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, args...);
+    return SP_OK;
+}
+
+// Per-n launchers, one translation unit each (sp_inst_frames.hip and sp_inst_frames_peak.hip are compiled once per LOG2N):
+// NAME<L>(a, format, stage_tw, fl, prefetch, device, stream, <what the kernel takes behind `groups`>).
+// SP_DECLARE_LAUNCH_N(NAME, SIZES, extra parameter types...) declares NAME and its specialisation for every L of SIZES.
+#define SP_LAUNCH_N_PARAMS \
+    const FrameArgs &a, int format, const double2 *stage_tw, const FramesLaunch &fl, int prefetch, int device, hipStream_t stream
+#define SP_SIZES_6_10(X, ...) X(6, __VA_ARGS__) X(7, __VA_ARGS__) X(8, __VA_ARGS__) X(9, __VA_ARGS__) X(10, __VA_ARGS__)
+#define SP_SIZES_6_13(X, ...) SP_SIZES_6_10(X, __VA_ARGS__) X(11, __VA_ARGS__) X(12, __VA_ARGS__) X(13, __VA_ARGS__)
+#define SP_DECLARE_LAUNCH_N_AT(L, NAME, ...) \
+    template <>                              \
+    int NAME<L>(SP_LAUNCH_N_PARAMS, ##__VA_ARGS__);
+#define SP_DECLARE_LAUNCH_N(NAME, SIZES, ...)       \
+    template <int L>                                \
+    int NAME(SP_LAUNCH_N_PARAMS, ##__VA_ARGS__);    \
+    SIZES(SP_DECLARE_LAUNCH_N_AT, NAME, ##__VA_ARGS__)
+
+// The body of a per-n launcher: SP_LAUNCH_VARIANT(KERNEL, extra arguments...) launches KERNEL<L, a.channel_mode, prefetch> and returns.
+// Expects in scope: L and the parameters of SP_LAUNCH_N_PARAMS.
+#define SP_LAUNCH_VARIANT_CP(KERNEL, C, P, ...) \
+    return launch_full_lds<KERNEL<L, C, P>>(fl.grid, fl.lds_bytes, device, stream, a, format, stage_tw, fl.gf, fl.groups, ##__VA_ARGS__);
+#define SP_LAUNCH_VARIANT_C(KERNEL, C, ...)                \
+    switch (prefetch) {                                    \
+    case 8: SP_LAUNCH_VARIANT_CP(KERNEL, C, 8, ##__VA_ARGS__) \
+    case 4: SP_LAUNCH_VARIANT_CP(KERNEL, C, 4, ##__VA_ARGS__) \
+    case 3: SP_LAUNCH_VARIANT_CP(KERNEL, C, 3, ##__VA_ARGS__) \
+    case 2: SP_LAUNCH_VARIANT_CP(KERNEL, C, 2, ##__VA_ARGS__) \
+    case 1: SP_LAUNCH_VARIANT_CP(KERNEL, C, 1, ##__VA_ARGS__) \
+    default: SP_LAUNCH_VARIANT_CP(KERNEL, C, 0, ##__VA_ARGS__) \
+    }
+#define SP_LAUNCH_VARIANT(KERNEL, ...)                                                           \
+    if (a.channel_mode) { SP_LAUNCH_VARIANT_C(KERNEL, true, ##__VA_ARGS__) } else { SP_LAUNCH_VARIANT_C(KERNEL, false, ##__VA_ARGS__) }
+
+SP_DECLARE_LAUNCH_N(launch_frames_n, SP_SIZES_6_13)
+
+#ifdef SP_INST_FRAMES_LOG2N
+template <>
+int launch_frames_n<SP_INST_FRAMES_LOG2N>(SP_LAUNCH_N_PARAMS)
+{
+    constexpr int L = SP_INST_FRAMES_LOG2N;
+    SP_LAUNCH_VARIANT(k_frames)
+}
+#endif
+
 // Host-side launch.  Returns SP_OK or SP_ERR_UNSUPPORTED.
 inline int launch_frames(const FrameArgs &a, int format, const double2 *stage_tw, int cu_count, int device, hipStream_t stream)
 {
     const int prefetch = frames_prefetch_width(a.sample_width, a.in_bounds, a.stride, a.width);
-    if (!frames_kernel_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2) return SP_ERR_UNSUPPORTED;
-    const int n = a.n;
-    const int gf = frames_group_frames(n, a.x_end - a.frame0, cu_count);
-    if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;   // (the write-out splits item numbers with shifts; every n in range gives a power of two)
-    const int groups = (a.x_end - a.frame0 + gf - 1) / gf;
-    const Layout lay = layout(n, a.lut_len, gf);
-    if (lay.total > 160 * 1024) return SP_ERR_UNSUPPORTED;
-    const int grid = frames_grid(groups, cu_count);
+    FramesLaunch fl;
+    if (frames_launch_rule(a.n, a.lut_len, a.x_end - a.frame0, cu_count, 0, fl)) return SP_ERR_UNSUPPORTED;
     switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, device, stream);
+#define SP_L(L) case L: return launch_frames_n<L>(a, format, stage_tw, fl, prefetch, device, stream);
         SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)
 #undef SP_L
     default: return SP_ERR_UNSUPPORTED;

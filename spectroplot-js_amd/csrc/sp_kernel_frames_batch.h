@@ -67,9 +67,7 @@ __device__ inline void load_frame_item(int format, const BatchItemK c, int64_t s
     const spfmt::View view{c->bytes, c->nbytes, c->nelem};
     switch (format) {
 #define SP_CASE(F) case F: load_frame<F>(fa, view, start, tl, T, LOG2N, win, re, im, centre); break;
-        SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
-        SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
-        SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32)
+        SP_FORMATS_BUT_CF64(SP_CASE)
 #undef SP_CASE
     default: load_frame<SP_FMT_CF64>(fa, view, start, tl, T, LOG2N, win, re, im, centre); break;
     }
@@ -100,10 +98,8 @@ __device__ inline void batch_flush(const FrameArgs &a, unsigned char *smem, doub
 #undef SP_AFTER_CELLS_READ
     double *const out_mm = it->out_minmax;
     if (tid < 2) {
-        typedef __attribute__((address_space(1))) double *GlobalF64;
         if (out_mm) {
-            if (tid == 0) __builtin_amdgcn_global_atomic_fmin_f64((GlobalF64)&out_mm[0], s_red[0]);
-            else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
+#include "sp_frames_range_atomics.inc.h"
         }
         s_red[tid] = tid ? -200.0 : 0.0;                                      // worker.js:35-36
     }
@@ -119,11 +115,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
     // the item of the workgroup's current group, the item of the frame requested next
     int cur = group_item_of(bgroup, min(xcd * chunk + lane_in_xcd, groups - 1)), rq = cur;
 
-    constexpr bool PF = PFB != 0;
-    const int sidx_pf = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
-    const int rounds = (group_frames + FPB - 1) / FPB;
-    uint32_t raw_lo[PF ? 16 : 1], raw_hi[PFB == 8 ? 16 : 1];
-    int raw_back = 0;
+#include "sp_frames_raw_regs.inc.h"
     auto request = [&](int xq) {
         if constexpr (PF) {
             // (the prefetching variants only run when every frame lies inside the buffer: launch_frames)
@@ -285,57 +277,33 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
     }
 }
 
-template <int L>
-int launch_frames_batch_n(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int prefetch,
-                          const BatchItem *items, const int32_t *group_item, int device, hipStream_t stream);
-#define SP_DECL(L)                                                                                                              \
-    template <>                                                                                                                 \
-    int launch_frames_batch_n<L>(const FrameArgs &, int, const double2 *, int, int, int, int, int, const BatchItem *, const int32_t *, int, \
-                                 hipStream_t);
-SP_DECL(6) SP_DECL(7) SP_DECL(8) SP_DECL(9) SP_DECL(10) SP_DECL(11) SP_DECL(12) SP_DECL(13)
-#undef SP_DECL
+SP_DECLARE_LAUNCH_N(launch_frames_batch_n, SP_SIZES_6_13, const BatchItem *, const int32_t *)
 
 #ifdef SP_INST_FRAMES_LOG2N
 // (a template of its own, so that the discarded branch below names no batch kernel for n >= 1024 and none is built)
-template <int L, bool C, int P>
-inline int launch_batch_variant(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups,
-                                const BatchItem *items, const int32_t *group_item, int device, hipStream_t stream)
+template <int L>
+inline int launch_batch_variant(SP_LAUNCH_N_PARAMS, const BatchItem *items, const int32_t *group_item)
 {
-    return launch_full_lds<k_frames_batch<L, C, P>>(grid, lds_bytes, device, stream, a, format, stage_tw, gf, groups, items, group_item);
+    SP_LAUNCH_VARIANT(k_frames_batch, items, group_item)
 }
 
 template <>
-int launch_frames_batch_n<SP_INST_FRAMES_LOG2N>(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf,
-                                                int groups, int prefetch, const BatchItem *items, const int32_t *group_item, int device,
-                                                hipStream_t stream)
+int launch_frames_batch_n<SP_INST_FRAMES_LOG2N>(SP_LAUNCH_N_PARAMS, const BatchItem *items, const int32_t *group_item)
 {
     constexpr int L = SP_INST_FRAMES_LOG2N;
-    if constexpr (L > kBatchMaxLog2N) {
-        return SP_ERR_UNSUPPORTED;   // (not instantiated: plan_batch renders these items one by one)
-    } else {
-#define SP_V(C, P) return launch_batch_variant<L, C, P>(a, format, stage_tw, grid, lds_bytes, gf, groups, items, group_item, device, stream);
-#define SP_CH(C)                                                                                              \
-    switch (prefetch) {                                                                                       \
-    case 8: SP_V(C, 8) case 4: SP_V(C, 4) case 3: SP_V(C, 3) case 2: SP_V(C, 2) case 1: SP_V(C, 1) default: SP_V(C, 0) \
-    }
-    if (a.channel_mode) { SP_CH(true) } else { SP_CH(false) }
-#undef SP_V
-#undef SP_CH
-    }
+    if constexpr (L > kBatchMaxLog2N) return SP_ERR_UNSUPPORTED;   // (not instantiated: plan_batch renders these items one by one)
+    else return launch_batch_variant<L>(a, format, stage_tw, fl, prefetch, device, stream, items, group_item);
 }
 #endif
 
-// One launch of k_frames_batch over `groups` groups (the caller's work list: items[], group_item[] on the device).
+// One launch of k_frames_batch over `groups` groups of gf frames (the caller's work list: items[], group_item[] on the device).
 inline int launch_frames_batch(const FrameArgs &a, int format, const double2 *stage_tw, int gf, int groups, int prefetch, const BatchItem *items,
                                const int32_t *group_item, int cu_count, int device, hipStream_t stream)
 {
-    if (!frames_kernel_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2 || groups < 1) return SP_ERR_UNSUPPORTED;
-    if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;
-    const Layout lay = layout(a.n, a.lut_len, gf);
-    if (lay.total > 160 * 1024) return SP_ERR_UNSUPPORTED;
-    const int grid = frames_grid(groups, cu_count);
+    FramesLaunch fl;
+    if (groups < 1 || frames_launch_rule(a.n, a.lut_len, groups, cu_count, gf, fl)) return SP_ERR_UNSUPPORTED;
     switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_batch_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, items, group_item, device, stream);
+#define SP_L(L) case L: return launch_frames_batch_n<L>(a, format, stage_tw, fl, prefetch, device, stream, items, group_item);
         SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)
 #undef SP_L
     default: return SP_ERR_UNSUPPORTED;

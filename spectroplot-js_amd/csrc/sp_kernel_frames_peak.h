@@ -17,8 +17,9 @@
 //     variants therefore request a sub-frame's samples when it starts (k_frames' LATE_PF order) instead of one sub-frame ahead: the 16 or
 //     32 registers of the raw words are then dead during the passes, and the partner wave of the SIMD covers the load.  (Requesting one
 //     sub-frame ahead spills in the I/Q variants too: profiles/peak_experiments.txt has both spill tables and the A/B.)
-// The stages are the fragments sp_frames_*.inc.h, #included as in k_frames and k_frames_batch (sp_kernel_frames.h says why they are
-// textual); this file keeps what is the detector's: the sub-frame loop, the hold, the launcher.
+// The stages and the shell of the loop (reply clear, write-out lambdas, publication of the request's number, finale) are the fragments
+// sp_frames_*.inc.h, #included as in k_frames (sp_kernel_frames.h says why they are textual and lists them); this file keeps what is
+// the detector's: the sub-frame loop, the hold, peak_count, its launch entry.
 #pragma once
 
 #include "sp_kernel_frames.h"
@@ -45,11 +46,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
     static_assert(!BLOCK_SYNC, "a sub-frame stays inside one wave");
     (void)LATE_PF;   // (k_frames' switch: every prefetching variant here requests a sub-frame's samples when it starts)
 
-    constexpr bool PF = PFB != 0;
-    const int sidx_pf = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
-    const int rounds = (group_frames + FPB - 1) / FPB;
-    uint32_t raw_lo[PF ? 16 : 1], raw_hi[PFB == 8 ? 16 : 1];
-    int raw_back = 0;
+#include "sp_frames_raw_regs.inc.h"
     // the raw words of the sub-frame that starts at sample sv (inside the capture: launch_frames_peak)
     auto request_at = [&](const int sv) {
         if constexpr (PF) {
@@ -69,22 +66,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
     constexpr bool LATE_SIDE = late_side_outputs(N);
     {
 #include "sp_frames_table_loads.inc.h"
-        // workgroup 0 clears the reply in a request's first launch, as in k_frames
-        if (owner) {
-            const LateArgs la = late_args();
-            unsigned long long *const out_c = la->out_c, *const out_cb = la->out_cb;
-            unsigned long long *const out_mm = (unsigned long long *)la->out_minmax;
-            constexpr int kClr = (kLdsMaxLut + SP_CB_HIST_SIZE + 63) / 64;
-#pragma unroll
-            for (int k = 0; k < kClr; k++) {
-                const int i = tid + 64 * k;
-                unsigned long long *const dst = i < kLdsMaxLut ? (out_c && i < a.lut_len ? out_c + i : nullptr)
-                                                               : (out_cb && i < kLdsMaxLut + SP_CB_HIST_SIZE ? out_cb + (i - kLdsMaxLut) : nullptr);
-                if (dst) __hip_atomic_store(dst, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 2 && out_mm)
-                __hip_atomic_store(out_mm + tid, tid ? 0xc069000000000000ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // -200.0, 0.0
-        }
+#include "sp_frames_reply_clear.inc.h"
 #include "sp_frames_table_stores.inc.h"
     }
 
@@ -95,25 +77,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
     uint32_t pf_word = 0;
 #include "sp_frames_epilogue_consts.inc.h"
 
-#define SP_X_END a.x_end
-    auto side_outputs = [&](const int x0, const int par) {
-        if (__builtin_amdgcn_readfirstlane(tid) >= 3 * group_frames) return;   // (wave-uniform: the waves that hold none of those threads)
-        const LateArgs la = late_args();
-        uint8_t *out_min = la->gauge_mins, *out_max = la->gauge_maxs, *out_amp = la->gauge_amps;
-        asm volatile("" : "+s"(out_min), "+s"(out_max), "+s"(out_amp));
-#include "sp_frames_side_outputs.inc.h"
-    };
-    auto drain_rows = [&](const int x0, const int part, const int nparts, const int f0, const int fcount, const int t0, const int dthreads,
-                          const bool nt_rows) {
-        const int dt = tid - t0;
-        if (dt < 0) return;
-        const LateArgs la = late_args();
-        uint8_t *const img = la->rgba;
-        const int img_width = la->width, img_waterfall = la->waterfall, img_fast = la->rgba_fast;
-#include "sp_frames_drain_rows.inc.h"
-    };
-#undef SP_X_END
-    auto drain = [&](const int x0, const int part, const int nparts) { drain_rows(x0, part, nparts, 0, group_frames, 0, kThreads, group_frames >= SP_NT_MIN_GROUP); };
+#include "sp_frames_writeout.inc.h"
     int drain_x0 = -1;
     int gpar = 0;   // parity of the workgroup's current group (s_amp)
     meet.arrive();
@@ -151,9 +115,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
                     asm volatile("" ::"v"(pf_word));
                     switch (format) {
 #define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                        SP_CASE(SP_FMT_CU4) SP_CASE(SP_FMT_CS4) SP_CASE(SP_FMT_CU8) SP_CASE(SP_FMT_CS8) SP_CASE(SP_FMT_CU12)
-                        SP_CASE(SP_FMT_CS12) SP_CASE(SP_FMT_CU16) SP_CASE(SP_FMT_CS16) SP_CASE(SP_FMT_CU32) SP_CASE(SP_FMT_CS32)
-                        SP_CASE(SP_FMT_CU64) SP_CASE(SP_FMT_CS64) SP_CASE(SP_FMT_CF32)
+                        SP_FORMATS_BUT_CF64(SP_CASE)
 #undef SP_CASE
                     default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
                     }
@@ -187,122 +149,36 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
 #include "sp_frames_pixels.inc.h"
 #undef SP_ABS2
             }
-            // Workgroup 0's first wave publishes the request's number once its clearing stores have landed (k_frames)
-            if (g == 0 && r == 0 && a.first && __builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const LateArgs la = late_args();
-                if (tid == 0) __hip_atomic_store(la->flag, la->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+#include "sp_frames_publish.inc.h"
         }
         drain_x0 = x0;
         gpar ^= 1;
     }
 
-    // ---- end of the workgroup's columns: as k_frames ends its frames ---------------------------------------------------------------
-    const LateArgs la = late_args();
-#define SP_LUT_LEN a.lut_len
-#define SP_CELLS a.cells
-#define SP_REPLY la
-#define SP_AFTER_CELLS_READ
-#include "sp_frames_hist_ranges.inc.h"
-    const unsigned int seen = __hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (HALVES && drain_x0 >= 0 && a.rgba) {
-        const int half = tid >> 8;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_fetch_add(&s_done[half], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        while (__hip_atomic_load(&s_done[half], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 4u) __builtin_amdgcn_s_sleep(2);
-        drain_rows(drain_x0, 0, 1, half * (group_frames / 2), group_frames / 2, half * (kThreads / 2), kThreads / 2, true);
-    }
-    lds_barrier();
-    if (drain_x0 >= 0 && !(HALVES && a.rgba)) drain(drain_x0, 0, 1);
-    {
-        constexpr int kPer = 3;
-        static_assert(kThreads * kPer >= kMaxCells, "every cell needs a thread");
-        unsigned int *const s_pre = (unsigned int *)(smem + kOffXch);
-        unsigned int *const s_part = s_pre + kThreads * kPer + 4;
-#include "sp_frames_hist_scan.inc.h"
-        if (seen != la->seq) {
-            // (bounded, as in k_frames: ~2 s of polling end in a failed launch instead of a hung device)
-            unsigned polls = 0;
-            while (__hip_atomic_load(la->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != la->seq) {
-                __builtin_amdgcn_s_sleep(32);
-                if (++polls > (1u << 22)) __builtin_trap();
-            }
-        }
-#include "sp_frames_hist_adds.inc.h"
-        if (drain_x0 >= 0) side_outputs(drain_x0, gpar ^ 1);
-        lds_barrier();
-        double *const out_mm = la->out_minmax;
-        if (tid < 2 && out_mm) {
-            typedef __attribute__((address_space(1))) double *GlobalF64;
-            if (tid == 0) __builtin_amdgcn_global_atomic_fmin_f64((GlobalF64)&out_mm[0], s_red[0]);
-            else __builtin_amdgcn_global_atomic_fmax_f64((GlobalF64)&out_mm[1], s_red[1]);
-        }
-    }
-#undef SP_LUT_LEN
-#undef SP_CELLS
-#undef SP_REPLY
-#undef SP_AFTER_CELLS_READ
+#include "sp_frames_finale.inc.h"
 }
 
-// Per-n launchers, one translation unit each (sp_inst_frames_peak.hip is compiled once per LOG2N).
-template <int L>
-int launch_frames_peak_n(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int prefetch,
-                         int peak_m, int peak_nsamp, int device, hipStream_t stream);
-#define SP_DECL(L)                                                                                                              \
-    template <>                                                                                                                 \
-    int launch_frames_peak_n<L>(const FrameArgs &, int, const double2 *, int, int, int, int, int, int, int, int, hipStream_t);
-SP_DECL(6) SP_DECL(7) SP_DECL(8) SP_DECL(9) SP_DECL(10)
-#undef SP_DECL
+SP_DECLARE_LAUNCH_N(launch_frames_peak_n, SP_SIZES_6_10, int, int)
 
 #ifdef SP_INST_PEAK_LOG2N
-template <int L, bool C, int P>
-inline int launch_peak_variant(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups, int peak_m,
-                               int peak_nsamp, int device, hipStream_t stream)
-{
-    // the per-device opt-in to the full LDS, as launch_full_lds (sp_kernel_frames.h)
-    static std::atomic<bool> attr_set[kMaxDevices];
-    if (device < 0 || device >= kMaxDevices || !attr_set[device].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void *)k_frames_peak<L, C, P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SP_ERR_HIP;
-        if (device >= 0 && device < kMaxDevices) attr_set[device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_frames_peak<L, C, P>), dim3((unsigned)grid), dim3(kFrameThreads), (size_t)lds_bytes, stream, a, format, stage_tw, gf,
-                       groups, peak_m, peak_nsamp);
-    return SP_OK;
-}
-
 template <>
-int launch_frames_peak_n<SP_INST_PEAK_LOG2N>(const FrameArgs &a, int format, const double2 *stage_tw, int grid, int lds_bytes, int gf, int groups,
-                                             int prefetch, int peak_m, int peak_nsamp, int device, hipStream_t stream)
+int launch_frames_peak_n<SP_INST_PEAK_LOG2N>(SP_LAUNCH_N_PARAMS, int peak_m, int peak_nsamp)
 {
     constexpr int L = SP_INST_PEAK_LOG2N;
-#define SP_V(C, P) return launch_peak_variant<L, C, P>(a, format, stage_tw, grid, lds_bytes, gf, groups, peak_m, peak_nsamp, device, stream);
-#define SP_CH(C)                                                                                              \
-    switch (prefetch) {                                                                                       \
-    case 8: SP_V(C, 8) case 4: SP_V(C, 4) case 3: SP_V(C, 3) case 2: SP_V(C, 2) case 1: SP_V(C, 1) default: SP_V(C, 0) \
-    }
-    if (a.channel_mode) { SP_CH(true) } else { SP_CH(false) }
-#undef SP_V
-#undef SP_CH
+    SP_LAUNCH_VARIANT(k_frames_peak, peak_m, peak_nsamp)
 }
 #endif
 
-// Host-side launch for a request with peak_m >= 2 sub-frames per column; groups and grid by launch_frames' rule on the columns.
+// Host-side launch for a request with peak_m >= 2 sub-frames per column; groups and grid by the launch rule on the columns.
 // peak_nsamp = floor(sampleCount).  Returns SP_OK or SP_ERR_UNSUPPORTED.
 inline int launch_frames_peak(const FrameArgs &a, int format, const double2 *stage_tw, int peak_m, int peak_nsamp, int cu_count, int device,
                               hipStream_t stream)
 {
     const int prefetch = frames_prefetch_width(a.sample_width, a.in_bounds, a.stride, a.width);
-    if (!frames_peak_supports(a.n) || a.lut_len > kLdsMaxLut || a.lut_len < 2 || peak_m < 2) return SP_ERR_UNSUPPORTED;
-    const int gf = frames_group_frames(a.n, a.x_end - a.frame0, cu_count);
-    if (gf & (gf - 1)) return SP_ERR_UNSUPPORTED;
-    const int groups = (a.x_end - a.frame0 + gf - 1) / gf;
-    const Layout lay = layout(a.n, a.lut_len, gf);
-    if (lay.total > 160 * 1024) return SP_ERR_UNSUPPORTED;
-    const int grid = frames_grid(groups, cu_count);
+    FramesLaunch fl;
+    if (!frames_peak_supports(a.n) || peak_m < 2 || frames_launch_rule(a.n, a.lut_len, a.x_end - a.frame0, cu_count, 0, fl)) return SP_ERR_UNSUPPORTED;
     switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_peak_n<L>(a, format, stage_tw, grid, lay.total, gf, groups, prefetch, peak_m, peak_nsamp, device, stream);
+#define SP_L(L) case L: return launch_frames_peak_n<L>(a, format, stage_tw, fl, prefetch, device, stream, peak_m, peak_nsamp);
         SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10)
 #undef SP_L
     default: return SP_ERR_UNSUPPORTED;

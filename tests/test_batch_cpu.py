@@ -1,18 +1,15 @@
 """Batches without a device: the new entry points are exported and check their arguments, the host's work list (sp_debug_batch_plan)
-covers every frame of every item once with launch_frames' rules, and the batch kernels leave k_frames as it was."""
+covers every frame of every item once with launch_frames' rules, and the batch kernels' prefetching variants use no scratch memory
+(tests/test_isa_checks.py compares the instruction streams of k_frames and k_frames_batch with their reference commits)."""
 import ctypes as C
-import glob
 import os
 import re
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from __graft_entry__ import ROOT, build, load_package
+import isa
+from __graft_entry__ import build, load_package
 
 SW = [1, 1, 2, 2, 3, 3, 4, 4, 8, 8, 16, 16, 8, 16]      # bytes per complex sample, enum sp_format order
 ELEM = [1, 1, 1, 1, 1, 1, 2, 2, 4, 4, 8, 8, 4, 8]        # element size of the typed view
@@ -133,31 +130,12 @@ def test_batch_work_list_on_random_item_lists(pkg):
     assert checked > 1500
 
 
-def _notes(obj):
-    llvm = "/opt/rocm/lib/llvm/bin"
-    with tempfile.TemporaryDirectory() as t:
-        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, os.path.join(t, "fb.bin")])
-        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + os.path.join(t, "fb.bin"),
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + os.path.join(t, "k.co")],
-                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        return subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", os.path.join(t, "k.co")], text=True)
-
-
-def _frame_objs():
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    if len(objs) < 8:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    assert len(objs) == 8
-    return objs
-
-
 def test_batch_kernels_prefetching_iq_variants_use_no_scratch_memory():
     """Every I/Q prefetching variant of k_frames_batch has a private segment of zero bytes and no spilled VGPR, as every k_frames one
     (test_isa_checks.py).  The batch kernel is built for n = 64 ... 512 only; no object holds one for a larger n."""
     seen = 0
-    for o in _frame_objs():
-        for blk in _notes(o).split(".name:")[1:]:
+    for o in isa.frame_objs():
+        for blk in isa.notes(o).split(".name:")[1:]:
             m = re.match(r"\s*_ZN4spk214k_frames_batchILi(\d+)ELb([01])ELi(\d+)E", blk)
             if not m:
                 continue
@@ -169,84 +147,3 @@ def test_batch_kernels_prefetching_iq_variants_use_no_scratch_memory():
             spill = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", blk).group(1))
             assert priv == 0 and spill == 0, (m.group(0), priv, spill)
     assert seen == 4 * 5           # four sizes x five prefetch widths
-
-
-def _k_frames_streams(objs, prefix="_ZN4spk28k_framesI"):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import check_lds_reads as c
-    out = {}
-    for o in objs:
-        cur = None
-        for ln in c.disassemble(o):
-            h = re.match(r"^[0-9a-f]+ <(.*)>:", ln)
-            if h:
-                cur = h.group(1) if h.group(1).startswith(prefix) else None
-                if cur:
-                    out[cur] = []
-                continue
-            t = re.sub(r"<[^>]*>", "", re.sub(r"^\s*[0-9a-f]+:\s*", "", ln.split("//")[0])).strip()
-            if cur and t and t != "...":
-                out[cur].append(t)
-    # what follows a kernel's last s_endpgm is alignment padding (zero dwords, which disassemble as v_cndmask_b32), not its code
-    for k, v in out.items():
-        ends = [i for i, t in enumerate(v) if t.startswith("s_endpgm")]
-        out[k] = v[:ends[-1] + 1] if ends else v
-    return out
-
-
-def test_k_frames_instruction_streams_match_the_parent_commit():
-    """Every k_frames<L, C, P> of this tree has the instruction stream (addresses stripped) of the commit before the batch kernel was
-    added: the batch path must not move the single-request kernels.  This guards that change only: a later commit that changes k_frames
-    on purpose replaces the reference below with its own parent (HEAD^ of the commit that last touched sp_kernel_frames.h's loop)."""
-    if shutil.which("git") is None or not os.path.isdir(os.path.join(ROOT, ".git")):
-        pytest.skip("no git history here to build the parent commit from")
-    git = lambda *a: subprocess.run(["git", "-C", ROOT] + list(a), capture_output=True, text=True)  # noqa: E731
-    added = git("log", "--diff-filter=A", "--format=%H", "--", "spectroplot-js_amd/csrc/sp_kernel_frames_batch.h").stdout.split()
-    ref = (added[-1] + "^") if added else "HEAD"
-    if git("rev-parse", "--verify", "-q", ref).returncode:
-        pytest.skip("the parent commit is not in this clone's history")
-    mine = _k_frames_streams(_frame_objs())
-    with tempfile.TemporaryDirectory() as t:
-        wt = os.path.join(t, "parent")
-        r = git("worktree", "add", "--detach", wt, ref)
-        if r.returncode:
-            pytest.skip("git worktree failed: " + r.stderr[-200:])
-        try:
-            subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(wt, "spectroplot-js_amd")]
-                                  + ["build/frames_%d.o" % lg for lg in range(6, 14)])
-            theirs = _k_frames_streams(sorted(glob.glob(os.path.join(wt, "spectroplot-js_amd", "build", "frames_*.o"))))
-        finally:
-            git("worktree", "remove", "--force", wt)
-    assert len(theirs) == 96 and set(mine) == set(theirs)
-    differ = [k for k in theirs if mine[k] != theirs[k]]
-    assert not differ, differ[:5]
-
-
-def test_k_frames_batch_instruction_streams_match_the_commit_that_added_them():
-    """Every k_frames_batch<L, C, P> of this tree (n = 64 ... 512) has the instruction stream (addresses stripped) of the commit that added
-    sp_kernel_frames_batch.h: sharing the frame loop's stages with k_frames (the sp_frames_*.inc.h fragments) must not move the batch
-    kernel either.  This guards that change only: a later commit that changes k_frames_batch on purpose replaces the reference below with
-    its own parent (HEAD^ of the commit that last touched the batch kernel's loop)."""
-    if shutil.which("git") is None or not os.path.isdir(os.path.join(ROOT, ".git")):
-        pytest.skip("no git history here to build the reference commit from")
-    git = lambda *a: subprocess.run(["git", "-C", ROOT] + list(a), capture_output=True, text=True)  # noqa: E731
-    added = git("log", "--diff-filter=A", "--format=%H", "--", "spectroplot-js_amd/csrc/sp_kernel_frames_batch.h").stdout.split()
-    ref = added[-1] if added else "HEAD"
-    if git("rev-parse", "--verify", "-q", ref).returncode:
-        pytest.skip("the reference commit is not in this clone's history")
-    prefix = "_ZN4spk214k_frames_batchI"
-    mine = _k_frames_streams(_frame_objs(), prefix)
-    with tempfile.TemporaryDirectory() as t:
-        wt = os.path.join(t, "reference")
-        r = git("worktree", "add", "--detach", wt, ref)
-        if r.returncode:
-            pytest.skip("git worktree failed: " + r.stderr[-200:])
-        try:
-            subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(wt, "spectroplot-js_amd")]
-                                  + ["build/frames_%d.o" % lg for lg in range(6, 14)])
-            theirs = _k_frames_streams(sorted(glob.glob(os.path.join(wt, "spectroplot-js_amd", "build", "frames_*.o"))), prefix)
-        finally:
-            git("worktree", "remove", "--force", wt)
-    assert len(theirs) == 48 and set(mine) == set(theirs)
-    differ = [k for k in theirs if mine[k] != theirs[k]]
-    assert not differ, differ[:5]

@@ -3,24 +3,17 @@
 The re-distributions of the frame loop read LDS with inline-asm ds_read_b64 instructions whose wait comes later, in a separate asm
 statement (sp_frame_parts.h); the compiler does not know the destination registers are invalid in between.  tools/check_lds_reads.py
 follows the in-order LDS counter through every kernel of the product and fails on any access to a register with an outstanding read."""
-import glob
-import importlib.util
 import os
+import re
 
 import pytest
 
-from __graft_entry__ import ROOT, build
-
-
-def _checker():
-    spec = importlib.util.spec_from_file_location("check_lds_reads", os.path.join(ROOT, "tools", "check_lds_reads.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+import isa
+from __graft_entry__ import ROOT
 
 
 def test_checker_sees_a_register_touched_before_its_read_has_returned():
-    c = _checker()
+    c = isa.checker()
     ok = """
 0000000000001000 <k>:
 	ds_write_b64 v10, v[2:3]                                   // 000000001000: D89A0000 0000020A
@@ -43,13 +36,8 @@ def test_checker_sees_a_register_touched_before_its_read_has_returned():
 
 
 def test_no_kernel_of_the_product_touches_a_register_with_an_outstanding_lds_read():
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "*.o")))
-    if len(objs) < 9:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "*.o")))
-    objs = [o for o in objs if not o.endswith("sp_host.o")]
-    assert len(objs) >= 9
-    c = _checker()
+    objs = isa.product_objs()
+    c = isa.checker()
     bad, reads = [], 0
     for o in objs:
         lines = c.disassemble(o)
@@ -63,31 +51,16 @@ def test_the_prefetching_iq_variants_of_the_frame_loop_use_no_scratch_memory():
     """A kernel that touches scratch (spilled VGPRs, or the argument structure dropped to the stack because a lambda was not inlined: it
     happened in an experiment and cost 40 %) launches its waves slower and reads its arguments from memory.  Every variant the BASELINE
     configs run - interleaved I/Q, samples prefetched (PFB != 0) - must have a private segment of zero bytes and no spilled VGPR."""
-    import re
-    import subprocess
-    import tempfile
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    if len(objs) < 8:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    assert len(objs) == 8
-    llvm = "/opt/rocm/lib/llvm/bin"
     seen = 0
-    with tempfile.TemporaryDirectory() as t:
-        for o in objs:
-            subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", o, os.path.join(t, "fb.bin")])
-            subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + os.path.join(t, "fb.bin"),
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + os.path.join(t, "k.co")],
-                                  stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", os.path.join(t, "k.co")], text=True)
-            for blk in notes.split(".name:")[1:]:
-                m = re.match(r"\s*_ZN4spk28k_framesILi(\d+)ELb([01])ELi(\d+)E", blk)
-                if not m or m.group(2) == "1" or m.group(3) == "0":
-                    continue
-                seen += 1
-                priv = int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1))
-                spill = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", blk).group(1))
-                assert priv == 0 and spill == 0, (m.group(0), priv, spill)
+    for o in isa.frame_objs():
+        for blk in isa.notes(o).split(".name:")[1:]:
+            m = re.match(r"\s*_ZN4spk28k_framesILi(\d+)ELb([01])ELi(\d+)E", blk)
+            if not m or m.group(2) == "1" or m.group(3) == "0":
+                continue
+            seen += 1
+            priv = int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1))
+            spill = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", blk).group(1))
+            assert priv == 0 and spill == 0, (m.group(0), priv, spill)
     assert seen == 8 * 5           # eight sizes x five prefetch widths
 
 
@@ -95,12 +68,8 @@ def test_the_prologue_waits_for_its_tables_not_for_the_first_frames_samples():
     """n <= 1024, prefetching variants: the first frame's 16 sample loads are issued BEHIND the table loads and the wait in front of the
     LDS table stores counts them (s_waitcnt vmcnt(16)).  Vector-memory operations complete in order: a vmcnt(0) there - the samples
     requested ahead of the tables, or a request the compiler cannot count - makes the table wait a wait for HBM (+1.5 us per launch)."""
-    import re
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    if len(objs) < 8:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o")))
-    c = _checker()
+    objs = isa.frame_objs()
+    c = isa.checker()
     seen = 0
     for o in objs:
         m = re.search(r"frames_(\d+)\.o$", o)
@@ -146,7 +115,6 @@ def test_the_instrumentation_patch_applies_to_the_kernel_sources():
 
 def _regs(operand):
     """VGPR numbers an operand names: 'v7' -> {7}, 'v[4:7]' -> {4..7}, anything else -> empty."""
-    import re
     m = re.fullmatch(r"v(\d+)", operand)
     if m:
         return {int(m.group(1))}
@@ -160,7 +128,6 @@ def store_hazards(lines, where=""):
     """gfx940 / gfx950: a VMEM store of more than 64 bits reads its data registers late - a VALU instruction that overwrites them needs 2
     wait states behind the store (LLVM's GCNHazardRecognizer inserts them for stores it knows; k_frames issues its write-out stores as
     inline asm, which it cannot see: ADVICE r5).  Returns the stores followed within 2 wait states by a VALU write to their data."""
-    import re
     ins = []
     for ln in lines:
         t = ln.replace("\t", " ").split("//")[0].strip()
@@ -203,12 +170,8 @@ def test_store_hazard_checker_sees_a_data_register_overwritten_too_early():
 
 
 def test_no_valu_write_lands_on_the_data_of_a_wide_store_within_two_wait_states():
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "*.o")))
-    if len(objs) < 9:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "*.o")))
-    objs = [o for o in objs if not o.endswith("sp_host.o")]
-    c = _checker()
+    objs = isa.product_objs()
+    c = isa.checker()
     bad, stores = [], 0
     for o in objs:
         lines = c.disassemble(o)
@@ -216,3 +179,35 @@ def test_no_valu_write_lands_on_the_data_of_a_wide_store_within_two_wait_states(
         bad += store_hazards(lines, os.path.basename(o))
     assert stores > 500            # the write-out's 16-byte stores are there, in every variant
     assert not bad, bad[:10]
+
+
+_BATCH_H = "spectroplot-js_amd/csrc/sp_kernel_frames_batch.h"
+_PEAK_H = "spectroplot-js_amd/csrc/sp_kernel_frames_peak.h"
+
+
+# family -> (prefix of the mangled names, the file whose first commit is the reference, "^" for that commit's parent, the objects, streams)
+STREAM_FAMILIES = {
+    "k_frames": ("_ZN4spk28k_framesI", _BATCH_H, "^", isa.FRAME_TARGETS, isa.frame_objs, 96),
+    "k_frames_batch": ("_ZN4spk214k_frames_batchI", _BATCH_H, "", isa.FRAME_TARGETS, isa.frame_objs, 48),
+    "k_frames_peak": ("_ZN4spk213k_frames_peakI", _PEAK_H, "", isa.PEAK_TARGETS, isa.peak_objs, 60),
+}
+
+
+@pytest.mark.parametrize("family", sorted(STREAM_FAMILIES))
+def test_frame_loop_instruction_streams_match_their_reference_commit(family):
+    """Every variant <L, C, P> of the three frame-loop kernels has the instruction stream (addresses stripped) of a reference build: k_frames
+    of the commit before the batch kernel was added, k_frames_batch of the commit that added sp_kernel_frames_batch.h, k_frames_peak of the
+    commit that added sp_kernel_frames_peak.h.  What the kernels share since - the sp_frames_*.inc.h fragments of the stages, of the
+    prologue, the write-out lambdas and the finale - must not move any of them.  This guards those changes only: a later commit that
+    changes a kernel on purpose replaces that family's reference with its own parent (HEAD^ of the commit that last touched the kernel's
+    loop)."""
+    prefix, added_file, parent, targets, objs, count = STREAM_FAMILIES[family]
+    try:
+        added = isa.commit_that_added(added_file)
+        theirs = isa.commit_streams(added + parent if added != "HEAD" else "HEAD", targets, prefix)
+    except isa.NoReference as e:
+        pytest.skip(str(e))
+    mine = isa.streams(objs(), prefix)
+    assert len(theirs) == count and set(mine) == set(theirs)
+    differ = [k for k in theirs if mine[k] != theirs[k]]
+    assert not differ, differ[:5]

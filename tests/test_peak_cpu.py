@@ -2,13 +2,13 @@
 construction the GPU tests use (tests/peakref.py) against the oracle where the two must agree, the ABI, and the compiled k_frames_peak
 variants with their register / spill table."""
 import ctypes as C
-import glob
 import os
 import re
 
 import numpy as np
 import pytest
 
+import isa
 import peakref
 import siggen
 from __graft_entry__ import ROOT, build, load_package
@@ -135,15 +135,10 @@ PEAK_SPILLS = {
 
 
 def test_k_frames_peak_variants_exist_with_the_documented_spill_table():
-    import test_batch_cpu as tb
-    objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "peak_*.o")))
-    if len(objs) < 5:
-        build()
-        objs = sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "peak_*.o")))
-    assert len(objs) == 5
+    objs = isa.peak_objs()
     seen = {}
     for o in objs:
-        for blk in tb._notes(o).split(".name:")[1:]:
+        for blk in isa.notes(o).split(".name:")[1:]:
             m = re.match(r"\s*_ZN4spk213k_frames_peakILi(\d+)ELb([01])ELi(\d+)E", blk)
             if not m:
                 continue
@@ -159,7 +154,7 @@ def test_k_frames_peak_variants_exist_with_the_documented_spill_table():
         if not ch and p:          # the variants the measured shapes run: no scratch memory at all inside the sub-frame loop
             assert priv == 0 and spill == 0, ((lg, ch, p), priv, spill)
     # no object of the sample detector's kernels holds a peak kernel, and the other way round
-    for o in sorted(glob.glob(os.path.join(ROOT, "spectroplot-js_amd", "build", "frames_*.o"))):
-        assert "k_frames_peak" not in tb._notes(o)
+    for o in isa.frame_objs():
+        assert "k_frames_peak" not in isa.notes(o)
     for o in objs:
-        assert "_ZN4spk28k_framesI" not in tb._notes(o)
+        assert "_ZN4spk28k_framesI" not in isa.notes(o)
