@@ -26,6 +26,8 @@
  *   sp_render_batch          lib/worker.js:23-156 per item + lib/easy.js:22-72 / lib/spectroplot.js:85-116   many instances' requests
  *                                                        queued on one worker pool (one Spectroplot per dropped file), on host buffers
  *   sp_debug_batch_plan      (none)                     (tests) the host's work list for a batch
+ *   sp_plan_debug_launch     (none)                     (tests) the launch sp_plan_execute would make for a request
+ *   sp_debug_frames_launch   (none)                     (tests) the frame-loop kernels' launch rule alone
  *   sp_merge_replies(_batch) lib/spectroplot.js:1229-1238   the caller's merge of the slices' histograms and dBfs range, on the device
  *   sp_place_strips          lib/spectroplot.js:1241-1244   the caller's putImageData of every slice's strip, on the device
  *   sp_group_render          lib/spectroplot.js:1206-1244, lib/samples.js:253-258   the caller's sliced render: one slice per device, the
@@ -379,6 +381,26 @@ int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_batch_item 
  */
 int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, int32_t cu_count, const size_t *nbytes, const int32_t *widths,
                         int32_t count, int64_t *out, size_t capacity, size_t *used);
+
+/*
+ * (tests) The launch sp_plan_execute would make for a request of nbytes bytes and `width` frames on this plan's context, whose reply's
+ * image is at `rgba` (only the address is looked at).  It is computed by the functions the launch path itself calls (request_shape,
+ * request_kernel, frames_prefetch_width, frames_launch_rule, rgba_fast in sp_api.hip / sp_kernel_frames.h); nothing is launched.
+ * out[] receives 11 int64 words: the kernel (0 nothing to render: width 0, 1 scratch_radix2, 3 k_frames, 4 k_frames_peak), log2 n,
+ * channel mode, the prefetching loader's sample width (0: the generic loaders), frames per group, groups, workgroups, dynamic LDS
+ * bytes (these four 0 behind the scratch kernel), whether the write-out stores the image in 16-byte pieces, the peak detector's
+ * sub-frames per column (1: the sample detector's request), the context's CU count.  *used = words needed (SP_ERR_INVALID_ARG if
+ * capacity is smaller).
+ */
+int sp_plan_debug_launch(const sp_plan *plan, size_t nbytes, int32_t width, const void *rgba, int64_t *out, size_t capacity, size_t *used);
+/*
+ * (tests) The launch rule of the three frame-loop kernels alone (frames_launch_rule, sp_kernel_frames.h), without a plan or a device:
+ * `count` frames - or columns of a peak request - on a part with cu_count CUs (gf_fixed = 0), or `count` groups of gf_fixed frames
+ * that a batch has dealt already.  out[] receives 4 int64 words: frames per group, groups, workgroups, dynamic LDS bytes.
+ * SP_ERR_UNSUPPORTED where the rule refuses (n outside 64 ... 8192, lut_len outside 2 ... 256).
+ */
+int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count, int32_t cu_count, int32_t gf_fixed, int64_t *out, size_t capacity,
+                           size_t *used);
 
 /* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else).
  * A peak plan answers what its M >= 2 requests take: "frames_peak" (64 <= n <= 1024 and what "frames" asks for) or "scratch_radix2". */

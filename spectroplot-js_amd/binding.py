@@ -159,6 +159,8 @@ class Library:
         L.sp_render_named_ex.argtypes = [vp, C.POINTER(_NamedRequest), i32, vp, sz, i32, C.POINTER(_Reply)]
         L.sp_plan_kernel_name_for.restype = C.c_char_p
         L.sp_plan_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_plan_debug_launch.argtypes = [vp, sz, i32, vp, vp, sz, C.POINTER(sz)]
+        L.sp_debug_frames_launch.argtypes = [i32, i32, C.c_int64, i32, i32, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -221,6 +223,24 @@ def debug_batch_plan(fmt, n, lut_len, cu_count, nbytes, widths):
     lib.check(lib.L.sp_debug_batch_plan(fid, int(n), int(lut_len), int(cu_count), nb.ctypes.data_as(C.c_void_p),
                                         wd.ctypes.data_as(C.c_void_p), len(wd), out.ctypes.data_as(C.c_void_p), cap, C.byref(used)))
     return int(out[0]), (int(out[1]), int(out[2])), (int(out[3]), int(out[4])), out[5:used.value].reshape(-1, 3)
+
+
+def debug_frames_launch(n, lut_len, count, cu_count, gf_fixed=0):
+    """The frame-loop kernels' launch rule alone (sp_debug_frames_launch): (frames per group, groups, workgroups, LDS bytes) for `count`
+    frames, or for `count` groups of gf_fixed frames; None where the rule refuses the shape."""
+    lib = Library.get()
+    out = np.zeros(4, np.int64)
+    used = C.c_size_t()
+    rc = lib.L.sp_debug_frames_launch(int(n), int(lut_len), int(count), int(cu_count), int(gf_fixed), out.ctypes.data_as(C.c_void_p), 4,
+                                      C.byref(used))
+    if rc == SP_ERR_UNSUPPORTED:
+        return None
+    lib.check(rc)
+    return tuple(int(v) for v in out)
+
+
+LAUNCH_FIELDS = ("kernel", "log2n", "channel_mode", "prefetch", "gf", "groups", "grid", "lds_bytes", "rgba_fast", "peak_m", "cu_count")
+KERNELS = {0: "none", 1: "scratch_radix2", 3: "frames", 4: "frames_peak"}      # enum Kernel (sp_api.hip)
 
 
 def peak_subframes(fmt, n, nbytes, width):
@@ -460,6 +480,17 @@ class Plan:
         if nbytes is None:
             return self.ctx.lib.L.sp_plan_kernel_name(self.h).decode()
         return self.ctx.lib.L.sp_plan_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def debug_launch(self, nbytes, width, rgba=0):
+        """What execute() would launch for a request of this shape whose image is at device address `rgba` (sp_plan_debug_launch): a
+        dict of LAUNCH_FIELDS, "kernel" as a name of KERNELS."""
+        out = np.zeros(len(LAUNCH_FIELDS), np.int64)
+        used = C.c_size_t()
+        self.ctx._chk(self.ctx.lib.L.sp_plan_debug_launch(self.h, int(nbytes), int(width), C.c_void_p(rgba or None),
+                                                          out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
+        d = dict(zip(LAUNCH_FIELDS, (int(v) for v in out)))
+        d["kernel"] = KERNELS[d["kernel"]]
+        return d
 
     def force_kernel(self, which):
         self.ctx._chk(self.ctx.lib.L.sp_plan_force_kernel(self.h, {"auto": 0, "scratch": 1, "frames": 3}[which]))

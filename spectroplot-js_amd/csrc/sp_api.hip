@@ -954,6 +954,47 @@ extern "C" int sp_plan_execute(sp_plan *plan, const void *d_bytes, size_t nbytes
     return plan_execute_range(plan, d_bytes, request_shape(plan, nbytes, width), 0, width < 0 ? 0 : width, true, true, out);
 }
 
+// (tests) What sp_plan_execute would launch for a request of this shape on this plan's context, from the launch path's own functions:
+// request_shape and request_kernel as plan_execute_range calls them, frames_prefetch_width and frames_launch_rule as launch_frames /
+// launch_frames_peak call them, rgba_fast on the reply's image pointer.  Nothing is launched and nothing on the device is touched.
+extern "C" int sp_plan_debug_launch(const sp_plan *plan, size_t nbytes, int32_t width, const void *rgba, int64_t *out, size_t capacity,
+                                    size_t *used)
+{
+    if (!plan || !plan->ctx || width < 0 || !used) return SP_ERR_INVALID_ARG;
+    const RequestShape shape = request_shape(plan, nbytes, width);
+    const spgeo::Geometry &g = shape.g;
+    const int n = plan->req.n, cu_count = plan->ctx->cu_count;
+    const int which = width == 0 ? kKernelAuto : request_kernel(plan, shape.peak.m);   // (width 0: the reply is only cleared)
+    spk2::FramesLaunch fl{0, 0, 0, 0};
+    int prefetch = 0;
+    if (finishes_request(which)) {
+        prefetch = spk2::frames_prefetch_width(plan->fmt.width, g.in_bounds, g.stride, g.width);
+        if (spk2::frames_launch_rule(n, plan->req.lut_len, width, cu_count, 0, fl)) return SP_ERR_UNSUPPORTED;
+    }
+    const int64_t v[] = {which, plan->levels, plan->req.channel_mode ? 1 : 0, prefetch, fl.gf, fl.groups, fl.grid, fl.lds_bytes,
+                         rgba_fast((const uint8_t *)rgba, width, n) ? 1 : 0, shape.peak.m, cu_count};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+// (tests) The launch rule alone, without a plan or a device: frames_launch_rule's answer for `count` frames (gf_fixed = 0) or `count`
+// groups of gf_fixed frames (a batch launch) on a part with cu_count CUs.
+extern "C" int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count, int32_t cu_count, int32_t gf_fixed, int64_t *out,
+                                      size_t capacity, size_t *used)
+{
+    if (n < 2 || sphost::log2_exact(n) < 0 || count < 1 || count > 2147483647 || cu_count < 1 || gf_fixed < 0 || !used) return SP_ERR_INVALID_ARG;
+    spk2::FramesLaunch fl{0, 0, 0, 0};
+    const int rc = spk2::frames_launch_rule(n, lut_len, count, cu_count, gf_fixed, fl);
+    if (rc) return rc;
+    const int64_t v[] = {fl.gf, fl.groups, fl.grid, fl.lds_bytes};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- merge of slice replies
 
 // `rank_stride`: 64-bit words between two ranks' records of the same render; blockIdx.y: the render of a batch (its records start

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import isa
+from launchref import batch_gf as _batch_gf, group_frames_for as _group_frames_for  # noqa: F401
 from __graft_entry__ import build, load_package
 
 SW = [1, 1, 2, 2, 3, 3, 4, 4, 8, 8, 16, 16, 8, 16]      # bytes per complex sample, enum sp_format order
@@ -47,22 +48,6 @@ def test_batch_symbols_and_argument_errors(pkg):
     assert lib.sp_render_batch(None, None, items, 2) == want
     with pytest.raises(pkg.SpectroplotError):
         pkg.binding.debug_batch_plan("cu8", 512, 256, 256, [100], [-1])
-
-
-def _group_frames_for(n, want):
-    fpb = 512 * 16 // n
-    unit = fpb
-    while unit % 4:
-        unit *= 2
-    cap = min((65536 if n >= 2048 else 32768) // n, want)
-    return max(cap // unit * unit, unit)
-
-
-def _batch_gf(n, total, cu):
-    want = 32
-    while want > 4 and (total + want - 1) // want < 2 * cu:
-        want >>= 1
-    return _group_frames_for(n, want)
 
 
 def _launch(fmt, n, nbytes, w):
