@@ -417,6 +417,36 @@ const char *sp_plan_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t 
 int sp_plan_force_kernel(sp_plan *plan, int32_t which);
 
 /*
+ * Per-bin min / max traces over a request: what a spectrum viewer draws as its min-hold and max-hold traces.
+ * The request's frames are sp_plan_execute's (the same geometry, limits and statuses; channel mode honoured).  With
+ * d(x, i) = dBfs - gain of frame x, bin i exactly as lib/worker.js:92-93, 102 computes it, the fold runs in order of x:
+ *     trace_min[y] = 0.0;   if (d(x, i) < trace_min[y]) trace_min[y] = d(x, i)
+ *     trace_max[y] = -200;  if (d(x, i) > trace_max[y]) trace_max[y] = d(x, i)
+ * with y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90): trace_*[y] belongs to image row y of the spectrogram layout and to
+ * column n - 1 - y of the waterfall layout, and the arrays are the same for both layouts.  This is the worker's own fold of a
+ * column's extremes (gauge_mins / gauge_maxs) with its own start values, turned by 90 degrees: a NaN never wins; a bin that is NaN
+ * in every column, and width == 0, give (0, -200); an all-zero frame gives trace_min = -inf.  Hence, bit for bit,
+ * min over y of trace_min[y] == dBfs_min and max over y of trace_max[y] == dBfs_max of sp_render on the same request.
+ * The outputs are two f64[n] arrays; either may be NULL.  No image is written and no other reply field is produced.
+ * Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.  (There is no mean-power trace: an f64
+ * sum over frames depends on the deal of frames to workgroups; min and max do not.)
+ *
+ * sp_plan_execute_traces: device-resident operands, asynchronous on the context's stream; d_trace_min / d_trace_max are device
+ * pointers, 8-byte aligned (SP_ERR_INVALID_ARG otherwise).  Three kernels and no request number: a stream that is being captured is
+ * not refused.
+ * sp_render_traces: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for a request whose image
+ * stays on the device (sp_plan_execute_from_host): a sparse request (stride > n) uploads only what its frames read, a large one
+ * travels in chunks of frames under the frame loops of earlier chunks; sp_context_last_upload_bytes reports what travelled.
+ * sp_plan_traces_kernel_name_for: "frames_traces" (64 <= n <= 1024 and a finite taper; LUT length and edge ranges do not matter)
+ * or "scratch_traces" (everything else).  sp_plan_force_kernel applies as to renders: 1 forces "scratch_traces", 3 means
+ * "frames_traces" where that kernel covers the plan.
+ */
+int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_trace_min, double *d_trace_max);
+int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *trace_min,
+                     double *trace_max);
+const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
  * Page-locked host memory for request / reply buffers: sp_render moves pinned buffers at the full rate of the host link, pageable
  * ones through the runtime's staging copies.  The N-API addon backs the reply ArrayBuffers it hands out with these.
  */

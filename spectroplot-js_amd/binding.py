@@ -161,6 +161,10 @@ class Library:
         L.sp_plan_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_plan_debug_launch.argtypes = [vp, sz, i32, vp, vp, sz, C.POINTER(sz)]
         L.sp_debug_frames_launch.argtypes = [i32, i32, C.c_int64, i32, i32, vp, sz, C.POINTER(sz)]
+        L.sp_plan_execute_traces.argtypes = [vp, vp, sz, i32, vp, vp]
+        L.sp_render_traces.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, vp]
+        L.sp_plan_traces_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_traces_kernel_name_for.argtypes = [vp, sz, i32]
 
     @classmethod
     def get(cls):
@@ -439,6 +443,23 @@ class Context:
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
+    def render_traces(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, lut=None, fill=None):
+        """sp_render_traces: the per-bin min-hold / max-hold traces of the request, {"trace_min": f64[n], "trace_max": f64[n]} in image
+        row order.  No image is rendered; `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a value the
+        output arrays hold before the call (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if lut is None:
+            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        tmin, tmax = np.zeros(n), np.zeros(n)
+        if fill is not None:
+            tmin[:] = fill
+            tmax[:] = fill
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), p(data), data.size, int(width), p(tmin), p(tmax)))
+        return {"trace_min": tmin, "trace_max": tmax}
+
     def plan_creations(self):
         n = C.c_int64()
         self._chk(self.lib.L.sp_context_plan_creations(self.h, C.byref(n)))
@@ -500,6 +521,16 @@ class Plan:
         rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
                      dbfs_minmax or None)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute(self.h, C.c_void_p(d_bytes), nbytes, int(width), C.byref(rep)))
+
+    def traces_kernel_name_for(self, nbytes, width):
+        """The frame loop execute_traces() launches for a request of this shape: "frames_traces" or "scratch_traces"."""
+        return self.ctx.lib.L.sp_plan_traces_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def execute_traces(self, d_bytes, nbytes, width, trace_min=0, trace_max=0):
+        """sp_plan_execute_traces: the per-bin min / max traces of the request into two f64[n] device arrays (addresses; 0 skips one).
+        Asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_traces(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                            C.c_void_p(trace_min or None), C.c_void_p(trace_max or None)))
 
     def execute_batch(self, items):
         """sp_plan_execute_batch: `items` = [(d_bytes, nbytes, width, {"rgba": addr, "gauge_mins": ..., "c_hist": ..., "cb_hist": ...,

@@ -18,6 +18,7 @@
 #include "sp_host.h"
 #include "sp_kernel_frames_batch.h"
 #include "sp_kernel_frames_peak.h"
+#include "sp_kernel_frames_traces.h"
 #include "sp_kernel_scratch.h"
 #include "sp_synth.h"
 #include "sp_cmap_tables.h"
@@ -102,6 +103,7 @@ struct sp_context {
     DeviceBuffer frame_minmax;   // 2 * width doubles (the scratch kernel's frame extremes, read by k_finish_frames)
     DeviceBuffer partial;        // [0,4) the number of the last request k_frames has started; the scratch kernel's {min,max} and histogram accumulators
     DeviceBuffer scratch;        // scratch kernel slabs
+    DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
     // staging for sp_render (host-buffer entry point)
     DeviceBuffer in_bytes, out_rgba, render_small;
     HostBuffer host_small;
@@ -371,6 +373,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->frame_minmax.release();
     ctx->partial.release();
     ctx->scratch.release();
+    ctx->traces_ws.release();
     ctx->in_bytes.release();
     ctx->out_rgba.release();
     ctx->render_small.release();
@@ -1316,6 +1319,209 @@ extern "C" int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbyte
 {
     if (!ctx || !nbytes) return SP_ERR_INVALID_ARG;
     *nbytes = ctx->last_upload_bytes;
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- per-bin min / max traces
+
+// k_frames_traces needs what k_frames needs of the transform - a finite taper (the (1, 0) butterflies skip their products on integer
+// samples) and the first-pass twiddle literals - and nothing of the picture: LUT length and edge ranges do not matter to a trace.
+static bool plan_traces_frames(const sp_plan *plan)
+{
+    return plan->force_kernel != kKernelScratch && spk2::frames_traces_supports(plan->req.n) && plan->taper_finite && plan->tw16_ok;
+}
+
+extern "C" const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
+    return !plan ? "" : plan_traces_frames(plan) ? "frames_traces" : "scratch_traces";
+}
+
+// what every traces entry point refuses before it touches the device
+static int check_traces(sp_plan *plan, const void *bytes, size_t nbytes, int32_t width)
+{
+    sp_context *ctx = plan->ctx;
+    if (plan->req.detector != SP_DETECTOR_SAMPLE)
+        return fail(ctx, SP_ERR_UNSUPPORTED, "traces of a peak plan are not supported (the traces fold the sample detector's frames)");
+    return check_capture(ctx, plan->fmt, plan->req.n, bytes, nbytes, width, nullptr, "");
+}
+
+static int traces_clear(sp_plan *plan)
+{
+    sp_context *ctx = plan->ctx;
+    const int n = plan->req.n;
+    const int rc = ctx->traces_ws.reserve(2 * (size_t)n * sizeof(unsigned long long));
+    if (rc) return fail(ctx, rc, "traces workspace: out of device memory");
+    hipLaunchKernelGGL(spk::k_traces_clear, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (unsigned long long *)ctx->traces_ws.p, n);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// The frame loop over frames [x_begin, x_end) of a traces request, into the context's workspace (`src`: as for plan_execute_range).
+static int traces_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = plan->req.n;
+    const bool frames = plan_traces_frames(plan);
+    if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
+    const size_t nbytes = src ? src->nbytes : g.nbytes;
+    spk::FrameArgs a{};
+    plan_frame_args(plan, a);
+    a.bytes = (const uint8_t *)(src ? src->bytes : d_bytes);
+    a.nbytes = (int64_t)nbytes;
+    a.nelem = (int64_t)(nbytes / (size_t)plan->fmt.elem);
+    a.stride = src ? src->stride : g.stride;
+    a.width = g.width;
+    a.in_bounds = src || g.in_bounds ? 1 : 0;
+    a.frame0 = x_begin;
+    a.x_end = x_end;
+    unsigned long long *const ws = (unsigned long long *)ctx->traces_ws.p;
+    hipStream_t s = ctx->stream;
+    if (frames) {
+        a.lut_len = spk2::kTracesLutLen;   // (the shared prologue copies this many LUT and edge entries: the plan's tables hold them)
+        a.cells = 0;
+        const int rc = spk2::launch_frames_traces(a, plan->req.format, plan->d_stage_tw, ws, ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, "k_frames_traces launch rejected the configuration");
+    } else {
+        // four slabs per workgroup (re, im, the bins' minima and maxima), capped at 256 MiB
+        long long blocks = (256ll << 20) / (32ll * n);
+        if (blocks > x_end - x_begin) blocks = x_end - x_begin;
+        if (blocks > 4 * ctx->cu_count) blocks = 4 * ctx->cu_count;
+        if (blocks < 1) blocks = 1;
+        int rc = ctx->scratch.reserve((size_t)blocks * 4 * (size_t)n * sizeof(double));
+        if (rc) return fail(ctx, rc, "scratch: out of device memory");
+        a.scratch = (double *)ctx->scratch.p;
+        rc = dispatch_format(plan->req.format, [&](auto F) {
+            constexpr int FMT = decltype(F)::value;
+            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
+            if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_traces<FMT, true>), grid, block, 0, s, a, ws);
+            else hipLaunchKernelGGL((spk::k_scratch_traces<FMT, false>), grid, block, 0, s, a, ws);
+            return SP_OK;
+        });
+        if (rc) return fail(ctx, rc, "bad format");
+    }
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+static int traces_finish(sp_plan *plan, double *d_trace_min, double *d_trace_max)
+{
+    sp_context *ctx = plan->ctx;
+    const int n = plan->req.n;
+    hipLaunchKernelGGL(spk::k_traces_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long *)ctx->traces_ws.p, n, plan->block_norm_db, plan->req.gain, d_trace_min, d_trace_max);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_trace_min,
+                                      double *d_trace_max)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_traces(plan, d_bytes, nbytes, width);
+    if (rc) return rc;
+    if ((((uintptr_t)d_trace_min | (uintptr_t)d_trace_max) & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "d_trace_min and d_trace_max must be 8-byte aligned");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    rc = traces_clear(plan);
+    if (!rc) rc = traces_range(plan, d_bytes, g, 0, width, nullptr);
+    if (!rc) rc = traces_finish(plan, d_trace_min, d_trace_max);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+// The capture comes from host memory by the upload plan of a request whose image does not cross the link (plan_upload as
+// sp_plan_execute_from_host calls it: the samples are the only transfer) - a packed sparse upload where stride > n, chunks of frames
+// where the request is large - and the extremes accumulate in the workspace over the chunks.
+extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *trace_min,
+                                double *trace_max)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    int rc = validate_request(ctx, req);
+    if (rc) return rc;
+    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
+    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, "bytes is null");
+    if (nbytes % (size_t)spfmt::describe(req->format).elem)
+        return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
+    if (req->detector != SP_DETECTOR_SAMPLE)
+        return fail(ctx, SP_ERR_UNSUPPORTED, "traces of a peak request are not supported (the traces fold the sample detector's frames)");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    sp_plan *plan = nullptr;
+    rc = cached_plan_for(ctx, req, &plan);
+    if (rc) return rc;
+    rc = check_traces(plan, bytes, nbytes, width);
+    if (rc) return rc;
+
+    const size_t n = (size_t)req->n;
+    const spfmt::Format f = plan->fmt;
+    hipStream_t s = ctx->stream;
+    const spgeo::Geometry g = spgeo::geometry(f, req->n, nbytes, width);
+    spgeo::UploadPlan u;
+    spgeo::plan_upload(g, plan_traces_frames(plan) && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"), true, 0, u);
+    const int chunks = (int)u.bounds.size() - 1;
+    const bool overlap = chunks > 1;   // the copies on copy_in, ordered by events, under the frame loops of earlier chunks
+    ctx->last_upload_bytes = u.link_bytes;
+    rc = ctx->in_bytes.reserve(u.dev_bytes);
+    if (!rc) rc = ctx->render_small.reserve(2 * n * sizeof(double) + 16);
+    if (rc) return fail(ctx, rc, "sp_render_traces: out of memory");
+    uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
+    double *const d_out = (double *)ctx->render_small.p;
+    hipError_t e = hipSuccess;
+    if (overlap) {
+        if (!ctx->copy_in) e = hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking);
+        for (int k = 0; k < chunks && e == hipSuccess; k++) {
+            if (!ctx->ev_arrived[k]) e = hipEventCreateWithFlags(&ctx->ev_arrived[k], hipEventDisableTiming);
+            if (e == hipSuccess && !ctx->ev_rendered[k]) e = hipEventCreateWithFlags(&ctx->ev_rendered[k], hipEventDisableTiming);
+        }
+        // whatever the stream still holds comes before this request's first copy into the staging buffer
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_rendered[0], s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_rendered[0], 0);
+    }
+    hipStream_t in_s = overlap ? ctx->copy_in : s;
+    if (e == hipSuccess) rc = traces_clear(plan);
+    size_t sent = 0;
+    for (int k = 0; k < chunks && e == hipSuccess && !rc; k++) {
+        const int32_t x0 = u.bounds[(size_t)k], x1 = u.bounds[(size_t)k + 1];
+        PackedSource ps{};
+        if (u.packed) {   // (the chunk as the kernel sees it: render_core says how)
+            const spgeo::PackedChunk &ch = u.chunks[(size_t)k];
+            e = upload_packed_chunk(ch, req->n, f.width, bytes, nbytes, in, in_s);
+            ps.bytes = in + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
+            ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
+            ps.nbytes -= ps.nbytes % (size_t)f.elem;
+            ps.stride = ch.stride2;
+        } else {
+            size_t need = nbytes;
+            if (k + 1 < chunks) {
+                need = (size_t)(g.start(x1 - 1) + (int64_t)req->n) * (size_t)f.width;
+                if (need > nbytes) need = nbytes;
+            }
+            if (need > sent) {
+                e = hipMemcpyAsync(in + sent, bytes + sent, need - sent, hipMemcpyHostToDevice, in_s);
+                sent = need;
+            }
+        }
+        if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
+        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
+        if (e == hipSuccess) rc = traces_range(plan, in, g, x0, x1, u.packed ? &ps : nullptr);
+    }
+    if (!rc && e == hipSuccess) rc = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
+    if (!rc && e == hipSuccess && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (!rc && e == hipSuccess && trace_max) e = hipMemcpyAsync(trace_max, d_out + n, n * sizeof(double), hipMemcpyDeviceToHost, s);
+    // (synchronous, and the one way out of a failed request: nothing of it is left in flight)
+    if (overlap && ctx->copy_in) (void)hipStreamSynchronize(ctx->copy_in);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, "sp_render_traces copies");
     return SP_OK;
 }
 

@@ -57,6 +57,77 @@ __device__ inline void scratch_stages(double *re, double *im, const double *__re
     }
 }
 
+// One frame on the slab: decode + taper, the radix-2 stages, the L/R split of channel mode.  Ends behind a barrier: every thread may
+// read any bin.  WIDE: four stages per barrier (k_scratch_radix2 says when).
+template <int FMT, bool WIDE>
+__device__ inline void scratch_frame(const FrameArgs &a, const spfmt::View &view, const int64_t start, double *re, double *im, const int tid)
+{
+    const int n = a.n;
+    // decode + taper, stored in bit-reversed order (fft_nayuki.js:57-69)            worker.js:70-75
+    for (int k = tid; k < n; k += kScratchThreads) {
+        double vi, vq;
+        if (a.in_bounds) {
+            spfmt::sample_fast<FMT>(a.bytes, start + k, vi, vq);
+        } else {
+            vi = spfmt::sample_checked<FMT>(view, start + k, 0);
+            vq = spfmt::sample_checked<FMT>(view, start + k, 1);
+        }
+        const double w = a.window[k];
+        const uint32_t j = a.levels ? bit_reverse((uint32_t)k, a.levels) : 0;
+        re[j] = w * vi;
+        im[j] = w * vq;
+    }
+    __syncthreads();
+
+    // radix-2 decimation in time, same butterfly arithmetic as fft_nayuki.js:72-88, up to four stages between barriers
+    if constexpr (!WIDE) {
+        for (int s = 1; s <= a.levels; s++) {
+            const int half = 1 << (s - 1);
+            for (int b = tid; b < (n >> 1); b += kScratchThreads) {
+                const int lowbits = b & (half - 1);
+                const int j = ((b >> (s - 1)) << s) | lowbits;
+                const int l = j + half;
+                const int k = lowbits << (a.levels - s);
+                const double c = a.cos_t[k], sn = a.sin_t[k];
+                const double rl = re[l], il = im[l];
+                const double tpre = rl * c + il * sn;
+                const double tpim = -rl * sn + il * c;
+                const double rj = re[j], ij = im[j];
+                re[l] = rj - tpre;
+                im[l] = ij - tpim;
+                re[j] = rj + tpre;
+                im[j] = ij + tpim;
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int s = 1; s <= a.levels; s += 4) {
+            const int left = a.levels - s + 1;
+            if (left >= 4) scratch_stages<4>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+            else if (left == 3) scratch_stages<3>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+            else if (left == 2) scratch_stages<2>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+            else scratch_stages<1>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
+            __syncthreads();
+        }
+    }
+
+    if (a.channel_mode) {   // fft_nayuki.js:103-119
+        for (int i = 1 + tid; i < (n >> 1); i += kScratchThreads) {
+            const double ra = re[i], rb = re[n - i], ia = im[i], ib = im[n - i];
+            re[i] = 0.5 * (ra + rb);
+            im[i] = 0.5 * (ia - ib);
+            re[n - i] = 0.5 * (ia + ib);
+            im[n - i] = 0.5 * (-ra + rb);
+        }
+        if (tid == 0) {
+            im[0] = 0.0;
+            re[n >> 1] = 0.0;   // = imag[0], already zeroed in the reference
+            im[n >> 1] = 0.0;
+        }
+        __syncthreads();
+    }
+}
+
 // WIDE: four stages per barrier (n >= 4096, where every thread still has an item); the narrow instance keeps the plain one-stage
 // loop and its small register footprint (the latency-bound small sizes need the occupancy: n = 32 ran 1.8 x slower in one kernel
 // with the 16-point items).
@@ -93,69 +164,7 @@ __global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameA
         for (int sub = 0; sub < subs; sub++) {
             const int64_t start = start0 + (int64_t)sub * n;
 
-            // decode + taper, stored in bit-reversed order (fft_nayuki.js:57-69)            worker.js:70-75
-            for (int k = tid; k < n; k += kScratchThreads) {
-                double vi, vq;
-                if (a.in_bounds) {
-                    spfmt::sample_fast<FMT>(a.bytes, start + k, vi, vq);
-                } else {
-                    vi = spfmt::sample_checked<FMT>(view, start + k, 0);
-                    vq = spfmt::sample_checked<FMT>(view, start + k, 1);
-                }
-                const double w = a.window[k];
-                const uint32_t j = a.levels ? bit_reverse((uint32_t)k, a.levels) : 0;
-                re[j] = w * vi;
-                im[j] = w * vq;
-            }
-            __syncthreads();
-
-            // radix-2 decimation in time, same butterfly arithmetic as fft_nayuki.js:72-88, up to four stages between barriers
-            if constexpr (!WIDE) {
-                for (int s = 1; s <= a.levels; s++) {
-                    const int half = 1 << (s - 1);
-                    for (int b = tid; b < (n >> 1); b += kScratchThreads) {
-                        const int lowbits = b & (half - 1);
-                        const int j = ((b >> (s - 1)) << s) | lowbits;
-                        const int l = j + half;
-                        const int k = lowbits << (a.levels - s);
-                        const double c = a.cos_t[k], sn = a.sin_t[k];
-                        const double rl = re[l], il = im[l];
-                        const double tpre = rl * c + il * sn;
-                        const double tpim = -rl * sn + il * c;
-                        const double rj = re[j], ij = im[j];
-                        re[l] = rj - tpre;
-                        im[l] = ij - tpim;
-                        re[j] = rj + tpre;
-                        im[j] = ij + tpim;
-                    }
-                    __syncthreads();
-                }
-            } else {
-                for (int s = 1; s <= a.levels; s += 4) {
-                    const int left = a.levels - s + 1;
-                    if (left >= 4) scratch_stages<4>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                    else if (left == 3) scratch_stages<3>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                    else if (left == 2) scratch_stages<2>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                    else scratch_stages<1>(re, im, a.cos_t, a.sin_t, n, a.levels, s, tid);
-                    __syncthreads();
-                }
-            }
-
-            if (a.channel_mode) {   // fft_nayuki.js:103-119
-                for (int i = 1 + tid; i < (n >> 1); i += kScratchThreads) {
-                    const double ra = re[i], rb = re[n - i], ia = im[i], ib = im[n - i];
-                    re[i] = 0.5 * (ra + rb);
-                    im[i] = 0.5 * (ia - ib);
-                    re[n - i] = 0.5 * (ia + ib);
-                    im[n - i] = 0.5 * (-ra + rb);
-                }
-                if (tid == 0) {
-                    im[0] = 0.0;
-                    re[n >> 1] = 0.0;   // = imag[0], already zeroed in the reference
-                    im[n >> 1] = 0.0;
-                }
-                __syncthreads();
-            }
+            scratch_frame<FMT, WIDE>(a, view, start, re, im, tid);
 
             if constexpr (PEAK) {
                 if (sub + 1 < subs) {
@@ -309,6 +318,70 @@ __global__ __launch_bounds__(kFinishThreads) void k_finish_frames(const FinishAr
             if (a.out_minmax) a.out_minmax[1] = d > -200.0 ? d : -200.0;
             a.mm_acc[1] = 0ull;
         }
+    }
+}
+
+// ---- per-bin min / max traces over a request (include/spectroplot_hip.h, sp_plan_execute_traces) ---------------------------------------
+// Three launches: k_traces_clear, a frame loop (k_frames_traces, sp_kernel_frames_traces.h, or k_scratch_traces here), k_traces_finish.
+// The workspace `ws` is u64[2 n]: the bit patterns of the smallest |X|^2 per bin, then of the largest (|X|^2 is never negative and
+// never -0, so their u64 order is the numeric order).
+
+// the identities of the two reductions: +inf, +0.0
+__global__ void k_traces_clear(unsigned long long *ws, const int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * n) ws[i] = i < n ? 0x7ff0000000000000ull : 0ull;
+}
+
+// The portable frame loop of a traces request: everything k_frames_traces does not take.  A workgroup owns the columns
+// frame0 + blockIdx.x + k * gridDim.x and keeps the bins' extremes across them in two more slabs (a thread meets the same bins in every
+// frame); its global atomics go out once per bin and workgroup, behind its last column.
+template <int FMT, bool WIDE>
+__global__ __launch_bounds__(kScratchThreads) void k_scratch_traces(const FrameArgs a, unsigned long long *const ws)
+{
+    const int tid = threadIdx.x;
+    const int n = a.n;
+    double *re = a.scratch + (size_t)blockIdx.x * 4 * (size_t)n;
+    double *im = re + n, *tmin = im + n, *tmax = tmin + n;
+    const spfmt::View view{a.bytes, a.nbytes, a.nelem};
+    if (a.frame0 + (int)blockIdx.x >= a.x_end) return;   // no column: nothing to add
+    for (int i = tid; i < n; i += kScratchThreads) {
+        tmin[i] = spjs::inf();
+        tmax[i] = 0.0;
+    }
+    for (int x = a.frame0 + blockIdx.x; x < a.x_end; x += gridDim.x) {
+        scratch_frame<FMT, WIDE>(a, view, frame_start(a.stride, x), re, im, tid);
+        for (int i = tid; i < n; i += kScratchThreads) {
+            const double r = re[i], q = im[i];
+            const double abs2 = r * r + q * q;                                                 // worker.js:92
+            tmin[i] = min_nn(tmin[i], abs2);   // (a NaN never wins)
+            tmax[i] = max_nn(tmax[i], abs2);
+        }
+        __syncthreads();   // the slab is written again by the next frame
+    }
+    for (int i = tid; i < n; i += kScratchThreads) {
+        atomicMin(&ws[i], (unsigned long long)__double_as_longlong(tmin[i]));
+        atomicMax(&ws[n + i], (unsigned long long)__double_as_longlong(tmax[i]));
+    }
+}
+
+// n threads: both held values of bin i through the restated log10 in the reference's operation order (d_of_abs2: worker.js:93, 100),
+// the fold's start values (0, -200) applied with `<` / `>` (worker.js:82-83, 102-103), stored at image row y (worker.js:90).
+// trace_min / trace_max: device pointers or nullptr.
+__global__ void k_traces_finish(const unsigned long long *ws, const int n, const double block_norm_db, const double gain, double *trace_min,
+                                double *trace_max)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int half = n >> 1;
+    const int y = i <= half ? half - i : half + n - i;
+    if (trace_min) {
+        const double d = d_of_abs2(__longlong_as_double((long long)ws[i]), block_norm_db, gain);
+        trace_min[y] = d < 0.0 ? d : 0.0;
+    }
+    if (trace_max) {
+        const double d = d_of_abs2(__longlong_as_double((long long)ws[n + i]), block_norm_db, gain);
+        trace_max[y] = d > -200.0 ? d : -200.0;
     }
 }
 

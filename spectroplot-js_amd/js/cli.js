@@ -6,12 +6,16 @@
  *
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
- *        [--full] --out image.ppm
+ *        [--full] [--traces traces.json] --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
  * Batch mode (--out-dir): one image per capture, DIR/<capture's file name>.ppm (or .rgba with --rgba), the same bytes a single-file
  * run writes for it.  Captures are grouped by format (each file's extension, or --format) and every group is rendered with ONE native
  * call (renderMany -> sp_render_batch).  --full is for single-file runs.
+ *
+ * --traces FILE (single-file runs, sample detector): the per-bin min-hold / max-hold traces of the same request over the whole capture
+ * (HipWorker.renderTraces -> sp_render_traces) as JSON beside the image: {n, width, trace_min: [n], trace_max: [n]} in image row order
+ * (row y of the spectrogram, column n - 1 - y of the waterfall); a value JSON cannot hold travels as the string 'Infinity' / '-Infinity'.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -36,6 +40,19 @@ function writeImage(img, out) {
 function readCapture(file) {
     const bytes = fs.readFileSync(file)
     return bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength)
+}
+
+// --traces: one request over the whole capture on one worker, with the taper and block_norm the image's request resolves to
+function writeTraces(buffer, format, n, width, opt) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const worker = new HipWorker()
+    return worker.renderTraces({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }).then(t => {
+        worker.terminate()
+        const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
+        fs.writeFileSync(opt.traces, JSON.stringify({ n, width, trace_min: plain(t.trace_min), trace_max: plain(t.trace_max) }))
+    }, e => { worker.terminate(); throw e })
 }
 
 // --out-dir: the captures grouped by format, each group in one batch; the option names resolve as the single-file run's do
@@ -107,6 +124,7 @@ function main(argv) {
             console.log(`${file}: ${format}, centre ${fr.freq} Hz, rate ${fr.rate} Hz -> ${opt.out} (${img.width} x ${img.height}), ` +
                 `dBfs ${img.dBfs_min.toFixed(2)} .. ${img.dBfs_max.toFixed(2)}, ${Date.now() - t0} ms`)
         })
+        .then(() => opt.traces === undefined ? null : writeTraces(buffer, format, n, width, opt))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

@@ -158,6 +158,42 @@ class HipWorker {
             channelMode: !!o.channelMode, waterfall: !!o.waterfall, detector: detectorId(o.detector) }
     }
 
+    /**
+     * Per-bin min-hold / max-hold traces of a request (sp_render_traces): the fields of a worker message - buffer, format, n, windowc,
+     * block_norm, gain, range, width, channelMode; cmap, waterfall and offset are not looked at - in, two Float64Array(n) in image row
+     * order out (row y of the spectrogram, column n - 1 - y of the waterfall).  No image is rendered.  Only the sample detector has
+     * traces.  Runs in the instance's request order; a malformed field rejects (and reports `onerror`) and
+     * never resolves to arrays.
+     * @returns {Promise<{trace_min: Float64Array, trace_max: Float64Array}>}
+     */
+    renderTraces(m) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._tracesRequest(m) } catch (e) { reject(e); return }
+            try {
+                addon().renderTraces(this._ctx, req, (err, r) => err ? reject(err) : resolve({ trace_min: r.trace_min, trace_max: r.trace_max }))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
+        return p
+    }
+
+    _tracesRequest(m) {
+        if (!(m && m.buffer)) throw Object.assign(new Error('a traces request needs a buffer'), { status: -1 })
+        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('traces of the peak detector are not supported'), { status: -4 })
+        const fmt = addon().parseFormat(String(m.format))
+        const windowc = m.windowc instanceof Float64Array ? m.windowc : new Float64Array(m.windowc)
+        let buffer = m.buffer
+        if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
+        return { format: fmt.id, buffer, n: m.n, windowc, block_norm: m.block_norm, gain: m.gain, range: m.range, width: m.width,
+            channelMode: !!m.channelMode }
+    }
+
+    /** Synchronous form of renderTraces (tests). */
+    renderTracesSync(m) { return addon().renderTracesSync(this._ctx, this._tracesRequest(m)) }
+
     /** Synchronous form of renderNamed (tests). */
     renderNamedSync(o) { return this._wrap(o, addon().renderNamedSync(this._ctx, this._namedRequest(o))) }
 

@@ -23,6 +23,7 @@
 //       runs sp_render on a libuv worker thread and calls cb(err, {rgba, gauge_mins, gauge_maxs, gauge_amps: ArrayBuffer,
 //       c_hist, cB_hist: Float64Array, dBfs_min, dBfs_max}) on the main thread
 //   renderSync(handle, req)                        -> the same reply object, synchronously
+//   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
 //   renderNamed(handle, req, cb) / renderNamedSync(handle, req)   req = {format, window, cmap: strings, buffer, n, gain, range, width,
 //                                    channelMode, waterfall}: sp_render_named - the library resolves the names as the reference's caller
 //                                    does (lib/spectroplot.js:238-264, 1113-1146) and keeps the plan while they repeat
@@ -877,6 +878,197 @@ napi_value RenderBatch(napi_env env, napi_callback_info info)
     return nullptr;
 }
 
+// ---- traces: renderTraces(handle, req, cb) / renderTracesSync(handle, req) ---------------------------------------------------------
+// req: {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} -> {trace_min, trace_max}, two Float64Array(n) in image
+// row order (sp_render_traces).  Every value is read with its status checked, as for a batch.
+struct TracesJob {
+    Ctx *owner = nullptr;
+    sp_request req{};
+    std::vector<double> window;
+    uint8_t lut[6] = {0, 0, 0, 255, 255, 255};   // (a trace has no colours; the plan wants a map)
+    const uint8_t *bytes = nullptr;
+    size_t nbytes = 0;
+    int32_t width = 0;
+    std::vector<double> out;   // trace_min, then trace_max
+    int status = SP_OK;
+    std::string error;
+    napi_async_work work = nullptr;
+    napi_ref cb_ref = nullptr, buf_ref = nullptr, ctx_ref = nullptr;
+};
+
+void free_traces(napi_env env, TracesJob *t)
+{
+    if (t->cb_ref) napi_delete_reference(env, t->cb_ref);
+    if (t->buf_ref) napi_delete_reference(env, t->buf_ref);
+    if (t->ctx_ref) napi_delete_reference(env, t->ctx_ref);
+    if (t->work) napi_delete_async_work(env, t->work);
+    delete t;
+}
+
+bool parse_traces(napi_env env, napi_value handle, napi_value req, TracesJob *t)
+{
+    void *p = nullptr;
+    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
+        napi_throw_type_error(env, nullptr, "context handle expected");
+        return false;
+    }
+    t->owner = (Ctx *)p;
+    if (t->owner->closed || !t->owner->c) {
+        napi_throw_error(env, nullptr, t->owner->g ? "renderTraces takes a context handle, not a group" : "context has been destroyed");
+        return false;
+    }
+    if (!checked_int32(env, req, "format", &t->req.format) || !checked_int32(env, req, "n", &t->req.n)) return false;
+    if (!checked_int32(env, req, "width", &t->width)) return false;
+    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode)) return false;
+    if (!checked_number(env, req, "block_norm", &t->req.block_norm) || !checked_number(env, req, "gain", &t->req.gain)) return false;
+    if (!checked_number(env, req, "range", &t->req.range)) return false;
+    if (t->req.n < 1 || t->width < 0) {
+        napi_throw_range_error(env, nullptr, "n must be positive and width must not be negative");
+        return false;
+    }
+    napi_value v, ab;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void *data = nullptr;
+    if (napi_get_named_property(env, req, "windowc", &v) != napi_ok
+        || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_float64_array) {
+        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
+        return false;
+    }
+    if (len < (size_t)t->req.n) {
+        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
+        return false;
+    }
+    t->window.assign((const double *)data, (const double *)data + len);
+    if (napi_get_named_property(env, req, "buffer", &v) != napi_ok || napi_get_arraybuffer_info(env, v, &data, &len) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
+        return false;
+    }
+    t->bytes = (const uint8_t *)data;
+    t->nbytes = len;
+    t->req.detector = SP_DETECTOR_SAMPLE;
+    t->req.lut_len = 2;
+    t->req.windowc = t->window.data();
+    t->req.lut_rgb = t->lut;
+    return true;
+}
+
+void run_traces(TracesJob *t)
+{
+    const size_t n = (size_t)t->req.n;
+    t->out.assign(2 * n, 0.0);
+    t->status = sp_render_traces(t->owner->c, &t->req, t->bytes, t->nbytes, t->width, t->out.data(), t->out.data() + n);
+    if (t->status != SP_OK) t->error = sp_last_error(t->owner->c);
+}
+
+napi_value traces_result(napi_env env, TracesJob *t)
+{
+    if (t->status != SP_OK) {
+        Job e;
+        e.status = t->status;
+        e.error = t->error;
+        return make_error(env, &e);
+    }
+    const size_t n = (size_t)t->req.n;
+    napi_value out, ab, ta;
+    void *data = nullptr;
+    if (napi_create_object(env, &out) != napi_ok || napi_create_arraybuffer(env, 2 * n * 8, &data, &ab) != napi_ok) return nullptr;
+    memcpy(data, t->out.data(), 2 * n * 8);
+    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "trace_min", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_typedarray(env, napi_float64_array, n, ab, n * 8, &ta) != napi_ok || napi_set_named_property(env, out, "trace_max", ta) != napi_ok)
+        return nullptr;
+    return out;
+}
+
+napi_value RenderTracesSync(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 2) {
+        napi_throw_type_error(env, nullptr, "renderTracesSync(handle, request)");
+        return nullptr;
+    }
+    TracesJob *t = new TracesJob;
+    if (!parse_traces(env, argv[0], argv[1], t)) { free_traces(env, t); return nullptr; }
+    if (t->owner->inflight > 0) {
+        free_traces(env, t);
+        napi_throw_error(env, nullptr, "a render is already in flight on this context");
+        return nullptr;
+    }
+    t->owner->inflight++;
+    run_traces(t);
+    t->owner->inflight--;
+    ctx_release(t->owner);
+    napi_value out = traces_result(env, t);
+    if (t->status != SP_OK) {
+        napi_throw(env, out);
+        out = nullptr;
+    }
+    free_traces(env, t);
+    return out;
+}
+
+void traces_exec_cb(napi_env, void *data) { run_traces((TracesJob *)data); }
+
+void traces_done_cb(napi_env env, napi_status, void *data)
+{
+    TracesJob *t = (TracesJob *)data;
+    t->owner->inflight--;
+    ctx_release(t->owner);
+    napi_value cb, global, argv[2], ignored;
+    napi_get_reference_value(env, t->cb_ref, &cb);
+    napi_get_global(env, &global);
+    if (t->status != SP_OK) {
+        argv[0] = traces_result(env, t);
+        napi_get_undefined(env, &argv[1]);
+    } else {
+        napi_get_null(env, &argv[0]);
+        argv[1] = traces_result(env, t);
+    }
+    napi_call_function(env, global, cb, 2, argv, &ignored);
+    free_traces(env, t);
+}
+
+napi_value RenderTraces(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    napi_valuetype ty = napi_undefined;
+    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
+        napi_throw_type_error(env, nullptr, "renderTraces(handle, request, callback)");
+        return nullptr;
+    }
+    TracesJob *t = new TracesJob;
+    if (!parse_traces(env, argv[0], argv[1], t)) { free_traces(env, t); return nullptr; }
+    if (t->owner->inflight > 0) {
+        free_traces(env, t);
+        napi_throw_error(env, nullptr, "a render is already in flight on this context");
+        return nullptr;
+    }
+    napi_value buf, name;
+    bool ok = napi_get_named_property(env, argv[1], "buffer", &buf) == napi_ok;
+    ok = ok && napi_create_reference(env, buf, 1, &t->buf_ref) == napi_ok;       // the input stays alive while the worker thread reads it
+    ok = ok && napi_create_reference(env, argv[2], 1, &t->cb_ref) == napi_ok;
+    ok = ok && napi_create_reference(env, argv[0], 1, &t->ctx_ref) == napi_ok;
+    ok = ok && napi_create_string_utf8(env, "spectroplot_hip.renderTraces", NAPI_AUTO_LENGTH, &name) == napi_ok;
+    ok = ok && napi_create_async_work(env, nullptr, name, traces_exec_cb, traces_done_cb, t, &t->work) == napi_ok;
+    if (ok) {
+        t->owner->inflight++;
+        if (napi_queue_async_work(env, t->work) != napi_ok) {
+            t->owner->inflight--;
+            ok = false;
+        }
+    }
+    if (!ok) {
+        free_traces(env, t);
+        napi_throw_error(env, nullptr, "could not queue the traces request");
+    }
+    return nullptr;
+}
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1195,6 +1387,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderNamedSync", nullptr, RenderNamedSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderBatch", nullptr, RenderBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderTraces", nullptr, RenderTraces, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"peakSubframes", nullptr, PeakSubframes, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},
