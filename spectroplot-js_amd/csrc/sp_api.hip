@@ -791,6 +791,32 @@ static bool rgba_fast(const uint8_t *rgba, int32_t width, int n)
     return rgba && ((uintptr_t)rgba & 15) == 0 && (width & 3) == 0 && width < (1 << 24) && (double)width * (double)n * 4.0 <= 4294967296.0;
 }
 
+// Where the frames [x_begin, x_end) lie, as the kernel reads them: in the capture at d_bytes with the request's stride, or in `src`, a
+// packed copy of this range's frames with its own address, length and stride (every frame inside it).
+static void frame_source_args(spk::FrameArgs &a, const sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin,
+                              int32_t x_end, const PackedSource *src)
+{
+    const size_t nbytes = src ? src->nbytes : g.nbytes;
+    a.bytes = (const uint8_t *)(src ? src->bytes : d_bytes);
+    a.nbytes = (int64_t)nbytes;
+    a.nelem = (int64_t)(nbytes / (size_t)plan->fmt.elem);
+    a.stride = src ? src->stride : g.stride;
+    a.width = g.width;
+    a.in_bounds = src || g.in_bounds ? 1 : 0;
+    a.frame0 = x_begin;
+    a.x_end = x_end;
+}
+
+// Workgroups of a scratch-kernel launch: each owns `slabs_per_group` slabs of n doubles, all of them capped at 256 MiB; no more
+// workgroups than frames or than four per CU.
+static long long scratch_blocks(int slabs_per_group, int n, int32_t frames, int cu_count)
+{
+    long long blocks = (256ll << 20) / (8ll * slabs_per_group * n);
+    if (blocks > frames) blocks = frames;
+    if (blocks > 4 * cu_count) blocks = 4 * cu_count;
+    return blocks < 1 ? 1 : blocks;
+}
+
 static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestShape &shape, int32_t x_begin, int32_t x_end, bool first,
                               bool last, const sp_reply *out, const PackedSource *src = nullptr)
 {
@@ -822,11 +848,6 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
 
     const int which = request_kernel(plan, peak.m);
     if (src && which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    // what the kernel reads: the capture with the request's stride, or a packed copy of this range's frames with its own
-    if (src) d_bytes = src->bytes;
-    const size_t nbytes = src ? src->nbytes : g.nbytes;
-    const double stride = src ? src->stride : g.stride;
-    const bool in_bounds = src ? true : g.in_bounds;
     rc = finishes_request(which) ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
     if (rc) return fail(ctx, rc, "workspace: out of device memory");
     int finish_blocks = 3 * ((width + spk::kFinishThreads - 1) / spk::kFinishThreads);   // three roles per 256 frames
@@ -852,14 +873,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
 
     spk::FrameArgs a{};
     plan_frame_args(plan, a);
-    a.bytes = (const uint8_t *)d_bytes;
-    a.nbytes = (int64_t)nbytes;
-    a.nelem = (int64_t)(nbytes / (size_t)f.elem);
-    a.stride = stride;
-    a.width = width;
-    a.in_bounds = in_bounds ? 1 : 0;
-    a.frame0 = x_begin;
-    a.x_end = x_end;
+    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
     a.rgba = out->rgba;
     a.frame_min = (double *)ctx->frame_minmax.p;
     a.frame_max = a.frame_min + width;
@@ -890,12 +904,9 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
         rc = spk2::launch_frames_peak(a, plan->req.format, plan->d_stage_tw, peak.m, peak_nsamp, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames_peak launch rejected the configuration");
     } else {
-        // scratch slabs: one per workgroup, capped at 256 MiB
-        const bool hold = peak.m >= 2;   // a third slab per workgroup: the largest |X|^2 per bin over the column's sub-frames
-        long long blocks = (256ll << 20) / ((hold ? 24ll : 16ll) * n);
-        if (blocks > x_end - x_begin) blocks = x_end - x_begin;
-        if (blocks > 4 * ctx->cu_count) blocks = 4 * ctx->cu_count;
-        if (blocks < 1) blocks = 1;
+        // two slabs per workgroup (re, im), and for a held peak a third: the largest |X|^2 per bin over the column's sub-frames
+        const bool hold = peak.m >= 2;
+        const long long blocks = scratch_blocks(hold ? 3 : 2, n, x_end - x_begin, ctx->cu_count);
         rc = ctx->scratch.reserve((size_t)blocks * (hold ? 3 : 2) * (size_t)n * sizeof(double));
         if (rc) return fail(ctx, rc, "scratch: out of device memory");
         a.scratch = (double *)ctx->scratch.p;
@@ -926,7 +937,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     fa.bytes = a.bytes;
     fa.nbytes = a.nbytes;
     fa.nelem = a.nelem;
-    fa.stride = stride;
+    fa.stride = a.stride;
     fa.n = n;
     fa.width = width;
     fa.format = plan->req.format;
@@ -1148,9 +1159,108 @@ static hipError_t download_band(uint8_t *host, size_t host_pitch, const uint8_t 
                             stream);
 }
 
-// sp_render / sp_render_strip / sp_plan_execute_from_host: the capture comes from HOST memory, in chunks of frames that travel while
-// earlier chunks are rendered.  `image_width` is the width in frames of the image reply->rgba points into (the strip's own width for
-// sp_render); it only matters for the spectrogram layout, whose rows are image_width pixels apart.
+// sp_render / sp_render_strip / sp_plan_execute_from_host / sp_render_traces: the capture comes from HOST memory.  Large requests are
+// rendered in chunks of frames: chunk k's samples travel to the device on copy_in while chunk k-1 is rendered and - where an image
+// comes back - chunk k-2's part of it travels back on copy_out (PCIe is full duplex; the kernels are a few per cent of the copies).
+// Chunks end on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.  A request
+// of one chunk does everything on the context's stream.  A sparse request (a frame-loop kernel) uploads only the samples its frames
+// read.  stream_chunks is the only code that carries an UploadPlan out; a request kind brings its launch and what follows every chunk.
+struct HostFeed {
+    const char *who;        // the entry point, for its error texts
+    const uint8_t *bytes;   // the capture, g.nbytes bytes of host memory
+    spgeo::Geometry g;
+    int32_t m;              // sub-frames per column: a contiguous chunk ends with its last column's last sub-frame (traces: 1)
+    bool packable;          // the request's kernel can read a packed chunk (SPECTROPLOT_HIP_NO_PACKED_UPLOAD overrides)
+    bool chunkable;         // plan_upload's: the request may be pipelined ...
+    size_t out_bytes;       // ... and the image that comes back over the link
+    bool download;          // after_chunk copies back on copy_out: that stream and the ev_rendered events are wanted
+    hipStream_t out_s;      // (set by stream_chunks) where after_chunk's copies go: copy_out, or the context's stream for one chunk
+};
+
+// a packed chunk as the kernel sees it: (virtual) sample 0 of its layout, a length that covers its last frame and one spare sample
+// (3-byte samples are fetched as dwords), its stride
+static PackedSource packed_source(const spgeo::PackedChunk &ch, const uint8_t *stage, int n, const spfmt::Format &f)
+{
+    PackedSource ps{};
+    ps.bytes = stage + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
+    ps.nbytes = (size_t)(ch.pos2_last + (int64_t)n + 1) * (size_t)f.width;
+    ps.nbytes -= ps.nbytes % (size_t)f.elem;
+    ps.stride = ch.stride2;
+    return ps;
+}
+
+// The one way out of a failed host-fed request: nothing of it is left in flight, and the next request re-initialises the accumulators
+// (harmless for a traces request, which has none: its workspace is cleared by every request).
+static void drain_streams(sp_context *ctx)
+{
+    if (ctx->copy_in) (void)hipStreamSynchronize(ctx->copy_in);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->copy_out) (void)hipStreamSynchronize(ctx->copy_out);
+    ctx->acc_dirty = true;
+}
+
+// launch(x0, x1, first, last, d_in, src): the frame loop over chunk [x0, x1) on the context's stream, from the staging buffer d_in (src:
+// the packed chunk, null for the contiguous upload); after_chunk(k, x0, x1): what follows chunk k's launch.  Both set the error they return.
+template <typename Launch, typename AfterChunk>
+static int stream_chunks(sp_context *ctx, const spfmt::Format &f, HostFeed &h, Launch &&launch, AfterChunk &&after_chunk)
+{
+    hipStream_t s = ctx->stream;
+    const spgeo::Geometry &g = h.g;
+    spgeo::UploadPlan u;
+    spgeo::plan_upload(g, h.packable && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"), h.chunkable, h.out_bytes, u);
+    const int chunks = (int)u.bounds.size() - 1;
+    const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
+    ctx->last_upload_bytes = u.link_bytes;
+    int rc = ctx->in_bytes.reserve(u.dev_bytes);
+    if (rc) return fail(ctx, rc, std::string(h.who) + ": out of memory");
+    uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
+    hipError_t e = hipSuccess;
+    if (overlap) {
+        if (!ctx->copy_in) e = hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking);
+        if (e == hipSuccess && h.download && !ctx->copy_out) e = hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking);
+        for (int k = 0; k < chunks && e == hipSuccess; k++) {
+            if (!ctx->ev_arrived[k]) e = hipEventCreateWithFlags(&ctx->ev_arrived[k], hipEventDisableTiming);
+            if (e == hipSuccess && h.download && !ctx->ev_rendered[k]) e = hipEventCreateWithFlags(&ctx->ev_rendered[k], hipEventDisableTiming);
+        }
+        // whatever the stream still holds (an sp_plan_execute_from_host still reading the staging buffer, the caller's own work) comes
+        // before this request's first copy; an idle stream is not waited for (that wait alone costs config 2 ~3 %)
+        const bool busy = hipStreamQuery(s) != hipSuccess;
+        (void)hipGetLastError();   // (hipErrorNotReady: the stream is busy, nothing failed)
+        if (e == hipSuccess && busy) e = hipEventRecord(ctx->ev_arrived[0], s);
+        if (e == hipSuccess && busy) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_arrived[0], 0);
+    }
+    hipStream_t in_s = overlap ? ctx->copy_in : s;
+    h.out_s = overlap && h.download ? ctx->copy_out : s;
+    size_t sent = 0;
+    for (int k = 0; k < chunks && e == hipSuccess && !rc; k++) {
+        const int32_t x0 = u.bounds[(size_t)k], x1 = u.bounds[(size_t)k + 1];
+        PackedSource ps{};
+        if (u.packed) {
+            e = upload_packed_chunk(u.chunks[(size_t)k], g.n, f.width, h.bytes, g.nbytes, in, in_s);
+            ps = packed_source(u.chunks[(size_t)k], in, g.n, f);
+        } else {
+            size_t need = g.nbytes;
+            if (k + 1 < chunks) {
+                need = (size_t)(g.start(x1 - 1) + (int64_t)h.m * g.n) * (size_t)f.width;
+                if (need > g.nbytes) need = g.nbytes;
+            }
+            if (need > sent) {
+                e = hipMemcpyAsync(in + sent, h.bytes + sent, need - sent, hipMemcpyHostToDevice, in_s);
+                sent = need;
+            }
+        }
+        if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
+        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
+        if (e == hipSuccess) rc = launch(x0, x1, k == 0, k + 1 == chunks, in, u.packed ? &ps : nullptr);
+        if (e == hipSuccess && !rc) rc = after_chunk(k, x0, x1);
+    }
+    if (e != hipSuccess) rc = hip_fail(ctx, e, (std::string(h.who) + " copies").c_str());
+    if (rc) drain_streams(ctx);
+    return rc;
+}
+
+// sp_render / sp_render_strip / sp_plan_execute_from_host.  `image_width` is the width in frames of the image reply->rgba points into
+// (the strip's own width for sp_render); it only matters for the spectrogram layout, whose rows are image_width pixels apart.
 // device_out = false: the reply's pointers are host pointers; the image travels back chunk by chunk, the small outputs in one copy, and
 // the call returns when everything has arrived.  device_out = true: the reply's pointers are device pointers (as for sp_plan_execute);
 // nothing comes back, and the call returns once everything is queued.
@@ -1176,90 +1286,34 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
         d.rgba = reply->rgba ? (uint8_t *)ctx->out_rgba.p : nullptr;
     }
 
-    // Large requests are rendered in chunks of frames: chunk k's samples travel to the device on copy_in while chunk k-1 is rendered
-    // and chunk k-2's part of the image travels back on copy_out (PCIe is full duplex; the kernels are a few per cent of the copies).
-    // Chunks end on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.  A
-    // request of one chunk does everything on the context's stream.  A sparse request (the frame-loop kernel) uploads only the
-    // samples its frames read.
-    const spfmt::Format f = plan->fmt;
     const RequestShape shape = request_shape(plan, nbytes, width);   // once, for the upload plan and every chunk's launch
-    spgeo::UploadPlan u;
     // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
     // (a peak request with M >= 2 sub-frames per column reads more than half of the capture: the contiguous upload, chunked by columns)
-    spgeo::plan_upload(shape.g, request_kernel(plan, shape.peak.m) == kKernelFrames && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"),
-                       device_out || reply->rgba, device_out ? 0 : rgba_bytes, u);
-    const int chunks = (int)u.bounds.size() - 1;
-    const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
-    ctx->last_upload_bytes = u.link_bytes;
-    rc = ctx->in_bytes.reserve(u.dev_bytes);
-    if (rc) return fail(ctx, rc, "sp_render: out of memory");
-    uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
-    hipError_t e = hipSuccess;
-    if (overlap) {
-        if (!ctx->copy_in) e = hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking);
-        if (e == hipSuccess && !ctx->copy_out) e = hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking);
-        for (int k = 0; k < chunks && e == hipSuccess; k++) {
-            if (!ctx->ev_arrived[k]) e = hipEventCreateWithFlags(&ctx->ev_arrived[k], hipEventDisableTiming);
-            if (e == hipSuccess && !ctx->ev_rendered[k]) e = hipEventCreateWithFlags(&ctx->ev_rendered[k], hipEventDisableTiming);
-        }
-        // whatever the stream still holds (an sp_plan_execute_from_host still reading the staging buffer, the caller's own work) comes
-        // before this request's first copy; an idle stream is not waited for (that wait alone costs config 2 ~3 %)
-        const bool busy = hipStreamQuery(s) != hipSuccess;
-        (void)hipGetLastError();   // (hipErrorNotReady: the stream is busy, nothing failed)
-        if (e == hipSuccess && busy) e = hipEventRecord(ctx->ev_rendered[0], s);
-        if (e == hipSuccess && busy) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_rendered[0], 0);
-    }
-    hipStream_t in_s = overlap ? ctx->copy_in : s, out_s = overlap ? ctx->copy_out : s;
+    HostFeed feed{"sp_render", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames,
+                  device_out || reply->rgba, device_out ? 0 : rgba_bytes, !device_out, nullptr};
     // (nothing to clear: the kernels overwrite every histogram count, both range values and every gauge byte)
-    size_t sent = 0;
-    for (int k = 0; k < chunks && e == hipSuccess; k++) {
-        const int32_t x0 = u.bounds[(size_t)k], x1 = u.bounds[(size_t)k + 1];
-        // a packed chunk as the kernel sees it: (virtual) sample 0 of its layout, a length that covers its last frame and one spare
-        // sample (3-byte samples are fetched as dwords), its stride
-        PackedSource ps{};
-        if (u.packed) {
-            const spgeo::PackedChunk &ch = u.chunks[(size_t)k];
-            e = upload_packed_chunk(ch, req->n, f.width, bytes, nbytes, in, in_s);
-            ps.bytes = in + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
-            ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
-            ps.nbytes -= ps.nbytes % (size_t)f.elem;
-            ps.stride = ch.stride2;
-        } else {
-            size_t need = nbytes;
-            if (k + 1 < chunks) {
-                need = (size_t)(shape.g.start(x1 - 1) + (int64_t)shape.peak.m * req->n) * (size_t)f.width;   // (the column's last sub-frame)
-                if (need > nbytes) need = nbytes;
-            }
-            if (need > sent) {
-                e = hipMemcpyAsync(in + sent, bytes + sent, need - sent, hipMemcpyHostToDevice, in_s);
-                sent = need;
-            }
-        }
-        if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
-        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
-        if (e == hipSuccess) rc = plan_execute_range(plan, in, shape, x0, x1, k == 0, k + 1 == chunks, &d, u.packed ? &ps : nullptr);
-        if (rc || e != hipSuccess) break;
-        if (device_out) continue;
-        if (overlap) e = hipEventRecord(ctx->ev_rendered[k], s);
-        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(out_s, ctx->ev_rendered[k], 0);
+    auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
+        return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src);
+    };
+    rc = stream_chunks(ctx, plan->fmt, feed, launch, [&](int k, int32_t x0, int32_t x1) {
+        hipError_t e = hipSuccess;
+        if (device_out) return (int)SP_OK;
+        if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
+        if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
         if (e == hipSuccess && reply->rgba && x1 > x0)
-            e = download_band(reply->rgba, host_pitch, (const uint8_t *)ctx->out_rgba.p, width, n, req->waterfall, x0, x1, out_s);
+            e = download_band(reply->rgba, host_pitch, (const uint8_t *)ctx->out_rgba.p, width, n, req->waterfall, x0, x1, feed.out_s);
+        return e == hipSuccess ? (int)SP_OK : hip_fail(ctx, e, "sp_render copies");
+    });
+    if (rc || device_out) return rc;
+    // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
+    // (separate copies into pageable memory cost more than the kernels of a small request)
+    hipError_t e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return hip_fail(ctx, e, "sp_render copies");
     }
-    if (!device_out && !rc && e == hipSuccess) {
-        // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
-        // (separate copies into pageable memory cost more than the kernels of a small request)
-        e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess && overlap) e = hipStreamSynchronize(out_s);
-    }
-    if (rc || e != hipSuccess) {   // the one way out of a failed request: nothing of it is left in flight
-        if (overlap && ctx->copy_in) (void)hipStreamSynchronize(ctx->copy_in);
-        (void)hipStreamSynchronize(s);
-        if (overlap && ctx->copy_out) (void)hipStreamSynchronize(ctx->copy_out);
-        ctx->acc_dirty = true;
-        return rc ? rc : hip_fail(ctx, e, "sp_render copies");
-    }
-    if (device_out) return SP_OK;
     rec.unpack_side(ctx->host_small.p, *reply);
     rec.unpack_gauges(ctx->host_small.p, *reply);
     return SP_OK;
@@ -1279,20 +1333,26 @@ static int cached_plan_for(sp_context *ctx, const sp_request *req, sp_plan **pla
     return SP_OK;
 }
 
+// What every host entry point refuses of its capture before it touches the device, in this order; then the context's device is current.
+static int check_host_capture(sp_context *ctx, const spfmt::Format &f, const uint8_t *bytes, size_t nbytes, int32_t width)
+{
+    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
+    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, "bytes is null");
+    // the reference constructs its typed view before anything else (worker.js:24)
+    if (nbytes % (size_t)f.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return SP_OK;
+}
+
 static int render_host(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
                        int32_t image_width)
 {
     if (!ctx || !reply) return SP_ERR_INVALID_ARG;
     int rc = validate_request(ctx, req);
     if (rc) return rc;
-    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
-    if (image_width < width) return fail(ctx, SP_ERR_INVALID_ARG, "image_width < width");
-    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, "bytes is null");
-    // the reference constructs its typed view before anything else (worker.js:24)
-    if (nbytes % (size_t)spfmt::describe(req->format).elem)
-        return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-
+    if (width >= 0 && image_width < width) return fail(ctx, SP_ERR_INVALID_ARG, "image_width < width");   // (a width < 0 is refused first)
+    rc = check_host_capture(ctx, spfmt::describe(req->format), bytes, nbytes, width);
+    if (rc) return rc;
     sp_plan *plan = nullptr;
     rc = cached_plan_for(ctx, req, &plan);
     if (rc) return rc;
@@ -1307,12 +1367,8 @@ extern "C" int sp_render(sp_context *ctx, const sp_request *req, const uint8_t *
 extern "C" int sp_plan_execute_from_host(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *d_reply)
 {
     if (!plan || !d_reply) return SP_ERR_INVALID_ARG;
-    sp_context *ctx = plan->ctx;
-    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
-    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, "bytes is null");
-    if (nbytes % (size_t)plan->fmt.elem) return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    return render_core(plan, bytes, nbytes, width, d_reply, width, true);
+    const int rc = check_host_capture(plan->ctx, plan->fmt, bytes, nbytes, width);
+    return rc ? rc : render_core(plan, bytes, nbytes, width, d_reply, width, true);
 }
 
 extern "C" int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbytes)
@@ -1337,13 +1393,12 @@ extern "C" const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_
     return !plan ? "" : plan_traces_frames(plan) ? "frames_traces" : "scratch_traces";
 }
 
-// what every traces entry point refuses before it touches the device
-static int check_traces(sp_plan *plan, const void *bytes, size_t nbytes, int32_t width)
+// what every traces entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
+static int check_traces(sp_context *ctx, int32_t detector, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width)
 {
-    sp_context *ctx = plan->ctx;
-    if (plan->req.detector != SP_DETECTOR_SAMPLE)
+    if (detector != SP_DETECTOR_SAMPLE)
         return fail(ctx, SP_ERR_UNSUPPORTED, "traces of a peak plan are not supported (the traces fold the sample detector's frames)");
-    return check_capture(ctx, plan->fmt, plan->req.n, bytes, nbytes, width, nullptr, "");
+    return check_capture(ctx, f, n, bytes, nbytes, width, nullptr, "");
 }
 
 static int traces_clear(sp_plan *plan)
@@ -1366,17 +1421,9 @@ static int traces_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometr
     const int n = plan->req.n;
     const bool frames = plan_traces_frames(plan);
     if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    const size_t nbytes = src ? src->nbytes : g.nbytes;
     spk::FrameArgs a{};
     plan_frame_args(plan, a);
-    a.bytes = (const uint8_t *)(src ? src->bytes : d_bytes);
-    a.nbytes = (int64_t)nbytes;
-    a.nelem = (int64_t)(nbytes / (size_t)plan->fmt.elem);
-    a.stride = src ? src->stride : g.stride;
-    a.width = g.width;
-    a.in_bounds = src || g.in_bounds ? 1 : 0;
-    a.frame0 = x_begin;
-    a.x_end = x_end;
+    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
     unsigned long long *const ws = (unsigned long long *)ctx->traces_ws.p;
     hipStream_t s = ctx->stream;
     if (frames) {
@@ -1385,11 +1432,8 @@ static int traces_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometr
         const int rc = spk2::launch_frames_traces(a, plan->req.format, plan->d_stage_tw, ws, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames_traces launch rejected the configuration");
     } else {
-        // four slabs per workgroup (re, im, the bins' minima and maxima), capped at 256 MiB
-        long long blocks = (256ll << 20) / (32ll * n);
-        if (blocks > x_end - x_begin) blocks = x_end - x_begin;
-        if (blocks > 4 * ctx->cu_count) blocks = 4 * ctx->cu_count;
-        if (blocks < 1) blocks = 1;
+        // four slabs per workgroup (re, im, the bins' minima and maxima)
+        const long long blocks = scratch_blocks(4, n, x_end - x_begin, ctx->cu_count);
         int rc = ctx->scratch.reserve((size_t)blocks * 4 * (size_t)n * sizeof(double));
         if (rc) return fail(ctx, rc, "scratch: out of device memory");
         a.scratch = (double *)ctx->scratch.p;
@@ -1421,7 +1465,7 @@ extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t
 {
     if (!plan) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
-    int rc = check_traces(plan, d_bytes, nbytes, width);
+    int rc = check_traces(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
     if (rc) return rc;
     if ((((uintptr_t)d_trace_min | (uintptr_t)d_trace_max) & 7) != 0)
         return fail(ctx, SP_ERR_INVALID_ARG, "d_trace_min and d_trace_max must be 8-byte aligned");
@@ -1439,87 +1483,40 @@ extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t
     return SP_OK;
 }
 
-// The capture comes from host memory by the upload plan of a request whose image does not cross the link (plan_upload as
-// sp_plan_execute_from_host calls it: the samples are the only transfer) - a packed sparse upload where stride > n, chunks of frames
-// where the request is large - and the extremes accumulate in the workspace over the chunks.
+// The capture comes from host memory as for a request whose image does not cross the link (stream_chunks as
+// sp_plan_execute_from_host feeds it: the samples are the only transfer, nothing follows a chunk) - a packed sparse upload where
+// stride > n, chunks of frames where the request is large - and the extremes accumulate in the workspace over the chunks.
 extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *trace_min,
                                 double *trace_max)
 {
     if (!ctx) return SP_ERR_INVALID_ARG;
     int rc = validate_request(ctx, req);
     if (rc) return rc;
-    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
-    if (nbytes && !bytes) return fail(ctx, SP_ERR_INVALID_ARG, "bytes is null");
-    if (nbytes % (size_t)spfmt::describe(req->format).elem)
-        return fail(ctx, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
-    if (req->detector != SP_DETECTOR_SAMPLE)
-        return fail(ctx, SP_ERR_UNSUPPORTED, "traces of a peak request are not supported (the traces fold the sample detector's frames)");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spfmt::Format f = spfmt::describe(req->format);
+    rc = check_host_capture(ctx, f, bytes, nbytes, width);
+    if (!rc) rc = check_traces(ctx, req->detector, f, req->n, bytes, nbytes, width);
+    if (rc) return rc;
     sp_plan *plan = nullptr;
     rc = cached_plan_for(ctx, req, &plan);
     if (rc) return rc;
-    rc = check_traces(plan, bytes, nbytes, width);
-    if (rc) return rc;
 
     const size_t n = (size_t)req->n;
-    const spfmt::Format f = plan->fmt;
     hipStream_t s = ctx->stream;
-    const spgeo::Geometry g = spgeo::geometry(f, req->n, nbytes, width);
-    spgeo::UploadPlan u;
-    spgeo::plan_upload(g, plan_traces_frames(plan) && !getenv("SPECTROPLOT_HIP_NO_PACKED_UPLOAD"), true, 0, u);
-    const int chunks = (int)u.bounds.size() - 1;
-    const bool overlap = chunks > 1;   // the copies on copy_in, ordered by events, under the frame loops of earlier chunks
-    ctx->last_upload_bytes = u.link_bytes;
-    rc = ctx->in_bytes.reserve(u.dev_bytes);
-    if (!rc) rc = ctx->render_small.reserve(2 * n * sizeof(double) + 16);
+    rc = ctx->render_small.reserve(2 * n * sizeof(double) + 16);
     if (rc) return fail(ctx, rc, "sp_render_traces: out of memory");
-    uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
     double *const d_out = (double *)ctx->render_small.p;
+    HostFeed feed{"sp_render_traces", bytes, spgeo::geometry(f, req->n, nbytes, width), 1, plan_traces_frames(plan), true, 0, false, nullptr};
+    // (the clear belongs to the first chunk's launch: queued earlier, it would make the stream look busy to the streamer)
+    auto launch = [&](int32_t x0, int32_t x1, bool first, bool, const uint8_t *d_in, const PackedSource *src) {
+        const int r = first ? traces_clear(plan) : SP_OK;
+        return r ? r : traces_range(plan, d_in, feed.g, x0, x1, src);
+    };
+    rc = stream_chunks(ctx, f, feed, launch, [](int, int32_t, int32_t) { return (int)SP_OK; });   // (nothing follows a chunk)
     hipError_t e = hipSuccess;
-    if (overlap) {
-        if (!ctx->copy_in) e = hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking);
-        for (int k = 0; k < chunks && e == hipSuccess; k++) {
-            if (!ctx->ev_arrived[k]) e = hipEventCreateWithFlags(&ctx->ev_arrived[k], hipEventDisableTiming);
-            if (e == hipSuccess && !ctx->ev_rendered[k]) e = hipEventCreateWithFlags(&ctx->ev_rendered[k], hipEventDisableTiming);
-        }
-        // whatever the stream still holds comes before this request's first copy into the staging buffer
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_rendered[0], s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_in, ctx->ev_rendered[0], 0);
-    }
-    hipStream_t in_s = overlap ? ctx->copy_in : s;
-    if (e == hipSuccess) rc = traces_clear(plan);
-    size_t sent = 0;
-    for (int k = 0; k < chunks && e == hipSuccess && !rc; k++) {
-        const int32_t x0 = u.bounds[(size_t)k], x1 = u.bounds[(size_t)k + 1];
-        PackedSource ps{};
-        if (u.packed) {   // (the chunk as the kernel sees it: render_core says how)
-            const spgeo::PackedChunk &ch = u.chunks[(size_t)k];
-            e = upload_packed_chunk(ch, req->n, f.width, bytes, nbytes, in, in_s);
-            ps.bytes = in + ch.dev_off - (size_t)ch.pos2_x0 * (size_t)f.width;
-            ps.nbytes = (size_t)(ch.pos2_last + (int64_t)req->n + 1) * (size_t)f.width;
-            ps.nbytes -= ps.nbytes % (size_t)f.elem;
-            ps.stride = ch.stride2;
-        } else {
-            size_t need = nbytes;
-            if (k + 1 < chunks) {
-                need = (size_t)(g.start(x1 - 1) + (int64_t)req->n) * (size_t)f.width;
-                if (need > nbytes) need = nbytes;
-            }
-            if (need > sent) {
-                e = hipMemcpyAsync(in + sent, bytes + sent, need - sent, hipMemcpyHostToDevice, in_s);
-                sent = need;
-            }
-        }
-        if (e == hipSuccess && overlap) e = hipEventRecord(ctx->ev_arrived[k], in_s);
-        if (e == hipSuccess && overlap) e = hipStreamWaitEvent(s, ctx->ev_arrived[k], 0);
-        if (e == hipSuccess) rc = traces_range(plan, in, g, x0, x1, u.packed ? &ps : nullptr);
-    }
-    if (!rc && e == hipSuccess) rc = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
-    if (!rc && e == hipSuccess && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (!rc) rc = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
+    if (!rc && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
     if (!rc && e == hipSuccess && trace_max) e = hipMemcpyAsync(trace_max, d_out + n, n * sizeof(double), hipMemcpyDeviceToHost, s);
-    // (synchronous, and the one way out of a failed request: nothing of it is left in flight)
-    if (overlap && ctx->copy_in) (void)hipStreamSynchronize(ctx->copy_in);
-    const hipError_t es = hipStreamSynchronize(s);
+    const hipError_t es = hipStreamSynchronize(s);   // (synchronous; the samples' stream has ended before this one)
     if (rc) return rc;
     if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, "sp_render_traces copies");
     return SP_OK;

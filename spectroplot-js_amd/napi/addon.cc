@@ -47,6 +47,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <sys/mman.h>
 #include <string>
@@ -232,8 +233,26 @@ void pool_free_cb(napi_env env, void *data, void *hint)
     delete t;
 }
 
-struct Job {
+// What every request kind has: the context it runs on, its outcome, and - for an asynchronous one - the work item and the references
+// that keep its callback (refs[0]) and whatever the worker thread reads (the handle, the input buffers) alive until the callback.
+// A kind adds its parsed request, run() for the worker thread and result() for a job that ended with SP_OK; its destructor gives back
+// the buffers that did not go to JavaScript.
+struct JobBase {
     Ctx *owner = nullptr;
+    int status = SP_OK;
+    std::string error;
+    napi_async_work work = nullptr;
+    std::vector<napi_ref> refs;
+    virtual ~JobBase() = default;
+    virtual void run() = 0;
+    virtual napi_value result(napi_env env) = 0;
+};
+
+struct Job;
+void run_job(Job *j);
+napi_value make_reply(napi_env env, Job *j);
+
+struct Job : JobBase {
     sp_context *ctx = nullptr;
     sp_group *group = nullptr;   // a group handle's job
     int32_t gather = SP_GROUP_GATHER_DEVICE;   // ... and where its strips meet (req.gather: 'device' | 'host')
@@ -256,11 +275,9 @@ struct Job {
     int rgba_pin = kUnpinned;
     std::vector<uint64_t> c_hist, cb_hist;
     double minmax[2] = {0.0, -200.0};
-    int status = SP_OK;
-    std::string error;
-    // async plumbing
-    napi_async_work work = nullptr;
-    napi_ref cb_ref = nullptr, buf_ref = nullptr, ctx_ref = nullptr;
+    void run() override { run_job(this); }
+    napi_value result(napi_env env) override { return make_reply(env, this); }
+    ~Job() override;
 };
 
 void free_cb(napi_env, void *data, void *) { free(data); }
@@ -499,18 +516,20 @@ napi_value make_reply(napi_env env, Job *j)
     return out;
 }
 
-void free_job(napi_env env, Job *j)
+Job::~Job()
 {
-    if (j->rgba) g_pool.give(j->rgba, j->rgba_size, j->rgba_pin);
-    free(j->gmin); free(j->gmax); free(j->gamp);
-    if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
-    if (j->cb_ref) napi_delete_reference(env, j->cb_ref);
-    if (j->buf_ref) napi_delete_reference(env, j->buf_ref);
+    if (rgba) g_pool.give(rgba, rgba_size, rgba_pin);
+    free(gmin); free(gmax); free(gamp);
+}
+
+void free_job(napi_env env, JobBase *j)
+{
+    for (napi_ref r : j->refs) napi_delete_reference(env, r);
     if (j->work) napi_delete_async_work(env, j->work);
     delete j;
 }
 
-napi_value make_error(napi_env env, Job *j)
+napi_value make_error(napi_env env, const JobBase *j)
 {
     napi_value err, text, code;
     const std::string m = j->error.empty() ? sp_status_string(j->status) : j->error;
@@ -521,74 +540,66 @@ napi_value make_error(napi_env env, Job *j)
     return err;
 }
 
-// An sp_context is one stream with one set of staging buffers: one render at a time.  HipWorker's promise queue already serialises
-// its requests; a second render on a handle whose first is still on a libuv thread is refused here rather than left to race.
-napi_value render_sync(napi_env env, napi_callback_info info, bool named)
+// An sp_context is one stream with one set of staging buffers: one request at a time.  HipWorker's promise queue already serialises
+// its requests; a second one on a handle whose first is still on a libuv thread is refused here rather than left to race.
+bool refuse_in_flight(napi_env env, JobBase *j)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Job *j = new Job;
-    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
-    if (j->owner->inflight > 0) {
-        free_job(env, j);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
-    }
+    if (j->owner->inflight == 0) return false;
+    free_job(env, j);
+    napi_throw_error(env, nullptr, "a render is already in flight on this context");
+    return true;
+}
+
+// A parsed job on the calling thread: its result, or its error thrown.
+napi_value run_sync(napi_env env, JobBase *j)
+{
+    if (refuse_in_flight(env, j)) return nullptr;
     j->owner->inflight++;
-    run_job(j);
+    j->run();
     j->owner->inflight--;
     ctx_release(j->owner);
     napi_value out = nullptr;
     if (j->status != SP_OK) napi_throw(env, make_error(env, j));
-    else out = make_reply(env, j);
+    else out = j->result(env);
     free_job(env, j);
     return out;
 }
-napi_value RenderSync(napi_env env, napi_callback_info info) { return render_sync(env, info, false); }
-napi_value RenderNamedSync(napi_env env, napi_callback_info info) { return render_sync(env, info, true); }
 
-void exec_cb(napi_env, void *data) { run_job((Job *)data); }
+void exec_cb(napi_env, void *data) { ((JobBase *)data)->run(); }
 
 void done_cb(napi_env env, napi_status, void *data)
 {
-    Job *j = (Job *)data;
+    JobBase *j = (JobBase *)data;
     j->owner->inflight--;
     ctx_release(j->owner);
-    napi_value cb, global, argv[2];
-    napi_get_reference_value(env, j->cb_ref, &cb);
+    napi_value cb, global, argv[2], ignored;
+    napi_get_reference_value(env, j->refs[0], &cb);
     napi_get_global(env, &global);
     if (j->status != SP_OK) {
         argv[0] = make_error(env, j);
         napi_get_undefined(env, &argv[1]);
     } else {
         napi_get_null(env, &argv[0]);
-        argv[1] = make_reply(env, j);
+        argv[1] = j->result(env);
     }
-    napi_value ignored;
     napi_call_function(env, global, cb, 2, argv, &ignored);
     free_job(env, j);
 }
 
-napi_value render_async(napi_env env, napi_callback_info info, bool named)
+// A parsed job onto a libuv thread.  `keep`: the callback first, then the handle (and with it the Ctx) and the inputs the worker thread
+// reads; `name`: the async resource; `could_not`: what is thrown if the job cannot be queued.
+napi_value queue_async(napi_env env, JobBase *j, std::initializer_list<napi_value> keep, const char *name, const char *could_not)
 {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Job *j = new Job;
-    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
-    if (j->owner->inflight > 0) {
-        free_job(env, j);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
+    if (refuse_in_flight(env, j)) return nullptr;
+    bool ok = true;
+    for (napi_value v : keep) {
+        napi_ref r = nullptr;
+        ok = ok && napi_create_reference(env, v, 1, &r) == napi_ok;
+        if (r) j->refs.push_back(r);
     }
-    napi_value buf, name;
-    bool ok = napi_get_named_property(env, argv[1], "buffer", &buf) == napi_ok;
-    ok = ok && napi_create_reference(env, buf, 1, &j->buf_ref) == napi_ok;       // keep the input alive while the worker thread reads it
-    ok = ok && napi_create_reference(env, argv[2], 1, &j->cb_ref) == napi_ok;
-    ok = ok && napi_create_reference(env, argv[0], 1, &j->ctx_ref) == napi_ok;   // the handle (and with it the Ctx) stays reachable while the job runs
-    ok = ok && napi_create_string_utf8(env, "spectroplot_hip.render", NAPI_AUTO_LENGTH, &name) == napi_ok;
-    ok = ok && napi_create_async_work(env, nullptr, name, exec_cb, done_cb, j, &j->work) == napi_ok;
+    napi_value res;
+    ok = ok && napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &res) == napi_ok;
+    ok = ok && napi_create_async_work(env, nullptr, res, exec_cb, done_cb, j, &j->work) == napi_ok;
     if (ok) {
         // counted only once the work is certain to run: done_cb is what takes the count down again
         j->owner->inflight++;
@@ -601,9 +612,33 @@ napi_value render_async(napi_env env, napi_callback_info info, bool named)
         Ctx *owner = j->owner;
         free_job(env, j);          // references, the work item, the buffers
         ctx_release(owner);        // a context closed meanwhile is destroyed here if nothing else holds it
-        napi_throw_error(env, nullptr, "could not queue the render");
+        napi_throw_error(env, nullptr, could_not);
     }
     return nullptr;
+}
+
+napi_value render_sync(napi_env env, napi_callback_info info, bool named)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Job *j = new Job;
+    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
+    return run_sync(env, j);
+}
+napi_value RenderSync(napi_env env, napi_callback_info info) { return render_sync(env, info, false); }
+napi_value RenderNamedSync(napi_env env, napi_callback_info info) { return render_sync(env, info, true); }
+
+napi_value render_async(napi_env env, napi_callback_info info, bool named)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Job *j = new Job;
+    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, j, {argv[2], argv[0], buf}, "spectroplot_hip.render", "could not queue the render");
 }
 napi_value Render(napi_env env, napi_callback_info info) { return render_async(env, info, false); }
 napi_value RenderNamed(napi_env env, napi_callback_info info) { return render_async(env, info, true); }
@@ -611,16 +646,18 @@ napi_value RenderNamed(napi_env env, napi_callback_info info) { return render_as
 // ---- batches: renderBatch(handle, req, [{buffer, width}], cb) / renderBatchSync(handle, req, items) -------------------------------
 // req is render's request without buffer and width; every item gets its own reply, shaped as render's (sp_render_batch).  Every
 // value is read with its status checked: a missing or non-numeric field throws instead of leaving a stale value behind.
-struct BatchJob {
-    Ctx *owner = nullptr;
+struct BatchJob;
+void run_batch(BatchJob *b);
+napi_value batch_result(napi_env env, BatchJob *b);
+
+struct BatchJob : JobBase {
     sp_request req{};
     std::vector<double> window;
     std::vector<uint8_t> lut;
     std::vector<Job *> items;
-    int status = SP_OK;
-    std::string error;
-    napi_async_work work = nullptr;
-    napi_ref cb_ref = nullptr, ctx_ref = nullptr, items_ref = nullptr;
+    void run() override { run_batch(this); }
+    napi_value result(napi_env env) override { return batch_result(env, this); }
+    ~BatchJob() override { for (Job *j : items) delete j; }
 };
 
 bool checked_number(napi_env env, napi_value obj, const char *name, double *out)
@@ -658,16 +695,6 @@ bool checked_bool(napi_env env, napi_value obj, const char *name, int32_t *out)
     }
     *out = r ? 1 : 0;
     return true;
-}
-
-void free_batch(napi_env env, BatchJob *b)
-{
-    for (Job *j : b->items) free_job(env, j);
-    if (b->cb_ref) napi_delete_reference(env, b->cb_ref);
-    if (b->ctx_ref) napi_delete_reference(env, b->ctx_ref);
-    if (b->items_ref) napi_delete_reference(env, b->items_ref);
-    if (b->work) napi_delete_async_work(env, b->work);
-    delete b;
 }
 
 bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value items, BatchJob *b)
@@ -776,12 +803,6 @@ void run_batch(BatchJob *b)
 
 napi_value batch_result(napi_env env, BatchJob *b)
 {
-    if (b->status != SP_OK) {
-        Job e;
-        e.status = b->status;
-        e.error = b->error;
-        return make_error(env, &e);
-    }
     napi_value arr;
     if (napi_create_array_with_length(env, b->items.size(), &arr) != napi_ok) return nullptr;
     for (size_t k = 0; k < b->items.size(); k++) {
@@ -801,44 +822,8 @@ napi_value RenderBatchSync(napi_env env, napi_callback_info info)
         return nullptr;
     }
     BatchJob *b = new BatchJob;
-    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_batch(env, b); return nullptr; }
-    if (b->owner->inflight > 0) {
-        free_batch(env, b);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
-    }
-    b->owner->inflight++;
-    run_batch(b);
-    b->owner->inflight--;
-    ctx_release(b->owner);
-    napi_value out = batch_result(env, b);
-    if (b->status != SP_OK) {
-        napi_throw(env, out);
-        out = nullptr;
-    }
-    free_batch(env, b);
-    return out;
-}
-
-void batch_exec_cb(napi_env, void *data) { run_batch((BatchJob *)data); }
-
-void batch_done_cb(napi_env env, napi_status, void *data)
-{
-    BatchJob *b = (BatchJob *)data;
-    b->owner->inflight--;
-    ctx_release(b->owner);
-    napi_value cb, global, argv[2], ignored;
-    napi_get_reference_value(env, b->cb_ref, &cb);
-    napi_get_global(env, &global);
-    if (b->status != SP_OK) {
-        argv[0] = batch_result(env, b);
-        napi_get_undefined(env, &argv[1]);
-    } else {
-        napi_get_null(env, &argv[0]);
-        argv[1] = batch_result(env, b);
-    }
-    napi_call_function(env, global, cb, 2, argv, &ignored);
-    free_batch(env, b);
+    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_job(env, b); return nullptr; }
+    return run_sync(env, b);
 }
 
 napi_value RenderBatch(napi_env env, napi_callback_info info)
@@ -852,37 +837,19 @@ napi_value RenderBatch(napi_env env, napi_callback_info info)
         return nullptr;
     }
     BatchJob *b = new BatchJob;
-    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_batch(env, b); return nullptr; }
-    if (b->owner->inflight > 0) {
-        free_batch(env, b);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
-    }
-    napi_value name;
-    bool ok = napi_create_reference(env, argv[2], 1, &b->items_ref) == napi_ok;   // the items (and their buffers) stay alive
-    ok = ok && napi_create_reference(env, argv[3], 1, &b->cb_ref) == napi_ok;
-    ok = ok && napi_create_reference(env, argv[0], 1, &b->ctx_ref) == napi_ok;
-    ok = ok && napi_create_string_utf8(env, "spectroplot_hip.renderBatch", NAPI_AUTO_LENGTH, &name) == napi_ok;
-    ok = ok && napi_create_async_work(env, nullptr, name, batch_exec_cb, batch_done_cb, b, &b->work) == napi_ok;
-    if (ok) {
-        b->owner->inflight++;
-        if (napi_queue_async_work(env, b->work) != napi_ok) {
-            b->owner->inflight--;
-            ok = false;
-        }
-    }
-    if (!ok) {
-        free_batch(env, b);
-        napi_throw_error(env, nullptr, "could not queue the batch");
-    }
-    return nullptr;
+    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_job(env, b); return nullptr; }
+    // (the items array keeps their buffers alive)
+    return queue_async(env, b, {argv[3], argv[0], argv[2]}, "spectroplot_hip.renderBatch", "could not queue the batch");
 }
 
 // ---- traces: renderTraces(handle, req, cb) / renderTracesSync(handle, req) ---------------------------------------------------------
 // req: {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} -> {trace_min, trace_max}, two Float64Array(n) in image
 // row order (sp_render_traces).  Every value is read with its status checked, as for a batch.
-struct TracesJob {
-    Ctx *owner = nullptr;
+struct TracesJob;
+void run_traces(TracesJob *t);
+napi_value traces_result(napi_env env, TracesJob *t);
+
+struct TracesJob : JobBase {
     sp_request req{};
     std::vector<double> window;
     uint8_t lut[6] = {0, 0, 0, 255, 255, 255};   // (a trace has no colours; the plan wants a map)
@@ -890,20 +857,9 @@ struct TracesJob {
     size_t nbytes = 0;
     int32_t width = 0;
     std::vector<double> out;   // trace_min, then trace_max
-    int status = SP_OK;
-    std::string error;
-    napi_async_work work = nullptr;
-    napi_ref cb_ref = nullptr, buf_ref = nullptr, ctx_ref = nullptr;
+    void run() override { run_traces(this); }
+    napi_value result(napi_env env) override { return traces_result(env, this); }
 };
-
-void free_traces(napi_env env, TracesJob *t)
-{
-    if (t->cb_ref) napi_delete_reference(env, t->cb_ref);
-    if (t->buf_ref) napi_delete_reference(env, t->buf_ref);
-    if (t->ctx_ref) napi_delete_reference(env, t->ctx_ref);
-    if (t->work) napi_delete_async_work(env, t->work);
-    delete t;
-}
 
 bool parse_traces(napi_env env, napi_value handle, napi_value req, TracesJob *t)
 {
@@ -963,12 +919,6 @@ void run_traces(TracesJob *t)
 
 napi_value traces_result(napi_env env, TracesJob *t)
 {
-    if (t->status != SP_OK) {
-        Job e;
-        e.status = t->status;
-        e.error = t->error;
-        return make_error(env, &e);
-    }
     const size_t n = (size_t)t->req.n;
     napi_value out, ab, ta;
     void *data = nullptr;
@@ -991,44 +941,8 @@ napi_value RenderTracesSync(napi_env env, napi_callback_info info)
         return nullptr;
     }
     TracesJob *t = new TracesJob;
-    if (!parse_traces(env, argv[0], argv[1], t)) { free_traces(env, t); return nullptr; }
-    if (t->owner->inflight > 0) {
-        free_traces(env, t);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
-    }
-    t->owner->inflight++;
-    run_traces(t);
-    t->owner->inflight--;
-    ctx_release(t->owner);
-    napi_value out = traces_result(env, t);
-    if (t->status != SP_OK) {
-        napi_throw(env, out);
-        out = nullptr;
-    }
-    free_traces(env, t);
-    return out;
-}
-
-void traces_exec_cb(napi_env, void *data) { run_traces((TracesJob *)data); }
-
-void traces_done_cb(napi_env env, napi_status, void *data)
-{
-    TracesJob *t = (TracesJob *)data;
-    t->owner->inflight--;
-    ctx_release(t->owner);
-    napi_value cb, global, argv[2], ignored;
-    napi_get_reference_value(env, t->cb_ref, &cb);
-    napi_get_global(env, &global);
-    if (t->status != SP_OK) {
-        argv[0] = traces_result(env, t);
-        napi_get_undefined(env, &argv[1]);
-    } else {
-        napi_get_null(env, &argv[0]);
-        argv[1] = traces_result(env, t);
-    }
-    napi_call_function(env, global, cb, 2, argv, &ignored);
-    free_traces(env, t);
+    if (!parse_traces(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
+    return run_sync(env, t);
 }
 
 napi_value RenderTraces(napi_env env, napi_callback_info info)
@@ -1042,31 +956,10 @@ napi_value RenderTraces(napi_env env, napi_callback_info info)
         return nullptr;
     }
     TracesJob *t = new TracesJob;
-    if (!parse_traces(env, argv[0], argv[1], t)) { free_traces(env, t); return nullptr; }
-    if (t->owner->inflight > 0) {
-        free_traces(env, t);
-        napi_throw_error(env, nullptr, "a render is already in flight on this context");
-        return nullptr;
-    }
-    napi_value buf, name;
-    bool ok = napi_get_named_property(env, argv[1], "buffer", &buf) == napi_ok;
-    ok = ok && napi_create_reference(env, buf, 1, &t->buf_ref) == napi_ok;       // the input stays alive while the worker thread reads it
-    ok = ok && napi_create_reference(env, argv[2], 1, &t->cb_ref) == napi_ok;
-    ok = ok && napi_create_reference(env, argv[0], 1, &t->ctx_ref) == napi_ok;
-    ok = ok && napi_create_string_utf8(env, "spectroplot_hip.renderTraces", NAPI_AUTO_LENGTH, &name) == napi_ok;
-    ok = ok && napi_create_async_work(env, nullptr, name, traces_exec_cb, traces_done_cb, t, &t->work) == napi_ok;
-    if (ok) {
-        t->owner->inflight++;
-        if (napi_queue_async_work(env, t->work) != napi_ok) {
-            t->owner->inflight--;
-            ok = false;
-        }
-    }
-    if (!ok) {
-        free_traces(env, t);
-        napi_throw_error(env, nullptr, "could not queue the traces request");
-    }
-    return nullptr;
+    if (!parse_traces(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderTraces", "could not queue the traces request");
 }
 
 napi_value DeviceCount(napi_env env, napi_callback_info)

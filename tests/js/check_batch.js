@@ -73,6 +73,34 @@ async function main() {
         try { got = native.renderBatchSync(h, req, items) } catch (e) { threw = true }
         if (!threw || got) failures.push(`renderBatchSync accepted ${what}`)
     }
+    // the job lifecycle the addon shares between its request kinds: while a batch is in flight on a handle, a second one is refused;
+    // a handle destroyed before the callback still delivers the batch, and is released once the batch has returned
+    {
+        const items = [{ buffer: capture(65536, 5), width: 200 }, { buffer: capture(9000, 6), width: 33 }, { buffer: capture(2048, 7), width: 0 }]
+        const want = native.renderBatchSync(h, req, items)
+        const h2 = native.createContext(0)
+        const done = new Promise((resolve, reject) => native.renderBatch(h2, req, items, (err, r) => err ? reject(err) : resolve(r)))
+        for (const [what, f] of [['renderBatch', () => native.renderBatch(h2, req, items, () => failures.push('a refused batch called back'))],
+                                 ['renderBatchSync', () => native.renderBatchSync(h2, req, items)]]) {
+            let msg = ''
+            try { f() } catch (e) { msg = e.message }
+            if (msg !== 'a render is already in flight on this context') failures.push(`${what} during a batch in flight: "${msg}"`)
+        }
+        if (native.destroyContext(h2) !== false) failures.push('destroyContext released a context with a batch in flight')
+        const got = await done
+        const bytes = (x) => new Uint8Array(x.buffer || x, x.byteOffset || 0, x.byteLength)
+        if (!Array.isArray(got) || got.length !== want.length) failures.push('renderBatch after destroyContext: no replies')
+        else for (let k = 0; k < want.length; k++) {
+            for (const f of ['rgba', 'gauge_mins', 'gauge_maxs', 'gauge_amps', 'c_hist', 'cB_hist'])
+                if (!same(bytes(got[k][f]), bytes(want[k][f]))) failures.push(`renderBatch after destroyContext: item ${k} ${f} differs`)
+            if (!Object.is(got[k].dBfs_min, want[k].dBfs_min) || !Object.is(got[k].dBfs_max, want[k].dBfs_max))
+                failures.push(`renderBatch after destroyContext: item ${k} dBfs range differs`)
+        }
+        if (want[0].rgba.byteLength !== 4 * 200 * 256 || !bytes(want[0].rgba).some(v => v !== 0)) failures.push('the lifecycle batch renders nothing')
+        let msg = ''
+        try { native.renderBatchSync(h2, req, items) } catch (e) { msg = e.message }
+        if (!/destroyed/.test(msg)) failures.push(`a destroyed handle took a batch: "${msg}"`)
+    }
     native.destroyContext(h)
 
     if (failures.length) { console.log(failures.join('\n')); process.exit(1) }

@@ -30,6 +30,7 @@ async function main(dir) {
     const cases = JSON.parse(fs.readFileSync(path.join(dir, 'cases.json'), 'utf8'))
     const worker = new HipWorker({ device: 0 })
     const ctx = native.createContext(0)
+    let last = null
     for (const c of cases) {
         const file = path.join(dir, c.file)
         const bytes = fs.readFileSync(file)
@@ -40,8 +41,10 @@ async function main(dir) {
             range: c.range, width: c.width, channelMode: c.channelMode, cmap: [[0, 0, 0], [255, 255, 255]], offset: 0 }
         check(`${c.id} renderTraces`, await worker.renderTraces(message), want)
         check(`${c.id} renderTracesSync (worker)`, worker.renderTracesSync(message), want)
-        check(`${c.id} renderTracesSync (addon)`, native.renderTracesSync(ctx, { format: native.parseFormat(c.format).id, buffer, n: c.n,
-            width: c.width, windowc: w.window, block_norm: 1.0 / w.weight, gain: c.gain, range: c.range, channelMode: c.channelMode }), want)
+        const req = { format: native.parseFormat(c.format).id, buffer, n: c.n, width: c.width, windowc: w.window, block_norm: 1.0 / w.weight,
+            gain: c.gain, range: c.range, channelMode: c.channelMode }
+        check(`${c.id} renderTracesSync (addon)`, native.renderTracesSync(ctx, req), want)
+        last = { id: c.id, req, want }
         // cli.js --traces: JSON beside the image
         const out = path.join(dir, c.id + '.json.out'), img = path.join(dir, c.id + '.rgba')
         execFileSync(process.execPath, [path.join(__dirname, '..', '..', 'spectroplot-js_amd', 'js', 'cli.js'), file, '--format', c.format, '--n',
@@ -71,6 +74,26 @@ async function main(dir) {
         try { native.renderTracesSync(ctx, { format: 'cu8', buffer, n: c.n, width: c.width }) } catch (e) { threw = true }
         if (!threw) throw new Error('addon: a request without its numbers did not throw')
         check(`${c.id} after the errors`, await worker.renderTraces(message), want)
+    }
+    // the job lifecycle the addon shares between its request kinds: while a traces request is in flight on a handle, a second one is
+    // refused; a handle destroyed before the callback still delivers the traces, and is released once the request has returned
+    {
+        const h = native.createContext(0)
+        const done = new Promise((resolve, reject) => native.renderTraces(h, last.req, (err, r) => err ? reject(err) : resolve(r)))
+        let called = false
+        for (const [what, f] of [['renderTraces', () => native.renderTraces(h, last.req, () => { called = true })],
+                                 ['renderTracesSync', () => native.renderTracesSync(h, last.req)]]) {
+            let msg = ''
+            try { f() } catch (e) { msg = e.message }
+            if (msg !== 'a render is already in flight on this context') throw new Error(`${what} during a request in flight: "${msg}"`)
+        }
+        if (native.destroyContext(h) !== false) throw new Error('destroyContext released a context with a request in flight')
+        check(`${last.id} renderTraces (addon) after destroyContext`, await done, last.want)
+        await new Promise(r => setImmediate(r))
+        if (called) throw new Error('a refused request called back')
+        let msg = ''
+        try { native.renderTracesSync(h, last.req) } catch (e) { msg = e.message }
+        if (!/destroyed/.test(msg)) throw new Error(`a destroyed handle took a request: "${msg}"`)
     }
     worker.terminate()
     native.destroyContext(ctx)

@@ -13,6 +13,7 @@ import siggen
 import tracesref
 from __graft_entry__ import load_package
 from oracle import pyoracle
+from test_gpu_parity import FROM_HOST, _assert_same as assert_same_reply
 
 pytestmark = pytest.mark.gpu
 
@@ -261,6 +262,64 @@ def test_chunked_contiguous_sp_render_traces(ctx):
     got = ctx.render_traces(fmt, data, n, win, 1.0 / weight, 3.0, 50.0, width, fill=_garbage())
     tracesref.assert_same(got, want, "contiguous, chunked")
     assert ctx.last_upload_bytes() == data.size
+
+
+def test_chunked_sp_render_traces_waits_for_a_queued_execute_from_host(pkg, ctx):
+    """sp_plan_execute_from_host returns with its copies and kernels still queued on the context's staging buffer; a chunked
+    sp_render_traces on the same context, called WITHOUT a synchronisation in between, must not upload over them: the queued render
+    against the oracle, the traces against sp_plan_execute_traces on a device copy, both bit for bit.  The capture sits in page-locked
+    memory and the stream is kept busy before it, so that its copies really are still queued.  Then once more behind a
+    synchronisation and without the busy work: the chunked request finds an idle stream, which it does not wait for."""
+    r_fmt, r_n, r_lg, W, r_wf = FROM_HOST[3]                  # sparse, one packed chunk: it shares the staging buffer's first bytes
+    r_data = siggen.generate(r_fmt, {"kind": "trinoise", "seed": 99 + r_n, "step": 7321, "gshift": 9, "amp": 0.5, "namp": 0.02}, 1 << r_lg)
+    r_win, r_weight = pyoracle.window("blackmanHarris", r_n)
+    i = np.arange(256)
+    lut = np.stack([i, 255 - i, (i * 7) & 255], axis=1).astype(np.uint8)
+    r_want = pyoracle.render(r_fmt, r_data, r_n, r_win, 1.0 / r_weight, 6.0, 30.0, lut, W, False, r_wf)
+    fmt, n, width = "CS16", 512, 20000                        # test_chunked_contiguous_sp_render_traces' shape
+    data = _capture(fmt, n, width, 262)
+    assert data.size >= 16 << 20 and width >= 1024
+    win, weight = pyoracle.window("hann", n)
+    want = _device_traces(ctx, fmt, n, width, data, win, 1.0 / weight)
+    assert not (want["trace_min"] == 0.0).any() and len(np.unique(want["trace_max"])) >= n // 2
+    plan = ctx.plan(r_fmt, r_n, r_win, 1.0 / r_weight, 6.0, 30.0, lut, False, r_wf)
+    sizes = [4 * W * r_n, W, W, W, 8 * 256, 8000, 16]
+    ptrs = [ctx.alloc(max(s_, 16)) for s_ in sizes]
+    L = ctx.lib.L
+    L.sp_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
+    L.sp_host_free.argtypes = [C.c_void_p]
+    h = C.c_void_p()
+    assert L.sp_host_alloc(r_data.size, C.byref(h)) == 0
+    pinned = np.ctypeslib.as_array(C.cast(h, C.POINTER(C.c_uint8)), shape=(r_data.size,))
+    pinned[:] = r_data
+    busy = ctx.alloc(1 << 30)
+    try:
+        # once before, so that nothing between the two calls below synchronises by itself (the traces' plan, staging buffers, streams)
+        tracesref.assert_same(ctx.render_traces(fmt, data, n, win, 1.0 / weight, 3.0, 50.0, width, fill=_garbage()), want, "before")
+        for queued in (True, False):
+            for p_, s_ in zip(ptrs, sizes):
+                ctx.memset(p_, 0xA5, max(s_, 16))
+            if queued:
+                for _ in range(16):                            # a few ms of work ahead of the request on the context's stream
+                    ctx.memset(busy, 0, 1 << 30)
+            plan.execute_from_host(pinned, W, *ptrs)
+            if not queued:
+                ctx.synchronize()
+            got = ctx.render_traces(fmt, data, n, win, 1.0 / weight, 3.0, 50.0, width, fill=_garbage())
+            ctx.synchronize()
+            assert ctx.last_upload_bytes() == data.size
+            r_got = {"rgba": ctx.download(ptrs[0], sizes[0]), "gauge_mins": ctx.download(ptrs[1], W), "gauge_maxs": ctx.download(ptrs[2], W),
+                     "gauge_amps": ctx.download(ptrs[3], W), "c_hist": ctx.download(ptrs[4], 8 * 256, np.uint64),
+                     "cB_hist": ctx.download(ptrs[5], 8000, np.uint64)}
+            mm = ctx.download(ptrs[6], 16, np.float64)
+            r_got["dBfs_min"], r_got["dBfs_max"] = float(mm[0]), float(mm[1])
+            assert_same_reply(r_got, r_want)
+            tracesref.assert_same(got, want, "behind a queued execute_from_host" if queued else "on an idle stream")
+    finally:
+        L.sp_host_free(h)
+        for p_ in ptrs + [busy]:
+            ctx.free(p_)
+        plan.close()
 
 
 def test_small_sparse_request_uploads_its_frames_only(ctx):
