@@ -210,6 +210,15 @@ int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbytes);
  */
 int sp_debug_upload_plan(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t want_image, int64_t *out, size_t capacity,
                          size_t *used);
+/*
+ * (tests) Where a sliced render of `count` workers puts its strips in the caller's image (lib/spectroplot.js:1208, 1244), without a
+ * device: the layout sp_group_render_ex follows with either gather.  Bands and the un-drawn rest are rectangles of bytes in the RGBA
+ * image: `rows` rows of `row bytes`, `pitch` bytes apart.  out[] receives int64 words: slice width, strip bytes, rest (frames no strip
+ * draws), the bands' pitch, row bytes and rows, the rest's offset, pitch, row bytes and rows; then per strip the byte offset of its band
+ * and the offset of its gauges.  *used = words needed (SP_ERR_INVALID_ARG if capacity is smaller).  tests/test_slice_layout_cpu.py
+ * checks it against the reference's formulas.
+ */
+int sp_debug_slice_layout(int32_t n, int32_t width, int32_t count, int32_t waterfall, int64_t *out, size_t capacity, size_t *used);
 
 /*
  * The same with the request given by names, as the reference's caller assembles its message from options

@@ -192,18 +192,9 @@ int dispatch_format(int32_t fmt, F &&f)
 
 int validate_request(sp_context *ctx, const sp_request *r)
 {
-    if (!r) return fail(ctx, SP_ERR_INVALID_ARG, "request is null");
-    if (r->format < 0 || r->format >= SP_FMT_COUNT) return fail(ctx, SP_ERR_INVALID_ARG, "unknown format id");
-    if (r->n < 1 || sphost::log2_exact(r->n) < 0) return fail(ctx, SP_ERR_NOT_POW2, "Length is not a power of 2");
-    if (r->n < 2) return fail(ctx, SP_ERR_UNSUPPORTED, "n = 1 is not supported (the reference writes no pixels for it)");
-    if (r->n > SP_MAX_N) return fail(ctx, SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
-    if (r->lut_len < 1 || r->lut_len > SP_MAX_LUT) return fail(ctx, SP_ERR_UNSUPPORTED, "lut_len must be 1..SP_MAX_LUT");
-    if (!r->windowc || !r->lut_rgb) return fail(ctx, SP_ERR_INVALID_ARG, "windowc / lut_rgb is null");
-    if (!(r->range > 0) || !std::isfinite(r->range)) return fail(ctx, SP_ERR_UNSUPPORTED, "range must be finite and > 0");
-    if (!std::isfinite(r->gain)) return fail(ctx, SP_ERR_UNSUPPORTED, "gain must be finite");
-    if (r->detector != SP_DETECTOR_SAMPLE && r->detector != SP_DETECTOR_PEAK)
-        return fail(ctx, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
-    return SP_OK;
+    std::string why;
+    const int rc = sphost::validate_request(r, why);
+    return rc ? fail(ctx, rc, why) : SP_OK;
 }
 
 }  // namespace
@@ -1074,6 +1065,7 @@ extern "C" int sp_merge_replies_batch(sp_context *ctx, const void *d_gathered, i
 // `strips` as an all-gather / gather delivers them, goes to columns [r * slice_width, (r + 1) * slice_width) of the n x width image
 // (spectrogram), or to rows [width - slice_width - r * slice_width, ...) of the width x n image (waterfall: row bands in reverse order).
 // One thread moves one V (16 bytes = 4 pixels where the widths allow, else one pixel); reads and writes are whole row pieces.
+// (spgeo::SliceLayout in sp_geometry.h is the host-side twin of this arithmetic.)
 template <typename V>
 __global__ void k_place_strips(uint8_t *__restrict__ image, const uint8_t *__restrict__ strips, int count, int n, int width, int slice_width,
                                int waterfall)

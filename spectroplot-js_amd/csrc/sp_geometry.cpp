@@ -203,3 +203,24 @@ extern "C" int sp_debug_upload_plan(int32_t format, int32_t n, size_t nbytes, in
     memcpy(out, v.data(), v.size() * 8);
     return SP_OK;
 }
+
+// (tests) The slice layout of a sliced render of this shape (spgeo::SliceLayout) - pure host arithmetic, no device.  out[]: slice width,
+// strip bytes, rest, the bands' pitch, row bytes and rows, the rest's offset, pitch, row bytes and rows; per strip its band's and its
+// gauges' offset.
+extern "C" int sp_debug_slice_layout(int32_t n, int32_t width, int32_t count, int32_t waterfall, int64_t *out, size_t capacity, size_t *used)
+{
+    if (n < 1 || width < 0 || count < 1 || !out || !used) return SP_ERR_INVALID_ARG;
+    const spgeo::SliceLayout s(n, width, count, waterfall != 0);
+    std::vector<int64_t> v;
+    for (size_t x : {s.slice_width, s.strip_bytes(), s.rest, s.band_pitch(), s.band_row_bytes(), s.band_rows(), s.rest_offset(), s.rest_pitch(),
+                     s.rest_row_bytes(), s.rest_rows()})
+        v.push_back((int64_t)x);
+    for (size_t r = 0; r < s.count; r++) {
+        v.push_back((int64_t)s.band_offset(r));
+        v.push_back((int64_t)s.gauge_offset(r));
+    }
+    *used = v.size();
+    if (v.size() > capacity) return SP_ERR_INVALID_ARG;
+    memcpy(out, v.data(), v.size() * 8);
+    return SP_OK;
+}

@@ -78,4 +78,32 @@ struct UploadPlan {
 // back over the link.
 void plan_upload(const Geometry &g, bool packable, bool chunkable, size_t out_bytes, UploadPlan &u);
 
+// ---- sliced renders: where the strips of `count` workers lie in the caller's image --------------------------------------------------
+// The caller's layout (lib/spectroplot.js:1206-1244), in bytes of the RGBA image: every worker renders sliceWidth = ~~(width / workers)
+// frames (:1208) and strip r is put at (r * sliceWidth, 0) of the width x n spectrogram - a band of columns - or at
+// (0, width - sliceWidth - r * sliceWidth) of the n x width waterfall - a band of rows, in reverse order (:1244).  The
+// width - workers * sliceWidth frames that no worker renders stay as the caller's fresh canvas has them: clear.  Bands and rest are
+// rectangles of `rows` rows of `row_bytes`, `pitch` bytes apart; a row band is one row.  The host-side twin of k_place_strips.
+struct SliceLayout {
+    size_t n, width, count;
+    bool waterfall;
+    size_t slice_width, rest;   // frames per strip; frames no strip draws
+    SliceLayout(int32_t n_, int32_t width_, int32_t count_, bool waterfall_)
+        : n((size_t)n_), width((size_t)width_), count((size_t)count_), waterfall(waterfall_), slice_width((size_t)(width_ / count_)),
+          rest(width - slice_width * count)
+    {
+    }
+    size_t image_bytes() const { return 4 * width * n; }
+    size_t strip_bytes() const { return 4 * slice_width * n; }
+    size_t band_offset(size_t r) const { return waterfall ? 4 * n * (width - slice_width - slice_width * r) : 4 * slice_width * r; }
+    size_t band_pitch() const { return waterfall ? strip_bytes() : 4 * width; }
+    size_t band_row_bytes() const { return waterfall ? strip_bytes() : 4 * slice_width; }
+    size_t band_rows() const { return waterfall ? 1 : n; }
+    size_t gauge_offset(size_t r) const { return slice_width * r; }   // slice r's gauges: columns [r * sliceWidth, (r + 1) * sliceWidth)
+    size_t rest_offset() const { return waterfall ? 0 : 4 * slice_width * count; }
+    size_t rest_pitch() const { return waterfall ? 4 * n * rest : 4 * width; }
+    size_t rest_row_bytes() const { return waterfall ? 4 * n * rest : 4 * rest; }
+    size_t rest_rows() const { return waterfall ? 1 : n; }
+};
+
 }  // namespace spgeo

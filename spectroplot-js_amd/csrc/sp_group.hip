@@ -26,6 +26,7 @@
 
 #include "../../include/spectroplot_hip.h"
 #include "sp_formats.h"
+#include "sp_geometry.h"
 #include "sp_host.h"
 
 namespace {
@@ -390,110 +391,146 @@ extern "C" int sp_group_root_bytes(const sp_group *g, size_t *image_bytes, size_
     return SP_OK;
 }
 
-// ---- SP_GROUP_GATHER_HOST: N host links side by side, nothing gathered on a device ----------------------------------------------------
-static int render_to_host(sp_group *g, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply)
-{
-    const int count = (int)g->m.size();
-    const spfmt::Format f = spfmt::describe(req->format);
-    const size_t n = (size_t)req->n, L = (size_t)req->lut_len, W = (size_t)width;
-    const size_t sw = (size_t)(width / count);                          // sliceWidth = ~~(width / workers), lib/spectroplot.js:1208
-    auto run_member = [&](int r) {
-        Member &mb = g->m[(size_t)r];
-        mb.status = SP_OK;
-        size_t b0 = 0, b1 = 0;
-        sp_slice_bounds(nbytes, f.width, r, count, &b0, &b1);          // lib/samples.js:253-258
-        mb.h_hist.assign(L + SP_CB_HIST_SIZE, 0);
-        sp_reply hr{};
-        if (reply->rgba)   // putImageData(strip, offset, 0) / (strip, 0, width - sliceWidth - offset), lib/spectroplot.js:1244
-            hr.rgba = req->waterfall ? reply->rgba + 4 * n * (W - sw - sw * (size_t)r) : reply->rgba + 4 * sw * (size_t)r;
-        hr.c_hist = mb.h_hist.data();
-        hr.cb_hist = mb.h_hist.data() + L;
-        hr.dbfs_minmax = mb.h_minmax;
-        hr.gauge_mins = reply->gauge_mins ? reply->gauge_mins + sw * (size_t)r : nullptr;
-        hr.gauge_maxs = reply->gauge_maxs ? reply->gauge_maxs + sw * (size_t)r : nullptr;
-        hr.gauge_amps = reply->gauge_amps ? reply->gauge_amps + sw * (size_t)r : nullptr;
-        const double t0 = now_ms();
-        mb.status = sp_render_strip(mb.ctx, req, bytes + b0, b1 - b0, (int32_t)sw, &hr, width);
-        mb.host_ms = now_ms() - t0;
-        if (mb.status) mb.error = sp_last_error(mb.ctx);
-    };
-    for_each_member(g, run_member);
-    for (Member &mb : g->m)
-        if (mb.status) return gfail(g, mb.status, mb.error);
-    g->transport = 3;
-    g->t_render = 0;
-    for (Member &mb : g->m) g->t_render = mb.host_ms > g->t_render ? mb.host_ms : g->t_render;
-    g->t_gather = g->t_download = 0;
+namespace {
 
-    // the caller's merge (lib/spectroplot.js:1125-1126, 1229-1238)
-    double mn = 0.0, mx = -200.0;
-    for (Member &mb : g->m) {
-        if (mb.h_minmax[0] < mn) mn = mb.h_minmax[0];
-        if (mb.h_minmax[1] > mx) mx = mb.h_minmax[1];
-    }
-    if (reply->dbfs_minmax) {
-        reply->dbfs_minmax[0] = mn;
-        reply->dbfs_minmax[1] = mx;
-    }
-    if (reply->c_hist)
-        for (size_t i = 0; i < L; i++) {
-            uint64_t s = 0;
-            for (Member &mb : g->m) s += mb.h_hist[i];
-            reply->c_hist[i] = s;
-        }
-    if (reply->cb_hist)
-        for (size_t i = 0; i < SP_CB_HIST_SIZE; i++) {
-            uint64_t s = 0;
-            for (Member &mb : g->m) s += mb.h_hist[L + i];
-            reply->cb_hist[i] = s;
-        }
-    // what no slice draws stays clear, as on the caller's fresh canvas (:1208: columns workers * sliceWidth ... width - 1)
-    const size_t rest = W - sw * (size_t)count;
-    if (rest) {
-        if (reply->rgba) {
-            if (req->waterfall) memset(reply->rgba, 0, 4 * n * rest);
-            else
-                for (size_t y = 0; y < n; y++) memset(reply->rgba + 4 * (W * y + sw * (size_t)count), 0, 4 * rest);
-        }
-        for (uint8_t *gp : {reply->gauge_mins, reply->gauge_maxs, reply->gauge_amps})
-            if (gp) memset(gp + sw * (size_t)count, 0, rest);
-    }
-    return SP_OK;
-}
+// One sliced render of a group: what the request, the reply and the group fix before a member runs, and the phases of the render.  A
+// phase returns its status and leaves the text of a failure in `why`; sp_group_render_ex is the one place that drains and reports.
+struct GroupRender {
+    sp_group *g;
+    const sp_request *req;
+    const uint8_t *bytes;
+    size_t nbytes;
+    int32_t width;
+    const sp_reply &reply;   // the caller's
+    const int count;
+    Member &root;
+    const spgeo::SliceLayout lay;
+    const sphost::ReplyRecord rec, side;   // a member's record; its histograms and range (what is merged)
+    const size_t small_pitch;              // the members' records lie this far apart on the root
+    const bool want_image;
+    // choose_transport's: RCCL or peer copies; the first member that sends; whether strips land beside the image, and how many
+    bool use_rccl = false, rccl_done = false, stage = false;
+    int first_sender = 1;
+    size_t staged = 0;
+    std::string why;
 
-extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
-                                  int32_t gather)
-{
-    if (!g || !req || !reply) return SP_ERR_INVALID_ARG;
-    if (gather != SP_GROUP_GATHER_DEVICE && gather != SP_GROUP_GATHER_HOST) return gfail(g, SP_ERR_INVALID_ARG, "unknown gather mode");
-    if (width < 0) return gfail(g, SP_ERR_INVALID_ARG, "width < 0");
-    if (nbytes && !bytes) return gfail(g, SP_ERR_INVALID_ARG, "bytes is null");
-    if (req->format < 0 || req->format >= SP_FMT_COUNT) return gfail(g, SP_ERR_INVALID_ARG, "unknown format id");
-    // (everything the plan cache below dereferences; the rest of the request is validated where the plans are made)
-    if (req->n < 1 || (req->n & (req->n - 1))) return gfail(g, SP_ERR_NOT_POW2, "Length is not a power of 2");
-    if (req->n > SP_MAX_N) return gfail(g, SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
-    if (req->lut_len < 1 || req->lut_len > SP_MAX_LUT) return gfail(g, SP_ERR_UNSUPPORTED, "lut_len must be 1..SP_MAX_LUT");
-    if (!req->windowc || !req->lut_rgb) return gfail(g, SP_ERR_INVALID_ARG, "windowc / lut_rgb is null");
-    if (req->detector != SP_DETECTOR_SAMPLE && req->detector != SP_DETECTOR_PEAK)
-        return gfail(g, SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
-    // (a slice is its own request with its own stride, hence its own sub-frame count: not built here)
-    if (req->detector != SP_DETECTOR_SAMPLE) return gfail(g, SP_ERR_UNSUPPORTED, "the peak detector is not supported in group renders");
-    const int count = (int)g->m.size();
-    const spfmt::Format f = spfmt::describe(req->format);
-    // the reference constructs its typed view over the whole buffer before it slices (lib/spectroplot.js:1096-1100)
-    if (nbytes % (size_t)f.elem) return gfail(g, SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
-    if (gather == SP_GROUP_GATHER_HOST) return render_to_host(g, req, bytes, nbytes, width, reply);
-    Member &root = g->m[0];
+    GroupRender(sp_group *g_, const sp_request *q, const uint8_t *b, size_t nb, int32_t w, const sp_reply &to)
+        : g(g_), req(q), bytes(b), nbytes(nb), width(w), reply(to), count((int)g_->m.size()), root(g_->m[0]),
+          lay(q->n, w, count, q->waterfall != 0), rec{(size_t)q->lut_len, lay.slice_width}, side{(size_t)q->lut_len, 0},
+          small_pitch((rec.bytes() + 15) & ~(size_t)15), want_image(to.rgba && lay.strip_bytes())
+    {
+    }
 
+    // the one convention for a failure: its status is returned, its text left in `why` (a member's HIP error: in the member's `error`)
+    int fail(int code, const std::string &msg)
+    {
+        why = msg;
+        return code;
+    }
+    static int hip(std::string &to, hipError_t e, const char *what)
+    {
+        if (e != hipSuccess) to = std::string(what) + hipGetErrorString(e);
+        return e == hipSuccess ? SP_OK : SP_ERR_HIP;
+    }
+    int gather_hip(hipError_t e) { return hip(why, e, "group gather: "); }
+
+    // What sp_group_render_ex refuses before it touches the group: the group's own refusals around the request as every entry point
+    // checks it (sphost::validate_request).
+    int check_request(int32_t gather)
+    {
+        if (gather != SP_GROUP_GATHER_DEVICE && gather != SP_GROUP_GATHER_HOST) return fail(SP_ERR_INVALID_ARG, "unknown gather mode");
+        if (width < 0) return fail(SP_ERR_INVALID_ARG, "width < 0");
+        if (nbytes && !bytes) return fail(SP_ERR_INVALID_ARG, "bytes is null");
+        if (const int rc = sphost::validate_request(req, why)) return rc;
+        // (a slice is its own request with its own stride, hence its own sub-frame count: not built here)
+        if (req->detector != SP_DETECTOR_SAMPLE) return fail(SP_ERR_UNSUPPORTED, "the peak detector is not supported in group renders");
+        // the reference constructs its typed view over the whole buffer before it slices (lib/spectroplot.js:1096-1100)
+        if (nbytes % (size_t)spfmt::describe(req->format).elem) return fail(SP_ERR_BYTE_LENGTH, "byte length is not a multiple of the element size");
+        return SP_OK;
+    }
+
+    // Every member's slice (lib/samples.js:253-258) through `render(member, r, slice, slice bytes)`, all members at once; a member keeps
+    // its status, its error text (its context's unless `render` left one) and the host clock of its render.
+    template <typename R>
+    int run_members(R &&render)
+    {
+        for_each_member(g, [&](int r) {
+            Member &mb = g->m[(size_t)r];
+            mb.error.clear();
+            size_t b0 = 0, b1 = 0;
+            sp_slice_bounds(nbytes, spfmt::describe(req->format).width, r, count, &b0, &b1);
+            const double t0 = now_ms();
+            mb.status = render(mb, r, bytes + b0, b1 - b0);
+            mb.host_ms = now_ms() - t0;
+            if (mb.status && mb.error.empty()) mb.error = sp_last_error(mb.ctx);
+        });
+        for (Member &mb : g->m)
+            if (mb.status) return fail(mb.status, mb.error);
+        return SP_OK;
+    }
+
+    // ---- SP_GROUP_GATHER_HOST: N host links side by side, nothing gathered on a device ------------------------------------------------
+    int render_to_host()
+    {
+        const size_t L = side.lut_len;
+        const int rc = run_members([&](Member &mb, int r, const uint8_t *slice, size_t slice_bytes) {
+            mb.h_hist.assign(L + SP_CB_HIST_SIZE, 0);
+            sp_reply hr{};
+            hr.rgba = reply.rgba ? reply.rgba + lay.band_offset((size_t)r) : nullptr;
+            hr.c_hist = mb.h_hist.data();
+            hr.cb_hist = mb.h_hist.data() + L;
+            hr.dbfs_minmax = mb.h_minmax;
+            hr.gauge_mins = reply.gauge_mins ? reply.gauge_mins + lay.gauge_offset((size_t)r) : nullptr;
+            hr.gauge_maxs = reply.gauge_maxs ? reply.gauge_maxs + lay.gauge_offset((size_t)r) : nullptr;
+            hr.gauge_amps = reply.gauge_amps ? reply.gauge_amps + lay.gauge_offset((size_t)r) : nullptr;
+            return sp_render_strip(mb.ctx, req, slice, slice_bytes, (int32_t)lay.slice_width, &hr, width);
+        });
+        if (rc) return rc;
+        g->transport = 3;
+        g->t_render = 0;
+        for (Member &mb : g->m) g->t_render = mb.host_ms > g->t_render ? mb.host_ms : g->t_render;
+        g->t_gather = g->t_download = 0;
+
+        // the caller's merge (lib/spectroplot.js:1125-1126, 1229-1238)
+        double mn = 0.0, mx = -200.0;
+        for (Member &mb : g->m) {
+            if (mb.h_minmax[0] < mn) mn = mb.h_minmax[0];
+            if (mb.h_minmax[1] > mx) mx = mb.h_minmax[1];
+        }
+        if (reply.dbfs_minmax) {
+            reply.dbfs_minmax[0] = mn;
+            reply.dbfs_minmax[1] = mx;
+        }
+        const auto sum = [&](uint64_t *to, size_t from, size_t bins) {
+            for (size_t i = 0; to && i < bins; i++) {
+                to[i] = 0;
+                for (Member &mb : g->m) to[i] += mb.h_hist[from + i];
+            }
+        };
+        sum(reply.c_hist, 0, L);
+        sum(reply.cb_hist, L, SP_CB_HIST_SIZE);
+        // what no slice draws stays clear, as on the caller's fresh canvas (:1208: columns workers * sliceWidth ... width - 1)
+        if (lay.rest) {
+            if (reply.rgba)
+                for (size_t y = 0; y < lay.rest_rows(); y++) memset(reply.rgba + lay.rest_offset() + lay.rest_pitch() * y, 0, lay.rest_row_bytes());
+            for (uint8_t *gp : {reply.gauge_mins, reply.gauge_maxs, reply.gauge_amps})
+                if (gp) memset(gp + lay.gauge_offset((size_t)count), 0, lay.rest);
+        }
+        return SP_OK;
+    }
+
+    // ---- SP_GROUP_GATHER_DEVICE ------------------------------------------------------------------------------------------------------
     // plans: one per member (its tables live on its device), kept while the request's constants repeat
-    if (!g->have_plan || !sphost::same_request(g->req, g->window, g->lut, req)) {
+    int ensure_plans()
+    {
+        if (g->have_plan && sphost::same_request(g->req, g->window, g->lut, req)) return SP_OK;
         drop_plans(g);
         for (Member &mb : g->m) {
             const int rc = sp_plan_create(mb.ctx, req, &mb.plan);
             if (rc) {
-                const std::string msg = sp_last_error(mb.ctx);
+                why = sp_last_error(mb.ctx);
                 drop_plans(g);
-                return gfail(g, rc, msg);
+                return rc;
             }
         }
         g->req = *req;
@@ -502,144 +539,132 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
         g->req.windowc = nullptr;
         g->req.lut_rgb = nullptr;
         g->have_plan = true;
+        return SP_OK;
     }
 
-    const size_t n = (size_t)req->n, L = (size_t)req->lut_len, W = (size_t)width;
-    const size_t sw = (size_t)(width / count);                          // sliceWidth = ~~(width / workers), lib/spectroplot.js:1208
-    const size_t strip_bytes = 4 * sw * n;
-    const sphost::ReplyRecord rec{L, sw}, side{L, 0};                  // a member's record; its histograms and range (what is merged)
-    const size_t small_pitch = (rec.bytes() + 15) & ~(size_t)15;
-    const bool want_image = reply->rgba && strip_bytes;
-
-    // ---- every member: its slice to its device, rendered there (all members at once) -------------------------------------------
-    auto run_member = [&](int r) {
-        Member &mb = g->m[(size_t)r];
-        mb.status = SP_OK;
-        size_t b0 = 0, b1 = 0;
-        sp_slice_bounds(nbytes, f.width, r, count, &b0, &b1);          // lib/samples.js:253-258
-        auto hip = [&](hipError_t e, const char *what) {
-            if (e != hipSuccess && mb.status == SP_OK) {
-                mb.status = SP_ERR_HIP;
-                mb.error = std::string(what) + ": " + hipGetErrorString(e);
-            }
-        };
-        hip(hipSetDevice(mb.device), "hipSetDevice");
-        if (mb.status) return;
-        hip(hipEventRecord(mb.started, mb.stream), "hipEventRecord");
-        if (mb.status) return;
-        sp_reply d = rec.view(mb.small.p);
-        d.rgba = reply->rgba ? (uint8_t *)mb.strip.p : nullptr;
-        // the slice travels in chunks of frames while earlier chunks are rendered (a sparse slice: only the samples its frames read)
-        const int rc = sp_plan_execute_from_host(mb.plan, bytes + b0, b1 - b0, (int32_t)sw, &d);
-        if (rc) {
-            mb.status = rc;
-            mb.error = sp_last_error(mb.ctx);
-            return;
-        }
-        hip(hipEventRecord(mb.rendered, mb.stream), "hipEventRecord");
-    };
     // (buffers first, on this thread: growing one frees the old block, and hipFree waits for the whole device - not something to do
     // next to another member's copy in flight; the capture's own staging buffer belongs to the member's context)
-    for (int r = 0; r < count; r++) {
-        Member &mb = g->m[(size_t)r];
-        if (hipSetDevice(mb.device) != hipSuccess) return gfail(g, SP_ERR_HIP, "hipSetDevice");
-        int rc = mb.strip.reserve(strip_bytes + 16);
-        if (!rc) rc = mb.small.reserve(small_pitch);
-        if (rc) return gfail(g, rc, "group member: out of device memory");
+    int reserve_member_buffers()
+    {
+        for (Member &mb : g->m) {
+            if (hipSetDevice(mb.device) != hipSuccess) return fail(SP_ERR_HIP, "hipSetDevice");
+            int rc = mb.strip.reserve(lay.strip_bytes() + 16);
+            if (!rc) rc = mb.small.reserve(small_pitch);
+            if (rc) return fail(rc, "group member: out of device memory");
+        }
+        return SP_OK;
     }
-    // ---- which transport: RCCL between distinct devices (or when forced), peer copies otherwise -------------------------------------
-    bool use_rccl = !g->no_rccl && g->rccl_state != kRcclFailed && (g->force_rccl || (count > 1 && g->distinct));
-    if (use_rccl && g->rccl_state == kRcclUntried) {
-        if (!g->rccl.load(g->rccl_lib.c_str())) {
-            give_up_rccl(g, g->rccl.why);
-        } else {
-            std::vector<int> devs;
-            for (Member &mb : g->m) devs.push_back(mb.device);
-            g->comms.assign((size_t)count, nullptr);
-            const int nrc = g->rccl.CommInitAll(g->comms.data(), count, devs.data());
-            if (nrc != 0) {
-                for (void *&c : g->comms) c = nullptr;   // (a failed init hands out no communicators)
-                give_up_rccl(g, "ncclCommInitAll: " + g->rccl.describe(nrc));
+
+    // ... and the root's gather targets, once the transport has said whether strips arrive beside the image
+    int reserve_root_buffers()
+    {
+        (void)hipSetDevice(root.device);
+        int rc = g->smalls.reserve(small_pitch * (size_t)count);
+        if (!rc && staged) rc = g->staging.reserve(lay.strip_bytes() * staged + 16);
+        if (!rc && reply.rgba) rc = g->image.reserve(lay.image_bytes() + 16);
+        if (!rc) rc = g->merged.reserve(side.bytes() * ((size_t)count + 1));   // the records end to end, then the merged record
+        return rc ? fail(rc, "group root: out of device memory") : SP_OK;
+    }
+
+    // which transport: RCCL between distinct devices (or when forced), peer copies otherwise.  RCCL is brought up once per group; a
+    // failure of it leaves a note and peer copies.
+    int choose_transport()
+    {
+        use_rccl = !g->no_rccl && g->rccl_state != kRcclFailed && (g->force_rccl || (count > 1 && g->distinct));
+        if (use_rccl && g->rccl_state == kRcclUntried) {
+            if (!g->rccl.load(g->rccl_lib.c_str())) {
+                give_up_rccl(g, g->rccl.why);
             } else {
-                g->rccl_state = kRcclReady;
+                std::vector<int> devs;
+                for (Member &mb : g->m) devs.push_back(mb.device);
+                g->comms.assign((size_t)count, nullptr);
+                const int nrc = g->rccl.CommInitAll(g->comms.data(), count, devs.data());
+                if (nrc != 0) {
+                    for (void *&c : g->comms) c = nullptr;   // (a failed init hands out no communicators)
+                    give_up_rccl(g, "ncclCommInitAll: " + g->rccl.describe(nrc));
+                } else {
+                    g->rccl_state = kRcclReady;
+                }
             }
+            use_rccl = g->rccl_state == kRcclReady;
         }
-        use_rccl = g->rccl_state == kRcclReady;
+        // under RCCL the root is a sender like every other member only in a forced one-member group (which has nothing else to send);
+        // otherwise its strip is already where the merge happens
+        first_sender = use_rccl && g->force_rccl && count == 1 ? 0 : 1;
+        // spectrogram strips are column bands: an RCCL receive is contiguous, so those strips land beside the image and are re-tiled;
+        // peers that cannot address the root's memory directly need the same block
+        stage = use_rccl && !lay.waterfall;
+        for (int r = 1; r < count; r++) stage = stage || !g->m[(size_t)r].peer_ok;
+        staged = want_image && stage ? (size_t)(count - (use_rccl ? first_sender : 1)) : 0;
+        return SP_OK;
     }
-    // under RCCL the root is a sender like every other member only in a forced one-member group (which has nothing else to send);
-    // otherwise its strip is already where the merge happens
-    const int first_sender = use_rccl && g->force_rccl && count == 1 ? 0 : 1;
-    // spectrogram strips are column bands: an RCCL receive is contiguous, so those strips land beside the image and are re-tiled;
-    // peers that cannot address the root's memory directly need the same block
-    bool stage = use_rccl && !req->waterfall;
-    for (int r = 1; r < count; r++) stage = stage || !g->m[(size_t)r].peer_ok;
-    const size_t staged = want_image && stage ? (size_t)(count - (use_rccl ? first_sender : 1)) : 0;
-    auto stage_slot = [&](int r) { return (char *)g->staging.p + strip_bytes * (size_t)(r - (use_rccl ? first_sender : 1)); };
 
-    hipError_t e = hipSetDevice(root.device);
-    int rc = g->smalls.reserve(small_pitch * (size_t)count);
-    if (!rc && staged) rc = g->staging.reserve(strip_bytes * staged + 16);
-    if (!rc && reply->rgba) rc = g->image.reserve(4 * W * n + 16);
-    if (!rc) rc = g->merged.reserve(side.bytes() * ((size_t)count + 1));   // the records end to end, then the merged record
-    if (rc) return gfail(g, rc, "group root: out of device memory");
+    // every member: its slice to its device, rendered there.  The slice travels in chunks of frames while earlier chunks are rendered
+    // (a sparse slice: only the samples its frames read)
+    int render_members()
+    {
+        return run_members([&](Member &mb, int, const uint8_t *slice, size_t slice_bytes) {
+            int rc = hip(mb.error, hipSetDevice(mb.device), "hipSetDevice: ");
+            if (!rc) rc = hip(mb.error, hipEventRecord(mb.started, mb.stream), "hipEventRecord: ");
+            if (rc) return rc;
+            sp_reply d = rec.view(mb.small.p);
+            d.rgba = reply.rgba ? (uint8_t *)mb.strip.p : nullptr;
+            rc = sp_plan_execute_from_host(mb.plan, slice, slice_bytes, (int32_t)lay.slice_width, &d);
+            return rc ? rc : hip(mb.error, hipEventRecord(mb.rendered, mb.stream), "hipEventRecord: ");
+        });
+    }
 
-    for_each_member(g, run_member);
-    for (Member &mb : g->m)
-        if (mb.status) {
-            drain(g);
-            return gfail(g, mb.status, mb.error);
-        }
+    // where on the root strip r goes in the image, where it waits beside the image, and where member r's record block lands
+    char *band(int r) const { return (char *)g->image.p + lay.band_offset((size_t)r); }
+    char *stage_slot(int r) const { return (char *)g->staging.p + lay.strip_bytes() * (size_t)(r - (use_rccl ? first_sender : 1)); }
+    char *small_slot(int r) const { return (char *)g->smalls.p + small_pitch * (size_t)r; }
 
-    // ---- gather to the root's device ------------------------------------------------------------------------------------------------
-    // where strip r goes in the image (lib/spectroplot.js:1244): a column band, or a row band in reverse order
-    auto band = [&](int r) {
-        return (char *)g->image.p + (req->waterfall ? 4 * n * (W - sw - sw * (size_t)r) : 4 * sw * (size_t)r);
-    };
     // strip r from `src` into its band, on member `on`'s stream.  Row bands (waterfall) are one contiguous copy.  Column bands on the
     // image's own device go through the placement kernel (sp_place_strips; a pitched device-to-device copy of 1024 rows of 1 MiB runs at
     // ~120 GB/s here, the kernel at HBM rate: 8 GiB of config-4 strips 129 -> ~10 ms), `cnt` strips laid end to end in one launch;
     // from another device a pitched peer copy.
-    std::string place_error;   // what sp_place_strips said, should it refuse
-    auto place = [&](Member &on, int r, const void *src, int cnt = 1) {
-        if (req->waterfall) return hipMemcpyAsync(band(r), src, strip_bytes, hipMemcpyDeviceToDevice, on.stream);
-        if (on.device == root.device) {
-            const int prc = sp_place_strips(on.ctx, (uint8_t *)g->image.p + 4 * sw * (size_t)r, (const uint8_t *)src, cnt, (int32_t)n, width, (int32_t)sw, 0);
-            if (prc != SP_OK) place_error = std::string("sp_place_strips: ") + sp_last_error(on.ctx);
-            return prc == SP_OK ? hipSuccess : hipErrorLaunchFailure;
-        }
-        return hipMemcpy2DAsync(band(r), 4 * W, src, 4 * sw, 4 * sw, n, hipMemcpyDeviceToDevice, on.stream);
-    };
-    e = hipSetDevice(root.device);
-    g->transport = 0;
+    int place(Member &on, int r, const void *src, int cnt = 1)
+    {
+        if (lay.waterfall) return gather_hip(hipMemcpyAsync(band(r), src, lay.strip_bytes(), hipMemcpyDeviceToDevice, on.stream));
+        if (on.device != root.device)
+            return gather_hip(hipMemcpy2DAsync(band(r), lay.band_pitch(), src, lay.band_row_bytes(), lay.band_row_bytes(), lay.band_rows(),
+                                               hipMemcpyDeviceToDevice, on.stream));
+        const int prc = sp_place_strips(on.ctx, (uint8_t *)band(r), (const uint8_t *)src, cnt, req->n, width, (int32_t)lay.slice_width, 0);
+        return prc == SP_OK ? SP_OK : fail(SP_ERR_HIP, std::string("group gather: sp_place_strips: ") + sp_last_error(on.ctx));
+    }
+
     // what no slice draws stays clear (:1208) - only that part is cleared: the members' copies into their bands are not ordered
     // behind the root's stream
-    if (e == hipSuccess && reply->rgba && n && sw * (size_t)count < W) {
-        const size_t rest = W - sw * (size_t)count;
-        if (req->waterfall) e = hipMemsetAsync(g->image.p, 0, 4 * n * rest, root.stream);
-        else e = hipMemset2DAsync((char *)g->image.p + 4 * sw * (size_t)count, 4 * W, 0, 4 * rest, n, root.stream);
+    int clear_rest()
+    {
+        hipError_t e = hipSetDevice(root.device);
+        g->transport = 0;
+        if (e == hipSuccess && reply.rgba && lay.rest) {
+            char *at = (char *)g->image.p + lay.rest_offset();
+            if (lay.waterfall) e = hipMemsetAsync(at, 0, lay.rest_row_bytes(), root.stream);
+            else e = hipMemset2DAsync(at, lay.rest_pitch(), 0, lay.rest_row_bytes(), lay.rest_rows(), root.stream);
+        }
+        return gather_hip(e);
     }
-    if (e != hipSuccess) {
-        drain(g);
-        return gfail(g, SP_ERR_HIP, std::string("group gather: ") + hipGetErrorString(e));
-    }
-    bool rccl_done = false;
-    if (use_rccl) {
-        // one grouped exchange: every sender ships its strip and its record block, the root posts the matching receives (the waterfall
-        // layout's straight into the image's row bands)
+
+    // one grouped exchange: every sender ships its strip and its record block, the root posts the matching receives (the waterfall
+    // layout's straight into the image's row bands).  A failure of RCCL is no failure of the render: rccl_done stays false.
+    int gather_rccl()
+    {
         int nrc = g->rccl.GroupStart();
         std::string where = "ncclGroupStart";
         for (int r = first_sender; r < count && nrc == 0; r++) {
             Member &mb = g->m[(size_t)r];
             if (want_image) {
                 where = "ncclSend / ncclRecv of a strip";
-                nrc = g->rccl.Send(mb.strip.p, strip_bytes, kNcclUint8, 0, g->comms[(size_t)r], mb.stream);
-                if (!nrc) nrc = g->rccl.Recv(req->waterfall ? band(r) : stage_slot(r), strip_bytes, kNcclUint8, r, g->comms[0], root.stream);
+                nrc = g->rccl.Send(mb.strip.p, lay.strip_bytes(), kNcclUint8, 0, g->comms[(size_t)r], mb.stream);
+                if (!nrc) nrc = g->rccl.Recv(lay.waterfall ? band(r) : stage_slot(r), lay.strip_bytes(), kNcclUint8, r, g->comms[0], root.stream);
             }
             if (!nrc) {
                 where = "ncclSend / ncclRecv of a record block";
                 nrc = g->rccl.Send(mb.small.p, small_pitch, kNcclUint8, 0, g->comms[(size_t)r], mb.stream);
             }
-            if (!nrc) nrc = g->rccl.Recv((char *)g->smalls.p + small_pitch * (size_t)r, small_pitch, kNcclUint8, r, g->comms[0], root.stream);
+            if (!nrc) nrc = g->rccl.Recv(small_slot(r), small_pitch, kNcclUint8, r, g->comms[0], root.stream);
         }
         const int erc = g->rccl.GroupEnd();
         if (nrc == 0 && erc != 0) {
@@ -647,93 +672,93 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
             where = "ncclGroupEnd";
         }
         if (nrc != 0) {
-            give_up_rccl(g, where + ": " + g->rccl.describe(nrc));   // drains every stream; the renders are complete, the copies below redo the gather
-        } else {
-            rccl_done = true;
-            g->transport = 1;
-            // the strips that arrived beside the image go to their column bands (the root's stream: behind its receives), one launch
-            if (want_image && !req->waterfall && count > first_sender) e = place(root, first_sender, stage_slot(first_sender), count - first_sender);
+            give_up_rccl(g, where + ": " + g->rccl.describe(nrc));   // drains every stream; the renders are complete, the copies redo the gather
+            return SP_OK;
         }
+        rccl_done = true;
+        g->transport = 1;
+        // the strips that arrived beside the image go to their column bands (the root's stream: behind its receives), one launch
+        if (want_image && !lay.waterfall && count > first_sender) return place(root, first_sender, stage_slot(first_sender), count - first_sender);
+        return SP_OK;
     }
-    if (!rccl_done && count > 1) {
-        // peer copies on the sender's stream (behind its render), the root's stream waits for each
+
+    // peer copies on the sender's stream (behind its render), the root's stream waits for each
+    int gather_peer()
+    {
         g->transport = 2;
-        for (int r = 1; r < count && e == hipSuccess; r++) {
+        int rc = SP_OK;
+        for (int r = 1; r < count && !rc; r++) {
             Member &mb = g->m[(size_t)r];
-            e = hipSetDevice(mb.device);
-            auto peer = [&](void *dst, const void *src, size_t nb) {
-                return mb.device == root.device ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, mb.stream)
-                                                : hipMemcpyPeerAsync(dst, root.device, src, mb.device, nb, mb.stream);
+            const auto peer = [&](void *dst, const void *src, size_t nb) {
+                return gather_hip(mb.device == root.device ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, mb.stream)
+                                                           : hipMemcpyPeerAsync(dst, root.device, src, mb.device, nb, mb.stream));
             };
+            rc = gather_hip(hipSetDevice(mb.device));
             bool restage = false;
-            if (e == hipSuccess && want_image) {
-                if (req->waterfall) e = peer(band(r), mb.strip.p, strip_bytes);          // a contiguous band of rows
-                else if (mb.peer_ok) e = place(mb, r, mb.strip.p);                       // a column band, written where it belongs
+            if (!rc && want_image) {
+                if (lay.waterfall) rc = peer(band(r), mb.strip.p, lay.strip_bytes());   // a contiguous band of rows
+                else if (mb.peer_ok) rc = place(mb, r, mb.strip.p);                      // a column band, written where it belongs
                 else {
-                    e = peer(stage_slot(r), mb.strip.p, strip_bytes);
+                    rc = peer(stage_slot(r), mb.strip.p, lay.strip_bytes());
                     restage = true;
                 }
             }
-            if (e == hipSuccess) e = peer((char *)g->smalls.p + small_pitch * (size_t)r, mb.small.p, small_pitch);
-            if (e == hipSuccess) e = hipEventRecord(mb.done, mb.stream);
-            if (e == hipSuccess) e = hipSetDevice(root.device);
-            if (e == hipSuccess) e = hipStreamWaitEvent(root.stream, mb.done, 0);
-            if (e == hipSuccess && restage) e = place(root, r, stage_slot(r));
+            if (!rc) rc = peer(small_slot(r), mb.small.p, small_pitch);
+            if (!rc) rc = gather_hip(hipEventRecord(mb.done, mb.stream));
+            if (!rc) rc = gather_hip(hipSetDevice(root.device));
+            if (!rc) rc = gather_hip(hipStreamWaitEvent(root.stream, mb.done, 0));
+            if (!rc && restage) rc = place(root, r, stage_slot(r));
         }
-        if (e == hipSuccess) e = hipSetDevice(root.device);
-    }
-    // the root's own strip and record block (its stream: behind its render) unless they went through the forced exchange
-    if (!(rccl_done && first_sender == 0)) {
-        if (e == hipSuccess && want_image) e = place(root, 0, root.strip.p);
-        if (e == hipSuccess) e = hipMemcpyAsync(g->smalls.p, root.small.p, small_pitch, hipMemcpyDeviceToDevice, root.stream);
-    }
-    if (e != hipSuccess) {
-        drain(g);
-        return gfail(g, SP_ERR_HIP, std::string("group gather: ") + (place_error.empty() ? hipGetErrorString(e) : place_error.c_str()));
+        return rc ? rc : gather_hip(hipSetDevice(root.device));
     }
 
-    // ---- the caller's merge on the root (lib/spectroplot.js:1229-1238) -----------------------------------------------------------------
-    // records sit small_pitch apart: sp_merge_replies takes them end to end, so they are packed first (count small copies)
-    DevBuf &packed = g->merged;   // [count records] then [merged record]
-    for (int r = 0; r < count && e == hipSuccess; r++)
-        e = hipMemcpyAsync((char *)packed.p + side.bytes() * (size_t)r, (char *)g->smalls.p + small_pitch * (size_t)r, side.bytes(),
-                           hipMemcpyDeviceToDevice, root.stream);
-    const sp_reply dm = side.view((char *)packed.p + side.bytes() * (size_t)count);
-    if (e == hipSuccess) {
-        rc = sp_merge_replies(root.ctx, packed.p, count, (int32_t)L, dm.c_hist, dm.cb_hist, dm.dbfs_minmax);
-        if (rc) {
-            drain(g);
-            return gfail(g, rc, sp_last_error(root.ctx));
+    // the root's own strip and record block (its stream: behind its render)
+    int place_root()
+    {
+        const int rc = want_image ? place(root, 0, root.strip.p) : SP_OK;
+        return rc ? rc : gather_hip(hipMemcpyAsync(small_slot(0), root.small.p, small_pitch, hipMemcpyDeviceToDevice, root.stream));
+    }
+
+    // the caller's merge on the root (lib/spectroplot.js:1229-1238), then image, records and merged record to the host.  Records sit
+    // small_pitch apart: sp_merge_replies takes them end to end, so they are packed first (count small copies)
+    int merge_and_download()
+    {
+        char *packed = (char *)g->merged.p;   // [count records] then [merged record]
+        hipError_t e = hipSuccess;
+        for (int r = 0; r < count && e == hipSuccess; r++)
+            e = hipMemcpyAsync(packed + side.bytes() * (size_t)r, small_slot(r), side.bytes(), hipMemcpyDeviceToDevice, root.stream);
+        const sp_reply dm = side.view(packed + side.bytes() * (size_t)count);
+        if (e == hipSuccess) {
+            const int rc = sp_merge_replies(root.ctx, packed, count, (int32_t)side.lut_len, dm.c_hist, dm.cb_hist, dm.dbfs_minmax);
+            if (rc) return fail(rc, sp_last_error(root.ctx));
         }
-    }
-    if (e == hipSuccess) e = hipEventRecord(g->gathered, root.stream);
-    if (e == hipSuccess && reply->rgba && W && n) e = hipMemcpyAsync(reply->rgba, g->image.p, 4 * W * n, hipMemcpyDeviceToHost, root.stream);
-    g->host_small.resize(small_pitch * (size_t)count + side.bytes());
-    if (e == hipSuccess) e = hipMemcpyAsync(g->host_small.data(), g->smalls.p, small_pitch * (size_t)count, hipMemcpyDeviceToHost, root.stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(g->host_small.data() + small_pitch * (size_t)count, dm.c_hist, side.bytes(), hipMemcpyDeviceToHost, root.stream);
-    if (e == hipSuccess) e = hipEventRecord(g->downloaded, root.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(root.stream);
-    for (int r = 1; r < count; r++) {   // (the senders' streams: their part of the exchange has long finished)
-        (void)hipSetDevice(g->m[(size_t)r].device);
-        const hipError_t e2 = hipStreamSynchronize(g->m[(size_t)r].stream);
-        if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) {
-        drain(g);
-        return gfail(g, SP_ERR_HIP, std::string("group download: ") + hipGetErrorString(e));
+        const size_t records = small_pitch * (size_t)count;
+        if (e == hipSuccess) e = hipEventRecord(g->gathered, root.stream);
+        if (e == hipSuccess && reply.rgba && lay.image_bytes())
+            e = hipMemcpyAsync(reply.rgba, g->image.p, lay.image_bytes(), hipMemcpyDeviceToHost, root.stream);
+        g->host_small.resize(records + side.bytes());
+        if (e == hipSuccess) e = hipMemcpyAsync(g->host_small.data(), g->smalls.p, records, hipMemcpyDeviceToHost, root.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(g->host_small.data() + records, dm.c_hist, side.bytes(), hipMemcpyDeviceToHost, root.stream);
+        if (e == hipSuccess) e = hipEventRecord(g->downloaded, root.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(root.stream);
+        for (int r = 1; r < count; r++) {   // (the senders' streams: their part of the exchange has long finished)
+            (void)hipSetDevice(g->m[(size_t)r].device);
+            const hipError_t e2 = hipStreamSynchronize(g->m[(size_t)r].stream);
+            if (e == hipSuccess) e = e2;
+        }
+        return hip(why, e, "group download: ");
     }
 
     // phase clocks (device events; a member's pair lives on its own device)
-    g->t_render = g->t_gather = g->t_download = 0;
-    for (Member &mb : g->m) {
-        float ms = 0;
-        (void)hipSetDevice(mb.device);
-        if (hipEventElapsedTime(&ms, mb.started, mb.rendered) == hipSuccess && ms > g->t_render) g->t_render = ms;
-    }
-    (void)hipSetDevice(root.device);
+    void read_clocks()
     {
+        g->t_render = g->t_gather = g->t_download = 0;
         float ms = 0;
+        for (Member &mb : g->m) {
+            (void)hipSetDevice(mb.device);
+            if (hipEventElapsedTime(&ms, mb.started, mb.rendered) == hipSuccess && ms > g->t_render) g->t_render = ms;
+        }
+        (void)hipSetDevice(root.device);
         if (hipEventElapsedTime(&ms, root.rendered, g->gathered) == hipSuccess) g->t_gather = ms;
         // members that share the root's device render one after the other: the gather starts when the LAST of them has rendered
         // (events of one device can be compared; on distinct devices the members render side by side and the root's event stands for all)
@@ -743,11 +768,47 @@ extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint
         (void)hipGetLastError();
     }
 
-    side.unpack_side(g->host_small.data() + small_pitch * (size_t)count, *reply);
-    // gauges: slice r's at columns [r * sliceWidth, (r + 1) * sliceWidth), the rest clear
-    for (uint8_t *gp : {reply->gauge_mins, reply->gauge_maxs, reply->gauge_amps})
-        if (gp) memset(gp, 0, W);
-    for (int r = 0; r < count; r++) rec.unpack_gauges(g->host_small.data() + small_pitch * (size_t)r, *reply, sw * (size_t)r);
+    // the merged side outputs, and the gauges: slice r's at columns [r * sliceWidth, (r + 1) * sliceWidth), the rest clear
+    void unpack()
+    {
+        side.unpack_side(g->host_small.data() + small_pitch * (size_t)count, reply);
+        for (uint8_t *gp : {reply.gauge_mins, reply.gauge_maxs, reply.gauge_amps})
+            if (gp) memset(gp, 0, lay.width);
+        for (int r = 0; r < count; r++) rec.unpack_gauges(g->host_small.data() + small_pitch * (size_t)r, reply, lay.gauge_offset((size_t)r));
+    }
+};
+
+}  // namespace
+
+extern "C" int sp_group_render_ex(sp_group *g, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                                  int32_t gather)
+{
+    if (!g || !req || !reply) return SP_ERR_INVALID_ARG;
+    GroupRender gr(g, req, bytes, nbytes, width, *reply);
+    int rc = gr.check_request(gather);
+    if (rc) return gfail(g, rc, gr.why);
+    if (gather == SP_GROUP_GATHER_HOST) {
+        rc = gr.render_to_host();
+        return rc ? gfail(g, rc, gr.why) : SP_OK;
+    }
+    rc = gr.ensure_plans();
+    if (!rc) rc = gr.reserve_member_buffers();
+    if (!rc) rc = gr.choose_transport();
+    if (!rc) rc = gr.reserve_root_buffers();
+    if (rc) return gfail(g, rc, gr.why);   // (no stream has been touched yet)
+
+    rc = gr.render_members();
+    if (!rc) rc = gr.clear_rest();
+    if (!rc && gr.use_rccl) rc = gr.gather_rccl();
+    if (!rc && !gr.rccl_done && gr.count > 1) rc = gr.gather_peer();
+    if (!rc && !(gr.rccl_done && gr.first_sender == 0)) rc = gr.place_root();   // (unless they went through the forced exchange)
+    if (!rc) rc = gr.merge_and_download();
+    if (rc) {
+        drain(g);
+        return gfail(g, rc, gr.why);
+    }
+    gr.read_clocks();
+    gr.unpack();
     return SP_OK;
 }
 

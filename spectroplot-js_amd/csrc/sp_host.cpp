@@ -367,6 +367,26 @@ void ReplyRecord::unpack_gauges(const void *base, const sp_reply &to, size_t at)
     if (to.gauge_amps) memcpy(to.gauge_amps + at, h.gauge_amps, width);
 }
 
+int validate_request(const sp_request *r, std::string &why)
+{
+    const auto no = [&](int code, const char *msg) {
+        why = msg;
+        return code;
+    };
+    if (!r) return no(SP_ERR_INVALID_ARG, "request is null");
+    if (r->format < 0 || r->format >= SP_FMT_COUNT) return no(SP_ERR_INVALID_ARG, "unknown format id");
+    if (r->n < 1 || log2_exact(r->n) < 0) return no(SP_ERR_NOT_POW2, "Length is not a power of 2");
+    if (r->n < 2) return no(SP_ERR_UNSUPPORTED, "n = 1 is not supported (the reference writes no pixels for it)");
+    if (r->n > SP_MAX_N) return no(SP_ERR_UNSUPPORTED, "n exceeds SP_MAX_N");
+    if (r->lut_len < 1 || r->lut_len > SP_MAX_LUT) return no(SP_ERR_UNSUPPORTED, "lut_len must be 1..SP_MAX_LUT");
+    if (!r->windowc || !r->lut_rgb) return no(SP_ERR_INVALID_ARG, "windowc / lut_rgb is null");
+    if (!(r->range > 0) || !std::isfinite(r->range)) return no(SP_ERR_UNSUPPORTED, "range must be finite and > 0");
+    if (!std::isfinite(r->gain)) return no(SP_ERR_UNSUPPORTED, "gain must be finite");
+    if (r->detector != SP_DETECTOR_SAMPLE && r->detector != SP_DETECTOR_PEAK)
+        return no(SP_ERR_INVALID_ARG, "detector must be SP_DETECTOR_SAMPLE or SP_DETECTOR_PEAK");
+    return SP_OK;
+}
+
 bool same_request(const sp_request &q, const std::vector<double> &window, const std::vector<uint8_t> &lut, const sp_request *r)
 {
     if (q.format != r->format || q.n != r->n || q.channel_mode != r->channel_mode || q.waterfall != r->waterfall || q.lut_len != r->lut_len

@@ -87,6 +87,9 @@ struct ReplyRecord {
     void unpack_gauges(const void *base, const sp_reply &to, size_t at = 0) const;
 };
 
+// What every entry point that takes a request refuses (a context's and a group's alike): SP_OK, or the status with its text in `why`.
+int validate_request(const sp_request *r, std::string &why);
+
 // Whether `r` has the constants a plan was built from (the kept request, its taper and its colour map): the plan can serve it.
 bool same_request(const sp_request &kept, const std::vector<double> &window, const std::vector<uint8_t> &lut, const sp_request *r);
 

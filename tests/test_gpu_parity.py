@@ -259,6 +259,26 @@ def test_group_render_rejects_what_it_cannot_read(pkg):
     g.close()
 
 
+def test_group_render_with_no_frame_to_draw_returns_the_fresh_canvas(pkg):
+    """Three members and a width of 2 (sliceWidth = ~~(2 / 3) = 0, lib/spectroplot.js:1208: every column is one that no slice draws) or 0:
+    the reference's canvas stays as created and nothing is counted.  Both layouts, both gathers.  Group.render's `dirty` pre-fills the
+    image and the three gauge arrays only: those checks show that the un-drawn rest is cleared; the histograms and the dBfs pair start
+    at their initial values, so their checks show only that nothing was added to them."""
+    g = pkg.Group([0, 0, 0])
+    win, weight = pyoracle.window("hann", 64)
+    lut = np.stack([np.arange(256)] * 3, axis=1).astype(np.uint8)
+    data = siggen.generate("CU8", {"kind": "trinoise", "seed": 7, "step": 7321, "gshift": 11, "amp": 0.5, "namp": 0.02}, 4096)
+    for width in (2, 0):
+        for waterfall in (False, True):
+            for gather in ("device", "host"):
+                m = g.render("CU8", data, 64, win, 1.0 / weight, 6.0, 30.0, lut, width, False, waterfall, gather=gather, dirty=0xAB)
+                what = (width, waterfall, gather)
+                for k in ("rgba", "gauge_mins", "gauge_maxs", "gauge_amps", "c_hist", "cB_hist"):
+                    assert not m[k].any(), (what, k)
+                assert (m["dBfs_min"], m["dBfs_max"]) == (0.0, -200.0), what
+    g.close()
+
+
 SEEDED = [
     # fmt, log2 samples, n, width, window, gain, range, channelMode, waterfall
     ("CF32", 18, 1024, 256, "blackmanHarris", 6, 30, False, False),
