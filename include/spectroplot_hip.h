@@ -32,6 +32,8 @@
  *   sp_place_strips          lib/spectroplot.js:1241-1244   the caller's putImageData of every slice's strip, on the device
  *   sp_group_render          lib/spectroplot.js:1206-1244, lib/samples.js:253-258   the caller's sliced render: one slice per device, the
  *                                                        strips gathered device to device (RCCL / peer copies), merged on the root
+ *   sp_plan_execute_index, sp_render_index   lib/worker.js:105-117   the same renders with the colour index per pixel, not its RGBA
+ *   sp_index_to_rgba         lib/worker.js:117-120      the LUT step alone, on an index image
  *   sp_synth_*               (none)                     device-side synthetic I/Q for benchmarks
  *
  * The request fields are the reference message's (lib/spectroplot.js:1213-1226):
@@ -199,6 +201,9 @@ int sp_render_strip(sp_context *ctx, const sp_request *req, const uint8_t *bytes
  * each 0.65 of its neighbour, shrinking towards the end of the longer transfer's direction.
  */
 int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbytes);
+/* (tests) In how many chunks of frames the streamer carried that request out (1: everything on the context's stream, nothing
+ * overlapped); sp_debug_upload_plan sizes a request's image at 4 bytes per pixel and cannot describe an indexed one. */
+int sp_context_last_chunks(const sp_context *ctx, int32_t *chunks);
 /*
  * (tests) The upload plan sp_render would follow for a request of this shape, without a device: how [0, width) is cut into chunks of
  * frames and, for a sparse request, the packed layout and the pitched copies of every chunk.  out[] receives int64 words: packed (0 / 1),
@@ -454,6 +459,47 @@ int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t nbytes, in
 int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *trace_min,
                      double *trace_max);
 const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
+ * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
+ *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
+ * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and
+ * j = n * (width - 1 - x) + (n - 1 - y) for the waterfall layout (width rows x n columns), y the image row of bin i (worker.js:90).
+ * With any LUT, lut_rgb[index[j]] with alpha 255 is sp_render's RGBA of the same request, byte for byte; bincount(index, lut_len) is
+ * c_hist exactly; every other reply field (gauges, both histograms, dBfs range) is sp_plan_execute's, bit for bit.  Geometry, limits,
+ * statuses, channel mode, both layouts, width 0 and 1, captures shorter than n (NaN frames index 0) and the detector are
+ * sp_plan_execute's.  lut_len > 256 returns SP_ERR_UNSUPPORTED: the reference allows longer maps, but a byte cannot hold their index.
+ * The image is a quarter of the RGBA image in device memory and on the host link, and a viewer that changes its colour map
+ * recolours it (sp_index_to_rgba, or a table lookup of its own) instead of rendering the capture again.
+ *
+ * sp_plan_execute_index: device operands, asynchronous, sp_plan_execute in every other respect - the same request-number handshake, so
+ *   not capturable into a hipGraph (SP_ERR_UNSUPPORTED on a capturing stream), and free to interleave with sp_plan_execute on one
+ *   context without a synchronisation in between.  d_reply->rgba must be NULL (SP_ERR_INVALID_ARG otherwise); d_index [width * n] may be
+ *   NULL: side outputs only.
+ * sp_render_index: host buffers, synchronous, the plan cached as by sp_render.  The capture travels as for sp_render - a packed upload
+ *   where stride > n, chunks of frames where the request is large - and the image comes back per chunk at 1 byte per pixel; the
+ *   chunking threshold counts the bytes that actually travel.  sp_context_last_upload_bytes reports as before.  reply->rgba must be NULL.
+ * sp_index_to_rgba: d_rgba[4 * pixels] = lut_rgb[d_index[i]], alpha 255, on the device and asynchronous on the context's stream;
+ *   lut_rgb is a HOST pointer to 3 * lut_len bytes (1 <= lut_len <= 256) that is read before the call returns.  An index >= lut_len
+ *   writes (0, 0, 0, 255).  Neither pointer needs any alignment.
+ * sp_plan_index_kernel_name_for: "frames_index" - k_frames_index, k_frames' frame loop with a write-out of the tile's bytes - for the
+ *   sample plans "frames" covers, or "render_extract" for everything else (n <= 32, n >= 16384, non-finite tapers, peak plans whichever
+ *   kernel their request takes, plans forced to kernel 1, and the L/R split with the generic loaders at n <= 256): the request's
+ *   ordinary kernel renders through an identity LUT into a temporary RGBA image of the context and a small kernel keeps byte 0 of every
+ *   pixel.  sp_plan_force_kernel applies: 1 forces "render_extract", 3 means "frames_index" where it covers the request.
+ * sp_plan_debug_index_launch: (tests) sp_plan_debug_launch's 11 words for the launch sp_plan_execute_index would make with the index
+ *   image at `index`: word 0 is 5 where k_frames_index runs, and word 8 then tells whether the write-out stores 16-byte pieces (base and
+ *   width multiples of 16, image below 4 GiB); on the render_extract path the words are the ordinary render's with word 8 = 0.
+ * Out of scope: batches, groups, sharding.py and strip placement (image_width) have no indexed form; no existing call gained a
+ * parameter, so none of them refuses anything new.
+ */
+int sp_plan_execute_index(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const sp_reply *d_reply, uint8_t *d_index);
+int sp_render_index(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                    uint8_t *index);
+int sp_index_to_rgba(sp_context *ctx, const uint8_t *d_index, size_t pixels, const uint8_t *lut_rgb, int32_t lut_len, uint8_t *d_rgba);
+const char *sp_plan_index_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_plan_debug_index_launch(const sp_plan *plan, size_t nbytes, int32_t width, const void *index, int64_t *out, size_t capacity,
+                               size_t *used);
 
 /*
  * Page-locked host memory for request / reply buffers: sp_render moves pinned buffers at the full rate of the host link, pageable

@@ -165,6 +165,12 @@ class Library:
         L.sp_render_traces.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, vp]
         L.sp_plan_traces_kernel_name_for.restype = C.c_char_p
         L.sp_plan_traces_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
+        L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
+        L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
+        L.sp_plan_index_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_index_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_plan_debug_index_launch.argtypes = [vp, sz, i32, vp, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -320,6 +326,12 @@ class Context:
         self._chk(self.lib.L.sp_context_last_upload_bytes(self.h, C.byref(v)))
         return v.value
 
+    def last_chunks(self):
+        """In how many chunks of frames the last host-fed request was carried out (sp_context_last_chunks)."""
+        v = C.c_int32()
+        self._chk(self.lib.L.sp_context_last_chunks(self.h, C.byref(v)))
+        return v.value
+
     def enable_timing(self, on=True):
         self._chk(self.lib.L.sp_context_enable_timing(self.h, int(on)))
 
@@ -460,6 +472,35 @@ class Context:
         self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), p(data), data.size, int(width), p(tmin), p(tmax)))
         return {"trace_min": tmin, "trace_max": tmax}
 
+    def render_index(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False,
+                     detector="sample", want_index=True, fill=None):
+        """sp_render_index: render()'s reply with "index" - one colour-index byte per pixel, u8[width * n] in the RGBA image's pixel
+        order - in place of "rgba".  want_index=False asks for the side outputs only; fill: a byte every output holds before the call
+        (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
+        W = int(width)
+        L = len(keep[1])
+        f = 0 if fill is None else int(fill)
+        out = {"index": np.full(max(W, 0) * n, f, np.uint8), "gauge_mins": np.full(max(W, 0), f, np.uint8),
+               "gauge_maxs": np.full(max(W, 0), f, np.uint8), "gauge_amps": np.full(max(W, 0), f, np.uint8),
+               "c_hist": np.full(L, f, np.uint64), "cB_hist": np.full(SP_CB_HIST_SIZE, f, np.uint64)}
+        mm = np.array([0.0, -200.0]) if fill is None else np.array([float(f), float(f)])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rep = _Reply(None, p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]), p(out["cB_hist"]), p(mm))
+        self._chk(self.lib.L.sp_render_index(self.h, C.byref(req), p(data), data.size, W, C.byref(rep),
+                                             p(out["index"]) if want_index else None))
+        out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
+        return out
+
+    def index_to_rgba(self, d_index, pixels, lut, d_rgba):
+        """sp_index_to_rgba: the RGBA image of an index image on the device (addresses) through `lut` (u8[lut_len][3], a host array);
+        an index the map does not have becomes (0, 0, 0, 255).  Asynchronous on the context's stream."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
+        self._chk(self.lib.L.sp_index_to_rgba(self.h, C.c_void_p(d_index or None), int(pixels), lut.ctypes.data_as(C.c_void_p), len(lut),
+                                              C.c_void_p(d_rgba or None)))
+
     def plan_creations(self):
         n = C.c_int64()
         self._chk(self.lib.L.sp_context_plan_creations(self.h, C.byref(n)))
@@ -531,6 +572,30 @@ class Plan:
         Asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_traces(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                             C.c_void_p(trace_min or None), C.c_void_p(trace_max or None)))
+
+    def index_kernel_name_for(self, nbytes, width):
+        """What execute_index() runs for a request of this shape: "frames_index" or "render_extract"."""
+        return self.ctx.lib.L.sp_plan_index_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def debug_index_launch(self, nbytes, width, index=0):
+        """debug_launch() for execute_index() with the index image at device address `index` (sp_plan_debug_index_launch); "kernel" is
+        "frames_index" where k_frames_index runs, "rgba_fast" then tells whether its write-out stores 16-byte pieces."""
+        out = np.zeros(len(LAUNCH_FIELDS), np.int64)
+        used = C.c_size_t()
+        self.ctx._chk(self.ctx.lib.L.sp_plan_debug_index_launch(self.h, int(nbytes), int(width), C.c_void_p(index or None),
+                                                                out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
+        d = dict(zip(LAUNCH_FIELDS, (int(v) for v in out)))
+        d["kernel"] = "frames_index" if d["kernel"] == 5 else KERNELS[d["kernel"]]
+        return d
+
+    def execute_index(self, d_bytes, nbytes, width, index=0, rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0,
+                      dbfs_minmax=0):
+        """sp_plan_execute_index: execute() with the picture as one colour-index byte per pixel at device address `index` (0: side
+        outputs only); `rgba` must stay 0 (the library refuses anything else)."""
+        rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
+                     dbfs_minmax or None)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_index(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width), C.byref(rep),
+                                                           C.c_void_p(index or None)))
 
     def execute_batch(self, items):
         """sp_plan_execute_batch: `items` = [(d_bytes, nbytes, width, {"rgba": addr, "gauge_mins": ..., "c_hist": ..., "cb_hist": ...,

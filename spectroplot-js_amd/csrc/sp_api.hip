@@ -19,6 +19,7 @@
 #include "sp_kernel_frames_batch.h"
 #include "sp_kernel_frames_peak.h"
 #include "sp_kernel_frames_traces.h"
+#include "sp_kernel_frames_index.h"
 #include "sp_kernel_scratch.h"
 #include "sp_synth.h"
 #include "sp_cmap_tables.h"
@@ -104,6 +105,7 @@ struct sp_context {
     DeviceBuffer partial;        // [0,4) the number of the last request k_frames has started; the scratch kernel's {min,max} and histogram accumulators
     DeviceBuffer scratch;        // scratch kernel slabs
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
+    DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
     // staging for sp_render (host-buffer entry point)
     DeviceBuffer in_bytes, out_rgba, render_small;
     HostBuffer host_small;
@@ -115,6 +117,7 @@ struct sp_context {
     long long plans_created = 0; // sp_context_plan_creations: how many plans (table sets on the device) this context has built
     bool acc_dirty = false;      // a request failed between its launches: accumulators must be re-initialised
     size_t last_upload_bytes = 0; // what the last sp_render sent over the host link (a sparse request sends its frames only)
+    int last_chunks = 0;          // ... and in how many chunks of frames the streamer carried that request out
     uint32_t seq = 0;            // requests started on this context (k_frames publishes the number once the reply is cleared; never 0)
     // sp_plan_execute_batch: the work list (item records, group -> item maps) on the device and its page-locked source, which is
     // rewritten only once the event says the previous batch's copy has read it
@@ -157,6 +160,7 @@ struct sp_plan {
     const uint32_t *d_lut = nullptr;
     const uint16_t *d_cell_g = nullptr, *d_cell_l = nullptr;   // merged-cell ranges per colour index / level (k_frames)
     const double2 *d_stage_tw = nullptr;   // per-stage twiddle tables for k_frames
+    DeviceBuffer ident_lut;         // indexed requests on the render_extract path: the LUT whose entry i is (i, 0, 0), built on first use
     int force_kernel = kKernelAuto;
 };
 
@@ -365,6 +369,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->partial.release();
     ctx->scratch.release();
     ctx->traces_ws.release();
+    ctx->index_rgba.release();
     ctx->in_bytes.release();
     ctx->out_rgba.release();
     ctx->render_small.release();
@@ -633,6 +638,7 @@ extern "C" void sp_plan_destroy(sp_plan *plan)
         if (plan->ctx->cached_plan == plan) plan->ctx->cached_plan = nullptr;
     }
     plan->tables.release();
+    plan->ident_lut.release();
     delete plan;
 }
 
@@ -808,8 +814,108 @@ static long long scratch_blocks(int slabs_per_group, int n, int32_t frames, int 
     return blocks < 1 ? 1 : blocks;
 }
 
+// ------------------------------------------------------------------------------------------------- indexed images: small kernels
+
+// k_frames_index may store the index image in 16-byte pieces with 32-bit offsets: base, width, the launch's first frame and its end are
+// multiples of 16 (every row piece of 16 frames then lies aligned and is whole or absent), the image is below 4 GiB
+static bool index_fast(const uint8_t *index, int32_t width, int n, int32_t x_begin, int32_t x_end)
+{
+    return index && ((uintptr_t)index & 15) == 0 && (width & 15) == 0 && ((x_begin | x_end) & 15) == 0 && width < (1 << 24)
+           && (double)width * (double)n <= 4294967296.0;
+}
+
+// Byte 0 of every pixel of a band of an RGBA image: `rows` rows of row_px pixels, pitch_px pixels apart in both images.  A thread takes
+// the four pixels [4q, 4q + 4) of a row: one 16-byte load and one dword store where both lie aligned and the row has them, else pixel
+// by pixel (a row's ragged end, rows that start off 16 bytes).
+__global__ void k_extract_index(const uint8_t *__restrict__ rgba, uint8_t *__restrict__ index, size_t row_px, size_t rows, size_t pitch_px)
+{
+    const size_t quads = (row_px + 3) / 4;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= quads * rows) return;
+    const size_t r = i / quads, q = i % quads;
+    const uint8_t *const src = rgba + 4 * (r * pitch_px + 4 * q);
+    uint8_t *const dst = index + r * pitch_px + 4 * q;
+    if (4 * q + 4 <= row_px && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 3) == 0) {
+        const uint4 v = *(const uint4 *)src;
+        *(uint32_t *)dst = (v.x & 255u) | ((v.y & 255u) << 8) | ((v.z & 255u) << 16) | (v.w << 24);
+        return;
+    }
+    for (size_t k = 0; k < 4 && 4 * q + k < row_px; k++) dst[k] = src[4 * k];
+}
+
+// frames [x_begin, x_end) of the temporary RGBA image -> the same frames of the index image (both `width` frames wide)
+static int extract_index_band(sp_context *ctx, const uint8_t *d_rgba, uint8_t *d_index, int32_t width, int n, bool waterfall, int32_t x_begin,
+                              int32_t x_end)
+{
+    const size_t W = (size_t)width, N = (size_t)n, band = (size_t)(x_end - x_begin);
+    // waterfall: rows width - x_end .. width - 1 - x_begin, contiguous; spectrogram: columns x_begin .. x_end - 1 of every row
+    const size_t first = waterfall ? N * (W - (size_t)x_end) : (size_t)x_begin;
+    const size_t row_px = waterfall ? N * band : band, rows = waterfall ? 1 : N, pitch = waterfall ? N * band : W;
+    const size_t blocks = (((row_px + 3) / 4) * rows + 255) / 256;
+    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one extraction launch");
+    hipLaunchKernelGGL(k_extract_index, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_rgba + 4 * first, d_index + first, row_px, rows, pitch);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// sp_index_to_rgba's table travels in the kernel arguments (1 KiB): nothing to copy, nothing of the caller's to keep alive
+struct IndexLut {
+    uint32_t v[256];
+};
+
+// index -> RGBA through a LUT.  The index image is read in 16-byte units from its first aligned byte on, one unit per thread: a 16-byte
+// load and four 16-byte stores where the unit's pixels lie aligned in the RGBA image, dword or byte stores where they do not; the
+// pixels in front of the first unit and behind the last one (at most 15 each) are taken byte-wise by workgroup 0's first threads.
+__global__ void k_index_to_rgba(const uint8_t *__restrict__ index, size_t pixels, const IndexLut lut, uint8_t *__restrict__ rgba)
+{
+    __shared__ uint32_t s_lut[256];
+    s_lut[threadIdx.x] = lut.v[threadIdx.x];
+    __syncthreads();
+    const auto put = [&](size_t i, uint32_t c) {
+        uint8_t *const d = rgba + 4 * i;
+        if (((uintptr_t)d & 3) == 0) {
+            *(uint32_t *)d = c;
+        } else {
+            for (int k = 0; k < 4; k++) d[k] = (uint8_t)(c >> (8 * k));
+        }
+    };
+    size_t head = (size_t)(-(intptr_t)(uintptr_t)index) & 15;
+    if (head > pixels) head = pixels;
+    const size_t units = (pixels - head) / 16, tail0 = head + 16 * units;
+    if (blockIdx.x == 0) {
+        const size_t t = threadIdx.x;
+        if (t < head) put(t, s_lut[index[t]]);
+        else if (t - head < pixels - tail0) put(tail0 + (t - head), s_lut[index[tail0 + (t - head)]]);
+    }
+    const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= units) return;
+    const size_t i0 = head + 16 * u;
+    const uint4 v = *(const uint4 *)(index + i0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    const bool wide = ((uintptr_t)(rgba + 4 * i0) & 15) == 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t c0 = s_lut[w[k] & 255u], c1 = s_lut[(w[k] >> 8) & 255u], c2 = s_lut[(w[k] >> 16) & 255u], c3 = s_lut[w[k] >> 24];
+        if (wide) {
+            *(uint4 *)(rgba + 4 * (i0 + 4 * k)) = make_uint4(c0, c1, c2, c3);
+        } else {
+            put(i0 + 4 * k, c0);
+            put(i0 + 4 * k + 1, c1);
+            put(i0 + 4 * k + 2, c2);
+            put(i0 + 4 * k + 3, c3);
+        }
+    }
+}
+
+// An indexed request's image (sp_plan_execute_index): `frames`: k_frames_index writes it; else the request's ordinary kernel renders
+// through the plan's identity LUT into the context's temporary RGBA image and k_extract_index keeps byte 0 of every pixel of the range.
+struct IndexTarget {
+    uint8_t *d_index;   // [width * n], may be null: side outputs only
+    bool frames;
+};
+
 static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestShape &shape, int32_t x_begin, int32_t x_end, bool first,
-                              bool last, const sp_reply *out, const PackedSource *src = nullptr)
+                              bool last, const sp_reply *out, const PackedSource *src = nullptr, const IndexTarget *ix = nullptr)
 {
     if (!plan || !out) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
@@ -885,10 +991,22 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     a.c_hist = (unsigned long long *)((char *)ctx->partial.p + 64);
     a.cb_hist = a.c_hist + SP_MAX_LUT;
     a.rgba_fast = rgba_fast(out->rgba, width, n);
+    if (ix && ix->frames) {
+        a.rgba = ix->d_index;
+        a.rgba_fast = index_fast(ix->d_index, width, n, x_begin, x_end);
+    } else if (ix && ix->d_index) {
+        a.rgba = (uint8_t *)ctx->index_rgba.p;   // (reserved and the LUT built by the caller: index_prepare)
+        a.rgba_fast = rgba_fast(a.rgba, width, n);
+        a.lut_rgba = (const uint32_t *)plan->ident_lut.p;
+    }
 
     if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
     const int32_t peak_nsamp = (int32_t)(peak.nsamp < 2147483647 ? peak.nsamp : 2147483647);
-    if (which == kKernelFrames) {
+    if (ix && ix->frames) {
+        if (which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "k_frames_index renders what k_frames renders");
+        rc = spk2::launch_frames_index(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, "k_frames_index launch rejected the configuration");
+    } else if (which == kKernelFrames) {
         rc = spk2::launch_frames(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames launch rejected the configuration");
     } else if (which == kKernelFramesPeak) {
@@ -913,6 +1031,10 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
         if (rc) return fail(ctx, rc, "bad format");
     }
     SP_HIP(ctx, hipGetLastError());
+    if (ix && !ix->frames && ix->d_index && x_end > x_begin) {
+        rc = extract_index_band(ctx, (const uint8_t *)ctx->index_rgba.p, ix->d_index, width, n, plan->req.waterfall != 0, x_begin, x_end);
+        if (rc) return rc;
+    }
     if (ctx->timing) {
         SP_HIP(ctx, hipEventRecord(ctx->ev1, s));
         ctx->timed = true;
@@ -1139,15 +1261,15 @@ static hipError_t upload_packed_chunk(const spgeo::PackedChunk &ch, int n, int s
 // apart) on `stream`: one copy where the band is contiguous on both sides (a waterfall band: rows width-1-x; the whole width of
 // equally wide images), a pitched copy of columns x0 .. x1-1 of every row otherwise.
 static hipError_t download_band(uint8_t *host, size_t host_pitch, const uint8_t *dev, int32_t width, size_t n, bool waterfall, int32_t x0,
-                                int32_t x1, hipStream_t stream)
+                                int32_t x1, hipStream_t stream, size_t px = 4)
 {
-    const size_t W = (size_t)width;
+    const size_t W = (size_t)width;   // px: bytes per pixel (4: RGBA, 1: an index image)
     if (waterfall) {
-        const size_t off = 4 * n * (W - (size_t)x1);
-        return hipMemcpyAsync(host + off, dev + off, 4 * n * (size_t)(x1 - x0), hipMemcpyDeviceToHost, stream);
+        const size_t off = px * n * (W - (size_t)x1);
+        return hipMemcpyAsync(host + off, dev + off, px * n * (size_t)(x1 - x0), hipMemcpyDeviceToHost, stream);
     }
-    if (x0 == 0 && x1 == width && host_pitch == 4 * W) return hipMemcpyAsync(host, dev, 4 * W * n, hipMemcpyDeviceToHost, stream);
-    return hipMemcpy2DAsync(host + 4 * (size_t)x0, host_pitch, dev + 4 * (size_t)x0, 4 * W, 4 * (size_t)(x1 - x0), n, hipMemcpyDeviceToHost,
+    if (x0 == 0 && x1 == width && host_pitch == px * W) return hipMemcpyAsync(host, dev, px * W * n, hipMemcpyDeviceToHost, stream);
+    return hipMemcpy2DAsync(host + px * (size_t)x0, host_pitch, dev + px * (size_t)x0, px * W, px * (size_t)(x1 - x0), n, hipMemcpyDeviceToHost,
                             stream);
 }
 
@@ -1203,6 +1325,7 @@ static int stream_chunks(sp_context *ctx, const spfmt::Format &f, HostFeed &h, L
     const int chunks = (int)u.bounds.size() - 1;
     const bool overlap = chunks > 1;   // copies on copy_in / copy_out, ordered by events
     ctx->last_upload_bytes = u.link_bytes;
+    ctx->last_chunks = chunks;
     int rc = ctx->in_bytes.reserve(u.dev_bytes);
     if (rc) return fail(ctx, rc, std::string(h.who) + ": out of memory");
     uint8_t *const in = (uint8_t *)ctx->in_bytes.p;
@@ -1367,6 +1490,177 @@ extern "C" int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbyte
 {
     if (!ctx || !nbytes) return SP_ERR_INVALID_ARG;
     *nbytes = ctx->last_upload_bytes;
+    return SP_OK;
+}
+
+extern "C" int sp_context_last_chunks(const sp_context *ctx, int32_t *chunks)
+{
+    if (!ctx || !chunks) return SP_ERR_INVALID_ARG;
+    *chunks = ctx->last_chunks;
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- indexed image replies
+
+// k_frames_index renders what k_frames renders of a sample plan, where its variant exists (frames_index_variant_built).
+static bool index_frames(const sp_plan *plan, const spgeo::Geometry &g)
+{
+    if (plan->req.detector != SP_DETECTOR_SAMPLE || request_kernel(plan, 1) != kKernelFrames) return false;
+    return spk2::frames_index_variant_built(plan->req.n, plan->req.channel_mode != 0,
+                                            spk2::frames_prefetch_width(plan->fmt.width, g.in_bounds, g.stride, g.width));
+}
+
+extern "C" const char *sp_plan_index_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    if (!plan) return "";
+    return index_frames(plan, spgeo::geometry(plan->fmt, plan->req.n, nbytes, width)) ? "frames_index" : "render_extract";
+}
+
+// what the render_extract path needs before its first launch: the temporary RGBA image and the plan's identity LUT
+static int index_prepare(sp_plan *plan, int32_t width)
+{
+    sp_context *ctx = plan->ctx;
+    int rc = ctx->index_rgba.reserve(4 * (size_t)width * (size_t)plan->req.n + 16);
+    if (rc) return fail(ctx, rc, "index workspace: out of device memory");
+    if (!plan->ident_lut.p) {
+        // (a table with static storage: the asynchronous copy may read it whenever it runs, so the entry point stays asynchronous)
+        static const std::vector<uint32_t> ident = [] {
+            std::vector<uint32_t> t(256);
+            for (uint32_t i = 0; i < 256; i++) t[i] = i | 0xff000000u;
+            return t;
+        }();
+        rc = plan->ident_lut.reserve(ident.size() * sizeof(uint32_t));
+        if (rc) return fail(ctx, rc, "identity LUT: out of device memory");
+        const hipError_t e = hipMemcpyAsync(plan->ident_lut.p, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            plan->ident_lut.release();
+            return hip_fail(ctx, e, "identity LUT upload");
+        }
+    }
+    return SP_OK;
+}
+
+// what every indexed entry point refuses of a plan or request and its reply
+static int check_index(sp_context *ctx, int32_t lut_len, const sp_reply *reply)
+{
+    if (lut_len > 256) return fail(ctx, SP_ERR_UNSUPPORTED, "an indexed image holds one byte per pixel: lut_len must be 256 at most");
+    if (reply->rgba) return fail(ctx, SP_ERR_INVALID_ARG, "an indexed request's reply must not carry an RGBA image (rgba must be NULL)");
+    return SP_OK;
+}
+
+static int no_object_status()
+{
+    int c = 0;
+    return hipGetDeviceCount(&c) != hipSuccess || c <= 0 ? SP_ERR_NO_DEVICE : SP_ERR_INVALID_ARG;
+}
+
+extern "C" int sp_plan_execute_index(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const sp_reply *d_reply, uint8_t *d_index)
+{
+    if (!plan) return no_object_status();
+    if (!d_reply) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_index(ctx, plan->req.lut_len, d_reply);
+    if (rc) return rc;
+    const RequestShape shape = request_shape(plan, nbytes, width);
+    const IndexTarget ix{d_index, index_frames(plan, shape.g)};
+    if (!ix.frames && d_index && width > 0) {
+        rc = check_capture(ctx, plan->fmt, plan->req.n, d_bytes, nbytes, width, d_reply, "");   // (before anything is allocated)
+        if (rc) return rc;
+        SP_HIP(ctx, hipSetDevice(ctx->device));
+        rc = refuse_capture(ctx, ctx->stream, "sp_plan_execute_index cannot be captured into a hipGraph (every launch carries its request's number)");
+        if (rc) return rc;
+        rc = index_prepare(plan, width);
+        if (rc) return rc;
+    }
+    return plan_execute_range(plan, d_bytes, shape, 0, width < 0 ? 0 : width, true, true, d_reply, nullptr, &ix);
+}
+
+// sp_render with an indexed image: a request kind of stream_chunks whose image travels back at 1 byte per pixel.
+extern "C" int sp_render_index(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                               uint8_t *index)
+{
+    if (!ctx) return no_object_status();
+    if (!reply) return SP_ERR_INVALID_ARG;
+    int rc = validate_request(ctx, req);
+    if (rc) return rc;
+    rc = check_index(ctx, req->lut_len, reply);
+    if (rc) return rc;
+    rc = check_host_capture(ctx, spfmt::describe(req->format), bytes, nbytes, width);
+    if (rc) return rc;
+    sp_plan *plan = nullptr;
+    rc = cached_plan_for(ctx, req, &plan);
+    if (rc) return rc;
+
+    hipStream_t s = ctx->stream;
+    const size_t W = (size_t)width, n = (size_t)req->n;
+    const size_t index_bytes = W * n;
+    const sphost::ReplyRecord rec{(size_t)req->lut_len, W};
+    rc = ctx->out_rgba.reserve(index_bytes + 16);   // (the device image of a host-fed request, here 1 byte per pixel)
+    if (!rc) rc = ctx->render_small.reserve(rec.bytes() + 16);
+    if (!rc) rc = ctx->host_small.reserve(rec.bytes() + 16);
+    if (rc) return fail(ctx, rc, "sp_render_index: out of memory");
+    sp_reply d = rec.view(ctx->render_small.p);
+    d.rgba = nullptr;
+    const RequestShape shape = request_shape(plan, nbytes, width);
+    const IndexTarget ix{index ? (uint8_t *)ctx->out_rgba.p : nullptr, index_frames(plan, shape.g)};
+    if (!ix.frames && ix.d_index && width > 0) {
+        rc = index_prepare(plan, width);
+        if (rc) return rc;
+    }
+    HostFeed feed{"sp_render_index", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames, index != nullptr,
+                  index ? index_bytes : 0, true, nullptr};
+    auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
+        return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src, &ix);
+    };
+    rc = stream_chunks(ctx, plan->fmt, feed, launch, [&](int k, int32_t x0, int32_t x1) {
+        hipError_t e = hipSuccess;
+        if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
+        if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
+        if (e == hipSuccess && index && x1 > x0)
+            e = download_band(index, req->waterfall ? n : W, ix.d_index, width, n, req->waterfall, x0, x1, feed.out_s, 1);
+        return e == hipSuccess ? (int)SP_OK : hip_fail(ctx, e, "sp_render_index copies");
+    });
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return hip_fail(ctx, e, "sp_render_index copies");
+    }
+    rec.unpack_side(ctx->host_small.p, *reply);
+    rec.unpack_gauges(ctx->host_small.p, *reply);
+    return SP_OK;
+}
+
+extern "C" int sp_index_to_rgba(sp_context *ctx, const uint8_t *d_index, size_t pixels, const uint8_t *lut_rgb, int32_t lut_len, uint8_t *d_rgba)
+{
+    if (!ctx) return no_object_status();
+    if (!lut_rgb || lut_len < 1 || lut_len > 256 || (pixels && (!d_index || !d_rgba))) return SP_ERR_INVALID_ARG;
+    if (!pixels) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    IndexLut lut;
+    for (int i = 0; i < 256; i++)
+        lut.v[i] = i < lut_len ? (uint32_t)lut_rgb[3 * i] | ((uint32_t)lut_rgb[3 * i + 1] << 8) | ((uint32_t)lut_rgb[3 * i + 2] << 16) | 0xff000000u
+                               : 0xff000000u;   // an index the map does not have: opaque black
+    const size_t blocks = (pixels / 16 + 255) / 256 + 1;
+    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one recolouring launch");
+    hipLaunchKernelGGL(k_index_to_rgba, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_index, pixels, lut, d_rgba);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// (tests) sp_plan_debug_launch's words for the launch sp_plan_execute_index would make; word 0 is 5 for k_frames_index, and word 8 tells
+// whether the write-out stores the index image in 16-byte pieces.
+extern "C" int sp_plan_debug_index_launch(const sp_plan *plan, size_t nbytes, int32_t width, const void *index, int64_t *out, size_t capacity,
+                                          size_t *used)
+{
+    int rc = sp_plan_debug_launch(plan, nbytes, width, nullptr, out, capacity, used);
+    if (rc) return rc;
+    if (width > 0 && index_frames(plan, spgeo::geometry(plan->fmt, plan->req.n, nbytes, width))) {
+        out[0] = 5;
+        out[8] = index_fast((const uint8_t *)index, width, plan->req.n, 0, width) ? 1 : 0;
+    }
     return SP_OK;
 }
 

@@ -6,7 +6,7 @@
  *
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
- *        [--full] [--traces traces.json] --out image.ppm
+ *        [--full] [--traces traces.json] [--index index.pgm] --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
  * Batch mode (--out-dir): one image per capture, DIR/<capture's file name>.ppm (or .rgba with --rgba), the same bytes a single-file
@@ -16,6 +16,9 @@
  * --traces FILE (single-file runs, sample detector): the per-bin min-hold / max-hold traces of the same request over the whole capture
  * (HipWorker.renderTraces -> sp_render_traces) as JSON beside the image: {n, width, trace_min: [n], trace_max: [n]} in image row order
  * (row y of the spectrogram, column n - 1 - y of the waterfall); a value JSON cannot hold travels as the string 'Infinity' / '-Infinity'.
+ *
+ * --index FILE (single-file runs): the same request over the whole capture as an indexed image (HipWorker.renderIndexed ->
+ * sp_render_index), written beside the image as a binary PGM (P5, maxval 255): one colour-index byte per pixel, rows as the image's.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -52,6 +55,22 @@ function writeTraces(buffer, format, n, width, opt) {
         worker.terminate()
         const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
         fs.writeFileSync(opt.traces, JSON.stringify({ n, width, trace_min: plain(t.trace_min), trace_max: plain(t.trace_max) }))
+    }, e => { worker.terminate(); throw e })
+}
+
+// --index: one request over the whole capture on one worker, with the taper, block_norm and end-forced colour map the image's request
+// resolves to
+function writeIndex(buffer, format, n, width, opt) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())
+    cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
+    const worker = new HipWorker()
+    return worker.renderIndexed({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), cmap, channelMode: !!opt.channelMode, waterfall: !!opt.waterfall, detector: opt.detector }).then(r => {
+        worker.terminate()
+        fs.writeFileSync(opt.index, Buffer.concat([Buffer.from(`P5\n${r.width} ${r.height}\n255\n`),
+            Buffer.from(r.index.buffer, r.index.byteOffset, r.index.byteLength)]))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -125,6 +144,7 @@ function main(argv) {
                 `dBfs ${img.dBfs_min.toFixed(2)} .. ${img.dBfs_max.toFixed(2)}, ${Date.now() - t0} ms`)
         })
         .then(() => opt.traces === undefined ? null : writeTraces(buffer, format, n, width, opt))
+        .then(() => opt.index === undefined ? null : writeIndex(buffer, format, n, width, opt))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

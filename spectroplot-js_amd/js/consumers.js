@@ -98,4 +98,28 @@ function gaugeColumns(reply, sliceWidth, minmaxHeight, ampHeight) {
     return out
 }
 
-module.exports = { colorRamp, rampMarkers, histogramOutlines, gaugeColumns, DEFAULT_THEME, DEFAULT_OPTS }
+/**
+ * The RGBA image of an indexed reply (HipWorker.renderIndexed) under a colour map: pixel j = cmap[index[j]] with alpha 255, and
+ * (0, 0, 0, 255) for an index the map does not have - the semantics of sp_index_to_rgba, so a viewer that changes its colour map
+ * recolours the image it holds instead of rendering the capture again.  `cmap`: the reference's array of [r, g, b] entries (stored
+ * with the clamping of the worker's Uint8ClampedArray image, lib/worker.js:118-121) or a packed Uint8Array of r, g, b triples.
+ * @returns {Uint8ClampedArray} 4 * index.length bytes
+ */
+function recolour(index, cmap) {
+    const packed = ArrayBuffer.isView(cmap)
+    const entries = packed ? Math.floor(cmap.length / 3) : cmap.length
+    const table = new Uint8ClampedArray(256 * 4)
+    for (let i = 0; i < 256; i++) {
+        if (i < entries) {
+            table[4 * i] = packed ? cmap[3 * i] : cmap[i][0]
+            table[4 * i + 1] = packed ? cmap[3 * i + 1] : cmap[i][1]
+            table[4 * i + 2] = packed ? cmap[3 * i + 2] : cmap[i][2]
+        }
+        table[4 * i + 3] = 255
+    }
+    const t32 = new Uint32Array(table.buffer), out = new Uint8ClampedArray(4 * index.length), o32 = new Uint32Array(out.buffer)
+    for (let j = 0; j < index.length; j++) o32[j] = t32[index[j]]
+    return out
+}
+
+module.exports = { colorRamp, rampMarkers, histogramOutlines, gaugeColumns, recolour, DEFAULT_THEME, DEFAULT_OPTS }

@@ -191,6 +191,51 @@ class HipWorker {
             channelMode: !!m.channelMode }
     }
 
+    /**
+     * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the
+     * message's colour map pixel j of imageData.data shows, so the reply is a quarter of the size and js/consumers.js `recolour` redraws
+     * it under another map without a render.  The message is a worker message (`detector: 'peak'` allowed; a colour map of more than 256
+     * entries is refused with status -4); the `postMessage` path itself stays RGBA.  Runs in the instance's request order; a malformed
+     * field rejects (and reports `onerror` with status -1) and never resolves to an image.
+     * @returns {Promise<{index: Uint8Array, width: number, height: number, c_hist: number[], cB_hist: number[], dBfs_min: number,
+     *          dBfs_max: number, gauge_mins: Uint8ClampedArray, gauge_maxs: Uint8ClampedArray, gauge_amps: Uint8ClampedArray}>}
+     */
+    renderIndexed(m) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._indexRequest(m) } catch (e) { reject(e); return }
+            try {
+                addon().renderIndex(this._ctx, req, (err, r) => err ? reject(err) : resolve(this._wrapIndex(m, r)))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => {
+            if (!this._closed) this._emit('error', { message: err.message, status: err.status === undefined ? -1 : err.status, error: err })
+        })
+        return p
+    }
+
+    _indexRequest(m) {
+        if (!(m && m.buffer)) throw Object.assign(new Error('an indexed request needs a buffer'), { status: -1 })
+        if (!Array.isArray(m.cmap)) throw Object.assign(new Error('an indexed request needs a colour map'), { status: -1 })
+        for (const k of ['n', 'width', 'block_norm', 'gain', 'range'])
+            if (typeof m[k] !== 'number') throw Object.assign(new Error(`${k} must be a number, not ${JSON.stringify(m[k]) || String(m[k])}`), { status: -1 })
+        return this._request(m)
+    }
+
+    _wrapIndex(m, r) {
+        return {
+            index: r.index, width: m.waterfall ? m.n : m.width, height: m.waterfall ? m.width : m.n,
+            cB_hist: plainArray(r.cB_hist), c_hist: plainArray(r.c_hist), dBfs_min: r.dBfs_min, dBfs_max: r.dBfs_max,
+            gauge_mins: new Uint8ClampedArray(r.gauge_mins), gauge_maxs: new Uint8ClampedArray(r.gauge_maxs),
+            gauge_amps: new Uint8ClampedArray(r.gauge_amps),
+        }
+    }
+
+    /** Synchronous form of renderIndexed (tests). */
+    renderIndexedSync(m) { return this._wrapIndex(m, addon().renderIndexSync(this._ctx, this._indexRequest(m))) }
+
     /** Synchronous form of renderTraces (tests). */
     renderTracesSync(m) { return addon().renderTracesSync(this._ctx, this._tracesRequest(m)) }
 

@@ -24,6 +24,8 @@
 //       c_hist, cB_hist: Float64Array, dBfs_min, dBfs_max}) on the main thread
 //   renderSync(handle, req)                        -> the same reply object, synchronously
 //   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
+//   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
+//                                    indices, in place of `rgba` (sp_render_index); req as for render
 //   renderNamed(handle, req, cb) / renderNamedSync(handle, req)   req = {format, window, cmap: strings, buffer, n, gain, range, width,
 //                                    channelMode, waterfall}: sp_render_named - the library resolves the names as the reference's caller
 //                                    does (lib/spectroplot.js:238-264, 1113-1146) and keeps the plan while they repeat
@@ -962,6 +964,160 @@ napi_value RenderTraces(napi_env env, napi_callback_info info)
     return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderTraces", "could not queue the traces request");
 }
 
+// ---- indexed images: renderIndex(handle, req, cb) / renderIndexSync(handle, req) -------------------------------------------------------
+// req as for render plus `detector` -> render's reply with `index` - a Uint8Array(width * n), one colour-index byte per pixel in the RGBA
+// image's pixel order, in a page-locked block of the reply pool - in place of `rgba` (sp_render_index).  Every value of the request is
+// read into a variable of its own with its status checked: a request that cannot be read throws and never renders.
+struct IndexJob : Job {
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t)
+{
+    void *p = nullptr;
+    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
+        napi_throw_type_error(env, nullptr, "context handle expected");
+        return false;
+    }
+    t->owner = (Ctx *)p;
+    if (t->owner->closed || !t->owner->c) {
+        napi_throw_error(env, nullptr, t->owner->g ? "renderIndex takes a context handle, not a group" : "context has been destroyed");
+        return false;
+    }
+    t->ctx = t->owner->c;
+    if (!checked_int32(env, req, "format", &t->req.format) || !checked_int32(env, req, "n", &t->req.n)) return false;
+    if (!checked_int32(env, req, "width", &t->width)) return false;
+    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode) || !checked_bool(env, req, "waterfall", &t->req.waterfall)) return false;
+    if (!read_detector(env, req, &t->req.detector)) return false;
+    if (!checked_number(env, req, "block_norm", &t->req.block_norm) || !checked_number(env, req, "gain", &t->req.gain)) return false;
+    if (!checked_number(env, req, "range", &t->req.range)) return false;
+    if (t->req.n < 1 || t->width < 0) {
+        napi_throw_range_error(env, nullptr, "n must be positive and width must not be negative");
+        return false;
+    }
+    napi_value v_win, v_lut, v_buf, ab_win, ab_lut;
+    napi_typedarray_type tt_win, tt_lut;
+    size_t len_win = 0, off_win = 0, len_lut = 0, off_lut = 0, len_buf = 0;
+    void *data_win = nullptr, *data_lut = nullptr, *data_buf = nullptr;
+    if (napi_get_named_property(env, req, "windowc", &v_win) != napi_ok
+        || napi_get_typedarray_info(env, v_win, &tt_win, &len_win, &data_win, &ab_win, &off_win) != napi_ok || tt_win != napi_float64_array) {
+        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
+        return false;
+    }
+    if (len_win < (size_t)t->req.n) {
+        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
+        return false;
+    }
+    t->window.assign((const double *)data_win, (const double *)data_win + len_win);
+    if (napi_get_named_property(env, req, "lut", &v_lut) != napi_ok
+        || napi_get_typedarray_info(env, v_lut, &tt_lut, &len_lut, &data_lut, &ab_lut, &off_lut) != napi_ok
+        || (tt_lut != napi_uint8_array && tt_lut != napi_uint8_clamped_array) || len_lut < 3) {
+        napi_throw_type_error(env, nullptr, "lut must be a Uint8Array of r, g, b triples");
+        return false;
+    }
+    t->lut.assign((const uint8_t *)data_lut, (const uint8_t *)data_lut + len_lut);
+    if (napi_get_named_property(env, req, "buffer", &v_buf) != napi_ok || napi_get_arraybuffer_info(env, v_buf, &data_buf, &len_buf) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
+        return false;
+    }
+    t->bytes = (const uint8_t *)data_buf;
+    t->nbytes = len_buf;
+    t->req.lut_len = (int32_t)(len_lut / 3);
+    t->req.windowc = t->window.data();
+    t->req.lut_rgb = t->lut.data();
+    return true;
+}
+
+void IndexJob::run()
+{
+    const size_t W = (size_t)width, n = (size_t)req.n;
+    rgba_size = W * n + 1;                                   // (Job's image block: here one byte per pixel)
+    rgba = (uint8_t *)g_pool.take(rgba_size, &rgba_pin);
+    gmin = (uint8_t *)calloc(W + 1, 1);
+    gmax = (uint8_t *)calloc(W + 1, 1);
+    gamp = (uint8_t *)calloc(W + 1, 1);
+    c_hist.assign((size_t)req.lut_len, 0);
+    cb_hist.assign(SP_CB_HIST_SIZE, 0);
+    if (!rgba || !gmin || !gmax || !gamp) {
+        status = SP_ERR_NOMEM;
+        error = "out of host memory";
+        return;
+    }
+    sp_reply r{};
+    r.gauge_mins = gmin; r.gauge_maxs = gmax; r.gauge_amps = gamp;
+    r.c_hist = c_hist.data(); r.cb_hist = cb_hist.data(); r.dbfs_minmax = minmax;
+    status = sp_render_index(ctx, &req, bytes, nbytes, width, &r, rgba);
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value IndexJob::result(napi_env env)
+{
+    const size_t W = (size_t)width, n = (size_t)req.n;
+    napi_value out, ab, ta, v;
+    if (napi_create_object(env, &out) != napi_ok) return nullptr;
+    PoolTag *tag = new PoolTag{rgba_size, rgba_pin};
+    if (napi_create_external_arraybuffer(env, rgba, W * n, pool_free_cb, tag, &ab) != napi_ok) {
+        delete tag;
+        return nullptr;
+    }
+    int64_t total = 0;
+    napi_adjust_external_memory(env, reply_weight(rgba_size), &total);
+    rgba = nullptr;   // owned by the ArrayBuffer now
+    if (napi_create_typedarray(env, napi_uint8_array, W * n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "index", ta) != napi_ok)
+        return nullptr;
+    const auto put_gauge = [&](const char *name, uint8_t *&p) {
+        napi_value gab;
+        if (napi_create_external_arraybuffer(env, p, W, free_cb, nullptr, &gab) != napi_ok) return false;
+        p = nullptr;
+        return napi_set_named_property(env, out, name, gab) == napi_ok;
+    };
+    if (!put_gauge("gauge_mins", gmin) || !put_gauge("gauge_maxs", gmax) || !put_gauge("gauge_amps", gamp)) return nullptr;
+    const auto put_hist = [&](const char *name, const std::vector<uint64_t> &h) {
+        napi_value hab, hta;
+        void *data = nullptr;
+        if (napi_create_arraybuffer(env, h.size() * 8, &data, &hab) != napi_ok) return false;
+        for (size_t i = 0; i < h.size(); i++) ((double *)data)[i] = (double)h[i];
+        return napi_create_typedarray(env, napi_float64_array, h.size(), hab, 0, &hta) == napi_ok
+               && napi_set_named_property(env, out, name, hta) == napi_ok;
+    };
+    if (!put_hist("c_hist", c_hist) || !put_hist("cB_hist", cb_hist)) return nullptr;
+    if (napi_create_double(env, minmax[0], &v) != napi_ok || napi_set_named_property(env, out, "dBfs_min", v) != napi_ok) return nullptr;
+    if (napi_create_double(env, minmax[1], &v) != napi_ok || napi_set_named_property(env, out, "dBfs_max", v) != napi_ok) return nullptr;
+    return out;
+}
+
+napi_value RenderIndexSync(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 2) {
+        napi_throw_type_error(env, nullptr, "renderIndexSync(handle, request)");
+        return nullptr;
+    }
+    IndexJob *t = new IndexJob;
+    if (!parse_index(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
+    return run_sync(env, t);
+}
+
+napi_value RenderIndex(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    napi_valuetype ty = napi_undefined;
+    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
+        napi_throw_type_error(env, nullptr, "renderIndex(handle, request, callback)");
+        return nullptr;
+    }
+    IndexJob *t = new IndexJob;
+    if (!parse_index(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderIndex", "could not queue the indexed request");
+}
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1282,6 +1438,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTraces", nullptr, RenderTraces, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"peakSubframes", nullptr, PeakSubframes, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},
