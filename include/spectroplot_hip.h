@@ -34,6 +34,8 @@
  *                                                        strips gathered device to device (RCCL / peer copies), merged on the root
  *   sp_plan_execute_index, sp_render_index   lib/worker.js:105-117   the same renders with the colour index per pixel, not its RGBA
  *   sp_index_to_rgba         lib/worker.js:117-120      the LUT step alone, on an index image
+ *   sp_plan_execute_density, sp_render_density, sp_density_from_index   lib/worker.js:105-117   how often each row showed each colour
+ *                                                        index: the persistence spectrum of a request, or of an index image
  *   sp_synth_*               (none)                     device-side synthetic I/Q for benchmarks
  *
  * The request fields are the reference message's (lib/spectroplot.js:1213-1226):
@@ -500,6 +502,50 @@ int sp_index_to_rgba(sp_context *ctx, const uint8_t *d_index, size_t pixels, con
 const char *sp_plan_index_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 int sp_plan_debug_index_launch(const sp_plan *plan, size_t nbytes, int32_t width, const void *index, int64_t *out, size_t capacity,
                                size_t *used);
+
+/*
+ * Persistence spectrum: how often each image row showed each colour index over a request - the frequency x level histogram a real-time
+ * spectrum analyser draws as its persistence display.  `density` is uint32_t[n * lut_len], row y at density + y * lut_len:
+ *     density[y * lut_len + g] = #{ x in [0, width) : index(x, y) == g }
+ * with index(x, y) = gray of lib/worker.js:105-117 for frame x and image row y (worker.js:90): the byte sp_plan_execute_index puts at
+ * pixel (x, y).  Row y is image row y of the spectrogram layout and column n - 1 - y of the waterfall layout; the array is the same for
+ * both layouts, as the traces are.  Hence, bit for bit: the sum over g of density[y][g] is `width` for every row (the NaN frames of a
+ * capture shorter than n count at index 0), and the sum over y of density[y][g] is c_hist[g] of sp_render on the same request.
+ * Geometry, limits, statuses, channel mode and detector are sp_plan_execute_index's (peak plans are accepted: a persistence display of
+ * held peaks); width 0 gives all zeros; lut_len > 256 returns SP_ERR_UNSUPPORTED.  The counts are integers added with integer atomics:
+ * the result does not depend on the deal of pixels to workgroups.  A cell cannot overflow within one request (width < 2^31); with
+ * `accumulate` it wraps modulo 2^32.
+ *
+ * sp_density_from_index (lib/worker.js:105-117, the count alone): the histogram of an index image the caller holds on the device, in the
+ *   layout `waterfall` names and at the pixel positions given for sp_plan_execute_index above; the companion of sp_index_to_rgba.
+ *   Asynchronous on the context's stream; it carries no request number, so a stream that is being captured is not refused.
+ *   accumulate == 0 overwrites d_density, accumulate != 0 adds to it (persistence over successive captures).  A byte >= lut_len is
+ *   counted nowhere.  d_index needs no alignment; d_density must be 4-byte aligned, 1 <= lut_len <= 256, n >= 1, width >= 0
+ *   (SP_ERR_INVALID_ARG otherwise).  width == 0 zeroes d_density when not accumulating and does nothing otherwise.
+ * sp_plan_execute_density (lib/worker.js:105-117 over the frame loop of :68-137): device operands, asynchronous.  The request's index
+ *   image is rendered into a workspace of the context - width * n bytes of device memory, grown and never shrunk, ordered on the
+ *   stream: that is this call's cost - by sp_plan_execute_index's path (k_frames_index where it covers the request, render_extract
+ *   elsewhere; sp_plan_force_kernel applies) and counted into d_density (device pointer, 4-byte aligned: SP_ERR_INVALID_ARG
+ *   otherwise).  The same request-number handshake: not capturable into a hipGraph (SP_ERR_UNSUPPORTED on a capturing stream), and
+ *   free to interleave with sp_plan_execute / sp_plan_execute_index on one context without a synchronisation.  The render's side
+ *   outputs go to a reply record of the context and are not returned.
+ * sp_render_density (lib/worker.js:23-156 with the count of :105-117 as its reply): host buffers, synchronous, the plan cached as by
+ *   sp_render.  The samples are the only transfer - packed where stride > n, in chunks of frames where the request is large, the
+ *   threshold counting the bytes that travel; every chunk's frames are rendered and counted behind its upload, and `density`
+ *   (4 * n * lut_len bytes of host memory) comes back in one copy.  sp_context_last_upload_bytes / sp_context_last_chunks report as before.
+ * sp_debug_density_launch (lib/worker.js:105-117; tests, no device needed): the counting kernel's decomposition for the frames
+ *   [x_begin, x_end) of an image of n rows and `width` frames, from the functions the launch itself calls.  out[] receives int64
+ *   words: workgroups, rows per workgroup, frames per workgroup, LDS bytes per workgroup, row bands, frame pieces; then per workgroup
+ *   the rectangle it counts: first row, end row, first frame, end frame.  The grid depends on n, the layout and the range only.
+ *   *used = words needed (SP_ERR_INVALID_ARG if capacity is smaller, or 0 <= x_begin <= x_end <= width does not hold).
+ * Out of scope: batches, groups and sharding.py (their merge would be an element-wise sum), and a bound on the workspace.
+ */
+int sp_density_from_index(sp_context *ctx, const uint8_t *d_index, int32_t n, int32_t width, int32_t waterfall, int32_t lut_len,
+                          uint32_t *d_density, int32_t accumulate);
+int sp_plan_execute_density(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, uint32_t *d_density, int32_t accumulate);
+int sp_render_density(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, uint32_t *density);
+int sp_debug_density_launch(int32_t n, int32_t width, int32_t waterfall, int32_t x_begin, int32_t x_end, int64_t *out, size_t capacity,
+                            size_t *used);
 
 /*
  * Page-locked host memory for request / reply buffers: sp_render moves pinned buffers at the full rate of the host link, pageable

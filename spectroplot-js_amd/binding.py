@@ -171,6 +171,10 @@ class Library:
         L.sp_plan_index_kernel_name_for.restype = C.c_char_p
         L.sp_plan_index_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_plan_debug_index_launch.argtypes = [vp, sz, i32, vp, vp, sz, C.POINTER(sz)]
+        L.sp_density_from_index.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
+        L.sp_plan_execute_density.argtypes = [vp, vp, sz, i32, vp, i32]
+        L.sp_render_density.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp]
+        L.sp_debug_density_launch.argtypes = [i32, i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -188,6 +192,20 @@ class Library:
         n = C.c_int32(0)
         self.L.sp_device_count(C.byref(n))
         return n.value
+
+    def debug_density_launch(self, n, width, waterfall=False, x_begin=0, x_end=None):
+        """The counting kernel's decomposition for the frames [x_begin, x_end) of an index image of n rows and `width` frames
+        (sp_debug_density_launch; no device needed): a dict of DENSITY_LAUNCH_FIELDS plus "rects", an int64 array of one
+        (first row, end row, first frame, end frame) per workgroup."""
+        x_end = int(width) if x_end is None else int(x_end)
+        used = C.c_size_t()
+        self.L.sp_debug_density_launch(int(n), int(width), int(bool(waterfall)), int(x_begin), x_end, None, 0, C.byref(used))
+        out = np.zeros(max(used.value, 1), np.int64)
+        self.check(self.L.sp_debug_density_launch(int(n), int(width), int(bool(waterfall)), int(x_begin), x_end,
+                                                  out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
+        d = dict(zip(DENSITY_LAUNCH_FIELDS, (int(v) for v in out[:6])))
+        d["rects"] = out[6:used.value].reshape(-1, 4)
+        return d
 
 
 def parse_format(name):
@@ -249,6 +267,7 @@ def debug_frames_launch(n, lut_len, count, cu_count, gf_fixed=0):
     return tuple(int(v) for v in out)
 
 
+DENSITY_LAUNCH_FIELDS = ("workgroups", "rows", "frames", "lds_bytes", "bands", "pieces")
 LAUNCH_FIELDS = ("kernel", "log2n", "channel_mode", "prefetch", "gf", "groups", "grid", "lds_bytes", "rgba_fast", "peak_m", "cu_count")
 KERNELS = {0: "none", 1: "scratch_radix2", 3: "frames", 4: "frames_peak"}      # enum Kernel (sp_api.hip)
 
@@ -501,6 +520,24 @@ class Context:
         self._chk(self.lib.L.sp_index_to_rgba(self.h, C.c_void_p(d_index or None), int(pixels), lut.ctypes.data_as(C.c_void_p), len(lut),
                                               C.c_void_p(d_rgba or None)))
 
+    def render_density(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False,
+                       detector="sample", fill=None):
+        """sp_render_density: the persistence spectrum of the request, np.uint32 [n, lut_len]: how many of the `width` frames showed
+        colour index g in image row y.  fill: a value the array holds before the call (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
+        out = np.full((int(n), len(keep[1])), 0 if fill is None else int(fill), np.uint32)
+        self._chk(self.lib.L.sp_render_density(self.h, C.byref(req), data.ctypes.data_as(C.c_void_p), data.size, int(width),
+                                               out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def density_from_index(self, d_index, n, width, waterfall, lut_len, d_density, accumulate=False):
+        """sp_density_from_index: the per-row counts of an index image on the device (addresses; the layout `waterfall` names) into
+        u32[n * lut_len] at d_density - overwritten, or added to with accumulate.  Asynchronous on the context's stream."""
+        self._chk(self.lib.L.sp_density_from_index(self.h, C.c_void_p(d_index or None), int(n), int(width), int(bool(waterfall)),
+                                                   int(lut_len), C.c_void_p(d_density or None), int(bool(accumulate))))
+
     def plan_creations(self):
         n = C.c_int64()
         self._chk(self.lib.L.sp_context_plan_creations(self.h, C.byref(n)))
@@ -596,6 +633,12 @@ class Plan:
                      dbfs_minmax or None)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_index(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width), C.byref(rep),
                                                            C.c_void_p(index or None)))
+
+    def execute_density(self, d_bytes, nbytes, width, d_density, accumulate=False):
+        """sp_plan_execute_density: the request's persistence spectrum into u32[n * lut_len] at device address d_density (overwritten,
+        or added to with accumulate).  The index image lives in a workspace of the context (width * n bytes).  Asynchronous."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_density(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                             C.c_void_p(d_density or None), int(bool(accumulate))))
 
     def execute_batch(self, items):
         """sp_plan_execute_batch: `items` = [(d_bytes, nbytes, width, {"rgba": addr, "gauge_mins": ..., "c_hist": ..., "cb_hist": ...,

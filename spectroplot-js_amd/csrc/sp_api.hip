@@ -106,6 +106,8 @@ struct sp_context {
     DeviceBuffer scratch;        // scratch kernel slabs
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
+    DeviceBuffer density_index;  // sp_plan_execute_density: the request's index image, width * n bytes (grown, never shrunk)
+    DeviceBuffer density_reply;  // ... and the reply record its render's side outputs go to (sphost::ReplyRecord)
     // staging for sp_render (host-buffer entry point)
     DeviceBuffer in_bytes, out_rgba, render_small;
     HostBuffer host_small;
@@ -370,6 +372,8 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->scratch.release();
     ctx->traces_ws.release();
     ctx->index_rgba.release();
+    ctx->density_index.release();
+    ctx->density_reply.release();
     ctx->in_bytes.release();
     ctx->out_rgba.release();
     ctx->render_small.release();
@@ -905,6 +909,184 @@ __global__ void k_index_to_rgba(const uint8_t *__restrict__ index, size_t pixels
             put(i0 + 4 * k + 3, c3);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------- persistence spectrum: the count
+
+// k_density_count's decomposition: a workgroup counts a rectangle of the index image - `rows` image rows x `frames` frames - into one
+// u32[256] histogram per row in LDS and then adds its non-zero cells to the caller's array.  It depends on n, the layout and the frame
+// range only.  Spectrogram layout (a row's frames are consecutive bytes): 8 rows x 2048 frames, 8 KiB of LDS, 16 Ki pixels against at
+// most 2048 global atomics.  Waterfall layout (a frame's bins are consecutive bytes, so a workgroup wants many bins for whole
+// cache lines): 64 rows x 512 frames, 64 KiB of LDS, 32 Ki pixels against at most 16 Ki global atomics.
+constexpr int kDensityThreads = 256;
+constexpr int kDensityRowsSpectrogram = 8, kDensityFramesSpectrogram = 2048;
+constexpr int kDensityRowsWaterfall = 64, kDensityFramesWaterfall = 512;
+constexpr int kDensityAhead = 4;   // loads a lane has in flight before it counts the first
+
+struct DensityShape {
+    int rows, frames;          // of one workgroup's rectangle
+    long long bands, pieces;   // ceil(n / rows) bands of rows x ceil(range / frames) pieces of frames: workgroup = band * pieces + piece
+};
+
+__host__ __device__ inline DensityShape density_shape(int n, bool waterfall, int x_begin, int x_end)
+{
+    DensityShape d;
+    d.rows = waterfall ? kDensityRowsWaterfall : kDensityRowsSpectrogram;
+    d.frames = waterfall ? kDensityFramesWaterfall : kDensityFramesSpectrogram;
+    d.bands = ((long long)n + d.rows - 1) / d.rows;
+    d.pieces = ((long long)x_end - x_begin + d.frames - 1) / d.frames;
+    return d;
+}
+
+// the rectangle of workgroup wg: rows [y0, y1) x frames [x0, x1), inside [0, n) x [x_begin, x_end)
+__host__ __device__ inline void density_rect(const DensityShape &d, int n, int x_begin, int x_end, long long wg, int &y0, int &y1, int &x0,
+                                             int &x1)
+{
+    const long long band = wg / d.pieces, piece = wg % d.pieces;
+    const long long ya = band * d.rows, yb = ya + d.rows, xa = x_begin + piece * d.frames, xb = xa + d.frames;
+    y0 = (int)ya;
+    y1 = (int)(yb < n ? yb : n);
+    x0 = (int)xa;
+    x1 = (int)(xb < x_end ? xb : x_end);
+}
+
+// The frames [x_begin, x_end) of an index image (n rows, `width` frames, either layout) counted per image row.  Slot s of the workgroup
+// keeps row y0 + s; the cell of index g is s * 256 + ((g + s) & 255): a histogram is 256 wide whatever lut_len is, so no byte can
+// index past it, and rotated by its slot, so that one index in neighbouring rows (a waterfall wave's lanes) lies in different banks.
+// Equal neighbours are merged before the LDS add - a lane's 16 frames of one row (spectrogram), a lane's successive frames of its four
+// bins (waterfall) - so a flat row costs one add per 16 pixels instead of 16 to one address.
+template <bool WATERFALL>
+__global__ void __launch_bounds__(kDensityThreads)
+k_density_count(const uint8_t *__restrict__ index, int n, int width, int x_begin, int x_end, int lut_len, uint32_t *__restrict__ density)
+{
+    constexpr int ROWS = WATERFALL ? kDensityRowsWaterfall : kDensityRowsSpectrogram;
+    __shared__ uint32_t s_h[ROWS * 256];
+    const int t = threadIdx.x;
+    for (int i = t; i < ROWS * 256; i += kDensityThreads) s_h[i] = 0;
+    __syncthreads();
+    const DensityShape d = density_shape(n, WATERFALL, x_begin, x_end);
+    int y0, y1, x0, x1;
+    density_rect(d, n, x_begin, x_end, (long long)blockIdx.x, y0, y1, x0, x1);
+    const auto add = [&](int slot, uint32_t g, uint32_t count) { atomicAdd(&s_h[slot * 256 + (int)((g + (uint32_t)slot) & 255u)], count); };
+
+    if (!WATERFALL) {
+        // image: n rows x width columns; 32 lanes per row, a lane takes 16 consecutive frames of its row per pass (512 frames a pass):
+        // one 16-byte load where the piece is whole and lies aligned, four dwords where it lies 4-byte aligned, else byte by byte.
+        // The loads of kDensityAhead passes are issued before the first of them is counted (a pass is a load and the LDS adds that
+        // wait for it; one after the other, a workgroup's time is its passes' memory latencies added up).
+        const int slot = t >> 5, y = y0 + slot;
+        if (y < y1) {
+            const uint8_t *const row = index + (size_t)y * (size_t)width;
+            const auto fetch = [&](long long xa, uint32_t (&w)[4]) -> int {   // -> the piece's pixels (0: it lies behind the range)
+                w[0] = w[1] = w[2] = w[3] = 0;
+                if (xa >= x1) return 0;
+                const uint8_t *const p = row + xa;
+                const int cnt = x1 - xa < 16 ? (int)(x1 - xa) : 16;
+                if (cnt == 16 && ((uintptr_t)p & 15) == 0) {
+                    const uint4 v = *(const uint4 *)p;
+                    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+                } else if (cnt == 16 && ((uintptr_t)p & 3) == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) w[k] = ((const uint32_t *)p)[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; k++)
+                        if (k < cnt) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
+                }
+                return cnt;
+            };
+            const auto count = [&](const uint32_t (&w)[4], int cnt) {
+                if (cnt < 1) return;
+                uint32_t cur = w[0] & 255u, run = 1;
+#pragma unroll
+                for (int k = 1; k < 16; k++) {
+                    const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 255u;
+                    if (k < cnt) {
+                        if (b == cur) {
+                            run++;
+                        } else {
+                            add(slot, cur, run);
+                            cur = b;
+                            run = 1;
+                        }
+                    }
+                }
+                add(slot, cur, run);
+            };
+            for (long long xa = (long long)x0 + 16 * (t & 31); xa < x1; xa += 512 * kDensityAhead) {
+                uint32_t w[kDensityAhead][4];
+                int cnt[kDensityAhead];
+#pragma unroll
+                for (int u = 0; u < kDensityAhead; u++) cnt[u] = fetch(xa + 512 * u, w[u]);
+#pragma unroll
+                for (int u = 0; u < kDensityAhead; u++) count(w[u], cnt[u]);
+            }
+        }
+    } else {
+        // image: width rows x n columns, frame x in row width - 1 - x, image row y in column n - 1 - y: the band's rows are the
+        // columns [n - y1, n - y0).  16 lanes per frame, a lane takes four consecutive columns (one dword where they exist and lie
+        // aligned, else bytes) of every 16th frame, kDensityAhead loads ahead as above; byte j of its word belongs to slot top - j.
+        const int cols = y1 - y0, q = t & 15, valid = cols - 4 * q < 4 ? cols - 4 * q : 4, top = cols - 1 - 4 * q;
+        if (valid > 0) {
+            const auto flush = [&](uint32_t word, uint32_t count) {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (j < valid) add(top - j, (word >> (8 * j)) & 255u, count);
+            };
+            const auto fetch = [&](long long x) -> uint32_t {   // (x < x1)
+                const uint8_t *const p = index + (size_t)((long long)width - 1 - x) * (size_t)n + (size_t)(n - y1 + 4 * q);
+                if (valid == 4 && ((uintptr_t)p & 3) == 0) return *(const uint32_t *)p;
+                uint32_t word = 0;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (j < valid) word |= (uint32_t)p[j] << (8 * j);
+                return word;
+            };
+            uint32_t held = 0, run = 0;
+            for (long long xa = (long long)x0 + (t >> 4); xa < x1; xa += 16 * kDensityAhead) {
+                uint32_t word[kDensityAhead];
+#pragma unroll
+                for (int u = 0; u < kDensityAhead; u++) word[u] = xa + 16 * u < x1 ? fetch(xa + 16 * u) : 0u;
+#pragma unroll
+                for (int u = 0; u < kDensityAhead; u++) {
+                    if (xa + 16 * u >= x1) continue;
+                    if (run && word[u] == held) {
+                        run++;
+                    } else {
+                        if (run) flush(held, run);
+                        held = word[u];
+                        run = 1;
+                    }
+                }
+            }
+            if (run) flush(held, run);
+        }
+    }
+    __syncthreads();
+    // the workgroup's share: its non-zero cells of indices the map has, one no-return atomic each (consecutive lanes, consecutive cells)
+    for (int i = t; i < ROWS * 256; i += kDensityThreads) {
+        const int slot = i >> 8, y = y0 + slot, g = (i - slot) & 255;
+        const uint32_t v = s_h[i];
+        if (v && y < y1 && g < lut_len) atomicAdd(&density[(size_t)y * (size_t)lut_len + (size_t)g], v);
+    }
+}
+
+// frames [x_begin, x_end) of the index image at d_index ADDED to d_density, on the context's stream
+static int density_count(sp_context *ctx, const uint8_t *d_index, int n, int32_t width, bool waterfall, int lut_len, int32_t x_begin,
+                         int32_t x_end, uint32_t *d_density)
+{
+    if (x_end <= x_begin) return SP_OK;
+    const DensityShape d = density_shape(n, waterfall, x_begin, x_end);
+    const long long grid = d.bands * d.pieces;
+    if (grid > 0x7fffffffll) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one counting launch");
+    if (waterfall)
+        hipLaunchKernelGGL(k_density_count<true>, dim3((unsigned)grid), dim3(kDensityThreads), 0, ctx->stream, d_index, n, width, x_begin, x_end,
+                           lut_len, d_density);
+    else
+        hipLaunchKernelGGL(k_density_count<false>, dim3((unsigned)grid), dim3(kDensityThreads), 0, ctx->stream, d_index, n, width, x_begin, x_end,
+                           lut_len, d_density);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
 }
 
 // An indexed request's image (sp_plan_execute_index): `frames`: k_frames_index writes it; else the request's ordinary kernel renders
@@ -1660,6 +1842,154 @@ extern "C" int sp_plan_debug_index_launch(const sp_plan *plan, size_t nbytes, in
     if (width > 0 && index_frames(plan, spgeo::geometry(plan->fmt, plan->req.n, nbytes, width))) {
         out[0] = 5;
         out[8] = index_fast((const uint8_t *)index, width, plan->req.n, 0, width) ? 1 : 0;
+    }
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- persistence spectrum
+
+// what every density entry point refuses of its colour-map length and its output
+static int check_density(sp_context *ctx, int32_t lut_len, const uint32_t *density)
+{
+    if (lut_len > 256) return fail(ctx, SP_ERR_UNSUPPORTED, "the density counts an indexed image's bytes: lut_len must be 256 at most");
+    if (lut_len < 1) return fail(ctx, SP_ERR_INVALID_ARG, "lut_len < 1");
+    if (!density || ((uintptr_t)density & 3) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "density must be a 4-byte aligned array of n * lut_len counts");
+    return SP_OK;
+}
+
+extern "C" int sp_density_from_index(sp_context *ctx, const uint8_t *d_index, int32_t n, int32_t width, int32_t waterfall, int32_t lut_len,
+                                     uint32_t *d_density, int32_t accumulate)
+{
+    if (!ctx) return no_object_status();
+    if (lut_len > 256) return fail(ctx, SP_ERR_INVALID_ARG, "lut_len must be 1 ... 256");   // (no request here whose map the reference allows)
+    int rc = check_density(ctx, lut_len, d_density);
+    if (rc) return rc;
+    if (n < 1 || width < 0 || (width > 0 && !d_index)) return fail(ctx, SP_ERR_INVALID_ARG, "n >= 1, width >= 0 and an index image are needed");
+    if ((double)width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (!accumulate) SP_HIP(ctx, hipMemsetAsync(d_density, 0, (size_t)n * (size_t)lut_len * sizeof(uint32_t), ctx->stream));
+    rc = density_count(ctx, d_index, n, width, waterfall != 0, lut_len, 0, width, d_density);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+// the index image and the reply record of a density request on device operands: both the context's, ordered on its stream
+static int density_prepare(sp_plan *plan, int32_t width, sp_reply *d, IndexTarget *ix, const spgeo::Geometry &g)
+{
+    sp_context *ctx = plan->ctx;
+    const sphost::ReplyRecord rec{(size_t)plan->req.lut_len, (size_t)width};
+    int rc = ctx->density_index.reserve((size_t)width * (size_t)plan->req.n + 16);
+    if (!rc) rc = ctx->density_reply.reserve(rec.bytes() + 16);
+    if (rc) return fail(ctx, rc, "density workspace: out of device memory");
+    *d = rec.view(ctx->density_reply.p);
+    d->rgba = nullptr;
+    *ix = IndexTarget{(uint8_t *)ctx->density_index.p, index_frames(plan, g)};
+    return !ix->frames && width > 0 ? index_prepare(plan, width) : (int)SP_OK;
+}
+
+extern "C" int sp_plan_execute_density(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, uint32_t *d_density, int32_t accumulate)
+{
+    if (!plan) return no_object_status();
+    sp_context *ctx = plan->ctx;
+    const int n = plan->req.n, lut_len = plan->req.lut_len;
+    int rc = check_density(ctx, lut_len, d_density);
+    if (rc) return rc;
+    rc = check_capture(ctx, plan->fmt, n, d_bytes, nbytes, width, nullptr, "");   // (before anything is allocated)
+    if (rc) return rc;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    rc = refuse_capture(ctx, s, "sp_plan_execute_density cannot be captured into a hipGraph (every launch carries its request's number)");
+    if (rc) return rc;
+    const RequestShape shape = request_shape(plan, nbytes, width);
+    sp_reply d{};
+    IndexTarget ix{};
+    rc = density_prepare(plan, width, &d, &ix, shape.g);
+    if (rc) return rc;
+    rc = plan_execute_range(plan, d_bytes, shape, 0, width, true, true, &d, nullptr, &ix);
+    if (rc) return rc;
+    if (!accumulate) SP_HIP(ctx, hipMemsetAsync(d_density, 0, (size_t)n * (size_t)lut_len * sizeof(uint32_t), s));
+    rc = density_count(ctx, ix.d_index, n, width, plan->req.waterfall != 0, lut_len, 0, width, d_density);
+    if (rc) return rc;
+    if (ctx->timing && width > 0) SP_HIP(ctx, hipEventRecord(ctx->ev1, s));   // (timing: the render's event pair now ends behind the count)
+    return SP_OK;
+}
+
+// A request kind of stream_chunks, fed as sp_render_traces is (the samples are the only transfer, nothing follows a chunk): every
+// chunk's launch renders its frames into the index image on the device and counts them; the counts come back in one copy.
+extern "C" int sp_render_density(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, uint32_t *density)
+{
+    if (!ctx) return no_object_status();
+    int rc = validate_request(ctx, req);
+    if (rc) return rc;
+    rc = check_density(ctx, req->lut_len, density);
+    if (rc) return rc;
+    const spfmt::Format f = spfmt::describe(req->format);
+    rc = check_host_capture(ctx, f, bytes, nbytes, width);
+    if (!rc) rc = check_capture(ctx, f, req->n, bytes, nbytes, width, nullptr, "");
+    if (rc) return rc;
+    sp_plan *plan = nullptr;
+    rc = cached_plan_for(ctx, req, &plan);
+    if (rc) return rc;
+
+    hipStream_t s = ctx->stream;
+    const int n = req->n, lut_len = req->lut_len;
+    const bool waterfall = req->waterfall != 0;
+    const size_t count_bytes = (size_t)n * (size_t)lut_len * sizeof(uint32_t);
+    rc = ctx->render_small.reserve(count_bytes + 16);
+    if (rc) return fail(ctx, rc, "sp_render_density: out of memory");
+    uint32_t *const d_density = (uint32_t *)ctx->render_small.p;
+    const RequestShape shape = request_shape(plan, nbytes, width);
+    sp_reply d{};
+    IndexTarget ix{};
+    rc = density_prepare(plan, width, &d, &ix, shape.g);
+    if (rc) return rc;
+    HostFeed feed{"sp_render_density", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames, true, 0, false, nullptr};
+    bool cleared = false;
+    // (the clear belongs to the first chunk's launch: queued earlier, it would make the stream look busy to the streamer)
+    auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
+        if (first) {
+            const hipError_t e = hipMemsetAsync(d_density, 0, count_bytes, s);
+            if (e != hipSuccess) return hip_fail(ctx, e, "sp_render_density clear");
+            cleared = true;
+        }
+        const int r = plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src, &ix);
+        return r ? r : density_count(ctx, ix.d_index, n, width, waterfall, lut_len, x0, x1, d_density);
+    };
+    rc = stream_chunks(ctx, f, feed, launch, [](int, int32_t, int32_t) { return (int)SP_OK; });   // (nothing follows a chunk)
+    hipError_t e = hipSuccess;
+    if (!rc && !cleared) e = hipMemsetAsync(d_density, 0, count_bytes, s);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(density, d_density, count_bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // (synchronous; the samples' stream has ended before this one)
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, "sp_render_density copies");
+    return SP_OK;
+}
+
+// (tests) k_density_count's decomposition from the functions its launch calls: six words, then every workgroup's rectangle.
+extern "C" int sp_debug_density_launch(int32_t n, int32_t width, int32_t waterfall, int32_t x_begin, int32_t x_end, int64_t *out, size_t capacity,
+                                       size_t *used)
+{
+    if (n < 1 || width < 0 || x_begin < 0 || x_end < x_begin || x_end > width || !used) return SP_ERR_INVALID_ARG;
+    const DensityShape d = density_shape(n, waterfall != 0, x_begin, x_end);
+    const long long grid = d.bands * d.pieces;
+    *used = 6 + 4 * (size_t)grid;
+    if (!out || capacity < *used) return SP_ERR_INVALID_ARG;
+    out[0] = grid;
+    out[1] = d.rows;
+    out[2] = d.frames;
+    out[3] = (int64_t)d.rows * 256 * (int64_t)sizeof(uint32_t);
+    out[4] = d.bands;
+    out[5] = d.pieces;
+    for (long long wg = 0; wg < grid; wg++) {
+        int y0, y1, x0, x1;
+        density_rect(d, n, x_begin, x_end, wg, y0, y1, x0, x1);
+        int64_t *const r = out + 6 + 4 * wg;
+        r[0] = y0, r[1] = y1, r[2] = x0, r[3] = x1;
     }
     return SP_OK;
 }

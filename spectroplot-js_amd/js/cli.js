@@ -6,7 +6,7 @@
  *
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
- *        [--full] [--traces traces.json] [--index index.pgm] --out image.ppm
+ *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
  * Batch mode (--out-dir): one image per capture, DIR/<capture's file name>.ppm (or .rgba with --rgba), the same bytes a single-file
@@ -19,6 +19,10 @@
  *
  * --index FILE (single-file runs): the same request over the whole capture as an indexed image (HipWorker.renderIndexed ->
  * sp_render_index), written beside the image as a binary PGM (P5, maxval 255): one colour-index byte per pixel, rows as the image's.
+ *
+ * --density FILE (single-file runs): the persistence spectrum of the same request over the whole capture (HipWorker.renderDensity ->
+ * sp_render_density), written as a binary PGM (P5, maxval 65535, big-endian): lut_len columns x n rows, row y the image row's counts
+ * per colour index, each value min(count, 65535).
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -71,6 +75,22 @@ function writeIndex(buffer, format, n, width, opt) {
         worker.terminate()
         fs.writeFileSync(opt.index, Buffer.concat([Buffer.from(`P5\n${r.width} ${r.height}\n255\n`),
             Buffer.from(r.index.buffer, r.index.byteOffset, r.index.byteLength)]))
+    }, e => { worker.terminate(); throw e })
+}
+
+// --density: one request over the whole capture on one worker, resolved as --index resolves its own; raw counts, saturated at 65535
+function writeDensity(buffer, format, n, width, opt) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())
+    cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
+    const worker = new HipWorker()
+    return worker.renderDensity({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), cmap, channelMode: !!opt.channelMode, waterfall: !!opt.waterfall, detector: opt.detector }).then(r => {
+        worker.terminate()
+        const body = Buffer.alloc(2 * r.density.length)
+        for (let i = 0; i < r.density.length; i++) body.writeUInt16BE(r.density[i] < 65535 ? r.density[i] : 65535, 2 * i)
+        fs.writeFileSync(opt.density, Buffer.concat([Buffer.from(`P5\n${r.lutLen} ${r.n}\n65535\n`), body]))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -145,6 +165,7 @@ function main(argv) {
         })
         .then(() => opt.traces === undefined ? null : writeTraces(buffer, format, n, width, opt))
         .then(() => opt.index === undefined ? null : writeIndex(buffer, format, n, width, opt))
+        .then(() => opt.density === undefined ? null : writeDensity(buffer, format, n, width, opt))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

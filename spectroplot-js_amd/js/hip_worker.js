@@ -233,6 +233,35 @@ class HipWorker {
         }
     }
 
+    /**
+     * The persistence spectrum of a worker message (sp_render_density): how many of the message's `width` frames showed colour index g in
+     * image row y - density[y * lutLen + g], row y of the spectrogram and column n - 1 - y of the waterfall, the same array for both
+     * layouts.  The message is renderIndexed's (`detector: 'peak'` allowed; a colour map of more than 256 entries is refused with status
+     * -4).  Runs in the instance's request order; a malformed field rejects (and reports `onerror` with status -1) and never resolves to
+     * counts.
+     * @returns {Promise<{density: Uint32Array, n: number, lutLen: number, width: number}>}
+     */
+    renderDensity(m) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._indexRequest(m) } catch (e) { reject(e); return }
+            try {
+                addon().renderDensity(this._ctx, req, (err, r) => err ? reject(err) : resolve(this._wrapDensity(r)))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => {
+            if (!this._closed) this._emit('error', { message: err.message, status: err.status === undefined ? -1 : err.status, error: err })
+        })
+        return p
+    }
+
+    _wrapDensity(r) { return { density: r.density, n: r.n, lutLen: r.lutLen, width: r.width } }
+
+    /** Synchronous form of renderDensity (tests). */
+    renderDensitySync(m) { return this._wrapDensity(addon().renderDensitySync(this._ctx, this._indexRequest(m))) }
+
     /** Synchronous form of renderIndexed (tests). */
     renderIndexedSync(m) { return this._wrapIndex(m, addon().renderIndexSync(this._ctx, this._indexRequest(m))) }
 

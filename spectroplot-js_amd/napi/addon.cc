@@ -24,6 +24,8 @@
 //       c_hist, cB_hist: Float64Array, dBfs_min, dBfs_max}) on the main thread
 //   renderSync(handle, req)                        -> the same reply object, synchronously
 //   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
+//   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
+//       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
 //                                    indices, in place of `rgba` (sp_render_index); req as for render
 //   renderNamed(handle, req, cb) / renderNamedSync(handle, req)   req = {format, window, cmap: strings, buffer, n, gain, range, width,
@@ -51,6 +53,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <mutex>
+#include <new>
 #include <sys/mman.h>
 #include <string>
 #include <vector>
@@ -973,7 +976,7 @@ struct IndexJob : Job {
     napi_value result(napi_env env) override;
 };
 
-bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t)
+bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t, const char *who = "renderIndex")
 {
     void *p = nullptr;
     if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
@@ -982,7 +985,7 @@ bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t)
     }
     t->owner = (Ctx *)p;
     if (t->owner->closed || !t->owner->c) {
-        napi_throw_error(env, nullptr, t->owner->g ? "renderIndex takes a context handle, not a group" : "context has been destroyed");
+        napi_throw_error(env, nullptr, t->owner->g ? (std::string(who) + " takes a context handle, not a group").c_str() : "context has been destroyed");
         return false;
     }
     t->ctx = t->owner->c;
@@ -1116,6 +1119,78 @@ napi_value RenderIndex(napi_env env, napi_callback_info info)
     napi_value buf = nullptr;   // (left null, it fails the queueing)
     napi_get_named_property(env, argv[1], "buffer", &buf);
     return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderIndex", "could not queue the indexed request");
+}
+
+// ---- persistence spectrum: renderDensity(handle, req, cb) / renderDensitySync(handle, req) ----------------------------------------------
+// req as for renderIndex -> {density, n, lutLen, width}: density a Uint32Array(n * lutLen), row y at y * lutLen - how many of the
+// request's frames showed colour index g in image row y (sp_render_density).  The request is read by parse_index: every value into a
+// variable of its own with its status checked, so a request that cannot be read throws and never counts.
+struct DensityJob : IndexJob {
+    std::vector<uint32_t> counts;
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+void DensityJob::run()
+{
+    // (a map the library refuses gets no array: its n * lut_len could be anything)
+    if (req.lut_len >= 1 && req.lut_len <= 256) {
+        try {
+            counts.assign((size_t)req.n * (size_t)req.lut_len, 0u);
+        } catch (const std::bad_alloc &) {
+            status = SP_ERR_NOMEM;
+            error = "out of host memory";
+            return;
+        }
+    }
+    uint32_t none = 0;
+    status = sp_render_density(ctx, &req, bytes, nbytes, width, counts.empty() ? &none : counts.data());
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value DensityJob::result(napi_env env)
+{
+    napi_value out, ab, ta, v;
+    void *data = nullptr;
+    if (napi_create_object(env, &out) != napi_ok || napi_create_arraybuffer(env, counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
+    memcpy(data, counts.data(), counts.size() * 4);
+    if (napi_create_typedarray(env, napi_uint32_array, counts.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "density", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, out, "n", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.lut_len, &v) != napi_ok || napi_set_named_property(env, out, "lutLen", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, out, "width", v) != napi_ok) return nullptr;
+    return out;
+}
+
+napi_value RenderDensitySync(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 2) {
+        napi_throw_type_error(env, nullptr, "renderDensitySync(handle, request)");
+        return nullptr;
+    }
+    DensityJob *t = new DensityJob;
+    if (!parse_index(env, argv[0], argv[1], t, "renderDensity")) { free_job(env, t); return nullptr; }
+    return run_sync(env, t);
+}
+
+napi_value RenderDensity(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    napi_valuetype ty = napi_undefined;
+    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
+        napi_throw_type_error(env, nullptr, "renderDensity(handle, request, callback)");
+        return nullptr;
+    }
+    DensityJob *t = new DensityJob;
+    if (!parse_index(env, argv[0], argv[1], t, "renderDensity")) { free_job(env, t); return nullptr; }
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderDensity", "could not queue the density request");
 }
 
 napi_value DeviceCount(napi_env env, napi_callback_info)
@@ -1440,6 +1515,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderDensitySync", nullptr, RenderDensitySync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"peakSubframes", nullptr, PeakSubframes, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},

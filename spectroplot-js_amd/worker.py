@@ -50,6 +50,16 @@ class HipWorker:
                 "offset": m.get("offset"), "gauge_mins": r["gauge_mins"], "gauge_maxs": r["gauge_maxs"],
                 "gauge_amps": r["gauge_amps"], "imageData": {"data": r["rgba"]}}
 
+    def render_density(self, m):
+        """The persistence spectrum of a worker message (js/hip_worker.js renderDensity): {'density': uint32 [n, lutLen], 'n', 'lutLen',
+        'width'} - how many of the message's frames showed colour index g in image row y."""
+        data = np.frombuffer(m["buffer"], dtype=np.uint8) if not isinstance(m["buffer"], np.ndarray) else m["buffer"]
+        lut = _lut_bytes(m["cmap"])
+        d = self.ctx.render_density(m["format"], data, m["n"], m["windowc"], m["block_norm"], m["gain"], m["range"], lut, m["width"],
+                                    bool(m.get("channelMode")), bool(m.get("waterfall")),
+                                    detector="sample" if m.get("detector") is None else m["detector"])
+        return {"density": d, "n": int(m["n"]), "lutLen": len(lut), "width": int(m["width"])}
+
 
 def render_sliced(render_fn, data, fmt, n, width, workers, windowc, weight, cmap, gain, rng, channel_mode=False,
                   waterfall=False, force_ends=True):
