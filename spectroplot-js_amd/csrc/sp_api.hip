@@ -778,12 +778,24 @@ static int check_capture(sp_context *ctx, const spfmt::Format &f, int n, const v
 
 // The request's number travels in the kernel arguments, and the frame loop's workgroups wait for workgroup 0 to publish it (the reply is
 // cleared first): a captured launch replayed from a hipGraph would find the number already there.  Refused.
-static int refuse_capture(sp_context *ctx, hipStream_t s, const char *message)
+static int refuse_capture(sp_context *ctx, hipStream_t s, const char *entry, const char *why)
 {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return fail(ctx, SP_ERR_UNSUPPORTED, message);
+    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(ctx, SP_ERR_UNSUPPORTED, std::string(entry) + " cannot be captured into a hipGraph" + why);
     (void)hipGetLastError();
     return SP_OK;
+}
+
+// What an entry point on device operands does before it allocates or queues anything: the capture's limits (`reply` as for
+// check_capture), the context's device made current, a stream under graph capture refused in the name of `entry`.
+static int device_operands(sp_context *ctx, const spfmt::Format &f, int n, const void *d_bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                           const char *entry)
+{
+    const int rc = check_capture(ctx, f, n, d_bytes, nbytes, width, reply, "");
+    if (rc) return rc;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return refuse_capture(ctx, ctx->stream, entry, " (every launch carries its request's number)");
 }
 
 // the write-out may store an image in 16-byte pieces with 32-bit offsets
@@ -1089,29 +1101,32 @@ static int density_count(sp_context *ctx, const uint8_t *d_index, int n, int32_t
     return SP_OK;
 }
 
-// An indexed request's image (sp_plan_execute_index): `frames`: k_frames_index writes it; else the request's ordinary kernel renders
-// through the plan's identity LUT into the context's temporary RGBA image and k_extract_index keeps byte 0 of every pixel of the range.
-struct IndexTarget {
-    uint8_t *d_index;   // [width * n], may be null: side outputs only
-    bool frames;
+// Where a request's picture goes.  kRgba: the request's kernel writes the RGBA image.  kIndexFrames: k_frames_index writes the index
+// image.  kIndexExtract: the request's ordinary kernel renders through the plan's identity LUT into the context's temporary RGBA image
+// and k_extract_index keeps byte 0 of every pixel of the range (the caller has run index_prepare).
+struct Picture {
+    enum Kind { kRgba, kIndexFrames, kIndexExtract } kind;
+    uint8_t *image;   // device memory: RGBA [4 * width * n] or index [width * n]; may be null: side outputs only
 };
 
+// an indexed request's picture (`frames`: index_frames' answer for the request); without an image nothing is there to extract
+static Picture index_picture(uint8_t *d_index, bool frames)
+{
+    return Picture{frames ? Picture::kIndexFrames : d_index ? Picture::kIndexExtract : Picture::kRgba, d_index};
+}
+
 static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestShape &shape, int32_t x_begin, int32_t x_end, bool first,
-                              bool last, const sp_reply *out, const PackedSource *src = nullptr, const IndexTarget *ix = nullptr)
+                              bool last, const sp_reply *out, const Picture &pic, const PackedSource *src = nullptr)
 {
     if (!plan || !out) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
     const spgeo::Geometry &g = shape.g;
     const spgeo::PeakShape &peak = shape.peak;
-    const spfmt::Format f = plan->fmt;
     const int n = plan->req.n;
     const int32_t width = g.width;
-    int rc = check_capture(ctx, f, n, d_bytes, g.nbytes, width, out, "");
+    int rc = device_operands(ctx, plan->fmt, n, d_bytes, g.nbytes, width, out, "sp_plan_execute");
     if (rc) return rc;
-    SP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    rc = refuse_capture(ctx, s, "sp_plan_execute cannot be captured into a hipGraph (every launch carries its request's number)");
-    if (rc) return rc;
 
     if (width == 0) {
         // nothing to draw; the reply keeps the loop's initial values (worker.js:35-36)
@@ -1153,7 +1168,6 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     spk::FrameArgs a{};
     plan_frame_args(plan, a);
     frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
-    a.rgba = out->rgba;
     a.frame_min = (double *)ctx->frame_minmax.p;
     a.frame_max = a.frame_min + width;
     a.scratch = nullptr;
@@ -1172,19 +1186,14 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     a.mm_acc = (unsigned long long *)((char *)ctx->partial.p + 16);
     a.c_hist = (unsigned long long *)((char *)ctx->partial.p + 64);
     a.cb_hist = a.c_hist + SP_MAX_LUT;
-    a.rgba_fast = rgba_fast(out->rgba, width, n);
-    if (ix && ix->frames) {
-        a.rgba = ix->d_index;
-        a.rgba_fast = index_fast(ix->d_index, width, n, x_begin, x_end);
-    } else if (ix && ix->d_index) {
-        a.rgba = (uint8_t *)ctx->index_rgba.p;   // (reserved and the LUT built by the caller: index_prepare)
-        a.rgba_fast = rgba_fast(a.rgba, width, n);
-        a.lut_rgba = (const uint32_t *)plan->ident_lut.p;
-    }
+    const bool extract = pic.kind == Picture::kIndexExtract;
+    a.rgba = extract ? (uint8_t *)ctx->index_rgba.p : pic.image;   // (reserved and the LUT built by the caller: index_prepare)
+    a.rgba_fast = pic.kind == Picture::kIndexFrames ? index_fast(a.rgba, width, n, x_begin, x_end) : rgba_fast(a.rgba, width, n);
+    if (extract) a.lut_rgba = (const uint32_t *)plan->ident_lut.p;
 
     if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
     const int32_t peak_nsamp = (int32_t)(peak.nsamp < 2147483647 ? peak.nsamp : 2147483647);
-    if (ix && ix->frames) {
+    if (pic.kind == Picture::kIndexFrames) {
         if (which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "k_frames_index renders what k_frames renders");
         rc = spk2::launch_frames_index(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, "k_frames_index launch rejected the configuration");
@@ -1213,8 +1222,8 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
         if (rc) return fail(ctx, rc, "bad format");
     }
     SP_HIP(ctx, hipGetLastError());
-    if (ix && !ix->frames && ix->d_index && x_end > x_begin) {
-        rc = extract_index_band(ctx, (const uint8_t *)ctx->index_rgba.p, ix->d_index, width, n, plan->req.waterfall != 0, x_begin, x_end);
+    if (extract && x_end > x_begin) {
+        rc = extract_index_band(ctx, a.rgba, pic.image, width, n, plan->req.waterfall != 0, x_begin, x_end);
         if (rc) return rc;
     }
     if (ctx->timing) {
@@ -1259,8 +1268,9 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
 
 extern "C" int sp_plan_execute(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const sp_reply *out)
 {
-    if (!plan) return SP_ERR_INVALID_ARG;
-    return plan_execute_range(plan, d_bytes, request_shape(plan, nbytes, width), 0, width < 0 ? 0 : width, true, true, out);
+    if (!plan || !out) return SP_ERR_INVALID_ARG;
+    return plan_execute_range(plan, d_bytes, request_shape(plan, nbytes, width), 0, width < 0 ? 0 : width, true, true, out,
+                              Picture{Picture::kRgba, out->rgba});
 }
 
 // (tests) What sp_plan_execute would launch for a request of this shape on this plan's context, from the launch path's own functions:
@@ -1556,52 +1566,71 @@ static int stream_chunks(sp_context *ctx, const spfmt::Format &f, HostFeed &h, L
     return rc;
 }
 
-// sp_render / sp_render_strip / sp_plan_execute_from_host.  `image_width` is the width in frames of the image reply->rgba points into
-// (the strip's own width for sp_render); it only matters for the spectrogram layout, whose rows are image_width pixels apart.
-// device_out = false: the reply's pointers are host pointers; the image travels back chunk by chunk, the small outputs in one copy, and
-// the call returns when everything has arrived.  device_out = true: the reply's pointers are device pointers (as for sp_plan_execute);
-// nothing comes back, and the call returns once everything is queued.
-static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply, int32_t image_width,
-                       bool device_out)
+// The small outputs of a request side by side in a context buffer on the device, as a reply without an image.
+static int device_reply_record(DeviceBuffer &buf, const sphost::ReplyRecord &rec, sp_reply *d)
+{
+    const int rc = buf.reserve(rec.bytes() + 16);
+    if (rc) return rc;
+    *d = rec.view(buf.p);
+    d->rgba = nullptr;
+    return SP_OK;
+}
+
+// The image of a host-fed request.  device_out = false: the reply's pointers are host pointers; the device image lies in `dev` and
+// travels back chunk by chunk, the small outputs in one copy, and the call returns when everything has arrived.  device_out = true:
+// the reply's pointers and `host` are device pointers (as for sp_plan_execute); the kernels write them, nothing comes back, and the
+// call returns once everything is queued.
+struct HostImage {
+    uint8_t *host;         // the caller's image; may be null: side outputs only
+    size_t px;             // bytes per pixel: 4 (RGBA) or 1 (an index image)
+    size_t host_pitch;     // bytes between rows of the caller's image
+    DeviceBuffer *dev;     // the context buffer that holds the device image
+    Picture::Kind kind;    // how plan_execute_range writes it
+    bool device_out;
+};
+
+// A host-fed request with an image (render_rgba, sp_render_index).  `who`: the entry point, for its error texts.
+static int render_image(sp_plan *plan, const char *who, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
+                        const HostImage &im)
 {
     sp_context *ctx = plan->ctx;
     const sp_request *req = &plan->req;
     hipStream_t s = ctx->stream;
 
     const size_t W = (size_t)width, n = (size_t)req->n;
-    const size_t rgba_bytes = 4 * W * n;
-    const size_t host_pitch = req->waterfall ? 4 * n : 4 * (size_t)image_width;   // bytes between rows of the caller's image
+    const size_t image_bytes = im.px * W * n;
     const sphost::ReplyRecord rec{(size_t)req->lut_len, W};   // the small outputs, side by side on the device
     int rc = SP_OK;
     sp_reply d = *reply;
-    if (!device_out) {
-        rc = ctx->out_rgba.reserve(rgba_bytes + 16);
-        if (!rc) rc = ctx->render_small.reserve(rec.bytes() + 16);
+    Picture pic{im.kind, im.host};
+    if (!im.device_out) {
+        rc = im.dev->reserve(image_bytes + 16);
+        if (!rc) rc = device_reply_record(ctx->render_small, rec, &d);
         if (!rc) rc = ctx->host_small.reserve(rec.bytes() + 16);
-        if (rc) return fail(ctx, rc, "sp_render: out of memory");
-        d = rec.view(ctx->render_small.p);
-        d.rgba = reply->rgba ? (uint8_t *)ctx->out_rgba.p : nullptr;
+        if (rc) return fail(ctx, rc, std::string(who) + ": out of memory");
+        pic.image = im.host ? (uint8_t *)im.dev->p : nullptr;
     }
 
     const RequestShape shape = request_shape(plan, nbytes, width);   // once, for the upload plan and every chunk's launch
     // (device_out: no image crosses the link, so the samples are the longer transfer whatever the image weighs)
     // (a peak request with M >= 2 sub-frames per column reads more than half of the capture: the contiguous upload, chunked by columns)
-    HostFeed feed{"sp_render", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames,
-                  device_out || reply->rgba, device_out ? 0 : rgba_bytes, !device_out, nullptr};
+    HostFeed feed{who, bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames,
+                  im.device_out || im.host, im.device_out ? 0 : image_bytes, !im.device_out, nullptr};
+    const auto copies_failed = [&](hipError_t e) { return hip_fail(ctx, e, (std::string(who) + " copies").c_str()); };
     // (nothing to clear: the kernels overwrite every histogram count, both range values and every gauge byte)
     auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
-        return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src);
+        return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, pic, src);
     };
     rc = stream_chunks(ctx, plan->fmt, feed, launch, [&](int k, int32_t x0, int32_t x1) {
         hipError_t e = hipSuccess;
-        if (device_out) return (int)SP_OK;
+        if (im.device_out) return (int)SP_OK;
         if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
         if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
-        if (e == hipSuccess && reply->rgba && x1 > x0)
-            e = download_band(reply->rgba, host_pitch, (const uint8_t *)ctx->out_rgba.p, width, n, req->waterfall, x0, x1, feed.out_s);
-        return e == hipSuccess ? (int)SP_OK : hip_fail(ctx, e, "sp_render copies");
+        if (e == hipSuccess && im.host && x1 > x0)
+            e = download_band(im.host, im.host_pitch, pic.image, width, n, req->waterfall, x0, x1, feed.out_s, im.px);
+        return e == hipSuccess ? (int)SP_OK : copies_failed(e);
     });
-    if (rc || device_out) return rc;
+    if (rc || im.device_out) return rc;
     // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
     // (separate copies into pageable memory cost more than the kernels of a small request)
     hipError_t e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
@@ -1609,10 +1638,46 @@ static int render_core(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
     if (e != hipSuccess) {
         drain_streams(ctx);
-        return hip_fail(ctx, e, "sp_render copies");
+        return copies_failed(e);
     }
     rec.unpack_side(ctx->host_small.p, *reply);
     rec.unpack_gauges(ctx->host_small.p, *reply);
+    return SP_OK;
+}
+
+// sp_render / sp_render_strip / sp_plan_execute_from_host.  `image_width` is the width in frames of the image reply->rgba points into
+// (the strip's own width for sp_render); it only matters for the spectrogram layout, whose rows are image_width pixels apart.
+static int render_rgba(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply, int32_t image_width,
+                       bool device_out)
+{
+    const HostImage im{reply->rgba, 4, 4 * (size_t)(plan->req.waterfall ? plan->req.n : image_width), &plan->ctx->out_rgba, Picture::kRgba, device_out};
+    return render_image(plan, "sp_render", bytes, nbytes, width, reply, im);
+}
+
+// sp_render_density / sp_render_traces: a host-fed request without an image, whose one small result accumulates on the device over the
+// chunks.  The samples are the only transfer and nothing follows a chunk (stream_chunks as sp_plan_execute_from_host feeds it).  A kind
+// brings clear() (its result back at its initial value), launch (stream_chunks') and tail(cleared, e): what it queues on the context's
+// stream once every chunk has been launched - `cleared`: clear() has run - with a failed copy's error left in e.  The call returns
+// when the stream has ended.
+template <typename Clear, typename Launch, typename Tail>
+static int render_result(sp_context *ctx, const spfmt::Format &f, HostFeed &feed, Clear &&clear, Launch &&launch, Tail &&tail)
+{
+    bool cleared = false;
+    // (the clear belongs to the first chunk's launch: queued earlier, it would make the stream look busy to the streamer)
+    auto chunk = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
+        if (first) {
+            const int r = clear();
+            if (r) return r;
+            cleared = true;
+        }
+        return launch(x0, x1, first, last, d_in, src);
+    };
+    int rc = stream_chunks(ctx, f, feed, chunk, [](int, int32_t, int32_t) { return (int)SP_OK; });   // (nothing follows a chunk)
+    hipError_t e = hipSuccess;
+    if (!rc) rc = tail(cleared, e);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);   // (synchronous; the samples' stream has ended before this one)
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, (std::string(feed.who) + " copies").c_str());
     return SP_OK;
 }
 
@@ -1641,31 +1706,42 @@ static int check_host_capture(sp_context *ctx, const spfmt::Format &f, const uin
     return SP_OK;
 }
 
-static int render_host(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply,
-                       int32_t image_width)
+// How every host entry point that takes a request begins: the request's validation, the kind's own refusals of the request, the
+// capture's, the kind's own refusals of the capture, then the context's cached plan.
+template <typename CheckRequest, typename CheckCapture>
+static int host_request(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, CheckRequest &&check_request,
+                        CheckCapture &&check_kind_capture, sp_plan **plan)
+{
+    int rc = validate_request(ctx, req);
+    if (!rc) rc = check_request();
+    if (!rc) rc = check_host_capture(ctx, spfmt::describe(req->format), bytes, nbytes, width);
+    if (!rc) rc = check_kind_capture();
+    return rc ? rc : cached_plan_for(ctx, req, plan);
+}
+static int no_check() { return SP_OK; }
+
+extern "C" int sp_render_strip(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width,
+                               const sp_reply *reply, int32_t image_width)
 {
     if (!ctx || !reply) return SP_ERR_INVALID_ARG;
-    int rc = validate_request(ctx, req);
-    if (rc) return rc;
-    if (width >= 0 && image_width < width) return fail(ctx, SP_ERR_INVALID_ARG, "image_width < width");   // (a width < 0 is refused first)
-    rc = check_host_capture(ctx, spfmt::describe(req->format), bytes, nbytes, width);
-    if (rc) return rc;
     sp_plan *plan = nullptr;
-    rc = cached_plan_for(ctx, req, &plan);
-    if (rc) return rc;
-    return render_core(plan, bytes, nbytes, width, reply, image_width, false);
+    const auto check = [&] {   // (a width < 0 is refused first)
+        return width >= 0 && image_width < width ? fail(ctx, SP_ERR_INVALID_ARG, "image_width < width") : (int)SP_OK;
+    };
+    const int rc = host_request(ctx, req, bytes, nbytes, width, check, no_check, &plan);
+    return rc ? rc : render_rgba(plan, bytes, nbytes, width, reply, image_width, false);
 }
 
 extern "C" int sp_render(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *reply)
 {
-    return render_host(ctx, req, bytes, nbytes, width, reply, width);
+    return sp_render_strip(ctx, req, bytes, nbytes, width, reply, width);
 }
 
 extern "C" int sp_plan_execute_from_host(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32_t width, const sp_reply *d_reply)
 {
     if (!plan || !d_reply) return SP_ERR_INVALID_ARG;
     const int rc = check_host_capture(plan->ctx, plan->fmt, bytes, nbytes, width);
-    return rc ? rc : render_core(plan, bytes, nbytes, width, d_reply, width, true);
+    return rc ? rc : render_rgba(plan, bytes, nbytes, width, d_reply, width, true);
 }
 
 extern "C" int sp_context_last_upload_bytes(const sp_context *ctx, size_t *nbytes)
@@ -1699,8 +1775,9 @@ extern "C" const char *sp_plan_index_kernel_name_for(const sp_plan *plan, size_t
 }
 
 // what the render_extract path needs before its first launch: the temporary RGBA image and the plan's identity LUT
-static int index_prepare(sp_plan *plan, int32_t width)
+static int index_prepare(sp_plan *plan, Picture::Kind kind, int32_t width)
 {
+    if (kind != Picture::kIndexExtract || width <= 0) return SP_OK;
     sp_context *ctx = plan->ctx;
     int rc = ctx->index_rgba.reserve(4 * (size_t)width * (size_t)plan->req.n + 16);
     if (rc) return fail(ctx, rc, "index workspace: out of device memory");
@@ -1744,17 +1821,13 @@ extern "C" int sp_plan_execute_index(sp_plan *plan, const void *d_bytes, size_t 
     int rc = check_index(ctx, plan->req.lut_len, d_reply);
     if (rc) return rc;
     const RequestShape shape = request_shape(plan, nbytes, width);
-    const IndexTarget ix{d_index, index_frames(plan, shape.g)};
-    if (!ix.frames && d_index && width > 0) {
-        rc = check_capture(ctx, plan->fmt, plan->req.n, d_bytes, nbytes, width, d_reply, "");   // (before anything is allocated)
-        if (rc) return rc;
-        SP_HIP(ctx, hipSetDevice(ctx->device));
-        rc = refuse_capture(ctx, ctx->stream, "sp_plan_execute_index cannot be captured into a hipGraph (every launch carries its request's number)");
-        if (rc) return rc;
-        rc = index_prepare(plan, width);
+    const Picture pic = index_picture(d_index, index_frames(plan, shape.g));
+    if (pic.kind == Picture::kIndexExtract && width > 0) {
+        rc = device_operands(ctx, plan->fmt, plan->req.n, d_bytes, nbytes, width, d_reply, "sp_plan_execute_index");   // (before anything is allocated)
         if (rc) return rc;
     }
-    return plan_execute_range(plan, d_bytes, shape, 0, width < 0 ? 0 : width, true, true, d_reply, nullptr, &ix);
+    rc = index_prepare(plan, pic.kind, width);
+    return rc ? rc : plan_execute_range(plan, d_bytes, shape, 0, width < 0 ? 0 : width, true, true, d_reply, pic);
 }
 
 // sp_render with an indexed image: a request kind of stream_chunks whose image travels back at 1 byte per pixel.
@@ -1763,56 +1836,14 @@ extern "C" int sp_render_index(sp_context *ctx, const sp_request *req, const uin
 {
     if (!ctx) return no_object_status();
     if (!reply) return SP_ERR_INVALID_ARG;
-    int rc = validate_request(ctx, req);
-    if (rc) return rc;
-    rc = check_index(ctx, req->lut_len, reply);
-    if (rc) return rc;
-    rc = check_host_capture(ctx, spfmt::describe(req->format), bytes, nbytes, width);
-    if (rc) return rc;
     sp_plan *plan = nullptr;
-    rc = cached_plan_for(ctx, req, &plan);
+    int rc = host_request(ctx, req, bytes, nbytes, width, [&] { return check_index(ctx, req->lut_len, reply); }, no_check, &plan);
     if (rc) return rc;
-
-    hipStream_t s = ctx->stream;
-    const size_t W = (size_t)width, n = (size_t)req->n;
-    const size_t index_bytes = W * n;
-    const sphost::ReplyRecord rec{(size_t)req->lut_len, W};
-    rc = ctx->out_rgba.reserve(index_bytes + 16);   // (the device image of a host-fed request, here 1 byte per pixel)
-    if (!rc) rc = ctx->render_small.reserve(rec.bytes() + 16);
-    if (!rc) rc = ctx->host_small.reserve(rec.bytes() + 16);
-    if (rc) return fail(ctx, rc, "sp_render_index: out of memory");
-    sp_reply d = rec.view(ctx->render_small.p);
-    d.rgba = nullptr;
-    const RequestShape shape = request_shape(plan, nbytes, width);
-    const IndexTarget ix{index ? (uint8_t *)ctx->out_rgba.p : nullptr, index_frames(plan, shape.g)};
-    if (!ix.frames && ix.d_index && width > 0) {
-        rc = index_prepare(plan, width);
-        if (rc) return rc;
-    }
-    HostFeed feed{"sp_render_index", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames, index != nullptr,
-                  index ? index_bytes : 0, true, nullptr};
-    auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
-        return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src, &ix);
-    };
-    rc = stream_chunks(ctx, plan->fmt, feed, launch, [&](int k, int32_t x0, int32_t x1) {
-        hipError_t e = hipSuccess;
-        if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
-        if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
-        if (e == hipSuccess && index && x1 > x0)
-            e = download_band(index, req->waterfall ? n : W, ix.d_index, width, n, req->waterfall, x0, x1, feed.out_s, 1);
-        return e == hipSuccess ? (int)SP_OK : hip_fail(ctx, e, "sp_render_index copies");
-    });
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
-    if (e != hipSuccess) {
-        drain_streams(ctx);
-        return hip_fail(ctx, e, "sp_render_index copies");
-    }
-    rec.unpack_side(ctx->host_small.p, *reply);
-    rec.unpack_gauges(ctx->host_small.p, *reply);
-    return SP_OK;
+    const bool frames = index_frames(plan, spgeo::geometry(plan->fmt, req->n, nbytes, width));
+    // (the device image of a host-fed request, here 1 byte per pixel)
+    const HostImage im{index, 1, req->waterfall ? (size_t)req->n : (size_t)width, &ctx->out_rgba, index_picture(index, frames).kind, false};
+    rc = index_prepare(plan, im.kind, width);
+    return rc ? rc : render_image(plan, "sp_render_index", bytes, nbytes, width, reply, im);
 }
 
 extern "C" int sp_index_to_rgba(sp_context *ctx, const uint8_t *d_index, size_t pixels, const uint8_t *lut_rgb, int32_t lut_len, uint8_t *d_rgba)
@@ -1879,17 +1910,15 @@ extern "C" int sp_density_from_index(sp_context *ctx, const uint8_t *d_index, in
 }
 
 // the index image and the reply record of a density request on device operands: both the context's, ordered on its stream
-static int density_prepare(sp_plan *plan, int32_t width, sp_reply *d, IndexTarget *ix, const spgeo::Geometry &g)
+static int density_prepare(sp_plan *plan, int32_t width, sp_reply *d, Picture *pic, const spgeo::Geometry &g)
 {
     sp_context *ctx = plan->ctx;
     const sphost::ReplyRecord rec{(size_t)plan->req.lut_len, (size_t)width};
     int rc = ctx->density_index.reserve((size_t)width * (size_t)plan->req.n + 16);
-    if (!rc) rc = ctx->density_reply.reserve(rec.bytes() + 16);
+    if (!rc) rc = device_reply_record(ctx->density_reply, rec, d);
     if (rc) return fail(ctx, rc, "density workspace: out of device memory");
-    *d = rec.view(ctx->density_reply.p);
-    d->rgba = nullptr;
-    *ix = IndexTarget{(uint8_t *)ctx->density_index.p, index_frames(plan, g)};
-    return !ix->frames && width > 0 ? index_prepare(plan, width) : (int)SP_OK;
+    *pic = index_picture((uint8_t *)ctx->density_index.p, index_frames(plan, g));
+    return index_prepare(plan, pic->kind, width);
 }
 
 extern "C" int sp_plan_execute_density(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, uint32_t *d_density, int32_t accumulate)
@@ -1898,76 +1927,62 @@ extern "C" int sp_plan_execute_density(sp_plan *plan, const void *d_bytes, size_
     sp_context *ctx = plan->ctx;
     const int n = plan->req.n, lut_len = plan->req.lut_len;
     int rc = check_density(ctx, lut_len, d_density);
+    if (!rc) rc = device_operands(ctx, plan->fmt, n, d_bytes, nbytes, width, nullptr, "sp_plan_execute_density");   // (before anything is allocated)
     if (rc) return rc;
-    rc = check_capture(ctx, plan->fmt, n, d_bytes, nbytes, width, nullptr, "");   // (before anything is allocated)
-    if (rc) return rc;
-    SP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    rc = refuse_capture(ctx, s, "sp_plan_execute_density cannot be captured into a hipGraph (every launch carries its request's number)");
-    if (rc) return rc;
     const RequestShape shape = request_shape(plan, nbytes, width);
     sp_reply d{};
-    IndexTarget ix{};
-    rc = density_prepare(plan, width, &d, &ix, shape.g);
+    Picture pic{};
+    rc = density_prepare(plan, width, &d, &pic, shape.g);
     if (rc) return rc;
-    rc = plan_execute_range(plan, d_bytes, shape, 0, width, true, true, &d, nullptr, &ix);
+    rc = plan_execute_range(plan, d_bytes, shape, 0, width, true, true, &d, pic);
     if (rc) return rc;
     if (!accumulate) SP_HIP(ctx, hipMemsetAsync(d_density, 0, (size_t)n * (size_t)lut_len * sizeof(uint32_t), s));
-    rc = density_count(ctx, ix.d_index, n, width, plan->req.waterfall != 0, lut_len, 0, width, d_density);
+    rc = density_count(ctx, pic.image, n, width, plan->req.waterfall != 0, lut_len, 0, width, d_density);
     if (rc) return rc;
     if (ctx->timing && width > 0) SP_HIP(ctx, hipEventRecord(ctx->ev1, s));   // (timing: the render's event pair now ends behind the count)
     return SP_OK;
 }
 
-// A request kind of stream_chunks, fed as sp_render_traces is (the samples are the only transfer, nothing follows a chunk): every
-// chunk's launch renders its frames into the index image on the device and counts them; the counts come back in one copy.
+// A request kind of render_result: every chunk's launch renders its frames into the index image on the device and counts them; the
+// counts come back in one copy.
 extern "C" int sp_render_density(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, uint32_t *density)
 {
     if (!ctx) return no_object_status();
-    int rc = validate_request(ctx, req);
-    if (rc) return rc;
-    rc = check_density(ctx, req->lut_len, density);
-    if (rc) return rc;
-    const spfmt::Format f = spfmt::describe(req->format);
-    rc = check_host_capture(ctx, f, bytes, nbytes, width);
-    if (!rc) rc = check_capture(ctx, f, req->n, bytes, nbytes, width, nullptr, "");
-    if (rc) return rc;
     sp_plan *plan = nullptr;
-    rc = cached_plan_for(ctx, req, &plan);
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width, [&] { return check_density(ctx, req->lut_len, density); },
+        [&] { return check_capture(ctx, spfmt::describe(req->format), req->n, bytes, nbytes, width, nullptr, ""); }, &plan);
     if (rc) return rc;
 
     hipStream_t s = ctx->stream;
     const int n = req->n, lut_len = req->lut_len;
-    const bool waterfall = req->waterfall != 0;
     const size_t count_bytes = (size_t)n * (size_t)lut_len * sizeof(uint32_t);
     rc = ctx->render_small.reserve(count_bytes + 16);
     if (rc) return fail(ctx, rc, "sp_render_density: out of memory");
     uint32_t *const d_density = (uint32_t *)ctx->render_small.p;
     const RequestShape shape = request_shape(plan, nbytes, width);
     sp_reply d{};
-    IndexTarget ix{};
-    rc = density_prepare(plan, width, &d, &ix, shape.g);
+    Picture pic{};
+    rc = density_prepare(plan, width, &d, &pic, shape.g);
     if (rc) return rc;
     HostFeed feed{"sp_render_density", bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames, true, 0, false, nullptr};
-    bool cleared = false;
-    // (the clear belongs to the first chunk's launch: queued earlier, it would make the stream look busy to the streamer)
-    auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
-        if (first) {
-            const hipError_t e = hipMemsetAsync(d_density, 0, count_bytes, s);
-            if (e != hipSuccess) return hip_fail(ctx, e, "sp_render_density clear");
-            cleared = true;
-        }
-        const int r = plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, src, &ix);
-        return r ? r : density_count(ctx, ix.d_index, n, width, waterfall, lut_len, x0, x1, d_density);
-    };
-    rc = stream_chunks(ctx, f, feed, launch, [](int, int32_t, int32_t) { return (int)SP_OK; });   // (nothing follows a chunk)
-    hipError_t e = hipSuccess;
-    if (!rc && !cleared) e = hipMemsetAsync(d_density, 0, count_bytes, s);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(density, d_density, count_bytes, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // (synchronous; the samples' stream has ended before this one)
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, "sp_render_density copies");
-    return SP_OK;
+    const auto zero = [&] { return hipMemsetAsync(d_density, 0, count_bytes, s); };
+    return render_result(
+        ctx, plan->fmt, feed,
+        [&] {
+            const hipError_t e = zero();
+            return e == hipSuccess ? (int)SP_OK : hip_fail(ctx, e, "sp_render_density clear");
+        },
+        [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
+            const int r = plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, pic, src);
+            return r ? r : density_count(ctx, pic.image, n, width, req->waterfall != 0, lut_len, x0, x1, d_density);
+        },
+        [&](bool cleared, hipError_t &e) {
+            if (!cleared) e = zero();   // (no chunk ran)
+            if (e == hipSuccess) e = hipMemcpyAsync(density, d_density, count_bytes, hipMemcpyDeviceToHost, s);
+            return (int)SP_OK;
+        });
 }
 
 // (tests) k_density_count's decomposition from the functions its launch calls: six words, then every workgroup's rectangle.
@@ -2099,21 +2114,16 @@ extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t
     return SP_OK;
 }
 
-// The capture comes from host memory as for a request whose image does not cross the link (stream_chunks as
-// sp_plan_execute_from_host feeds it: the samples are the only transfer, nothing follows a chunk) - a packed sparse upload where
-// stride > n, chunks of frames where the request is large - and the extremes accumulate in the workspace over the chunks.
+// A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
+// extremes accumulate in the workspace over the chunks.
 extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *trace_min,
                                 double *trace_max)
 {
     if (!ctx) return SP_ERR_INVALID_ARG;
-    int rc = validate_request(ctx, req);
-    if (rc) return rc;
-    const spfmt::Format f = spfmt::describe(req->format);
-    rc = check_host_capture(ctx, f, bytes, nbytes, width);
-    if (!rc) rc = check_traces(ctx, req->detector, f, req->n, bytes, nbytes, width);
-    if (rc) return rc;
     sp_plan *plan = nullptr;
-    rc = cached_plan_for(ctx, req, &plan);
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width, no_check,
+        [&] { return check_traces(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
     if (rc) return rc;
 
     const size_t n = (size_t)req->n;
@@ -2121,27 +2131,16 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
     rc = ctx->render_small.reserve(2 * n * sizeof(double) + 16);
     if (rc) return fail(ctx, rc, "sp_render_traces: out of memory");
     double *const d_out = (double *)ctx->render_small.p;
-    HostFeed feed{"sp_render_traces", bytes, spgeo::geometry(f, req->n, nbytes, width), 1, plan_traces_frames(plan), true, 0, false, nullptr};
-    // (the clear belongs to the first chunk's launch: queued earlier, it would make the stream look busy to the streamer)
-    auto launch = [&](int32_t x0, int32_t x1, bool first, bool, const uint8_t *d_in, const PackedSource *src) {
-        const int r = first ? traces_clear(plan) : SP_OK;
-        return r ? r : traces_range(plan, d_in, feed.g, x0, x1, src);
-    };
-    rc = stream_chunks(ctx, f, feed, launch, [](int, int32_t, int32_t) { return (int)SP_OK; });   // (nothing follows a chunk)
-    hipError_t e = hipSuccess;
-    if (!rc) rc = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
-    if (!rc && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (!rc && e == hipSuccess && trace_max) e = hipMemcpyAsync(trace_max, d_out + n, n * sizeof(double), hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // (synchronous; the samples' stream has ended before this one)
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess) return hip_fail(ctx, e != hipSuccess ? e : es, "sp_render_traces copies");
-    return SP_OK;
-}
-
-extern "C" int sp_render_strip(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width,
-                               const sp_reply *reply, int32_t image_width)
-{
-    return render_host(ctx, req, bytes, nbytes, width, reply, image_width);
+    HostFeed feed{"sp_render_traces", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_traces_frames(plan), true, 0, false, nullptr};
+    return render_result(
+        ctx, plan->fmt, feed, [&] { return traces_clear(plan); },
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) { return traces_range(plan, d_in, feed.g, x0, x1, src); },
+        [&](bool, hipError_t &e) {
+            const int r = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
+            if (!r && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (!r && e == hipSuccess && trace_max) e = hipMemcpyAsync(trace_max, d_out + n, n * sizeof(double), hipMemcpyDeviceToHost, s);
+            return r;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name
@@ -2330,7 +2329,7 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
     if (rc) return rc;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    rc = refuse_capture(ctx, s, "sp_plan_execute_batch cannot be captured into a hipGraph");
+    rc = refuse_capture(ctx, s, "sp_plan_execute_batch", "");
     if (rc) return rc;
     std::vector<size_t> nb((size_t)count);
     std::vector<int32_t> wd((size_t)count);
@@ -2344,7 +2343,7 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
         // a plan outside k_frames: the items one by one, as sp_plan_execute renders them
         for (int i = 0; i < count; i++) {
             rc = plan_execute_range(plan, items[i].bytes, request_shape(plan, items[i].nbytes, items[i].width), 0, items[i].width, true, true,
-                                    &items[i].reply);
+                                    &items[i].reply, Picture{Picture::kRgba, items[i].reply.rgba});
             if (rc) return rc;
         }
         return SP_OK;
@@ -2448,7 +2447,7 @@ extern "C" int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_
     if (plan_kernel(plan) != kKernelFrames) {
         // a plan outside k_frames: item by item through sp_render's path
         for (int i = 0; i < count; i++) {
-            rc = render_core(plan, (const uint8_t *)items[i].bytes, items[i].nbytes, items[i].width, &items[i].reply, items[i].width, false);
+            rc = render_rgba(plan, (const uint8_t *)items[i].bytes, items[i].nbytes, items[i].width, &items[i].reply, items[i].width, false);
             if (rc) return rc;
             uploaded += ctx->last_upload_bytes;
         }

@@ -847,26 +847,17 @@ napi_value RenderBatch(napi_env env, napi_callback_info info)
     return queue_async(env, b, {argv[3], argv[0], argv[2]}, "spectroplot_hip.renderBatch", "could not queue the batch");
 }
 
-// ---- traces: renderTraces(handle, req, cb) / renderTracesSync(handle, req) ---------------------------------------------------------
-// req: {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} -> {trace_min, trace_max}, two Float64Array(n) in image
-// row order (sp_render_traces).  Every value is read with its status checked, as for a batch.
-struct TracesJob;
-void run_traces(TracesJob *t);
-napi_value traces_result(napi_env env, TracesJob *t);
-
-struct TracesJob : JobBase {
-    sp_request req{};
-    std::vector<double> window;
-    uint8_t lut[6] = {0, 0, 0, 255, 255, 255};   // (a trace has no colours; the plan wants a map)
-    const uint8_t *bytes = nullptr;
-    size_t nbytes = 0;
-    int32_t width = 0;
-    std::vector<double> out;   // trace_min, then trace_max
-    void run() override { run_traces(this); }
-    napi_value result(napi_env env) override { return traces_result(env, this); }
+// ---- checked requests: traces, indexed images, persistence spectrum ----------------------------------------------------------------------
+// Every value of such a request is read into a variable of its own with its status checked, as for a batch: a request that cannot be
+// read throws and never renders.  What differs between the kinds: the names in their texts, and whether the request carries a picture
+// (`waterfall`, `detector`, `lut`); one without gets the sample detector and a 2-entry map (the plan wants one).
+struct CheckedKind {
+    const char *who;   // in "<who> takes a context handle, not a group"
+    bool picture;
+    const char *sync_usage, *async_usage, *resource, *could_not_queue;
 };
 
-bool parse_traces(napi_env env, napi_value handle, napi_value req, TracesJob *t)
+bool parse_checked(napi_env env, napi_value handle, napi_value req, Job *t, const CheckedKind &kind)
 {
     void *p = nullptr;
     if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
@@ -875,124 +866,15 @@ bool parse_traces(napi_env env, napi_value handle, napi_value req, TracesJob *t)
     }
     t->owner = (Ctx *)p;
     if (t->owner->closed || !t->owner->c) {
-        napi_throw_error(env, nullptr, t->owner->g ? "renderTraces takes a context handle, not a group" : "context has been destroyed");
-        return false;
-    }
-    if (!checked_int32(env, req, "format", &t->req.format) || !checked_int32(env, req, "n", &t->req.n)) return false;
-    if (!checked_int32(env, req, "width", &t->width)) return false;
-    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode)) return false;
-    if (!checked_number(env, req, "block_norm", &t->req.block_norm) || !checked_number(env, req, "gain", &t->req.gain)) return false;
-    if (!checked_number(env, req, "range", &t->req.range)) return false;
-    if (t->req.n < 1 || t->width < 0) {
-        napi_throw_range_error(env, nullptr, "n must be positive and width must not be negative");
-        return false;
-    }
-    napi_value v, ab;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void *data = nullptr;
-    if (napi_get_named_property(env, req, "windowc", &v) != napi_ok
-        || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_float64_array) {
-        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
-        return false;
-    }
-    if (len < (size_t)t->req.n) {
-        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
-        return false;
-    }
-    t->window.assign((const double *)data, (const double *)data + len);
-    if (napi_get_named_property(env, req, "buffer", &v) != napi_ok || napi_get_arraybuffer_info(env, v, &data, &len) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
-        return false;
-    }
-    t->bytes = (const uint8_t *)data;
-    t->nbytes = len;
-    t->req.detector = SP_DETECTOR_SAMPLE;
-    t->req.lut_len = 2;
-    t->req.windowc = t->window.data();
-    t->req.lut_rgb = t->lut;
-    return true;
-}
-
-void run_traces(TracesJob *t)
-{
-    const size_t n = (size_t)t->req.n;
-    t->out.assign(2 * n, 0.0);
-    t->status = sp_render_traces(t->owner->c, &t->req, t->bytes, t->nbytes, t->width, t->out.data(), t->out.data() + n);
-    if (t->status != SP_OK) t->error = sp_last_error(t->owner->c);
-}
-
-napi_value traces_result(napi_env env, TracesJob *t)
-{
-    const size_t n = (size_t)t->req.n;
-    napi_value out, ab, ta;
-    void *data = nullptr;
-    if (napi_create_object(env, &out) != napi_ok || napi_create_arraybuffer(env, 2 * n * 8, &data, &ab) != napi_ok) return nullptr;
-    memcpy(data, t->out.data(), 2 * n * 8);
-    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "trace_min", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_typedarray(env, napi_float64_array, n, ab, n * 8, &ta) != napi_ok || napi_set_named_property(env, out, "trace_max", ta) != napi_ok)
-        return nullptr;
-    return out;
-}
-
-napi_value RenderTracesSync(napi_env env, napi_callback_info info)
-{
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 2) {
-        napi_throw_type_error(env, nullptr, "renderTracesSync(handle, request)");
-        return nullptr;
-    }
-    TracesJob *t = new TracesJob;
-    if (!parse_traces(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
-    return run_sync(env, t);
-}
-
-napi_value RenderTraces(napi_env env, napi_callback_info info)
-{
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    napi_valuetype ty = napi_undefined;
-    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
-        napi_throw_type_error(env, nullptr, "renderTraces(handle, request, callback)");
-        return nullptr;
-    }
-    TracesJob *t = new TracesJob;
-    if (!parse_traces(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
-    napi_value buf = nullptr;   // (left null, it fails the queueing)
-    napi_get_named_property(env, argv[1], "buffer", &buf);
-    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderTraces", "could not queue the traces request");
-}
-
-// ---- indexed images: renderIndex(handle, req, cb) / renderIndexSync(handle, req) -------------------------------------------------------
-// req as for render plus `detector` -> render's reply with `index` - a Uint8Array(width * n), one colour-index byte per pixel in the RGBA
-// image's pixel order, in a page-locked block of the reply pool - in place of `rgba` (sp_render_index).  Every value of the request is
-// read into a variable of its own with its status checked: a request that cannot be read throws and never renders.
-struct IndexJob : Job {
-    void run() override;
-    napi_value result(napi_env env) override;
-};
-
-bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t, const char *who = "renderIndex")
-{
-    void *p = nullptr;
-    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
-        napi_throw_type_error(env, nullptr, "context handle expected");
-        return false;
-    }
-    t->owner = (Ctx *)p;
-    if (t->owner->closed || !t->owner->c) {
-        napi_throw_error(env, nullptr, t->owner->g ? (std::string(who) + " takes a context handle, not a group").c_str() : "context has been destroyed");
+        napi_throw_error(env, nullptr, t->owner->g ? (std::string(kind.who) + " takes a context handle, not a group").c_str() : "context has been destroyed");
         return false;
     }
     t->ctx = t->owner->c;
     if (!checked_int32(env, req, "format", &t->req.format) || !checked_int32(env, req, "n", &t->req.n)) return false;
     if (!checked_int32(env, req, "width", &t->width)) return false;
-    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode) || !checked_bool(env, req, "waterfall", &t->req.waterfall)) return false;
-    if (!read_detector(env, req, &t->req.detector)) return false;
+    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode)) return false;
+    t->req.detector = SP_DETECTOR_SAMPLE;
+    if (kind.picture && (!checked_bool(env, req, "waterfall", &t->req.waterfall) || !read_detector(env, req, &t->req.detector))) return false;
     if (!checked_number(env, req, "block_norm", &t->req.block_norm) || !checked_number(env, req, "gain", &t->req.gain)) return false;
     if (!checked_number(env, req, "range", &t->req.range)) return false;
     if (t->req.n < 1 || t->width < 0) {
@@ -1013,24 +895,109 @@ bool parse_index(napi_env env, napi_value handle, napi_value req, IndexJob *t, c
         return false;
     }
     t->window.assign((const double *)data_win, (const double *)data_win + len_win);
-    if (napi_get_named_property(env, req, "lut", &v_lut) != napi_ok
-        || napi_get_typedarray_info(env, v_lut, &tt_lut, &len_lut, &data_lut, &ab_lut, &off_lut) != napi_ok
-        || (tt_lut != napi_uint8_array && tt_lut != napi_uint8_clamped_array) || len_lut < 3) {
-        napi_throw_type_error(env, nullptr, "lut must be a Uint8Array of r, g, b triples");
-        return false;
+    t->lut = {0, 0, 0, 255, 255, 255};   // (a request without a picture has no colours; the plan wants a map)
+    if (kind.picture) {
+        if (napi_get_named_property(env, req, "lut", &v_lut) != napi_ok
+            || napi_get_typedarray_info(env, v_lut, &tt_lut, &len_lut, &data_lut, &ab_lut, &off_lut) != napi_ok
+            || (tt_lut != napi_uint8_array && tt_lut != napi_uint8_clamped_array) || len_lut < 3) {
+            napi_throw_type_error(env, nullptr, "lut must be a Uint8Array of r, g, b triples");
+            return false;
+        }
+        t->lut.assign((const uint8_t *)data_lut, (const uint8_t *)data_lut + len_lut);
     }
-    t->lut.assign((const uint8_t *)data_lut, (const uint8_t *)data_lut + len_lut);
     if (napi_get_named_property(env, req, "buffer", &v_buf) != napi_ok || napi_get_arraybuffer_info(env, v_buf, &data_buf, &len_buf) != napi_ok) {
         napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
         return false;
     }
     t->bytes = (const uint8_t *)data_buf;
     t->nbytes = len_buf;
-    t->req.lut_len = (int32_t)(len_lut / 3);
+    t->req.lut_len = (int32_t)(t->lut.size() / 3);
     t->req.windowc = t->window.data();
     t->req.lut_rgb = t->lut.data();
     return true;
 }
+
+// The entry pair of a checked kind whose job is a J: <kind>Sync(handle, req) and <kind>(handle, req, cb).
+template <typename J>
+napi_value checked_sync(napi_env env, napi_callback_info info, const CheckedKind &kind)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 2) {
+        napi_throw_type_error(env, nullptr, kind.sync_usage);
+        return nullptr;
+    }
+    J *t = new J;
+    if (!parse_checked(env, argv[0], argv[1], t, kind)) { free_job(env, t); return nullptr; }
+    return run_sync(env, t);
+}
+
+template <typename J>
+napi_value checked_async(napi_env env, napi_callback_info info, const CheckedKind &kind)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    napi_valuetype ty = napi_undefined;
+    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
+        napi_throw_type_error(env, nullptr, kind.async_usage);
+        return nullptr;
+    }
+    J *t = new J;
+    if (!parse_checked(env, argv[0], argv[1], t, kind)) { free_job(env, t); return nullptr; }
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, t, {argv[2], argv[0], buf}, kind.resource, kind.could_not_queue);
+}
+
+// ---- traces: renderTraces(handle, req, cb) / renderTracesSync(handle, req) ---------------------------------------------------------
+// req: {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} -> {trace_min, trace_max}, two Float64Array(n) in image
+// row order (sp_render_traces).
+const CheckedKind kTraces{"renderTraces", false, "renderTracesSync(handle, request)", "renderTraces(handle, request, callback)",
+                          "spectroplot_hip.renderTraces", "could not queue the traces request"};
+
+struct TracesJob : Job {
+    std::vector<double> out;   // trace_min, then trace_max
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+void TracesJob::run()
+{
+    const size_t n = (size_t)req.n;
+    out.assign(2 * n, 0.0);
+    status = sp_render_traces(ctx, &req, bytes, nbytes, width, out.data(), out.data() + n);
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value TracesJob::result(napi_env env)
+{
+    const size_t n = (size_t)req.n;
+    napi_value obj, ab, ta;
+    void *data = nullptr;
+    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, 2 * n * 8, &data, &ab) != napi_ok) return nullptr;
+    memcpy(data, out.data(), 2 * n * 8);
+    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "trace_min", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_typedarray(env, napi_float64_array, n, ab, n * 8, &ta) != napi_ok || napi_set_named_property(env, obj, "trace_max", ta) != napi_ok)
+        return nullptr;
+    return obj;
+}
+
+napi_value RenderTracesSync(napi_env env, napi_callback_info info) { return checked_sync<TracesJob>(env, info, kTraces); }
+napi_value RenderTraces(napi_env env, napi_callback_info info) { return checked_async<TracesJob>(env, info, kTraces); }
+
+// ---- indexed images: renderIndex(handle, req, cb) / renderIndexSync(handle, req) -------------------------------------------------------
+// req as for render plus `detector` -> render's reply with `index` - a Uint8Array(width * n), one colour-index byte per pixel in the RGBA
+// image's pixel order, in a page-locked block of the reply pool - in place of `rgba` (sp_render_index).
+const CheckedKind kIndex{"renderIndex", true, "renderIndexSync(handle, request)", "renderIndex(handle, request, callback)",
+                         "spectroplot_hip.renderIndex", "could not queue the indexed request"};
+
+struct IndexJob : Job {
+    void run() override;
+    napi_value result(napi_env env) override;
+};
 
 void IndexJob::run()
 {
@@ -1090,41 +1057,15 @@ napi_value IndexJob::result(napi_env env)
     return out;
 }
 
-napi_value RenderIndexSync(napi_env env, napi_callback_info info)
-{
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 2) {
-        napi_throw_type_error(env, nullptr, "renderIndexSync(handle, request)");
-        return nullptr;
-    }
-    IndexJob *t = new IndexJob;
-    if (!parse_index(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
-    return run_sync(env, t);
-}
-
-napi_value RenderIndex(napi_env env, napi_callback_info info)
-{
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    napi_valuetype ty = napi_undefined;
-    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
-        napi_throw_type_error(env, nullptr, "renderIndex(handle, request, callback)");
-        return nullptr;
-    }
-    IndexJob *t = new IndexJob;
-    if (!parse_index(env, argv[0], argv[1], t)) { free_job(env, t); return nullptr; }
-    napi_value buf = nullptr;   // (left null, it fails the queueing)
-    napi_get_named_property(env, argv[1], "buffer", &buf);
-    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderIndex", "could not queue the indexed request");
-}
+napi_value RenderIndexSync(napi_env env, napi_callback_info info) { return checked_sync<IndexJob>(env, info, kIndex); }
+napi_value RenderIndex(napi_env env, napi_callback_info info) { return checked_async<IndexJob>(env, info, kIndex); }
 
 // ---- persistence spectrum: renderDensity(handle, req, cb) / renderDensitySync(handle, req) ----------------------------------------------
 // req as for renderIndex -> {density, n, lutLen, width}: density a Uint32Array(n * lutLen), row y at y * lutLen - how many of the
-// request's frames showed colour index g in image row y (sp_render_density).  The request is read by parse_index: every value into a
-// variable of its own with its status checked, so a request that cannot be read throws and never counts.
+// request's frames showed colour index g in image row y (sp_render_density).
+const CheckedKind kDensity{"renderDensity", true, "renderDensitySync(handle, request)", "renderDensity(handle, request, callback)",
+                           "spectroplot_hip.renderDensity", "could not queue the density request"};
+
 struct DensityJob : IndexJob {
     std::vector<uint32_t> counts;
     void run() override;
@@ -1162,36 +1103,8 @@ napi_value DensityJob::result(napi_env env)
     return out;
 }
 
-napi_value RenderDensitySync(napi_env env, napi_callback_info info)
-{
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 2) {
-        napi_throw_type_error(env, nullptr, "renderDensitySync(handle, request)");
-        return nullptr;
-    }
-    DensityJob *t = new DensityJob;
-    if (!parse_index(env, argv[0], argv[1], t, "renderDensity")) { free_job(env, t); return nullptr; }
-    return run_sync(env, t);
-}
-
-napi_value RenderDensity(napi_env env, napi_callback_info info)
-{
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    napi_valuetype ty = napi_undefined;
-    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
-        napi_throw_type_error(env, nullptr, "renderDensity(handle, request, callback)");
-        return nullptr;
-    }
-    DensityJob *t = new DensityJob;
-    if (!parse_index(env, argv[0], argv[1], t, "renderDensity")) { free_job(env, t); return nullptr; }
-    napi_value buf = nullptr;   // (left null, it fails the queueing)
-    napi_get_named_property(env, argv[1], "buffer", &buf);
-    return queue_async(env, t, {argv[2], argv[0], buf}, "spectroplot_hip.renderDensity", "could not queue the density request");
-}
+napi_value RenderDensitySync(napi_env env, napi_callback_info info) { return checked_sync<DensityJob>(env, info, kDensity); }
+napi_value RenderDensity(napi_env env, napi_callback_info info) { return checked_async<DensityJob>(env, info, kDensity); }
 
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {

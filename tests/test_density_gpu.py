@@ -298,6 +298,35 @@ def test_chunked_host_path_and_sparse_upload(ctx):
     _assert_density(got, want, n, W, wf, want["c_hist"], "sparse render_density")
 
 
+# (the request, what it takes): 16 MiB of samples at width 1024 - the smallest request the streamer cuts - for every way through the
+# host path that the test above does not take.  A peak request of one sub-frame per column is the sample detector's reply from
+# k_frames, through the temporary RGBA image.
+CHUNKED = {
+    "contiguous frames_index": ("sample", 1, 1, "frames_index"),
+    "packed frames_index": ("sample", 3, 2, "frames_index"),
+    "packed render_extract": ("peak", 3, 2, "render_extract"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(CHUNKED))
+def test_chunked_host_path_every_path(ctx, case):
+    detector, num, den, kernel = CHUNKED[case]
+    fmt, n, W, lut = "CF32", 2048, 1024, base._lut()
+    data = siggen.generate(fmt, GEN, n + (W - 1) * n * num // den)
+    assert W * n * 8 >= 16 << 20
+    win, weight = pyoracle.window("hann", n)
+    want = pyoracle.render(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W)
+    plan = ctx.plan(fmt, n, win, 1.0 / weight, GAIN, RANGE, lut, detector=detector)
+    try:
+        assert plan.index_kernel_name_for(data.size, W) == kernel and plan.kernel_name(data.size, W) == "frames"
+    finally:
+        plan.close()
+    got = ctx.render_density(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W, detector=detector, fill=0xABABABAB)
+    assert ctx.last_chunks() > 1, "the request was not chunked"
+    assert (ctx.last_upload_bytes() < data.size) == (num > den)
+    _assert_density(got, want, n, W, False, want["c_hist"], case)
+
+
 # ---- one context, no synchronisation in between --------------------------------------------------------------------------------------
 
 def test_density_rgba_index_density_interleave_without_a_sync(ctx):

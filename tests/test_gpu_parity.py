@@ -499,21 +499,28 @@ def test_pixels_straddling_every_index_edge(pkg, ctx):
     assert len(np.unique(want["rgba"].reshape(-1, 4)[:, 0])) > 250
 
 
-@pytest.mark.parametrize("fmt,lg,n,width,wf", [("CF32", 21, 1024, 2048, False), ("CF32", 21, 1024, 2000, True), ("CU8", 23, 512, 16384, False),
-                                                ("CS16", 22, 2048, 3001, False)],
-                         ids=["cf32_hop", "cf32_frac_wf", "cu8_8chunks", "cs16_overlap"])
-def test_large_host_requests_render_in_overlapped_chunks(pkg, ctx, fmt, lg, n, width, wf):
+@pytest.mark.parametrize("fmt,lg,n,width,wf,L", [("CF32", 21, 1024, 2048, False, 256), ("CF32", 21, 1024, 2000, True, 256),
+                                                  ("CU8", 23, 512, 16384, False, 256), ("CS16", 22, 2048, 3001, False, 256),
+                                                  ("CF32", 21, 2048, 1024, False, 300)],
+                         ids=["cf32_hop", "cf32_frac_wf", "cu8_8chunks", "cs16_overlap", "cf32_scratch"])
+def test_large_host_requests_render_in_overlapped_chunks(pkg, ctx, fmt, lg, n, width, wf, L):
     """sp_render walks a large request in chunks of frames (samples in, render, image band out on three streams).  Whole
-    reply against the oracle: chunk seams (frame groups, copied byte ranges, column / row bands) must not show."""
+    reply against the oracle: chunk seams (frame groups, copied byte ranges, column / row bands) must not show.  A colour map of more
+    than 256 entries takes the scratch kernel (16 MiB of samples, stride n: the contiguous upload, the smallest request that is cut)."""
     S = 1 << lg
     data = siggen.generate(fmt, {"kind": "trinoise", "seed": 321, "step": 7321, "gshift": 11, "amp": 0.5, "namp": 0.02}, S)
     win, weight = pyoracle.window("hann", n)
-    i = np.arange(256)
-    lut = np.stack([i, 255 - i, (i * 7) & 255], axis=1).astype(np.uint8)
+    i = np.arange(L)
+    lut = np.stack([i & 255, (255 - i) & 255, (i * 7) & 255], axis=1).astype(np.uint8)
     want = pyoracle.render(fmt, data, n, win, 1.0 / weight, 6.0, 30.0, lut, width, False, wf)
     for _ in range(2):                                   # twice: the second request reuses streams, events and staging buffers
         got = ctx.render(fmt, data, n, win, 1.0 / weight, 6.0, 30.0, lut, width, False, wf)
         _assert_same(got, want)
+    if L > 256:
+        plan = ctx.plan(fmt, n, win, 1.0 / weight, 6.0, 30.0, lut, False, wf)
+        assert plan.kernel_name() == "scratch_radix2"
+        plan.close()
+        assert ctx.last_chunks() > 1 and ctx.last_upload_bytes() == data.size
 
 
 SPARSE = [(f, 256, 18, 131, False) for f in ("CU4", "CS4", "CU8", "CS8", "CU12", "CS12", "CU16", "CS16", "CU32", "CS32", "CU64", "CS64", "CF32", "CF64")] + [
@@ -558,9 +565,14 @@ FROM_HOST = [
     ("CU8", 512, 0, 200, False),          # sparse, integer stride
     ("CF32", 64, 12, 7, False),           # a tiny request: one plain copy
 ]
+# ... and on the scratch kernel (sizes outside the frame loop)
+FROM_HOST_SCRATCH = [
+    ("CS16", 32, 10, 40, False),          # one plain copy
+    ("CU8", 16384, 23, 1024, False),      # overlapping frames, 16 MiB in: the contiguous upload in chunks
+]
 
 
-@pytest.mark.parametrize("fmt,n,lg,width,wf", FROM_HOST, ids=lambda v: str(v))
+@pytest.mark.parametrize("fmt,n,lg,width,wf", FROM_HOST + FROM_HOST_SCRATCH, ids=lambda v: str(v))
 def test_plan_execute_from_host_matches_the_oracle(pkg, ctx, fmt, n, lg, width, wf):
     """sp_plan_execute_from_host (what a group member does with its slice): the capture in host memory, uploaded in chunks of frames
     under the renders - a sparse request only the samples its frames read - and every output left in HBM.  Queued twice back to back
@@ -574,6 +586,7 @@ def test_plan_execute_from_host_matches_the_oracle(pkg, ctx, fmt, n, lg, width, 
     lut = np.stack([i, 255 - i, (i * 7) & 255], axis=1).astype(np.uint8)
     want = pyoracle.render(fmt, data, n, win, 1.0 / weight, 6.0, 30.0, lut, width, False, wf)
     plan = ctx.plan(fmt, n, win, 1.0 / weight, 6.0, 30.0, lut, False, wf)
+    assert (plan.kernel_name() == "scratch_radix2") == (n < 64 or n > 8192)
     W = width
     sizes = [4 * W * n, W, W, W, 8 * 256, 8000, 16]
     ptrs = [ctx.alloc(max(s_, 16)) for s_ in sizes]
@@ -588,6 +601,8 @@ def test_plan_execute_from_host_matches_the_oracle(pkg, ctx, fmt, n, lg, width, 
         assert W * n * sw <= sent <= W * n * sw * 3 // 2 and sent <= data.size * 3 // 4, (sent, W * n * sw, data.size)
     else:
         assert sent == data.size
+    if (fmt, n, lg, width, wf) in FROM_HOST_SCRATCH:
+        assert (ctx.last_chunks() > 1) == (data.size >= 16 << 20 and W >= 1024)
     got = {"rgba": ctx.download(ptrs[0], sizes[0]), "gauge_mins": ctx.download(ptrs[1], W), "gauge_maxs": ctx.download(ptrs[2], W),
            "gauge_amps": ctx.download(ptrs[3], W), "c_hist": ctx.download(ptrs[4], 8 * 256, np.uint64),
            "cB_hist": ctx.download(ptrs[5], 8000, np.uint64)}

@@ -261,3 +261,44 @@ def test_render_index_in_chunks(ctx, wf):
     _host_same(got, want, "chunked wf=%d" % wf)
     assert ctx.last_chunks() >= 4, "the request was not chunked: %d chunk(s)" % ctx.last_chunks()
     assert ctx.last_upload_bytes() == data.size
+
+
+# (the request, what it takes): 16 MiB of samples at width 1024 - the smallest request the streamer cuts - for every way through the
+# host path that test_render_index_in_chunks does not take.  A peak request of one sub-frame per column is the sample detector's
+# reply from k_frames, through the temporary RGBA image.
+CHUNKED = {
+    "packed frames_index": ("sample", 3, 2, "frames_index"),
+    "contiguous render_extract": ("peak", 1, 1, "render_extract"),
+    "packed render_extract": ("peak", 3, 2, "render_extract"),
+}
+
+
+@pytest.mark.parametrize("wf", [False, True])
+@pytest.mark.parametrize("case", sorted(CHUNKED))
+def test_render_index_in_chunks_every_path(ctx, case, wf):
+    detector, num, den, kernel = CHUNKED[case]
+    n, fmt, W, lut = 2048, "CF32", 1024, base._lut()
+    data = siggen.generate(fmt, GEN, n + (W - 1) * n * num // den)
+    assert W * n * 8 >= 16 << 20
+    win, weight = pyoracle.window("hann", n)
+    want = pyoracle.render(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W, False, wf)
+    plan = ctx.plan(fmt, n, win, 1.0 / weight, GAIN, RANGE, lut, False, wf, detector)
+    try:
+        assert plan.index_kernel_name_for(data.size, W) == kernel and plan.kernel_name(data.size, W) == "frames"
+    finally:
+        plan.close()
+    got = ctx.render_index(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W, False, wf, detector=detector, fill=0xAB)
+    _host_same(got, want, "%s wf=%d" % (case, wf))
+    assert ctx.last_chunks() > 1, "the request was not chunked"
+    assert (ctx.last_upload_bytes() < data.size) == (num > den)
+
+
+def test_render_index_of_a_peak_request_in_one_chunk(ctx):
+    """sp_render_index through render_extract in one chunk: a peak request of three sub-frames per column."""
+    n, fmt, W, lut = 128, "CU8", 37, base._lut()
+    data, win, weight = _request(fmt, n, W, n + 36 * 3 * n + 19)
+    want = peakref.expected(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W, False, False)
+    assert want["M"] == 3
+    got = ctx.render_index(fmt, data, n, win, 1.0 / weight, GAIN, RANGE, lut, W, detector="peak", fill=0xAB)
+    _host_same(got, want, "peak, one chunk")
+    assert ctx.last_chunks() == 1 and ctx.last_upload_bytes() == data.size

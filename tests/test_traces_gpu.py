@@ -264,6 +264,23 @@ def test_chunked_contiguous_sp_render_traces(ctx):
     assert ctx.last_upload_bytes() == data.size
 
 
+def test_chunked_contiguous_sp_render_traces_on_the_portable_kernel(ctx):
+    """n = 2048 (scratch_traces), stride n, 16 MiB at width 1024 - the smallest request the streamer cuts - against the oracle."""
+    fmt, n, width = "CF32", 2048, 1024
+    data = _capture(fmt, n, width, n)
+    assert data.size >= 16 << 20
+    win, weight = pyoracle.window("hann", n)
+    want = tracesref.expected(fmt, data, n, win, 1.0 / weight, 3.0, 50.0, width, False)
+    plan = ctx.plan(fmt, n, win, 1.0 / weight, 3.0, 50.0, tracesref._LUT)
+    try:
+        assert plan.traces_kernel_name_for(data.size, width) == "scratch_traces"
+    finally:
+        plan.close()
+    got = ctx.render_traces(fmt, data, n, win, 1.0 / weight, 3.0, 50.0, width, fill=_garbage())
+    tracesref.assert_same(got, want, "contiguous, chunked, portable")
+    assert ctx.last_chunks() > 1 and ctx.last_upload_bytes() == data.size
+
+
 def test_chunked_sp_render_traces_waits_for_a_queued_execute_from_host(pkg, ctx):
     """sp_plan_execute_from_host returns with its copies and kernels still queued on the context's staging buffer; a chunked
     sp_render_traces on the same context, called WITHOUT a synchronisation in between, must not upload over them: the queued render
