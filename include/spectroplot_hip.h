@@ -463,6 +463,45 @@ int sp_render_traces(sp_context *ctx, const sp_request *req, const uint8_t *byte
 const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
+ * Power plane replies: the numeric spectrogram behind every other reply, |X|^2 per frame and bin as f64.
+ * `power` is double[width * n], frame-major:
+ *     power[x * n + y] = real[i] * real[i] + imag[i] * imag[i]
+ * of frame x, bin i exactly as lib/worker.js:70-92 computes it - behind the taper, the transform and, in channel mode, splitreal; two
+ * multiplies and one add, never contracted - with y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90): y is image row y of the
+ * spectrogram layout and column n - 1 - y of the waterfall layout, as for the traces and the density, and the plan's `waterfall` flag
+ * does not change the array.  The request's frames are sp_plan_execute's (the same geometry, positions, limits and statuses; channel
+ * mode honoured).  A frame that reads past the capture gives NaN, as the reference does, and A NaN IS ANY NaN: its payload and sign
+ * are unspecified.  Every other value is bit-exact, +0.0, +inf and denormals included; |X|^2 is never -0.  width == 0 writes nothing
+ * and returns SP_OK.  Gain, range, LUT and block_norm do not reach the plane.  A plane has no reduction, so it does not depend on the
+ * deal of frames to workgroups (the CU count).
+ * Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED, as for the traces.
+ * The dB plane is db[k] = (5 * log10(power[k]) + block_norm_db + gain) - gain in exactly that operation order (worker.js:93, 100),
+ * log10 the engine's function as the library restates it: 0 gives -inf, NaN gives NaN.
+ *
+ * sp_plan_execute_power: device operands, asynchronous on the context's stream.  d_power must be 8-byte aligned and non-NULL when
+ *   width > 0 (SP_ERR_INVALID_ARG otherwise).  ONE launch, no workspace of the context's beyond the portable kernel's slabs, no request
+ *   number, handshake, bounded wait or trap: a stream that is being captured is not refused, and the call may be interleaved with
+ *   sp_plan_execute / _index / _traces on one context without a synchronisation.  All plane offsets are 64-bit (8 * width * n may pass
+ *   4 GiB).
+ * sp_plan_power_to_db: d_db[k] = db of d_power[k] for k < count with the plan's block_norm_db and gain, asynchronous on the context's
+ *   stream; both pointers 8-byte aligned device pointers (SP_ERR_INVALID_ARG otherwise); d_db == d_power converts in place;
+ *   count == 0 queues nothing.
+ * sp_render_power: host buffers, synchronous, the plan cached as by sp_render.  The capture travels as for sp_render - a packed upload
+ *   where stride > n, chunks of frames where the request is large (the plane, 8 * width * n bytes, counts as the reply that comes
+ *   back) - and rows [x0, x1) of the plane come back behind every chunk in one contiguous copy; with db != 0 they are converted in
+ *   place on the device first, so `power` then holds the dB plane.  `power` must be 8-byte aligned and non-NULL when width > 0.
+ *   sp_context_last_upload_bytes / sp_context_last_chunks report as before.
+ * sp_plan_power_kernel_name_for: "frames_power" - k_frames_power, k_frames' frame loop with one 8-byte store per bin - where
+ *   "frames_traces" would be answered (64 <= n <= 1024, a finite taper, the plan not forced to kernel 1), or "scratch_power" for
+ *   everything else.  sp_plan_force_kernel applies as to the traces.
+ * Out of scope: the held plane of a peak plan, batches, groups, sharding.py, and a [y][x] (spectrogram-major) plane.
+ */
+int sp_plan_execute_power(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_power);
+int sp_plan_power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db);
+int sp_render_power(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *power);
+const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

@@ -165,6 +165,11 @@ class Library:
         L.sp_render_traces.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, vp]
         L.sp_plan_traces_kernel_name_for.restype = C.c_char_p
         L.sp_plan_traces_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_plan_execute_power.argtypes = [vp, vp, sz, i32, vp]
+        L.sp_plan_power_to_db.argtypes = [vp, vp, sz, vp]
+        L.sp_render_power.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, i32, vp]
+        L.sp_plan_power_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_power_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -491,6 +496,23 @@ class Context:
         self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), p(data), data.size, int(width), p(tmin), p(tmax)))
         return {"trace_min": tmin, "trace_max": tmax}
 
+    def render_power(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, db=False, lut=None, fill=None):
+        """sp_render_power: the numeric spectrogram of the request, f64 [width, n]: |X|^2 of frame x at image row y in [x, y], or with
+        db=True its dB plane.  No image is rendered; `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a
+        byte the output array holds before the call (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if lut is None:
+            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        W = max(int(width), 0)
+        power = np.zeros((W, int(n)), np.float64)
+        if fill is not None:
+            power.view(np.uint8)[...] = fill
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self.lib.L.sp_render_power(self.h, C.byref(req), p(data), data.size, int(width), 1 if db else 0, p(power)))
+        return power
+
     def render_index(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False,
                      detector="sample", want_index=True, fill=None):
         """sp_render_index: render()'s reply with "index" - one colour-index byte per pixel, u8[width * n] in the RGBA image's pixel
@@ -609,6 +631,21 @@ class Plan:
         Asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_traces(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                             C.c_void_p(trace_min or None), C.c_void_p(trace_max or None)))
+
+    def power_kernel_name_for(self, nbytes, width):
+        """The frame loop execute_power() launches for a request of this shape: "frames_power" or "scratch_power"."""
+        return self.ctx.lib.L.sp_plan_power_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def execute_power(self, d_bytes, nbytes, width, d_power):
+        """sp_plan_execute_power: |X|^2 of every frame and bin into the f64 [width, n] device array at address d_power (frame-major,
+        image row order within a frame).  One launch, asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_power(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                           C.c_void_p(d_power or None)))
+
+    def power_to_db(self, d_power, count, d_db):
+        """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place
+        where they are equal).  Asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_power_to_db(self.h, C.c_void_p(d_power or None), int(count), C.c_void_p(d_db or None)))
 
     def index_kernel_name_for(self, nbytes, width):
         """What execute_index() runs for a request of this shape: "frames_index" or "render_extract"."""

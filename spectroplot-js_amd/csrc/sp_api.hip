@@ -19,6 +19,7 @@
 #include "sp_kernel_frames_batch.h"
 #include "sp_kernel_frames_peak.h"
 #include "sp_kernel_frames_traces.h"
+#include "sp_kernel_frames_power.h"
 #include "sp_kernel_frames_index.h"
 #include "sp_kernel_scratch.h"
 #include "sp_synth.h"
@@ -105,6 +106,7 @@ struct sp_context {
     DeviceBuffer partial;        // [0,4) the number of the last request k_frames has started; the scratch kernel's {min,max} and histogram accumulators
     DeviceBuffer scratch;        // scratch kernel slabs
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
+    DeviceBuffer power_plane;    // sp_render_power: the request's plane on the device, 8 * width * n bytes (grown, never shrunk)
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
     DeviceBuffer density_index;  // sp_plan_execute_density: the request's index image, width * n bytes (grown, never shrunk)
     DeviceBuffer density_reply;  // ... and the reply record its render's side outputs go to (sphost::ReplyRecord)
@@ -371,6 +373,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->partial.release();
     ctx->scratch.release();
     ctx->traces_ws.release();
+    ctx->power_plane.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
     ctx->density_reply.release();
@@ -2141,6 +2144,167 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
             if (!r && e == hipSuccess && trace_max) e = hipMemcpyAsync(trace_max, d_out + n, n * sizeof(double), hipMemcpyDeviceToHost, s);
             return r;
         });
+}
+
+// ------------------------------------------------------------------------------------------------- power plane replies
+
+// k_frames_power needs what k_frames_traces needs of a plan (plan_traces_frames): nothing of the picture reaches a plane either.
+static bool plan_power_frames(const sp_plan *plan)
+{
+    return plan->force_kernel != kKernelScratch && spk2::frames_power_supports(plan->req.n) && plan->taper_finite && plan->tw16_ok;
+}
+
+extern "C" const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
+    return !plan ? "" : plan_power_frames(plan) ? "frames_power" : "scratch_power";
+}
+
+// what every power entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
+static int check_power(sp_context *ctx, int32_t detector, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width)
+{
+    if (detector != SP_DETECTOR_SAMPLE)
+        return fail(ctx, SP_ERR_UNSUPPORTED, "the power plane of a peak plan is not supported (the plane holds the sample detector's frames)");
+    return check_capture(ctx, f, n, bytes, nbytes, width, nullptr, "");
+}
+
+// The frame loop over frames [x_begin, x_end) of a power request into the plane at d_power, frame x at d_power + x * n (`src`: as for
+// plan_execute_range).  One launch.
+static int power_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
+                       double *d_power)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = plan->req.n;
+    const bool frames = plan_power_frames(plan);
+    if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
+    spk::FrameArgs a{};
+    plan_frame_args(plan, a);
+    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
+    hipStream_t s = ctx->stream;
+    if (frames) {
+        a.lut_len = spk2::kPowerLutLen;   // (the shared prologue copies this many LUT and edge entries: the plan's tables hold them)
+        a.cells = 0;
+        const int rc = spk2::launch_frames_power(a, plan->req.format, plan->d_stage_tw, d_power, ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, "k_frames_power launch rejected the configuration");
+    } else {
+        // two slabs per workgroup (re, im)
+        const long long blocks = scratch_blocks(2, n, x_end - x_begin, ctx->cu_count);
+        int rc = ctx->scratch.reserve((size_t)blocks * 2 * (size_t)n * sizeof(double));
+        if (rc) return fail(ctx, rc, "scratch: out of device memory");
+        a.scratch = (double *)ctx->scratch.p;
+        rc = dispatch_format(plan->req.format, [&](auto F) {
+            constexpr int FMT = decltype(F)::value;
+            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
+            if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_power<FMT, true>), grid, block, 0, s, a, d_power);
+            else hipLaunchKernelGGL((spk::k_scratch_power<FMT, false>), grid, block, 0, s, a, d_power);
+            return SP_OK;
+        });
+        if (rc) return fail(ctx, rc, "bad format");
+    }
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// d_db[k] = d of d_power[k], k < count, on the context's stream (count > 0; in place where the pointers are equal)
+static int power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db)
+{
+    sp_context *ctx = plan->ctx;
+    size_t blocks = (count + 255) / 256;
+    const size_t most = 16 * (size_t)ctx->cu_count;   // (a grid-stride loop: enough workgroups to fill the chip)
+    if (blocks > most) blocks = most;
+    hipLaunchKernelGGL(spk::k_power_to_db, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_power, count, plan->block_norm_db, plan->req.gain,
+                       d_db);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+extern "C" int sp_plan_execute_power(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_power)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    if (rc) return rc;
+    if (width > 0 && (!d_power || ((uintptr_t)d_power & 7) != 0))
+        return fail(ctx, SP_ERR_INVALID_ARG, "d_power must be an 8-byte aligned array of width * n doubles");
+    if (width == 0) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    rc = power_range(plan, d_bytes, g, 0, width, nullptr, d_power);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_plan_power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    if (count && (!d_power || !d_db)) return fail(ctx, SP_ERR_INVALID_ARG, "d_power and d_db must not be null");
+    if ((((uintptr_t)d_power | (uintptr_t)d_db) & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "d_power and d_db must be 8-byte aligned");
+    if (!count) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = power_to_db(plan, d_power, count, d_db);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+// A request kind of stream_chunks - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
+// plane comes back chunk by chunk: rows [x0, x1) of it are one contiguous copy.
+extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *power)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    sp_plan *plan = nullptr;
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width,
+        [&] {
+            return width > 0 && (!power || ((uintptr_t)power & 7) != 0)
+                       ? fail(ctx, SP_ERR_INVALID_ARG, "power must be an 8-byte aligned array of width * n doubles")
+                       : (int)SP_OK;
+        },
+        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+    if (rc) return rc;
+
+    const size_t n = (size_t)req->n, plane_bytes = sizeof(double) * (size_t)width * n;
+    hipStream_t s = ctx->stream;
+    rc = ctx->power_plane.reserve(plane_bytes + 16);
+    if (rc) return fail(ctx, rc, "sp_render_power: out of memory");
+    double *const d_plane = (double *)ctx->power_plane.p;
+    HostFeed feed{"sp_render_power", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_power_frames(plan), true, plane_bytes, true, nullptr};
+    const auto copies_failed = [&](hipError_t e) { return hip_fail(ctx, e, "sp_render_power copies"); };
+    rc = stream_chunks(
+        ctx, plan->fmt, feed,
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
+            int r = power_range(plan, d_in, feed.g, x0, x1, src, d_plane);
+            if (!r && db && x1 > x0) r = power_to_db(plan, d_plane + (size_t)x0 * n, (size_t)(x1 - x0) * n, d_plane + (size_t)x0 * n);
+            return r;
+        },
+        [&](int k, int32_t x0, int32_t x1) {
+            hipError_t e = hipSuccess;
+            if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
+            if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
+            if (e == hipSuccess && x1 > x0)
+                e = hipMemcpyAsync(power + (size_t)x0 * n, d_plane + (size_t)x0 * n, sizeof(double) * (size_t)(x1 - x0) * n, hipMemcpyDeviceToHost,
+                                   feed.out_s);
+            return e == hipSuccess ? (int)SP_OK : copies_failed(e);
+        });
+    if (rc) return rc;
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return copies_failed(e);
+    }
+    return SP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

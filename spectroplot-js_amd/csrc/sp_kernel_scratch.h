@@ -385,4 +385,38 @@ __global__ void k_traces_finish(const unsigned long long *ws, const int n, const
     }
 }
 
+// ---- the numeric spectrogram (include/spectroplot_hip.h, sp_plan_execute_power) ------------------------------------------------------------
+// One launch: a frame loop (k_frames_power, sp_kernel_frames_power.h, or k_scratch_power here) that stores |X|^2 of frame x, bin i at
+// power[x * n + y], y the image row of bin i (worker.js:90).  No workspace beyond the slabs, no atomics, nothing to clear or finish.
+
+// The portable frame loop of a power request: everything k_frames_power does not take.  A workgroup owns the columns
+// frame0 + blockIdx.x + k * gridDim.x and stores each column's n values behind its transform.
+template <int FMT, bool WIDE>
+__global__ __launch_bounds__(kScratchThreads) void k_scratch_power(const FrameArgs a, double *const power)
+{
+    const int tid = threadIdx.x;
+    const int n = a.n;
+    double *re = a.scratch + (size_t)blockIdx.x * 2 * (size_t)n;
+    double *im = re + n;
+    const spfmt::View view{a.bytes, a.nbytes, a.nelem};
+    const int half = n >> 1;
+    for (int x = a.frame0 + blockIdx.x; x < a.x_end; x += gridDim.x) {
+        scratch_frame<FMT, WIDE>(a, view, frame_start(a.stride, x), re, im, tid);
+        double *const col = power + (size_t)x * (size_t)n;   // (64-bit: 8 * width * n passes 4 GiB)
+        for (int i = tid; i < n; i += kScratchThreads) {
+            const double r = re[i], q = im[i];
+            col[i <= half ? half - i : half + n - i] = r * r + q * q;                          // worker.js:90, 92
+        }
+        __syncthreads();   // the slab is written again by the next frame
+    }
+}
+
+// d_db[k] = d of d_power[k] through the restated log10 in the reference's operation order (d_of_abs2: worker.js:93, 100), k < count.
+// Every element is read before it is written and by the same thread, so d_db may be d_power.
+__global__ void k_power_to_db(const double *d_power, const size_t count, const double block_norm_db, const double gain, double *d_db)
+{
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) d_db[k] = d_of_abs2(d_power[k], block_norm_db, gain);
+}
+
 }  // namespace spk

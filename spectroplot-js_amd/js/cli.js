@@ -6,7 +6,8 @@
  *
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
- *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] --out image.ppm
+ *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] [--power power.f64] [--power-db db.f64]
+ *        --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
  * Batch mode (--out-dir): one image per capture, DIR/<capture's file name>.ppm (or .rgba with --rgba), the same bytes a single-file
@@ -23,6 +24,10 @@
  * --density FILE (single-file runs): the persistence spectrum of the same request over the whole capture (HipWorker.renderDensity ->
  * sp_render_density), written as a binary PGM (P5, maxval 65535, big-endian): lut_len columns x n rows, row y the image row's counts
  * per colour index, each value min(count, 65535).
+ *
+ * --power FILE / --power-db FILE (single-file runs, sample detector): the numeric spectrogram of the same request over the whole capture
+ * (HipWorker.renderPower -> sp_render_power) as raw little-endian f64, width * n values, frame-major: |X|^2 (or, for --power-db, the dB
+ * value 5 log10 |X|^2 + block_norm's dB) of frame x at value x * n + y, y the image row.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -59,6 +64,19 @@ function writeTraces(buffer, format, n, width, opt) {
         worker.terminate()
         const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
         fs.writeFileSync(opt.traces, JSON.stringify({ n, width, trace_min: plain(t.trace_min), trace_max: plain(t.trace_max) }))
+    }, e => { worker.terminate(); throw e })
+}
+
+// --power / --power-db: one request over the whole capture on one worker, resolved as --traces resolves its own; the plane's bytes as they
+// are (every host this runs on is little-endian)
+function writePower(buffer, format, n, width, opt, db) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const worker = new HipWorker()
+    return worker.renderPower({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
+        worker.terminate()
+        fs.writeFileSync(db ? opt['power-db'] : opt.power, Buffer.from(r.power.buffer, r.power.byteOffset, r.power.byteLength))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -166,6 +184,8 @@ function main(argv) {
         .then(() => opt.traces === undefined ? null : writeTraces(buffer, format, n, width, opt))
         .then(() => opt.index === undefined ? null : writeIndex(buffer, format, n, width, opt))
         .then(() => opt.density === undefined ? null : writeDensity(buffer, format, n, width, opt))
+        .then(() => opt.power === undefined ? null : writePower(buffer, format, n, width, opt, false))
+        .then(() => opt['power-db'] === undefined ? null : writePower(buffer, format, n, width, opt, true))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

@@ -192,6 +192,37 @@ class HipWorker {
     }
 
     /**
+     * The numeric spectrogram of a request (sp_render_power): the fields renderTraces reads in, |X|^2 of every frame and bin out as one
+     * Float64Array(width * n), frame-major - frame x at power[x * n + y], y the image row (row y of the spectrogram, column n - 1 - y
+     * of the waterfall) - or, with `{db: true}`, its dB plane (5 log10 |X|^2 + block_norm's dB, gain cancelled as the worker cancels
+     * it).  No image is rendered; gain, range and colour map do not reach the power plane.  Only the sample detector has a plane.  Runs
+     * in the instance's request order; a malformed field rejects (and reports `onerror`) and never resolves to an array.
+     * @returns {Promise<{power: Float64Array, width: number, n: number}>}
+     */
+    renderPower(m, opt) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._powerRequest(m, opt) } catch (e) { reject(e); return }
+            try {
+                addon().renderPower(this._ctx, req, (err, r) => err ? reject(err) : resolve({ power: r.power, width: r.width, n: r.n }))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
+        return p
+    }
+
+    _powerRequest(m, opt) {
+        if (!(m && m.buffer)) throw Object.assign(new Error('a power request needs a buffer'), { status: -1 })
+        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the power plane of the peak detector is not supported'), { status: -4 })
+        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db) })
+    }
+
+    /** Synchronous form of renderPower (tests). */
+    renderPowerSync(m, opt) { return addon().renderPowerSync(this._ctx, this._powerRequest(m, opt)) }
+
+    /**
      * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the
      * message's colour map pixel j of imageData.data shows, so the reply is a quarter of the size and js/consumers.js `recolour` redraws
      * it under another map without a render.  The message is a worker message (`detector: 'peak'` allowed; a colour map of more than 256

@@ -24,6 +24,7 @@
 //       c_hist, cB_hist: Float64Array, dBfs_min, dBfs_max}) on the main thread
 //   renderSync(handle, req)                        -> the same reply object, synchronously
 //   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
+//   renderPower(handle, req, cb) / renderPowerSync(handle, req) -> {power, width, n}: |X|^2 (or dB) per frame and bin as f64, no image
 //   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
 //       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
@@ -282,6 +283,8 @@ struct Job : JobBase {
     double minmax[2] = {0.0, -200.0};
     void run() override { run_job(this); }
     napi_value result(napi_env env) override { return make_reply(env, this); }
+    // a checked kind's own request fields, read behind the shared ones (parse_checked); false: it has thrown
+    virtual bool parse_own(napi_env, napi_value) { return true; }
     ~Job() override;
 };
 
@@ -929,7 +932,7 @@ napi_value checked_sync(napi_env env, napi_callback_info info, const CheckedKind
         return nullptr;
     }
     J *t = new J;
-    if (!parse_checked(env, argv[0], argv[1], t, kind)) { free_job(env, t); return nullptr; }
+    if (!parse_checked(env, argv[0], argv[1], t, kind) || !t->parse_own(env, argv[1])) { free_job(env, t); return nullptr; }
     return run_sync(env, t);
 }
 
@@ -945,7 +948,7 @@ napi_value checked_async(napi_env env, napi_callback_info info, const CheckedKin
         return nullptr;
     }
     J *t = new J;
-    if (!parse_checked(env, argv[0], argv[1], t, kind)) { free_job(env, t); return nullptr; }
+    if (!parse_checked(env, argv[0], argv[1], t, kind) || !t->parse_own(env, argv[1])) { free_job(env, t); return nullptr; }
     napi_value buf = nullptr;   // (left null, it fails the queueing)
     napi_get_named_property(env, argv[1], "buffer", &buf);
     return queue_async(env, t, {argv[2], argv[0], buf}, kind.resource, kind.could_not_queue);
@@ -1105,6 +1108,56 @@ napi_value DensityJob::result(napi_env env)
 
 napi_value RenderDensitySync(napi_env env, napi_callback_info info) { return checked_sync<DensityJob>(env, info, kDensity); }
 napi_value RenderDensity(napi_env env, napi_callback_info info) { return checked_async<DensityJob>(env, info, kDensity); }
+
+// ---- power plane: renderPower(handle, req, cb) / renderPowerSync(handle, req) ----------------------------------------------------------
+// req as for renderTraces plus `db` (boolean) -> {power, width, n}: power a Float64Array(width * n), frame-major - |X|^2 of frame x at
+// image row y in power[x * n + y], or its dB plane with db - in a page-locked block of the reply pool (sp_render_power).
+const CheckedKind kPower{"renderPower", false, "renderPowerSync(handle, request)", "renderPower(handle, request, callback)",
+                         "spectroplot_hip.renderPower", "could not queue the power request"};
+
+struct PowerJob : Job {
+    int32_t db = 0;
+    bool parse_own(napi_env env, napi_value r) override { return checked_bool(env, r, "db", &db); }
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+void PowerJob::run()
+{
+    const size_t W = (size_t)width, n = (size_t)req.n;
+    rgba_size = W * n * sizeof(double) + 8;                  // (Job's image block: here one f64 per frame and bin)
+    rgba = (uint8_t *)g_pool.take(rgba_size, &rgba_pin);
+    if (!rgba) {
+        status = SP_ERR_NOMEM;
+        error = "out of host memory";
+        return;
+    }
+    status = sp_render_power(ctx, &req, bytes, nbytes, width, db, (double *)rgba);
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value PowerJob::result(napi_env env)
+{
+    const size_t W = (size_t)width, n = (size_t)req.n;
+    napi_value out, ab, ta, v;
+    if (napi_create_object(env, &out) != napi_ok) return nullptr;
+    PoolTag *tag = new PoolTag{rgba_size, rgba_pin};
+    if (napi_create_external_arraybuffer(env, rgba, W * n * sizeof(double), pool_free_cb, tag, &ab) != napi_ok) {
+        delete tag;
+        return nullptr;
+    }
+    int64_t total = 0;
+    napi_adjust_external_memory(env, reply_weight(rgba_size), &total);
+    rgba = nullptr;   // owned by the ArrayBuffer now
+    if (napi_create_typedarray(env, napi_float64_array, W * n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "power", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, out, "width", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, out, "n", v) != napi_ok) return nullptr;
+    return out;
+}
+
+napi_value RenderPowerSync(napi_env env, napi_callback_info info) { return checked_sync<PowerJob>(env, info, kPower); }
+napi_value RenderPower(napi_env env, napi_callback_info info) { return checked_async<PowerJob>(env, info, kPower); }
 
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
@@ -1426,6 +1479,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTraces", nullptr, RenderTraces, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderPower", nullptr, RenderPower, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderPowerSync", nullptr, RenderPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},
