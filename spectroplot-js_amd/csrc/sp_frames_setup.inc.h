@@ -1,5 +1,5 @@
 // Frame-loop fragment (sp_kernel_frames.h explains the fragments): the kernel's shape and LDS layout, the thread's place in them, the
-// workgroup's share of the groups.  First in the bodies of k_frames and k_frames_batch.
+// workgroup's share of the groups.  First in the body of every frame-loop kernel.
 // Expects in scope: LOG2N, CH, PFB, a, group_frames, groups.
     constexpr int kThreads = kFrameThreads;   // eight waves, two per SIMD, one workgroup per CU
     constexpr int N = 1 << LOG2N;

@@ -37,19 +37,27 @@
 // Measured alternatives (three waves per SIMD, two workgroups per CU, LDS-DMA input, other batch / slice / chain counts) are recorded in
 // DESIGN.md section 6.2; the cost-attribution switches and per-wave clock stamps that produced profiles/ live in
 // tools/experiments/frames_instrumentation.patch (tools/build_variant.sh applies it), not here.
-// The stages this kernel shares with k_frames_batch (sp_kernel_frames_batch.h) are fragment files, sp_frames_*.inc.h, #included inside
-// both kernel bodies.  The inclusion is textual on purpose: the compiler sees the tokens it saw when each kernel spelled the stages out,
-// so neither kernel's code moves (a shared function, even a local alias, moved k_frames' instruction streams).  A fragment's first
-// comment lists the names it expects in scope; an expression that differs between the kernels is a macro (SP_X_END, ...) that each
-// kernel defines around the include.  tests/test_isa_checks.py compares every k_frames, k_frames_batch and k_frames_peak instruction
-// stream with a reference build.  Who includes what (F = k_frames, B = k_frames_batch, P = k_frames_peak, sp_kernel_frames_peak.h):
-//   * F B P  the stages: setup, raw_regs, table_loads, table_stores, epilogue_consts, decode_pf, fft, lr_split, pixels (P defines
-//            SP_ABS2); the bodies side_outputs and drain_rows (inside each kernel's lambdas); hist_ranges, hist_scan, hist_adds and
-//            range_atomics (F and P through finale, B in batch_flush);
-//   * F P    the shell of a single request's loop: reply_clear (workgroup 0 clears the reply), publish (the request's number), writeout
-//            (the lambdas side_outputs, drain_rows, drain), finale (everything behind the group loop: split last write-out, scan, the
-//            bounded poll for the request's number, adds, last side outputs, dBfs range).  B keeps its own lambdas and batch_flush:
-//            they read the item record, and its replies are cleared by a kernel queued ahead, so it has no handshake.
+// The six frame-loop kernels - k_frames (F), k_frames_index (I, sp_kernel_frames_index.h), k_frames_batch (B, ..._batch.h), k_frames_peak
+// (P, ..._peak.h), k_frames_traces (T, ..._traces.h), k_frames_power (W, ..._power.h) - are built from fragment files, sp_frames_*.inc.h,
+// #included inside the kernel bodies; the loop's order and why it is so is commented there, once.  The inclusion is textual on purpose:
+// the compiler sees the tokens it saw when each kernel spelled its loop out, so no kernel's code moves (a shared function, even a local
+// alias, moved k_frames' instruction streams; so does a declaration that changes its place - sp_frames_setup.inc.h cannot take the
+// four that follow the request in every body).  A fragment's first comment lists the names it expects in scope; an expression that
+// differs between the kernels is a macro (SP_X_END, ...) that each kernel defines around the include.  tests/test_isa_checks.py
+// compares every instruction stream of the six kernels with a reference build.  Who includes what:
+//   * F I        request_body: the whole body of a kernel that renders one request's picture (I defines SP_DRAIN_ROWS_BODY around it);
+//   * T W        plain_body: the whole body behind setup of a kernel without a picture, around the kernel's own epilogue per frame
+//                (SP_FRAME_TAIL: traces_fold, power_store);
+//   * all six    setup, raw_regs (with the HALVES slot mapping), table_loads, table_stores, taper, slot_deal, frame_regs, decode_pf,
+//                passes (fft and lr_split, and around them the two write-out slices unless SP_NO_WRITEOUT), directly or through a body;
+//   * F I T W    request (the lambda) and next_frame (the next frame, its request, the loaders; F I define SP_TOUCH_AHEAD); load_generic
+//                through it, P directly.  B spells both out over its item records, P has request_at and no frame ahead;
+//   * F I B P    epilogue_consts, pixels (P defines SP_ABS2); the bodies side_outputs and drain_rows (I: drain_rows_index) inside each
+//                kernel's lambdas; hist_ranges, hist_scan, hist_adds and range_atomics (F I P through finale, B in batch_flush);
+//   * F I P      the shell of a single request's loop: reply_clear (workgroup 0 clears the reply), publish (the request's number), writeout
+//                (the lambdas side_outputs, drain_rows, drain), finale (everything behind the group loop: split last write-out, scan, the
+//                bounded poll for the request's number, adds, last side outputs, dBfs range).  B keeps its own lambdas and batch_flush:
+//                they read the item record, and its replies are cleared by a kernel queued ahead, so it has no handshake.
 // The switches over a format id expand SP_FORMATS_BUT_CF64 (sp_formats.h).
 #pragma once
 
@@ -368,135 +376,10 @@ template <int LOG2N, bool CH, int PFB>
 __global__ __launch_bounds__(kFrameThreads, 1) void k_frames(const FrameArgs a, const int format, const double2 *__restrict__ stage_tw,
                                                        const int group_frames, const int groups)
 {
-#include "sp_frames_setup.inc.h"
-
-#include "sp_frames_raw_regs.inc.h"
-    auto request = [&](int xq) {
-        if constexpr (PF) {
-            // (the prefetching variants only run when every frame lies inside the buffer: launch_frames)
-            const int xc = xq < a.x_end ? xq : a.x_end - 1;
-            constexpr bool UNI = T >= 64;   // a frame per wave or more: its start is wave-uniform
-            const int sv = frame_start_in_bounds(a.stride, xc);
-            const int64_t st = UNI ? __builtin_amdgcn_readfirstlane(sv) : sv;
-            if constexpr (PFB == 3) raw_back = (st + N) * 3 + 1 > a.nbytes ? 1 : 0;
-            issue_raw<PFB, UNI>(a.bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
-        }
-    };
-    // n = 1024, 32-frame groups: the first / second waves of the SIMDs each take one half of a group's frames
-    const bool HALVES = T == 64 && group_frames == 32;
-    const int fs0 = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + fs % (FPB / 2) : fs;     // the slot's frame in a group's first round
-    // n <= 1024 requests the first frame's samples behind the table loads, below (config 2: -1.6 us per launch); above, where the tables
-    // are a quarter of the size and the taper goes to registers after them, the old order measures the same (n = 2048) or 1.3 % better
-    // (n = 8192: the other order shifts the loop's register allocation)
-    constexpr bool REQ_AFTER_TABLES = PF && !LATE_PF && LOG2N <= 10;
-    if (PF && !LATE_PF && !REQ_AFTER_TABLES && xcd * chunk + lane_in_xcd < g_end) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
-
-    // workgroup 0's first wave owns the reply's initial state in the first launch of a request (below)
-    const bool owner = blockIdx.x == 0 && __builtin_amdgcn_readfirstlane(tid >> 6) == 0 && a.first;   // (wave-uniform)
-    constexpr bool WIN_LDS = lds_win_in_lds(N);   // taper in LDS for n <= 1024, in registers for the whole launch above
-    double *s_win = (double *)(smem + lay.off_win);
-    constexpr int MMS = mm_slots(N);
-    constexpr bool LATE_SIDE = late_side_outputs(N);
-    {
-#include "sp_frames_table_loads.inc.h"
-#include "sp_frames_reply_clear.inc.h"
-        // The first frame's samples are requested BEHIND the table loads (vector-memory operations complete in order: requested ahead of
-        // them, the wait for the tables - L2 hits - was a wait for the samples from HBM), and unconditionally (a frame past the end is
-        // clamped), so that the compiler can count the 16 younger loads in that wait: s_waitcnt vmcnt(16).
-        if constexpr (REQ_AFTER_TABLES) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
-#include "sp_frames_table_stores.inc.h"
-    }
-
-    const double *const wbase = s_win + tl;   // stored as the threads read it: entry e*T + tl = taper[rev4(e)*T + rev(tl)]
-    double win_reg[WIN_LDS ? 1 : 16];
-    if constexpr (!WIN_LDS) {
-        const int sidx = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
-#pragma unroll
-        for (int e = 0; e < 16; e++) win_reg[e] = a.window[rev4(e) * T + sidx];
-    }
-    lds_barrier();
-
-    const spfmt::View view{a.bytes, a.nbytes, a.nelem};
-    uint32_t pf_word = 0;
-#include "sp_frames_epilogue_consts.inc.h"
-
-#include "sp_frames_writeout.inc.h"
-    int drain_x0 = -1;
-    int gpar = 0;   // parity of the workgroup's current group (s_amp)
-    meet.arrive();   // the first re-distribution only waits (exchange<.., SECOND = false>)
-    for (int g = xcd * chunk + lane_in_xcd; g < g_end; g += per_xcd) {
-        const int x0 = a.frame0 + g * group_frames;
-        for (int r = 0; r < rounds; r++) {
-            // HALVES: the first waves of the SIMDs (slots 0 .. FPB/2-1) own the group's first half of the frames, the second waves the
-            // other half, so that each set can write its half out by itself after the workgroup's last group
-            const int fr = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + r * (FPB / 2) + fs % (FPB / 2) : r * FPB + fs;
-            const int xr = x0 + fr;
-            if (fr >= group_frames) continue;   // a slot without a frame in the group's last round (its next frame is already requested)
-            const bool live = xr < a.x_end;
-            const int x = live ? xr : a.x_end - 1;
-            const int64_t start = frame_start(a.stride, x);
-
-            double re[16], im[16];
-            double win[16];
-            double2 *const centre = tl == 0 ? &s_amp[gpar * group_frames + fr] : nullptr;   // thread 0 of the frame: where its raw centre sample goes
-            bool nonfinite = true;   // wave-uniform
-#pragma unroll
-            for (int e = 0; e < 16; e++) win[e] = WIN_LDS ? wbase[e * T] : win_reg[WIN_LDS ? 0 : e];
-            // the frame this slot processes next: the same slot one round on, or its frame in the workgroup's next group
-            const int xn = (r + 1 < rounds && (HALVES || fr + FPB < group_frames)) ? xr + (HALVES ? FPB / 2 : FPB)
-                                                                         : (g + per_xcd < g_end ? a.frame0 + (g + per_xcd) * group_frames + fs0 : -1);
-            if constexpr (PF && LATE_PF) request(xr);
-            if constexpr (PF) {
-#include "sp_frames_decode_pf.inc.h"
-                if (!LATE_PF && xn >= 0) request(xn);           // in flight during this frame's butterflies
-            } else {
-                asm volatile("" ::"v"(pf_word));
-                if (a.in_bounds && xn >= 0 && xn < a.x_end) {
-                    const int lines = (N * a.sample_width + 127) >> 7;
-                    const int64_t nb = (int64_t)frame_start(a.stride, xn) * a.sample_width;
-                    for (int l = tl; l < lines; l += T) pf_word = *(const uint32_t *)(a.bytes + ((nb + (int64_t)l * 128) & ~(int64_t)3));
-                }
-                switch (format) {
-#define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                    SP_FORMATS_BUT_CF64(SP_CASE)
-#undef SP_CASE
-                default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                }
-            }
-
-            unsigned tw_off = 0;
-            asm volatile("" : "+s"(tw_off));
-            const double2 *tw = stage_tw + tw_off;
-            // the previous group's write-out goes in two slices around this frame's passes, so that its stores drain while the SIMDs compute
-            if (drain_x0 >= 0) {
-                lds_barrier();
-                if constexpr (!LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                drain(drain_x0, 0, 2);
-            }
-#include "sp_frames_fft.inc.h"
-
-#include "sp_frames_lr_split.inc.h"
-
-            if (drain_x0 >= 0) {
-                drain(drain_x0, 1, 2);
-                lds_barrier();
-                // The previous group's side outputs, here: the two waves that evaluate them (a software log10, ~1 us) next meet the
-                // others at the start of the following group, where the first waves of the SIMDs arrive early anyway; in front of this
-                // barrier they held everybody up.  (The frames' extremes and centre samples are kept per group parity for it.)
-                if constexpr (LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                drain_x0 = -1;
-            }
-#include "sp_frames_pixels.inc.h"
-#include "sp_frames_publish.inc.h"
-        }
-        drain_x0 = x0;
-        gpar ^= 1;
-    }
-
-#include "sp_frames_finale.inc.h"
+#include "sp_frames_request_body.inc.h"
 }
 
-// The launch rules of the three frame-loop kernels (sp_api.hip's batch plan follows them too).
+// The launch rules of the frame-loop kernels (sp_api.hip's batch plan follows them too).
 // Frames per group for a launch over total_frames frames: 32, or fewer while that leaves less than two groups per CU.
 inline int frames_group_frames(int n, int64_t total_frames, int cu_count)
 {
@@ -556,7 +439,7 @@ inline int launch_full_lds(int grid, int lds_bytes, int device, hipStream_t stre
     return SP_OK;
 }
 
-// Per-n launchers, one translation unit each (sp_inst_frames.hip and sp_inst_frames_peak.hip are compiled once per LOG2N):
+// Per-n launchers, one translation unit each (sp_inst_frames.hip is compiled once per kernel family and LOG2N):
 // NAME<L>(a, format, stage_tw, fl, prefetch, device, stream, <what the kernel takes behind `groups`>).
 // SP_DECLARE_LAUNCH_N(NAME, SIZES, extra parameter types...) declares NAME and its specialisation for every L of SIZES.
 #define SP_LAUNCH_N_PARAMS \
@@ -572,20 +455,44 @@ inline int launch_full_lds(int grid, int lds_bytes, int device, hipStream_t stre
     SIZES(SP_DECLARE_LAUNCH_N_AT, NAME, ##__VA_ARGS__)
 
 // The body of a per-n launcher: SP_LAUNCH_VARIANT(KERNEL, extra arguments...) launches KERNEL<L, a.channel_mode, prefetch> and returns.
-// Expects in scope: L and the parameters of SP_LAUNCH_N_PARAMS.
-#define SP_LAUNCH_VARIANT_CP(KERNEL, C, P, ...) \
-    return launch_full_lds<KERNEL<L, C, P>>(fl.grid, fl.lds_bytes, device, stream, a, format, stage_tw, fl.gf, fl.groups, ##__VA_ARGS__);
-#define SP_LAUNCH_VARIANT_C(KERNEL, C, ...)                \
-    switch (prefetch) {                                    \
-    case 8: SP_LAUNCH_VARIANT_CP(KERNEL, C, 8, ##__VA_ARGS__) \
-    case 4: SP_LAUNCH_VARIANT_CP(KERNEL, C, 4, ##__VA_ARGS__) \
-    case 3: SP_LAUNCH_VARIANT_CP(KERNEL, C, 3, ##__VA_ARGS__) \
-    case 2: SP_LAUNCH_VARIANT_CP(KERNEL, C, 2, ##__VA_ARGS__) \
-    case 1: SP_LAUNCH_VARIANT_CP(KERNEL, C, 1, ##__VA_ARGS__) \
-    default: SP_LAUNCH_VARIANT_CP(KERNEL, C, 0, ##__VA_ARGS__) \
+// SP_LAUNCH_VARIANT_IF(BUILT, KERNEL, extra arguments...) does so for the variants that the predicate BUILT(n, channel_mode, prefetch)
+// keeps and returns SP_ERR_UNSUPPORTED for the others, which are not compiled either: the generic lambda is a template, and a
+// template's discarded branch is not instantiated.  Expects in scope: L and the parameters of SP_LAUNCH_N_PARAMS.
+template <bool C, int P>
+struct Variant {
+    static constexpr bool c = C;
+    static constexpr int p = P;
+};
+constexpr bool frames_variant_built(int, bool, int) { return true; }
+#define SP_LAUNCH_VARIANT_C(C)                      \
+    switch (prefetch) {                             \
+    case 8: return launch_cp(Variant<C, 8>{});      \
+    case 4: return launch_cp(Variant<C, 4>{});      \
+    case 3: return launch_cp(Variant<C, 3>{});      \
+    case 2: return launch_cp(Variant<C, 2>{});      \
+    case 1: return launch_cp(Variant<C, 1>{});      \
+    default: return launch_cp(Variant<C, 0>{});     \
     }
-#define SP_LAUNCH_VARIANT(KERNEL, ...)                                                           \
-    if (a.channel_mode) { SP_LAUNCH_VARIANT_C(KERNEL, true, ##__VA_ARGS__) } else { SP_LAUNCH_VARIANT_C(KERNEL, false, ##__VA_ARGS__) }
+#define SP_LAUNCH_VARIANT_IF(BUILT, KERNEL, ...)                                                                                       \
+    auto launch_cp = [&](auto v) -> int {                                                                                              \
+        using V = decltype(v);                                                                                                         \
+        if constexpr (BUILT(1 << L, V::c, V::p))                                                                                       \
+            return launch_full_lds<KERNEL<L, V::c, V::p>>(fl.grid, fl.lds_bytes, device, stream, a, format, stage_tw, fl.gf, fl.groups, \
+                                                          ##__VA_ARGS__);                                                              \
+        else return SP_ERR_UNSUPPORTED;                                                                                                \
+    };                                                                                                                                 \
+    if (a.channel_mode) { SP_LAUNCH_VARIANT_C(true) } else { SP_LAUNCH_VARIANT_C(false) }
+#define SP_LAUNCH_VARIANT(KERNEL, ...) SP_LAUNCH_VARIANT_IF(frames_variant_built, KERNEL, ##__VA_ARGS__)
+
+// The end of a host-side launch: SP_LAUNCH_LEVELS(SIZES, NAME, extra arguments...) returns NAME<a.levels>(...) for the sizes of SIZES,
+// SP_ERR_UNSUPPORTED for any other.  Expects in scope: prefetch, fl and the launch's a, format, stage_tw, device, stream.
+#define SP_LAUNCH_LEVELS_AT(L, NAME, ...) \
+    case L: return NAME<L>(a, format, stage_tw, fl, prefetch, device, stream, ##__VA_ARGS__);
+#define SP_LAUNCH_LEVELS(SIZES, NAME, ...)              \
+    switch (a.levels) {                                 \
+        SIZES(SP_LAUNCH_LEVELS_AT, NAME, ##__VA_ARGS__) \
+    default: return SP_ERR_UNSUPPORTED;                 \
+    }
 
 SP_DECLARE_LAUNCH_N(launch_frames_n, SP_SIZES_6_13)
 
@@ -604,12 +511,7 @@ inline int launch_frames(const FrameArgs &a, int format, const double2 *stage_tw
     const int prefetch = frames_prefetch_width(a.sample_width, a.in_bounds, a.stride, a.width);
     FramesLaunch fl;
     if (frames_launch_rule(a.n, a.lut_len, a.x_end - a.frame0, cu_count, 0, fl)) return SP_ERR_UNSUPPORTED;
-    switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_n<L>(a, format, stage_tw, fl, prefetch, device, stream);
-        SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)
-#undef SP_L
-    default: return SP_ERR_UNSUPPORTED;
-    }
+    SP_LAUNCH_LEVELS(SP_SIZES_6_13, launch_frames_n)
 }
 
 }  // namespace spk2

@@ -11,19 +11,20 @@
 //     first of a group of another item;
 //   * no reply clearing and no request number: sp_plan_execute_batch queues a small clearing kernel ahead of the launch on the same
 //     stream, so no workgroup waits for another (dispatch order is undefined) and the context's single-request state is not touched.
-// The stages of the loop are k_frames' own, the fragments sp_frames_*.inc.h (sp_kernel_frames.h says why they are textual); this file
-// keeps what is the batch's: the item records, the group loop with its item switches, batch_flush and the launchers.  The measured
-// figures in the fragments' comments were measured on k_frames.
+// The stages of the loop are k_frames' own, the fragments sp_frames_*.inc.h (sp_kernel_frames.h says why they are textual and lists
+// them); this file keeps what is the batch's: the item records, the group loop with its item switches, the request and the next
+// frame over two items' records, batch_flush and the launchers.  The measured figures in the fragments' comments were measured on k_frames.
 #pragma once
 
 #include "sp_kernel_frames.h"
 
 namespace spk2 {
 
-// k_frames_batch is built for n <= 512 only.  There its prefetching variants keep k_frames' register budget (no scratch, no spilled
+// k_frames_batch is built for n <= 512 only (frames_batch_variant_built).  There its prefetching variants keep k_frames' register budget (no scratch, no spilled
 // VGPR); at n >= 1024 the item bookkeeping on top of the frame loop's peak cost them scratch and spills.  Larger plans render the items
 // of a batch one by one through k_frames: a capture of n >= 1024 fills the chip with far fewer frames, which is what batching buys.
 constexpr int kBatchMaxLog2N = 9;
+__host__ __device__ constexpr bool frames_batch_variant_built(int n, bool, int) { return n <= (1 << kBatchMaxLog2N); }
 
 // k_frames_batch (sp_plan_execute_batch): one record per item of a batch, which shares the plan (the fields of FrameArgs that describe
 // a capture, an image and a reply are taken from here instead).  A group of frames never spans two items; an item's groups are
@@ -116,9 +117,9 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
     int cur = group_item_of(bgroup, min(xcd * chunk + lane_in_xcd, groups - 1)), rq = cur;
 
 #include "sp_frames_raw_regs.inc.h"
+    // (sp_frames_request.inc.h with the capture, its length, stride and end taken from the record of item `rq`: its own copy, see there)
     auto request = [&](int xq) {
         if constexpr (PF) {
-            // (the prefetching variants only run when every frame lies inside the buffer: launch_frames)
             const BatchItemK rr = item_rec(bitems, rq);
             const int xe = rr->width;
             const int xc = xq < xe ? xq : xe - 1;
@@ -129,30 +130,18 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
             issue_raw<PFB, UNI>(rr->bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
         }
     };
-    // (HALVES, fs0 and the first request's place: as in k_frames)
-    const bool HALVES = T == 64 && group_frames == 32;
-    const int fs0 = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + fs % (FPB / 2) : fs;
+    // (the first request's place: as in sp_frames_request_body.inc.h)
     constexpr bool REQ_AFTER_TABLES = PF && !LATE_PF && LOG2N <= 10;
     if (PF && !LATE_PF && !REQ_AFTER_TABLES && xcd * chunk + lane_in_xcd < g_end) request((xcd * chunk + lane_in_xcd - item_rec(bitems, rq)->first_group) * group_frames + fs0);
 
-    constexpr bool WIN_LDS = lds_win_in_lds(N);   // taper in LDS for n <= 1024, in registers for the whole launch above
-    double *s_win = (double *)(smem + lay.off_win);
-    constexpr int MMS = mm_slots(N);
-    constexpr bool LATE_SIDE = late_side_outputs(N);
+#include "sp_frames_prologue_consts.inc.h"
     {
 #include "sp_frames_table_loads.inc.h"
         if constexpr (REQ_AFTER_TABLES) request((xcd * chunk + lane_in_xcd - item_rec(bitems, rq)->first_group) * group_frames + fs0);
 #include "sp_frames_table_stores.inc.h"
     }
 
-    const double *const wbase = s_win + tl;   // stored as the threads read it: entry e*T + tl = taper[rev4(e)*T + rev(tl)]
-    double win_reg[WIN_LDS ? 1 : 16];
-    if constexpr (!WIN_LDS) {
-        const int sidx = (int)(__brev((unsigned)tl) >> (32 - (LOG2N - 4)));
-#pragma unroll
-        for (int e = 0; e < 16; e++) win_reg[e] = a.window[rev4(e) * T + sidx];
-    }
-    lds_barrier();
+#include "sp_frames_taper.inc.h"
 
     uint32_t pf_word = 0;
 #include "sp_frames_epilogue_consts.inc.h"
@@ -203,25 +192,17 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
         }
         const int x0 = (g - item_rec(bitems, cur)->first_group) * group_frames;
         for (int r = 0; r < rounds; r++) {
-            // HALVES: the first waves of the SIMDs (slots 0 .. FPB/2-1) own the group's first half of the frames, the second waves the
-            // other half, so that each set can write its half out by itself after the workgroup's last group
-            const int fr = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + r * (FPB / 2) + fs % (FPB / 2) : r * FPB + fs;
-            const int xr = x0 + fr;
-            if (fr >= group_frames) continue;   // a slot without a frame in the group's last round (its next frame is already requested)
-            const BatchItemK cr = item_rec(bitems, cur);
-            const int x_end = cr->width;
-            const bool live = xr < x_end;
-            const int x = live ? xr : x_end - 1;
+#define SP_SLOT_RECORD const BatchItemK cr = item_rec(bitems, cur); const int x_end = cr->width;
+#define SP_X_END x_end
+#include "sp_frames_slot_deal.inc.h"
+#undef SP_X_END
+#undef SP_SLOT_RECORD
             const int64_t start = frame_start(cr->stride, x);
 
-            double re[16], im[16];
-            double win[16];
             double2 *const centre = tl == 0 ? &s_amp[gpar * group_frames + fr] : nullptr;   // thread 0 of the frame: where its raw centre sample goes
-            bool nonfinite = true;   // wave-uniform
-#pragma unroll
-            for (int e = 0; e < 16; e++) win[e] = WIN_LDS ? wbase[e * T] : win_reg[WIN_LDS ? 0 : e];
-            // the frame this slot processes next: the same slot one round on, or its frame in the workgroup's next group - whose item's
-            // record is read here, in the group's last round
+#include "sp_frames_frame_regs.inc.h"
+            // sp_frames_next_frame.inc.h with the next frame's item (`rq`, whose record is read here, in the group's last round) in every
+            // expression and load_frame_item as the generic loader: its own copy
             const bool same_group = r + 1 < rounds && (HALVES || fr + FPB < group_frames);
             rq = same_group || g + per_xcd >= g_end ? cur : group_item_of(bgroup, g + per_xcd);
             const int xn = same_group ? xr + (HALVES ? FPB / 2 : FPB)
@@ -244,25 +225,7 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
                 load_frame_item<LOG2N>(format, cr, start, tl, win, re, im, centre);
             }
 
-            unsigned tw_off = 0;
-            asm volatile("" : "+s"(tw_off));
-            const double2 *tw = stage_tw + tw_off;
-            // (the previous group's write-out in two slices around the passes, as in k_frames)
-            if (drain_x0 >= 0) {
-                lds_barrier();
-                if constexpr (!LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                drain(drain_x0, 0, 2);
-            }
-#include "sp_frames_fft.inc.h"
-
-#include "sp_frames_lr_split.inc.h"
-
-            if (drain_x0 >= 0) {
-                drain(drain_x0, 1, 2);
-                lds_barrier();
-                if constexpr (LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                drain_x0 = -1;
-            }
+#include "sp_frames_passes.inc.h"
 #include "sp_frames_pixels.inc.h"
         }
         drain_x0 = x0;
@@ -280,19 +243,11 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_batch(const FrameAr
 SP_DECLARE_LAUNCH_N(launch_frames_batch_n, SP_SIZES_6_13, const BatchItem *, const int32_t *)
 
 #ifdef SP_INST_FRAMES_LOG2N
-// (a template of its own, so that the discarded branch below names no batch kernel for n >= 1024 and none is built)
-template <int L>
-inline int launch_batch_variant(SP_LAUNCH_N_PARAMS, const BatchItem *items, const int32_t *group_item)
-{
-    SP_LAUNCH_VARIANT(k_frames_batch, items, group_item)
-}
-
 template <>
 int launch_frames_batch_n<SP_INST_FRAMES_LOG2N>(SP_LAUNCH_N_PARAMS, const BatchItem *items, const int32_t *group_item)
 {
     constexpr int L = SP_INST_FRAMES_LOG2N;
-    if constexpr (L > kBatchMaxLog2N) return SP_ERR_UNSUPPORTED;   // (not instantiated: plan_batch renders these items one by one)
-    else return launch_batch_variant<L>(a, format, stage_tw, fl, prefetch, device, stream, items, group_item);
+    SP_LAUNCH_VARIANT_IF(frames_batch_variant_built, k_frames_batch, items, group_item)   // (n >= 1024: plan_batch renders the items one by one)
 }
 #endif
 
@@ -302,12 +257,7 @@ inline int launch_frames_batch(const FrameArgs &a, int format, const double2 *st
 {
     FramesLaunch fl;
     if (groups < 1 || frames_launch_rule(a.n, a.lut_len, groups, cu_count, gf, fl)) return SP_ERR_UNSUPPORTED;
-    switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_batch_n<L>(a, format, stage_tw, fl, prefetch, device, stream, items, group_item);
-        SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10) SP_L(11) SP_L(12) SP_L(13)
-#undef SP_L
-    default: return SP_ERR_UNSUPPORTED;
-    }
+    SP_LAUNCH_LEVELS(SP_SIZES_6_13, launch_frames_batch_n, items, group_item)
 }
 
 }  // namespace spk2

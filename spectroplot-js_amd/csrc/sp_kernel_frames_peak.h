@@ -17,9 +17,8 @@
 //     variants therefore request a sub-frame's samples when it starts (k_frames' LATE_PF order) instead of one sub-frame ahead: the 16 or
 //     32 registers of the raw words are then dead during the passes, and the partner wave of the SIMD covers the load.  (Requesting one
 //     sub-frame ahead spills in the I/Q variants too: profiles/peak_experiments.txt has both spill tables and the A/B.)
-// The stages and the shell of the loop (reply clear, write-out lambdas, publication of the request's number, finale) are the fragments
-// sp_frames_*.inc.h, #included as in k_frames (sp_kernel_frames.h says why they are textual and lists them); this file keeps what is
-// the detector's: the sub-frame loop, the hold, peak_count, its launch entry.
+// The stages and the shell of the loop are the fragments sp_frames_*.inc.h (sp_kernel_frames.h says why they are textual and lists
+// them); this file keeps what is the detector's: the sub-frame loop, request_at, the hold, peak_count, its launch entry.
 #pragma once
 
 #include "sp_kernel_frames.h"
@@ -56,22 +55,17 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
             issue_raw<PFB, UNI>(a.bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
         }
     };
-    const bool HALVES = T == 64 && group_frames == 32;   // (as in k_frames)
 
     const bool owner = blockIdx.x == 0 && __builtin_amdgcn_readfirstlane(tid >> 6) == 0 && a.first;   // (wave-uniform)
-    constexpr bool WIN_LDS = lds_win_in_lds(N);
+#include "sp_frames_prologue_consts.inc.h"
     static_assert(WIN_LDS, "n <= 1024 keeps the taper in LDS");
-    double *s_win = (double *)(smem + lay.off_win);
-    constexpr int MMS = mm_slots(N);
-    constexpr bool LATE_SIDE = late_side_outputs(N);
     {
 #include "sp_frames_table_loads.inc.h"
 #include "sp_frames_reply_clear.inc.h"
 #include "sp_frames_table_stores.inc.h"
     }
 
-    const double *const wbase = s_win + tl;   // stored as the threads read it: entry e*T + tl = taper[rev4(e)*T + rev(tl)]
-    lds_barrier();
+#include "sp_frames_taper.inc.h"
 
     const spfmt::View view{a.bytes, a.nbytes, a.nelem};
     uint32_t pf_word = 0;
@@ -84,11 +78,9 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
     for (int g = xcd * chunk + lane_in_xcd; g < g_end; g += per_xcd) {
         const int x0 = a.frame0 + g * group_frames;
         for (int r = 0; r < rounds; r++) {
-            const int fr = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + r * (FPB / 2) + fs % (FPB / 2) : r * FPB + fs;
-            const int xr = x0 + fr;
-            if (fr >= group_frames) continue;   // a slot without a column in the group's last round
-            const bool live = xr < a.x_end;
-            const int x = live ? xr : a.x_end - 1;
+#define SP_X_END a.x_end
+#include "sp_frames_slot_deal.inc.h"   // (a frame there is a column here)
+#undef SP_X_END
             // the column's frame (sub-frame 0) and how many of its M sub-frames exist
             const int p0 = PF ? frame_start_in_bounds(a.stride, x) : frame_start(a.stride, x);
             const int cnt = peak_count(peak_nsamp, p0, N, peak_m);
@@ -101,45 +93,19 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_peak(const FrameArg
                 const bool last_sub = j + 1 == peak_m;
                 const int64_t start = (int64_t)p0 + (int64_t)(j < cnt ? j : cnt - 1) * N;
 
-                double re[16], im[16];
-                double win[16];
                 // thread 0 of the column's FIRST sub-frame: where the raw centre sample of gauge_amps goes
                 double2 *const centre = tl == 0 && j == 0 ? &s_amp[gpar * group_frames + fr] : nullptr;
-                bool nonfinite = true;   // wave-uniform
-#pragma unroll
-                for (int e = 0; e < 16; e++) win[e] = wbase[e * T];
+#include "sp_frames_frame_regs.inc.h"
                 if constexpr (PF) {
                     request_at((int)start);
 #include "sp_frames_decode_pf.inc.h"
                 } else {
                     asm volatile("" ::"v"(pf_word));
-                    switch (format) {
-#define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                        SP_FORMATS_BUT_CF64(SP_CASE)
-#undef SP_CASE
-                    default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                    }
+#include "sp_frames_load_generic.inc.h"
                 }
 
-                unsigned tw_off = 0;
-                asm volatile("" : "+s"(tw_off));
-                const double2 *tw = stage_tw + tw_off;
-                // the previous group's write-out in two slices around the passes of this group's first sub-frame, as in k_frames
-                if (drain_x0 >= 0) {
-                    lds_barrier();
-                    if constexpr (!LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                    drain(drain_x0, 0, 2);
-                }
-#include "sp_frames_fft.inc.h"
-
-#include "sp_frames_lr_split.inc.h"
-
-                if (drain_x0 >= 0) {
-                    drain(drain_x0, 1, 2);
-                    lds_barrier();
-                    if constexpr (LATE_SIDE) side_outputs(drain_x0, gpar ^ 1);
-                    drain_x0 = -1;
-                }
+                // (the previous group's write-out goes around the passes of this group's first sub-frame)
+#include "sp_frames_passes.inc.h"
                 if (!last_sub) {
 #pragma unroll
                     for (int e = 0; e < 16; e++) hold[e] = max_raw(hold[e], re[e] * re[e] + im[e] * im[e]);   // worker.js:92, held
@@ -177,12 +143,7 @@ inline int launch_frames_peak(const FrameArgs &a, int format, const double2 *sta
     const int prefetch = frames_prefetch_width(a.sample_width, a.in_bounds, a.stride, a.width);
     FramesLaunch fl;
     if (!frames_peak_supports(a.n) || peak_m < 2 || frames_launch_rule(a.n, a.lut_len, a.x_end - a.frame0, cu_count, 0, fl)) return SP_ERR_UNSUPPORTED;
-    switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_peak_n<L>(a, format, stage_tw, fl, prefetch, device, stream, peak_m, peak_nsamp);
-        SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10)
-#undef SP_L
-    default: return SP_ERR_UNSUPPORTED;
-    }
+    SP_LAUNCH_LEVELS(SP_SIZES_6_10, launch_frames_peak_n, peak_m, peak_nsamp)
 }
 
 }  // namespace spk2

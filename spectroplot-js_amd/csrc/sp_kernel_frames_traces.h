@@ -6,8 +6,8 @@
 // (k_traces_finish).  Three launches on the context's stream, no request number and no handshake between them:
 //   * k_traces_clear (sp_kernel_scratch.h, as k_traces_finish) sets the context's workspace u64[2 n] to the identities of the two
 //     reductions, the bit patterns of +inf (bins' minima, words [0, n)) and +0.0 (maxima, words [n, 2 n));
-//   * k_frames_traces runs k_frames' frame loop - the same launch rule, deal of groups to workgroups, loaders and LATE_PF order, the
-//     stages from the fragments sp_frames_*.inc.h - up to the L/R split.  Its epilogue per bin is |X|^2, v_max_f64 with 0.0 and v_min_f64
+//   * k_frames_traces runs k_frames' frame loop up to the L/R split (sp_frames_plain_body.inc.h; sp_kernel_frames.h lists the
+//     fragments).  Its epilogue per bin (sp_frames_traces_fold.inc.h) is |X|^2, v_max_f64 with 0.0 and v_min_f64
 //     with +inf (a NaN becomes the reduction's identity; |X|^2 is never negative and never -0, so the u64 order of the bit patterns is
 //     the numeric order) and two fire-and-forget 64-bit LDS atomics into the workgroup's pair of arrays u64[n], which sit where k_frames
 //     keeps its tile.  (In registers they would be 64 VGPRs held across a loop that sits at ~245 of 256: DESIGN.md section 11.)  A slot
@@ -51,91 +51,17 @@ __global__ __launch_bounds__(kFrameThreads, 1) void k_frames_traces(const FrameA
     static_assert(!BLOCK_SYNC, "a frame stays inside one wave");
     (void)edge_g, (void)edge_cb, (void)s_amp, (void)tile_pitch, (void)cmax;   // (the picture's: not used here)
     unsigned long long *const s_tmin = (unsigned long long *)s_tile, *const s_tmax = s_tmin + N;   // the workgroup's extremes per bin
-
-#include "sp_frames_raw_regs.inc.h"
-    auto request = [&](int xq) {
-        if constexpr (PF) {
-            // (the prefetching variants only run when every frame lies inside the buffer: launch_frames_traces)
-            const int xc = xq < a.x_end ? xq : a.x_end - 1;
-            constexpr bool UNI = T >= 64;   // a frame per wave: its start is wave-uniform
-            const int sv = frame_start_in_bounds(a.stride, xc);
-            const int64_t st = UNI ? __builtin_amdgcn_readfirstlane(sv) : sv;
-            if constexpr (PFB == 3) raw_back = (st + N) * 3 + 1 > a.nbytes ? 1 : 0;
-            issue_raw<PFB, UNI>(a.bytes, st, T, sidx_pf, raw_lo, raw_hi, raw_back);
-        }
-    };
-    const bool HALVES = T == 64 && group_frames == 32;   // (as in k_frames)
-    const int fs0 = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + fs % (FPB / 2) : fs;
-
-    constexpr bool WIN_LDS = lds_win_in_lds(N);
-    static_assert(WIN_LDS, "n <= 1024 keeps the taper in LDS");
-    double *s_win = (double *)(smem + lay.off_win);
-    constexpr int MMS = mm_slots(N);
-    constexpr bool LATE_SIDE = late_side_outputs(N);
-    {
-#include "sp_frames_table_loads.inc.h"
-        // the first frame's samples behind the table loads, unconditionally, as in k_frames
-        if constexpr (PF && !LATE_PF) request(a.frame0 + (xcd * chunk + lane_in_xcd) * group_frames + fs0);
-#include "sp_frames_table_stores.inc.h"
-        for (int i = tid; i < N; i += kThreads) {
-            s_tmin[i] = 0x7ff0000000000000ull;
-            s_tmax[i] = 0ull;
-        }
-    }
-
-    const double *const wbase = s_win + tl;   // stored as the threads read it: entry e*T + tl = taper[rev4(e)*T + rev(tl)]
-    lds_barrier();
-
-    const spfmt::View view{a.bytes, a.nbytes, a.nelem};
     const double pinf = __longlong_as_double(0x7ff0000000000000ll);
-    meet.arrive();
-    for (int g = xcd * chunk + lane_in_xcd; g < g_end; g += per_xcd) {
-        const int x0 = a.frame0 + g * group_frames;
-        for (int r = 0; r < rounds; r++) {
-            const int fr = HALVES ? (fs / (FPB / 2)) * (group_frames / 2) + r * (FPB / 2) + fs % (FPB / 2) : r * FPB + fs;
-            const int xr = x0 + fr;
-            if (fr >= group_frames) continue;   // a slot without a frame in the group's last round (its next frame is already requested)
-            const int x = xr < a.x_end ? xr : a.x_end - 1;   // past the end: the last column again (the fold is idempotent)
-            const int64_t start = frame_start(a.stride, x);
 
-            double re[16], im[16];
-            double win[16];
-            double2 *const centre = nullptr;   // (no gauge_amps here)
-            bool nonfinite = true;   // wave-uniform
-#pragma unroll
-            for (int e = 0; e < 16; e++) win[e] = wbase[e * T];
-            // the frame this slot processes next: the same slot one round on, or its frame in the workgroup's next group
-            const int xn = (r + 1 < rounds && (HALVES || fr + FPB < group_frames)) ? xr + (HALVES ? FPB / 2 : FPB)
-                                                                         : (g + per_xcd < g_end ? a.frame0 + (g + per_xcd) * group_frames + fs0 : -1);
-            if constexpr (PF && LATE_PF) request(xr);
-            if constexpr (PF) {
-#include "sp_frames_decode_pf.inc.h"
-                if (!LATE_PF && xn >= 0) request(xn);           // in flight during this frame's butterflies
-            } else {
-                switch (format) {
-#define SP_CASE(F) case F: load_frame<F>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                    SP_FORMATS_BUT_CF64(SP_CASE)
-#undef SP_CASE
-                default: load_frame<SP_FMT_CF64>(a, view, start, tl, T, LOG2N, win, re, im, centre); break;
-                }
-            }
-
-            unsigned tw_off = 0;
-            asm volatile("" : "+s"(tw_off));
-            const double2 *tw = stage_tw + tw_off;
-#include "sp_frames_fft.inc.h"
-
-#include "sp_frames_lr_split.inc.h"
-
-            // register e of thread tl holds bin i = tl + e*T
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const double v = re[e] * re[e] + im[e] * im[e];                                   // worker.js:92
-                atomicMin(&s_tmin[tl + e * T], (unsigned long long)__double_as_longlong(min_raw(pinf, v)));
-                atomicMax(&s_tmax[tl + e * T], (unsigned long long)__double_as_longlong(max_raw(0.0, v)));
-            }
-        }
+#define SP_AFTER_TABLES                        \
+    for (int i = tid; i < N; i += kThreads) {  \
+        s_tmin[i] = 0x7ff0000000000000ull;     \
+        s_tmax[i] = 0ull;                      \
     }
+#define SP_FRAME_TAIL "sp_frames_traces_fold.inc.h"
+#include "sp_frames_plain_body.inc.h"
+#undef SP_FRAME_TAIL
+#undef SP_AFTER_TABLES
 
     // the workgroup's share goes to the workspace: one pair of atomics per bin, none from a workgroup that had no group
     if (xcd * chunk + lane_in_xcd >= g_end) return;   // (uniform over the workgroup)
@@ -172,12 +98,7 @@ inline int launch_frames_traces(const FrameArgs &a, int format, const double2 *s
         return SP_ERR_UNSUPPORTED;
     fl.lds_bytes = traces_layout(a.n, a.lut_len, fl.gf).total;
     if (fl.lds_bytes > 160 * 1024) return SP_ERR_UNSUPPORTED;
-    switch (a.levels) {
-#define SP_L(L) case L: return launch_frames_traces_n<L>(a, format, stage_tw, fl, prefetch, device, stream, ws);
-        SP_L(6) SP_L(7) SP_L(8) SP_L(9) SP_L(10)
-#undef SP_L
-    default: return SP_ERR_UNSUPPORTED;
-    }
+    SP_LAUNCH_LEVELS(SP_SIZES_6_10, launch_frames_traces_n, ws)
 }
 
 }  // namespace spk2

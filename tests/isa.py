@@ -15,6 +15,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 PKG = os.path.join(ROOT, "spectroplot-js_amd")
 FRAME_TARGETS = tuple("build/frames_%d.o" % lg for lg in range(6, 14))     # k_frames and k_frames_batch
 PEAK_TARGETS = tuple("build/peak_%d.o" % lg for lg in range(6, 11))        # k_frames_peak
+INDEX_TARGETS = tuple("build/index_%d.o" % lg for lg in range(6, 14))      # k_frames_index
+TRACES_TARGETS = tuple("build/traces_%d.o" % lg for lg in range(6, 11))    # k_frames_traces
+POWER_TARGETS = tuple("build/power_%d.o" % lg for lg in range(6, 11))      # k_frames_power
 
 
 def _built(pattern, at_least):
@@ -33,6 +36,24 @@ def frame_objs():
 
 def peak_objs():
     objs = _built("peak_*.o", 5)
+    assert len(objs) == 5
+    return objs
+
+
+def index_objs():
+    objs = _built("index_*.o", 8)
+    assert len(objs) == 8
+    return objs
+
+
+def traces_objs():
+    objs = _built("traces_*.o", 5)
+    assert len(objs) == 5
+    return objs
+
+
+def power_objs():
+    objs = _built("power_*.o", 5)
     assert len(objs) == 5
     return objs
 

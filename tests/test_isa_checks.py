@@ -183,6 +183,9 @@ def test_no_valu_write_lands_on_the_data_of_a_wide_store_within_two_wait_states(
 
 _BATCH_H = "spectroplot-js_amd/csrc/sp_kernel_frames_batch.h"
 _PEAK_H = "spectroplot-js_amd/csrc/sp_kernel_frames_peak.h"
+_INDEX_H = "spectroplot-js_amd/csrc/sp_kernel_frames_index.h"
+_TRACES_H = "spectroplot-js_amd/csrc/sp_kernel_frames_traces.h"
+_POWER_H = "spectroplot-js_amd/csrc/sp_kernel_frames_power.h"
 
 
 # family -> (prefix of the mangled names, the file whose first commit is the reference, "^" for that commit's parent, the objects, streams)
@@ -190,15 +193,20 @@ STREAM_FAMILIES = {
     "k_frames": ("_ZN4spk28k_framesI", _BATCH_H, "^", isa.FRAME_TARGETS, isa.frame_objs, 96),
     "k_frames_batch": ("_ZN4spk214k_frames_batchI", _BATCH_H, "", isa.FRAME_TARGETS, isa.frame_objs, 48),
     "k_frames_peak": ("_ZN4spk213k_frames_peakI", _PEAK_H, "", isa.PEAK_TARGETS, isa.peak_objs, 60),
+    # (no later commit changed one of these three on purpose: each is pinned to the commit that added its header; k_frames_index has the
+    # 96 variants of k_frames less the three that frames_index_variant_built drops)
+    "k_frames_index": ("_ZN4spk214k_frames_indexI", _INDEX_H, "", isa.INDEX_TARGETS, isa.index_objs, 93),
+    "k_frames_traces": ("_ZN4spk215k_frames_tracesI", _TRACES_H, "", isa.TRACES_TARGETS, isa.traces_objs, 60),
+    "k_frames_power": ("_ZN4spk214k_frames_powerI", _POWER_H, "", isa.POWER_TARGETS, isa.power_objs, 60),
 }
 
 
 @pytest.mark.parametrize("family", sorted(STREAM_FAMILIES))
 def test_frame_loop_instruction_streams_match_their_reference_commit(family):
-    """Every variant <L, C, P> of the three frame-loop kernels has the instruction stream (addresses stripped) of a reference build: k_frames
-    of the commit before the batch kernel was added, k_frames_batch of the commit that added sp_kernel_frames_batch.h, k_frames_peak of the
-    commit that added sp_kernel_frames_peak.h.  What the kernels share since - the sp_frames_*.inc.h fragments of the stages, of the
-    prologue, the write-out lambdas and the finale - must not move any of them.  This guards those changes only: a later commit that
+    """Every variant <L, C, P> of the six frame-loop kernels has the instruction stream (addresses stripped) of a reference build: k_frames
+    of the commit before the batch kernel was added, each other kernel of the commit that added its header (sp_kernel_frames_batch.h,
+    _peak.h, _index.h, _traces.h, _power.h).  What the kernels share since - the sp_frames_*.inc.h fragments of the stages, of the
+    prologue, of the loop's shell, the write-out lambdas, the finale and the two whole bodies - must not move any of them.  This guards those changes only: a later commit that
     changes a kernel on purpose replaces that family's reference with its own parent (HEAD^ of the commit that last touched the kernel's
     loop)."""
     prefix, added_file, parent, targets, objs, count = STREAM_FAMILIES[family]
