@@ -444,8 +444,8 @@ int sp_plan_force_kernel(sp_plan *plan, int32_t which);
  * in every column, and width == 0, give (0, -200); an all-zero frame gives trace_min = -inf.  Hence, bit for bit,
  * min over y of trace_min[y] == dBfs_min and max over y of trace_max[y] == dBfs_max of sp_render on the same request.
  * The outputs are two f64[n] arrays; either may be NULL.  No image is written and no other reply field is produced.
- * Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.  (There is no mean-power trace: an f64
- * sum over frames depends on the deal of frames to workgroups; min and max do not.)
+ * Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.  (The mean-power trace is sp_plan_execute_mean
+ * below: an f64 sum over frames would depend on the deal of frames to workgroups, so it is an exact sum; min and max need none.)
  *
  * sp_plan_execute_traces: device-resident operands, asynchronous on the context's stream; d_trace_min / d_trace_max are device
  * pointers, 8-byte aligned (SP_ERR_INVALID_ARG otherwise).  Three kernels and no request number: a stream that is being captured is
@@ -500,6 +500,52 @@ int sp_plan_execute_power(sp_plan *plan, const void *d_bytes, size_t nbytes, int
 int sp_plan_power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db);
 int sp_render_power(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *power);
 const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
+ * Exact mean-power trace: the average spectrum of a request (a Welch PSD), bit-exact like the min and max traces.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y - the same geometry, limits, statuses, channel
+ * mode and row order y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90) - `mean` is double[n]:
+ *     mean[y] = RN( sum over x in [0, width) of power[x][y] ) / (double)width
+ * The sum is the EXACT real-number sum.  RN is one IEEE-754 round-to-nearest-even to f64; a sum at or above 2^1024 - 2^970 gives +inf.
+ * The division is one correctly rounded f64 division.  In Python: math.fsum(column) / width, with OverflowError read as +inf.
+ * A row with a NaN in any frame is NaN, and A NaN IS ANY NaN, as for the plane; otherwise a row with +inf in any frame is +inf.
+ * width == 0 writes NaN to all n entries (0 / 0).  The array is the same for both layouts and does not depend on gain, range, LUT or
+ * block_norm.  Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED, as for the plane and the
+ * traces.  The dB form is sp_plan_power_to_db applied to the n means: the dB of the mean power, NOT the mean of the dB values.
+ * How: |X|^2 is never negative, so every value is a 53-bit integer times a power of two; the values are added into a wide fixed-point
+ * accumulator per row (66 64-bit cells, cell k weighing 2^(32 k - 1074), and a count of NaNs and of +inf) with integer adds only, and
+ * the accumulator is rounded once.  Integer adds commute: THE RESULT DOES NOT DEPEND ON THE CU COUNT, THE DEAL OF FRAMES TO WORKGROUPS,
+ * THE CHUNKING OF A HOST-FED REQUEST OR THE WINDOW DESCRIBED BELOW.
+ * Cost: a workspace of the context, (66 + 2) * 8 * n bytes of device memory (0.5 MiB at n = 1024, 544 MiB at SP_MAX_N), grown and
+ * never shrunk, cleared on the stream by every request.
+ *
+ * sp_power_mean: the mean of a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_plan_power_to_db, as sp_density_from_index is of the index image.  Asynchronous on the context's stream; it carries no request
+ *   number, so a stream that is being captured is not refused.  n >= 1 (any n, not only powers of two), width >= 0, both pointers
+ *   8-byte aligned, d_mean non-NULL, d_power non-NULL when width > 0 (SP_ERR_INVALID_ARG otherwise).  The values must not be negative:
+ *   the sign bit of a value is not looked at.
+ * sp_plan_execute_mean: device operands, asynchronous.  The plane is never held whole: the frames are rendered block by block by
+ *   sp_plan_execute_power's frame loop (k_frames_power or k_scratch_power; sp_plan_force_kernel applies) into a bounded window of the
+ *   context - 64 MiB by default and at least one frame - and accumulated behind each block; then the sum is finished.  The checks are
+ *   sp_plan_execute_power's; d_mean must be 8-byte aligned and non-NULL (SP_ERR_INVALID_ARG otherwise).  No request number: the call
+ *   may be interleaved with sp_plan_execute / _index / _power on one context without a synchronisation.
+ * sp_render_mean: host buffers, synchronous, the plan cached as by sp_render.  The samples are the only bulk transfer and travel as for
+ *   sp_render_traces - a packed upload where stride > n, chunks of frames where the request is large; every chunk's frames are rendered
+ *   into the window and accumulated behind its upload, and n doubles come back in one copy, converted to dB on the device first when
+ *   db != 0.  `mean` must be 8-byte aligned and non-NULL.  sp_context_last_upload_bytes / sp_context_last_chunks report as before.
+ * sp_context_set_mean_window: (tests) the window's size in bytes; 0 restores the default.  A window below one frame holds one frame.
+ * sp_debug_exact_sum: (tests, no device needed) *sum = RN(exact sum) of `count` non-negative values through the host side of the code
+ *   the kernels run, with the NaN and inf rule; the empty sum is +0.0.  A negative value, -0.0 or -inf returns SP_ERR_INVALID_ARG.
+ * sp_plan_mean_kernel_name_for: "frames_power+mean" or "scratch_power+mean", following sp_plan_power_kernel_name_for.
+ * Out of scope: peak plans, batches, groups and sharding.py (their merge would be an element-wise integer sum of the cells),
+ * accumulation over successive captures, the accumulation fused into the frame loop, and a bound on the workspace.
+ */
+int sp_power_mean(sp_context *ctx, const double *d_power, int32_t n, int32_t width, double *d_mean);
+int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_mean);
+int sp_render_mean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *mean);
+int sp_context_set_mean_window(sp_context *ctx, size_t bytes);
+int sp_debug_exact_sum(const double *values, size_t count, double *sum);
+const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.

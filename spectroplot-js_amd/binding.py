@@ -170,6 +170,13 @@ class Library:
         L.sp_render_power.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, i32, vp]
         L.sp_plan_power_kernel_name_for.restype = C.c_char_p
         L.sp_plan_power_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_power_mean.argtypes = [vp, vp, i32, i32, vp]
+        L.sp_plan_execute_mean.argtypes = [vp, vp, sz, i32, vp]
+        L.sp_render_mean.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, i32, vp]
+        L.sp_context_set_mean_window.argtypes = [vp, sz]
+        L.sp_debug_exact_sum.argtypes = [vp, sz, C.POINTER(dbl)]
+        L.sp_plan_mean_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_mean_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -211,6 +218,16 @@ class Library:
         d = dict(zip(DENSITY_LAUNCH_FIELDS, (int(v) for v in out[:6])))
         d["rects"] = out[6:used.value].reshape(-1, 4)
         return d
+
+
+def exact_sum(values):
+    """sp_debug_exact_sum: the correctly rounded sum of non-negative doubles (math.fsum's) through the host side of the code the mean
+    kernels run; any NaN gives NaN, else any +inf gives +inf, a sum that rounds past DBL_MAX gives +inf.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    out = C.c_double()
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_exact_sum(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, C.byref(out)))
+    return out.value
 
 
 def parse_format(name):
@@ -513,6 +530,32 @@ class Context:
         self._chk(self.lib.L.sp_render_power(self.h, C.byref(req), p(data), data.size, int(width), 1 if db else 0, p(power)))
         return power
 
+    def render_mean(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, db=False, lut=None, fill=None):
+        """sp_render_mean: the exact mean-power trace of the request, f64[n] in image row order: the correctly rounded sum of |X|^2 over
+        the frames divided by width, or with db=True the dB of it.  No image is rendered; `lut` only takes part in the plan-cache key
+        (default: two grey entries).  fill: a byte the output array holds before the call (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if lut is None:
+            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        mean = np.zeros(int(n), np.float64)
+        if fill is not None:
+            mean.view(np.uint8)[...] = fill
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self.lib.L.sp_render_mean(self.h, C.byref(req), p(data), data.size, int(width), 1 if db else 0, p(mean)))
+        return mean
+
+    def power_mean(self, d_power, n, width, d_mean):
+        """sp_power_mean: the exact mean over the frames of the f64 [width, n] plane at device address d_power into f64[n] at d_mean.
+        Asynchronous on the context's stream."""
+        self._chk(self.lib.L.sp_power_mean(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_mean or None)))
+
+    def set_mean_window(self, nbytes=0):
+        """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
+        The result does not depend on it (tests)."""
+        self._chk(self.lib.L.sp_context_set_mean_window(self.h, int(nbytes)))
+
     def render_index(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False,
                      detector="sample", want_index=True, fill=None):
         """sp_render_index: render()'s reply with "index" - one colour-index byte per pixel, u8[width * n] in the RGBA image's pixel
@@ -641,6 +684,16 @@ class Plan:
         image row order within a frame).  One launch, asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_power(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                            C.c_void_p(d_power or None)))
+
+    def mean_kernel_name_for(self, nbytes, width):
+        """What execute_mean() launches for a request of this shape: "frames_power+mean" or "scratch_power+mean"."""
+        return self.ctx.lib.L.sp_plan_mean_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def execute_mean(self, d_bytes, nbytes, width, d_mean):
+        """sp_plan_execute_mean: the exact mean of |X|^2 over the request's frames into the f64[n] device array at address d_mean
+        (image row order).  Asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_mean(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                          C.c_void_p(d_mean or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -22,6 +22,7 @@
 #include "sp_kernel_frames_power.h"
 #include "sp_kernel_frames_index.h"
 #include "sp_kernel_scratch.h"
+#include "sp_kernel_mean.h"
 #include "sp_synth.h"
 #include "sp_cmap_tables.h"
 
@@ -107,6 +108,9 @@ struct sp_context {
     DeviceBuffer scratch;        // scratch kernel slabs
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
     DeviceBuffer power_plane;    // sp_render_power: the request's plane on the device, 8 * width * n bytes (grown, never shrunk)
+    DeviceBuffer mean_ws;        // a mean request's exact-sum cells, u64[spx::kSlots][n] (sp_kernel_mean.h; grown, never shrunk)
+    DeviceBuffer mean_window;    // ... and the block of frames of its plane that is being accumulated (mean_window_bytes at the most)
+    size_t mean_window_bytes = 0; // sp_context_set_mean_window: 0 is the default, kMeanWindowDefault
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
     DeviceBuffer density_index;  // sp_plan_execute_density: the request's index image, width * n bytes (grown, never shrunk)
     DeviceBuffer density_reply;  // ... and the reply record its render's side outputs go to (sphost::ReplyRecord)
@@ -374,6 +378,8 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->scratch.release();
     ctx->traces_ws.release();
     ctx->power_plane.release();
+    ctx->mean_ws.release();
+    ctx->mean_window.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
     ctx->density_reply.release();
@@ -2305,6 +2311,167 @@ extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uin
         return copies_failed(e);
     }
     return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- exact mean-power trace
+
+// The default size of the window a mean request's plane passes through, block of frames by block of frames.
+constexpr size_t kMeanWindowDefault = (size_t)64 << 20;
+
+extern "C" const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
+    return !plan ? "" : plan_power_frames(plan) ? "frames_power+mean" : "scratch_power+mean";
+}
+
+extern "C" int sp_context_set_mean_window(sp_context *ctx, size_t bytes)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    ctx->mean_window_bytes = bytes;
+    return SP_OK;
+}
+
+extern "C" int sp_debug_exact_sum(const double *values, size_t count, double *sum)
+{
+    if (!sum || (count && !values)) return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> bits(count);
+    if (count) memcpy(bits.data(), values, count * sizeof(double));
+    uint64_t r = 0;
+    if (!spx::exact_sum_bits(bits.data(), count, &r)) return SP_ERR_INVALID_ARG;
+    memcpy(sum, &r, sizeof r);
+    return SP_OK;
+}
+
+// the frames of a plane of n rows that one block of the window holds: at least one
+static int32_t mean_block_frames(const sp_context *ctx, int n, int32_t width)
+{
+    const size_t window = ctx->mean_window_bytes ? ctx->mean_window_bytes : kMeanWindowDefault;
+    size_t frames = window / (sizeof(double) * (size_t)n);
+    if (frames < 1) frames = 1;
+    return frames < (size_t)width ? (int32_t)frames : width;
+}
+
+// The workspace of a request of n rows, zero on the stream: (66 + 2) * 8 * n bytes.
+static int mean_clear(sp_context *ctx, int n)
+{
+    const size_t bytes = (size_t)spx::kSlots * sizeof(unsigned long long) * (size_t)n;
+    const int rc = ctx->mean_ws.reserve(bytes);
+    if (rc) return fail(ctx, rc, "mean workspace: out of device memory");
+    SP_HIP(ctx, hipMemsetAsync(ctx->mean_ws.p, 0, bytes, ctx->stream));
+    return SP_OK;
+}
+
+// Adds the `frames` frames of the frame-major plane at d_plane (n rows each) into the workspace.
+static int mean_accumulate(sp_context *ctx, const double *d_plane, int n, long long frames)
+{
+    if (frames <= 0) return SP_OK;
+    const int pieces = spk::mean_pieces(n, frames, ctx->cu_count);
+    const long long per = (frames + pieces - 1) / pieces;
+    hipLaunchKernelGGL(spk::k_mean_accumulate, dim3((unsigned)spk::mean_bands(n), (unsigned)pieces), dim3(spk::kMeanThreads), 0, ctx->stream,
+                       d_plane, n, frames, per, (unsigned long long *)ctx->mean_ws.p);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+static int mean_finish(sp_context *ctx, int n, int32_t width, double *d_mean)
+{
+    hipLaunchKernelGGL(spk::k_mean_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long *)ctx->mean_ws.p, n, (int)width, d_mean);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// The frames [x_begin, x_end) of a mean request: rendered block by block into the context's window by the power request's frame loop
+// and added to the workspace behind each block.  (The frame loop puts frame x at base + x * n: the window stands in for the block's
+// part of a whole plane.)
+static int mean_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = plan->req.n;
+    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
+    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
+    if (rc) return fail(ctx, rc, "mean window: out of device memory");
+    double *const d_win = (double *)ctx->mean_window.p;
+    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
+        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
+        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
+        rc = power_range(plan, d_bytes, g, x0, x1, src, base);
+        if (!rc) rc = mean_accumulate(ctx, d_win, n, x1 - x0);
+    }
+    return rc;
+}
+
+extern "C" int sp_power_mean(sp_context *ctx, const double *d_power, int32_t n, int32_t width, double *d_mean)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_mean: n >= 1 and width >= 0 are required");
+    if (!d_mean || (width > 0 && !d_power) || (((uintptr_t)d_power | (uintptr_t)d_mean) & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_mean: d_power and d_mean must be 8-byte aligned device pointers");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    int rc = mean_clear(ctx, n);
+    if (!rc) rc = mean_accumulate(ctx, d_power, n, width);
+    if (!rc) rc = mean_finish(ctx, n, width, d_mean);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_mean)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    if (rc) return rc;
+    if (!d_mean || ((uintptr_t)d_mean & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "d_mean must be an 8-byte aligned array of n doubles");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    rc = mean_clear(ctx, plan->req.n);
+    if (!rc) rc = mean_range(plan, d_bytes, g, 0, width, nullptr);
+    if (!rc) rc = mean_finish(ctx, plan->req.n, width, d_mean);
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
+// A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
+// exact sums accumulate in the workspace over the chunks; n doubles come back.
+extern "C" int sp_render_mean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *mean)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    sp_plan *plan = nullptr;
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width,
+        [&] {
+            return !mean || ((uintptr_t)mean & 7) != 0 ? fail(ctx, SP_ERR_INVALID_ARG, "mean must be an 8-byte aligned array of n doubles") : (int)SP_OK;
+        },
+        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+    if (rc) return rc;
+
+    const size_t n = (size_t)req->n;
+    hipStream_t s = ctx->stream;
+    rc = ctx->render_small.reserve(n * sizeof(double) + 16);
+    if (rc) return fail(ctx, rc, "sp_render_mean: out of memory");
+    double *const d_out = (double *)ctx->render_small.p;
+    HostFeed feed{"sp_render_mean", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_power_frames(plan), true, 0, false, nullptr};
+    return render_result(
+        ctx, plan->fmt, feed, [&] { return mean_clear(ctx, req->n); },
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) { return mean_range(plan, d_in, feed.g, x0, x1, src); },
+        [&](bool cleared, hipError_t &e) {
+            int r = cleared ? (int)SP_OK : mean_clear(ctx, req->n);   // (no chunk at all: the sum of no frames)
+            if (!r) r = mean_finish(ctx, req->n, width, d_out);
+            if (!r && db) r = power_to_db(plan, d_out, n, d_out);
+            if (!r) e = hipMemcpyAsync(mean, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
+            return r;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

@@ -7,6 +7,7 @@
  *   node spectroplot-js_amd/js/cli.js capture_433.92M_250k.cu8 --n 1024 --width 2048 [--format cu8] [--window blackmanHarris]
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
  *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] [--power power.f64] [--power-db db.f64]
+ *        [--mean mean.f64] [--mean-db mean_db.f64]
  *        --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
@@ -28,6 +29,10 @@
  * --power FILE / --power-db FILE (single-file runs, sample detector): the numeric spectrogram of the same request over the whole capture
  * (HipWorker.renderPower -> sp_render_power) as raw little-endian f64, width * n values, frame-major: |X|^2 (or, for --power-db, the dB
  * value 5 log10 |X|^2 + block_norm's dB) of frame x at value x * n + y, y the image row.
+ *
+ * --mean FILE / --mean-db FILE (single-file runs, sample detector): the exact mean-power trace of the same request over the whole capture
+ * (HipWorker.renderMean -> sp_render_mean) as raw little-endian f64, n values in image row order: per row the correctly rounded sum of
+ * |X|^2 over the frames divided by width (or, for --mean-db, the dB of that mean).
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -77,6 +82,18 @@ function writePower(buffer, format, n, width, opt, db) {
         range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
         worker.terminate()
         fs.writeFileSync(db ? opt['power-db'] : opt.power, Buffer.from(r.power.buffer, r.power.byteOffset, r.power.byteLength))
+    }, e => { worker.terminate(); throw e })
+}
+
+// --mean / --mean-db: as --power, n values
+function writeMean(buffer, format, n, width, opt, db) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const worker = new HipWorker()
+    return worker.renderMean({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
+        worker.terminate()
+        fs.writeFileSync(db ? opt['mean-db'] : opt.mean, Buffer.from(r.mean.buffer, r.mean.byteOffset, r.mean.byteLength))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -186,6 +203,8 @@ function main(argv) {
         .then(() => opt.density === undefined ? null : writeDensity(buffer, format, n, width, opt))
         .then(() => opt.power === undefined ? null : writePower(buffer, format, n, width, opt, false))
         .then(() => opt['power-db'] === undefined ? null : writePower(buffer, format, n, width, opt, true))
+        .then(() => opt.mean === undefined ? null : writeMean(buffer, format, n, width, opt, false))
+        .then(() => opt['mean-db'] === undefined ? null : writeMean(buffer, format, n, width, opt, true))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

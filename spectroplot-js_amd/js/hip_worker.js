@@ -223,6 +223,37 @@ class HipWorker {
     renderPowerSync(m, opt) { return addon().renderPowerSync(this._ctx, this._powerRequest(m, opt)) }
 
     /**
+     * The exact mean-power trace of a request (sp_render_mean) - the average spectrum, a Welch PSD: the fields renderTraces reads in, one
+     * Float64Array(n) in image row order out: per row the correctly rounded sum of |X|^2 over the request's frames divided by width, so
+     * the same bits on every device and for every chunking - or, with `{db: true}`, the dB of that mean (not the mean of the dB values).
+     * No image is rendered.  Only the sample detector has a mean.  Runs in the instance's request order; a malformed field rejects (and
+     * reports `onerror`) and never resolves to an array.
+     * @returns {Promise<{mean: Float64Array, width: number, n: number}>}
+     */
+    renderMean(m, opt) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._meanRequest(m, opt) } catch (e) { reject(e); return }
+            try {
+                addon().renderMean(this._ctx, req, (err, r) => err ? reject(err) : resolve({ mean: r.mean, width: r.width, n: r.n }))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
+        return p
+    }
+
+    _meanRequest(m, opt) {
+        if (!(m && m.buffer)) throw Object.assign(new Error('a mean request needs a buffer'), { status: -1 })
+        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the mean power of the peak detector is not supported'), { status: -4 })
+        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db) })
+    }
+
+    /** Synchronous form of renderMean (tests). */
+    renderMeanSync(m, opt) { return addon().renderMeanSync(this._ctx, this._meanRequest(m, opt)) }
+
+    /**
      * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the
      * message's colour map pixel j of imageData.data shows, so the reply is a quarter of the size and js/consumers.js `recolour` redraws
      * it under another map without a render.  The message is a worker message (`detector: 'peak'` allowed; a colour map of more than 256

@@ -25,6 +25,7 @@
 //   renderSync(handle, req)                        -> the same reply object, synchronously
 //   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
 //   renderPower(handle, req, cb) / renderPowerSync(handle, req) -> {power, width, n}: |X|^2 (or dB) per frame and bin as f64, no image
+//   renderMean(handle, req, cb) / renderMeanSync(handle, req) -> {mean, width, n}: the exact mean of |X|^2 over the frames per row (or its dB)
 //   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
 //       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
@@ -1159,6 +1160,42 @@ napi_value PowerJob::result(napi_env env)
 napi_value RenderPowerSync(napi_env env, napi_callback_info info) { return checked_sync<PowerJob>(env, info, kPower); }
 napi_value RenderPower(napi_env env, napi_callback_info info) { return checked_async<PowerJob>(env, info, kPower); }
 
+// ---- exact mean-power trace: renderMean(handle, req, cb) / renderMeanSync(handle, req) -------------------------------------------------
+// req as for renderPower -> {mean, width, n}: mean a Float64Array(n) in image row order - the correctly rounded sum of |X|^2 over the
+// request's frames divided by width, or the dB of it with db (sp_render_mean).
+const CheckedKind kMean{"renderMean", false, "renderMeanSync(handle, request)", "renderMean(handle, request, callback)",
+                        "spectroplot_hip.renderMean", "could not queue the mean request"};
+
+struct MeanJob : PowerJob {
+    std::vector<double> out;
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+void MeanJob::run()
+{
+    out.assign((size_t)req.n, 0.0);
+    status = sp_render_mean(ctx, &req, bytes, nbytes, width, db, out.data());
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value MeanJob::result(napi_env env)
+{
+    const size_t n = (size_t)req.n;
+    napi_value obj, ab, ta, v;
+    void *data = nullptr;
+    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, n * 8, &data, &ab) != napi_ok) return nullptr;
+    memcpy(data, out.data(), n * 8);
+    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "mean", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
+    return obj;
+}
+
+napi_value RenderMeanSync(napi_env env, napi_callback_info info) { return checked_sync<MeanJob>(env, info, kMean); }
+napi_value RenderMean(napi_env env, napi_callback_info info) { return checked_async<MeanJob>(env, info, kMean); }
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1481,6 +1518,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderPower", nullptr, RenderPower, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderPowerSync", nullptr, RenderPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderMean", nullptr, RenderMean, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderMeanSync", nullptr, RenderMeanSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},

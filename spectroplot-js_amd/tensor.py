@@ -1,13 +1,39 @@
-"""The numeric spectrogram as a torch tensor: sp_plan_execute_power on torch's current stream.
+"""The numeric spectrogram and its exact mean as torch tensors: sp_plan_execute_power / _mean on torch's current stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
 library (include/spectroplot_hip.h, "Power plane replies"), resident on the capture's device and ordered on torch's current stream:
 whatever the caller queues next on that stream - a reduction, a percentile, a network - sees the finished plane without a host
 synchronisation.
 """
+import contextlib
+
 import torch
 
 from . import binding
+
+
+@contextlib.contextmanager
+def _on_current_stream(ctx, dev, operands):
+    """Binds the context to torch's current stream of `dev` for the calls in the body (see power()), records the operands on it and puts
+    the context's previous binding back on the way out."""
+    current = torch.cuda.current_stream(dev)
+    stream = current
+    if stream.cuda_stream == 0:
+        stream = torch.cuda.Stream(device=dev)
+        stream.wait_stream(current)   # whatever produced the capture there
+    previous = ctx.get_stream()
+    if previous != stream.cuda_stream:
+        ctx.synchronize()
+    ctx.set_stream(stream.cuda_stream)
+    try:
+        with torch.cuda.stream(stream):
+            for t in operands:
+                t.record_stream(stream)
+            yield
+    finally:
+        ctx.set_stream(previous)
+    if stream is not current:
+        current.wait_stream(stream)   # the caller's stream (the null stream) sees the result in order
 
 
 def power(plan, capture, width, db=False, out=None):
@@ -31,24 +57,21 @@ def power(plan, capture, width, db=False, out=None):
         out = torch.empty((max(width, 0), n), dtype=torch.float64, device=dev)
     elif out.dtype != torch.float64 or out.device != dev or not out.is_contiguous() or out.numel() != count:
         raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.power: out must be a contiguous float64 tensor of width * n on the capture's device")
-    current = torch.cuda.current_stream(dev)
-    stream = current
-    if stream.cuda_stream == 0:
-        stream = torch.cuda.Stream(device=dev)
-        stream.wait_stream(current)   # whatever produced the capture there
-    previous = ctx.get_stream()
-    if previous != stream.cuda_stream:
-        ctx.synchronize()
-    ctx.set_stream(stream.cuda_stream)
-    try:
-        with torch.cuda.stream(stream):
-            capture.record_stream(stream)
-            out.record_stream(stream)
-            plan.execute_power(capture.data_ptr(), capture.numel(), width, out.data_ptr())
-            if db and count:
-                plan.power_to_db(out.data_ptr(), count, out.data_ptr())
-    finally:
-        ctx.set_stream(previous)
-    if stream is not current:
-        current.wait_stream(stream)   # the caller's stream (the null stream) sees the plane in order
+    with _on_current_stream(ctx, dev, (capture, out)):
+        plan.execute_power(capture.data_ptr(), capture.numel(), width, out.data_ptr())
+        if db and count:
+            plan.power_to_db(out.data_ptr(), count, out.data_ptr())
     return out.view(max(width, 0), n)
+
+
+def mean(plan, capture, width):
+    """The exact mean-power trace of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [n] on the same device: the
+    correctly rounded sum of |X|^2 over the `width` frames divided by width, per image row (include/spectroplot_hip.h, "Exact
+    mean-power trace").  `plan` is a binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as
+    power() queues its plane; the plane itself is never held whole."""
+    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
+        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.mean: capture must be a contiguous uint8 CUDA tensor")
+    out = torch.empty((plan.n,), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_mean(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
+    return out
