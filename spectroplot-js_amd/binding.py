@@ -321,6 +321,39 @@ def _make_request(fmt_id, n, windowc, block_norm, gain, rng, lut, channel_mode, 
     return req, (windowc, lut)
 
 
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _host_reply(width, n, lut_len, image="rgba", px=4, fill=None):
+    """The reply of a host-fed request in numpy arrays: (dict with the picture under `image` at px bytes per pixel, the dBfs
+    [min, max] array, the _Reply over both - an "index" picture is not part of it).  fill: a byte every output holds before the call."""
+    W, f = max(int(width), 0), 0 if fill is None else int(fill)
+    out = {image: np.full(px * W * n, f, np.uint8), "gauge_mins": np.full(W, f, np.uint8), "gauge_maxs": np.full(W, f, np.uint8),
+           "gauge_amps": np.full(W, f, np.uint8), "c_hist": np.full(lut_len, f, np.uint64), "cB_hist": np.full(SP_CB_HIST_SIZE, f, np.uint64)}
+    mm = np.array([0.0, -200.0]) if fill is None else np.array([float(f), float(f)])
+    rep = _Reply(_p(out[image]) if image == "rgba" else None, _p(out["gauge_mins"]), _p(out["gauge_maxs"]), _p(out["gauge_amps"]),
+                 _p(out["c_hist"]), _p(out["cB_hist"]), _p(mm))
+    return out, mm, rep
+
+
+def _device_reply(rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0, dbfs_minmax=0):
+    """The _Reply of device addresses (ints); 0 or None skips that output."""
+    return _Reply(*[a or None for a in (rgba, gauge_mins, gauge_maxs, gauge_amps, c_hist, cb_hist, dbfs_minmax)])
+
+
+def _no_picture_lut(lut):
+    """The colour map of a request that renders no picture: the caller's, or two grey entries (it only takes part in the plan-cache key)."""
+    return np.array([[0, 0, 0], [255, 255, 255]], np.uint8) if lut is None else lut
+
+
+def _launch_dict(words):
+    """sp_plan_debug_launch's words as a dict of LAUNCH_FIELDS, "kernel" as a name (5: k_frames_index)."""
+    d = dict(zip(LAUNCH_FIELDS, (int(v) for v in words)))
+    d["kernel"] = "frames_index" if d["kernel"] == 5 else KERNELS[d["kernel"]]
+    return d
+
+
 class Context:
     """One device + stream; the analogue of one reference Worker instance."""
 
@@ -435,14 +468,8 @@ class Context:
         req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
         W = int(width)
         L = len(keep[1])
-        out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
-               "gauge_maxs": np.zeros(max(W, 0), np.uint8), "gauge_amps": np.zeros(max(W, 0), np.uint8),
-               "c_hist": np.zeros(L, np.uint64), "cB_hist": np.zeros(SP_CB_HIST_SIZE, np.uint64)}
-        mm = np.array([0.0, -200.0])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rep = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
-                     p(out["cB_hist"]), p(mm))
-        self._chk(self.lib.L.sp_render(self.h, C.byref(req), p(data), data.size, W, C.byref(rep)))
+        out, mm, rep = _host_reply(W, n, L)
+        self._chk(self.lib.L.sp_render(self.h, C.byref(req), _p(data), data.size, W, C.byref(rep)))
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
@@ -456,20 +483,13 @@ class Context:
             raise ValueError("one width per capture")
         req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)   # (peak: refused)
         L = len(keep[1])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         outs, mms = [], []
         items = (_BatchItem * max(len(datas), 1))()
         for k, (d, w) in enumerate(zip(datas, widths)):
-            W = int(w)
-            out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
-                   "gauge_maxs": np.zeros(max(W, 0), np.uint8), "gauge_amps": np.zeros(max(W, 0), np.uint8),
-                   "c_hist": np.zeros(L, np.uint64), "cB_hist": np.zeros(SP_CB_HIST_SIZE, np.uint64)}
-            mm = np.array([0.0, -200.0])
+            out, mm, items[k].reply = _host_reply(w, n, L)
             items[k].bytes = d.ctypes.data
             items[k].nbytes = d.size
-            items[k].width = W
-            items[k].reply = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
-                                    p(out["cB_hist"]), p(mm))
+            items[k].width = int(w)
             outs.append(out)
             mms.append(mm)
         self._chk(self.lib.L.sp_render_batch(self.h, C.byref(req), items, len(datas)))
@@ -485,14 +505,8 @@ class Context:
         L = named_resolve(window, cmap)[2]
         req = _NamedRequest(str(fmt).encode(), str(window).encode(), str(cmap).encode(), int(n), int(bool(channel_mode)),
                             int(bool(waterfall)), float(gain), float(rng))
-        out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
-               "gauge_maxs": np.zeros(max(W, 0), np.uint8), "gauge_amps": np.zeros(max(W, 0), np.uint8),
-               "c_hist": np.zeros(L, np.uint64), "cB_hist": np.zeros(SP_CB_HIST_SIZE, np.uint64)}
-        mm = np.array([0.0, -200.0])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rep = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
-                     p(out["cB_hist"]), p(mm))
-        self._chk(self.lib.L.sp_render_named_ex(self.h, C.byref(req), detector_id(detector), p(data), data.size, W, C.byref(rep)))
+        out, mm, rep = _host_reply(W, n, L)
+        self._chk(self.lib.L.sp_render_named_ex(self.h, C.byref(req), detector_id(detector), _p(data), data.size, W, C.byref(rep)))
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
@@ -502,15 +516,12 @@ class Context:
         output arrays hold before the call (tests)."""
         fid, _ = parse_format(fmt)
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        if lut is None:
-            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
         tmin, tmax = np.zeros(n), np.zeros(n)
         if fill is not None:
             tmin[:] = fill
             tmax[:] = fill
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), p(data), data.size, int(width), p(tmin), p(tmax)))
+        self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), _p(data), data.size, int(width), _p(tmin), _p(tmax)))
         return {"trace_min": tmin, "trace_max": tmax}
 
     def render_power(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, db=False, lut=None, fill=None):
@@ -519,15 +530,12 @@ class Context:
         byte the output array holds before the call (tests)."""
         fid, _ = parse_format(fmt)
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        if lut is None:
-            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
         W = max(int(width), 0)
         power = np.zeros((W, int(n)), np.float64)
         if fill is not None:
             power.view(np.uint8)[...] = fill
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._chk(self.lib.L.sp_render_power(self.h, C.byref(req), p(data), data.size, int(width), 1 if db else 0, p(power)))
+        self._chk(self.lib.L.sp_render_power(self.h, C.byref(req), _p(data), data.size, int(width), 1 if db else 0, _p(power)))
         return power
 
     def render_mean(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, db=False, lut=None, fill=None):
@@ -536,14 +544,11 @@ class Context:
         (default: two grey entries).  fill: a byte the output array holds before the call (tests)."""
         fid, _ = parse_format(fmt)
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        if lut is None:
-            lut = np.array([[0, 0, 0], [255, 255, 255]], np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, False)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
         mean = np.zeros(int(n), np.float64)
         if fill is not None:
             mean.view(np.uint8)[...] = fill
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._chk(self.lib.L.sp_render_mean(self.h, C.byref(req), p(data), data.size, int(width), 1 if db else 0, p(mean)))
+        self._chk(self.lib.L.sp_render_mean(self.h, C.byref(req), _p(data), data.size, int(width), 1 if db else 0, _p(mean)))
         return mean
 
     def power_mean(self, d_power, n, width, d_mean):
@@ -566,15 +571,9 @@ class Context:
         req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
         W = int(width)
         L = len(keep[1])
-        f = 0 if fill is None else int(fill)
-        out = {"index": np.full(max(W, 0) * n, f, np.uint8), "gauge_mins": np.full(max(W, 0), f, np.uint8),
-               "gauge_maxs": np.full(max(W, 0), f, np.uint8), "gauge_amps": np.full(max(W, 0), f, np.uint8),
-               "c_hist": np.full(L, f, np.uint64), "cB_hist": np.full(SP_CB_HIST_SIZE, f, np.uint64)}
-        mm = np.array([0.0, -200.0]) if fill is None else np.array([float(f), float(f)])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rep = _Reply(None, p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]), p(out["cB_hist"]), p(mm))
-        self._chk(self.lib.L.sp_render_index(self.h, C.byref(req), p(data), data.size, W, C.byref(rep),
-                                             p(out["index"]) if want_index else None))
+        out, mm, rep = _host_reply(W, n, L, "index", 1, fill)
+        self._chk(self.lib.L.sp_render_index(self.h, C.byref(req), _p(data), data.size, W, C.byref(rep),
+                                             _p(out["index"]) if want_index else None))
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])
         return out
 
@@ -652,17 +651,14 @@ class Plan:
         used = C.c_size_t()
         self.ctx._chk(self.ctx.lib.L.sp_plan_debug_launch(self.h, int(nbytes), int(width), C.c_void_p(rgba or None),
                                                           out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
-        d = dict(zip(LAUNCH_FIELDS, (int(v) for v in out)))
-        d["kernel"] = KERNELS[d["kernel"]]
-        return d
+        return _launch_dict(out)
 
     def force_kernel(self, which):
         self.ctx._chk(self.ctx.lib.L.sp_plan_force_kernel(self.h, {"auto": 0, "scratch": 1, "frames": 3}[which]))
 
     def execute(self, d_bytes, nbytes, width, rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0, dbfs_minmax=0):
         """All pointer arguments are device addresses (ints); 0 skips that output. Asynchronous on the context's stream."""
-        rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
-                     dbfs_minmax or None)
+        rep = _device_reply(rgba, gauge_mins, gauge_maxs, gauge_amps, c_hist, cb_hist, dbfs_minmax)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute(self.h, C.c_void_p(d_bytes), nbytes, int(width), C.byref(rep)))
 
     def traces_kernel_name_for(self, nbytes, width):
@@ -711,16 +707,13 @@ class Plan:
         used = C.c_size_t()
         self.ctx._chk(self.ctx.lib.L.sp_plan_debug_index_launch(self.h, int(nbytes), int(width), C.c_void_p(index or None),
                                                                 out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
-        d = dict(zip(LAUNCH_FIELDS, (int(v) for v in out)))
-        d["kernel"] = "frames_index" if d["kernel"] == 5 else KERNELS[d["kernel"]]
-        return d
+        return _launch_dict(out)
 
     def execute_index(self, d_bytes, nbytes, width, index=0, rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0,
                       dbfs_minmax=0):
         """sp_plan_execute_index: execute() with the picture as one colour-index byte per pixel at device address `index` (0: side
         outputs only); `rgba` must stay 0 (the library refuses anything else)."""
-        rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
-                     dbfs_minmax or None)
+        rep = _device_reply(rgba, gauge_mins, gauge_maxs, gauge_amps, c_hist, cb_hist, dbfs_minmax)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_index(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width), C.byref(rep),
                                                            C.c_void_p(index or None)))
 
@@ -739,7 +732,7 @@ class Plan:
             arr[k].bytes = d_bytes or None
             arr[k].nbytes = int(nbytes)
             arr[k].width = int(width)
-            arr[k].reply = _Reply(*[outs.get(key) or None for key in keys])
+            arr[k].reply = _device_reply(*[outs.get(key) for key in keys])
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_batch(self.h, arr, len(items)))
 
     def execute_from_host(self, data, width, rgba=0, gauge_mins=0, gauge_maxs=0, gauge_amps=0, c_hist=0, cb_hist=0, dbfs_minmax=0):
@@ -747,8 +740,7 @@ class Plan:
         synchronised), the outputs are device addresses as for execute().  The samples travel in chunks under the renders; a sparse
         request uploads only what its frames read (ctx.last_upload_bytes())."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
-        rep = _Reply(rgba or None, gauge_mins or None, gauge_maxs or None, gauge_amps or None, c_hist or None, cb_hist or None,
-                     dbfs_minmax or None)
+        rep = _device_reply(rgba, gauge_mins, gauge_maxs, gauge_amps, c_hist, cb_hist, dbfs_minmax)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_from_host(self.h, data.ctypes.data_as(C.c_void_p), data.size, int(width), C.byref(rep)))
         return data
 
@@ -812,18 +804,12 @@ class Group:
         req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)   # (peak: refused)
         W = int(width)
         L = len(keep[1])
-        out = {"rgba": np.zeros(4 * max(W, 0) * n, np.uint8), "gauge_mins": np.zeros(max(W, 0), np.uint8),
-               "gauge_maxs": np.zeros(max(W, 0), np.uint8), "gauge_amps": np.zeros(max(W, 0), np.uint8),
-               "c_hist": np.zeros(L, np.uint64), "cB_hist": np.zeros(SP_CB_HIST_SIZE, np.uint64)}
-        mm = np.array([0.0, -200.0])
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rep = _Reply(p(out["rgba"]), p(out["gauge_mins"]), p(out["gauge_maxs"]), p(out["gauge_amps"]), p(out["c_hist"]),
-                     p(out["cB_hist"]), p(mm))
+        out, mm, rep = _host_reply(W, n, L)
         if dirty is not None:
             for k in ("rgba", "gauge_mins", "gauge_maxs", "gauge_amps"):
                 out[k][:] = dirty
         mode = {"device": 0, "host": 1}[gather]
-        status = self.lib.L.sp_group_render_ex(self.h, C.byref(req), p(data), data.size, W, C.byref(rep), mode)
+        status = self.lib.L.sp_group_render_ex(self.h, C.byref(req), _p(data), data.size, W, C.byref(rep), mode)
         if status:
             raise SpectroplotError(status, self.lib.L.sp_group_last_error(self.h).decode() or self.lib.L.sp_status_string(status).decode())
         out["dBfs_min"], out["dBfs_max"] = float(mm[0]), float(mm[1])

@@ -209,6 +209,21 @@ int validate_request(sp_context *ctx, const sp_request *r)
     return rc ? fail(ctx, rc, why) : SP_OK;
 }
 
+// The context's timing pair around what body() queues on the context's stream: ev0 in front of it and ev1 behind it where timing is
+// on.  A body that fails leaves ev1 and `timed` as they were.
+template <typename Body>
+int timed(sp_context *ctx, Body &&body)
+{
+    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = body();
+    if (rc) return rc;
+    if (ctx->timing) {
+        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    return SP_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------- host helpers
@@ -839,6 +854,24 @@ static long long scratch_blocks(int slabs_per_group, int n, int32_t frames, int 
     return blocks < 1 ? 1 : blocks;
 }
 
+// One scratch-kernel launch over `frames` frames: the workgroups, their `slabs` slabs each in the context's scratch buffer (a.scratch),
+// then launch(F, WIDE, grid, block) names the kernel - F: the format as an integral_constant, WIDE: std::true_type from n = 4096 on.
+template <typename Launch>
+static int scratch_launch(sp_context *ctx, int32_t format, spk::FrameArgs &a, int slabs, int32_t frames, Launch &&launch)
+{
+    const long long blocks = scratch_blocks(slabs, a.n, frames, ctx->cu_count);
+    int rc = ctx->scratch.reserve((size_t)blocks * (size_t)slabs * (size_t)a.n * sizeof(double));
+    if (rc) return fail(ctx, rc, "scratch: out of device memory");
+    a.scratch = (double *)ctx->scratch.p;
+    rc = dispatch_format(format, [&](auto F) {
+        const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
+        if (a.n >= 4096) launch(F, std::true_type{}, grid, block);
+        else launch(F, std::false_type{}, grid, block);
+        return SP_OK;
+    });
+    return rc ? fail(ctx, rc, "bad format") : SP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- indexed images: small kernels
 
 // k_frames_index may store the index image in 16-byte pieces with 32-bit offsets: base, width, the launch's first frame and its end are
@@ -1200,45 +1233,35 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     a.rgba_fast = pic.kind == Picture::kIndexFrames ? index_fast(a.rgba, width, n, x_begin, x_end) : rgba_fast(a.rgba, width, n);
     if (extract) a.lut_rgba = (const uint32_t *)plan->ident_lut.p;
 
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
     const int32_t peak_nsamp = (int32_t)(peak.nsamp < 2147483647 ? peak.nsamp : 2147483647);
-    if (pic.kind == Picture::kIndexFrames) {
-        if (which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "k_frames_index renders what k_frames renders");
-        rc = spk2::launch_frames_index(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames_index launch rejected the configuration");
-    } else if (which == kKernelFrames) {
-        rc = spk2::launch_frames(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames launch rejected the configuration");
-    } else if (which == kKernelFramesPeak) {
-        rc = spk2::launch_frames_peak(a, plan->req.format, plan->d_stage_tw, peak.m, peak_nsamp, ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames_peak launch rejected the configuration");
-    } else {
-        // two slabs per workgroup (re, im), and for a held peak a third: the largest |X|^2 per bin over the column's sub-frames
-        const bool hold = peak.m >= 2;
-        const long long blocks = scratch_blocks(hold ? 3 : 2, n, x_end - x_begin, ctx->cu_count);
-        rc = ctx->scratch.reserve((size_t)blocks * (hold ? 3 : 2) * (size_t)n * sizeof(double));
-        if (rc) return fail(ctx, rc, "scratch: out of device memory");
-        a.scratch = (double *)ctx->scratch.p;
-        rc = dispatch_format(plan->req.format, [&](auto F) {
-            constexpr int FMT = decltype(F)::value;
-            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
-            if (hold && n >= 4096) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, true, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
-            else if (hold) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, false, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
-            else if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, true, false>), grid, block, 0, s, a, 1, peak_nsamp);
-            else hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, false, false>), grid, block, 0, s, a, 1, peak_nsamp);
-            return SP_OK;
-        });
-        if (rc) return fail(ctx, rc, "bad format");
-    }
-    SP_HIP(ctx, hipGetLastError());
-    if (extract && x_end > x_begin) {
-        rc = extract_index_band(ctx, a.rgba, pic.image, width, n, plan->req.waterfall != 0, x_begin, x_end);
-        if (rc) return rc;
-    }
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, s));
-        ctx->timed = true;
-    }
+    rc = timed(ctx, [&]() -> int {
+        int r = SP_OK;
+        if (pic.kind == Picture::kIndexFrames) {
+            if (which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "k_frames_index renders what k_frames renders");
+            r = spk2::launch_frames_index(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
+            if (r) return fail(ctx, r, "k_frames_index launch rejected the configuration");
+        } else if (which == kKernelFrames) {
+            r = spk2::launch_frames(a, plan->req.format, plan->d_stage_tw, ctx->cu_count, ctx->device, s);
+            if (r) return fail(ctx, r, "k_frames launch rejected the configuration");
+        } else if (which == kKernelFramesPeak) {
+            r = spk2::launch_frames_peak(a, plan->req.format, plan->d_stage_tw, peak.m, peak_nsamp, ctx->cu_count, ctx->device, s);
+            if (r) return fail(ctx, r, "k_frames_peak launch rejected the configuration");
+        } else {
+            // two slabs per workgroup (re, im), and for a held peak a third: the largest |X|^2 per bin over the column's sub-frames
+            const bool hold = peak.m >= 2;
+            r = scratch_launch(ctx, plan->req.format, a, hold ? 3 : 2, x_end - x_begin, [&](auto F, auto WIDE, dim3 grid, dim3 block) {
+                constexpr int FMT = decltype(F)::value;
+                constexpr bool W = decltype(WIDE)::value;
+                if (hold) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, W, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
+                else hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, W, false>), grid, block, 0, s, a, 1, peak_nsamp);
+            });
+            if (r) return r;
+        }
+        SP_HIP(ctx, hipGetLastError());
+        if (extract && x_end > x_begin) return extract_index_band(ctx, a.rgba, pic.image, width, n, plan->req.waterfall != 0, x_begin, x_end);
+        return SP_OK;
+    });
+    if (rc) return rc;
 
     if (!last) return SP_OK;
     if (finishes_request(which)) {   // k_frames / k_frames_peak has finished the request itself
@@ -1575,6 +1598,32 @@ static int stream_chunks(sp_context *ctx, const spfmt::Format &f, HostFeed &h, L
     return rc;
 }
 
+// stream_chunks for a request whose reply comes back chunk by chunk (feed.download): copy(x0, x1, stream) queues the copy of the frames
+// [x0, x1) - never empty - on `stream`, which waits for the chunk's launch first; tail() queues what else the request has for the
+// context's stream once every chunk has been launched.  Returns when everything has arrived.
+template <typename Launch, typename Copy, typename Tail>
+static int download_chunks(sp_context *ctx, const spfmt::Format &f, HostFeed &feed, Launch &&launch, Copy &&copy, Tail &&tail)
+{
+    hipStream_t s = ctx->stream;
+    const auto copies_failed = [&](hipError_t e) { return hip_fail(ctx, e, (std::string(feed.who) + " copies").c_str()); };
+    const int rc = stream_chunks(ctx, f, feed, launch, [&](int k, int32_t x0, int32_t x1) {
+        hipError_t e = hipSuccess;
+        if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
+        if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
+        if (e == hipSuccess && x1 > x0) e = copy(x0, x1, feed.out_s);
+        return e == hipSuccess ? (int)SP_OK : copies_failed(e);
+    });
+    if (rc) return rc;
+    hipError_t e = tail();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
+    if (e != hipSuccess) {
+        drain_streams(ctx);
+        return copies_failed(e);
+    }
+    return SP_OK;
+}
+
 // The small outputs of a request side by side in a context buffer on the device, as a reply without an image.
 static int device_reply_record(DeviceBuffer &buf, const sphost::ReplyRecord &rec, sp_reply *d)
 {
@@ -1604,7 +1653,6 @@ static int render_image(sp_plan *plan, const char *who, const uint8_t *bytes, si
 {
     sp_context *ctx = plan->ctx;
     const sp_request *req = &plan->req;
-    hipStream_t s = ctx->stream;
 
     const size_t W = (size_t)width, n = (size_t)req->n;
     const size_t image_bytes = im.px * W * n;
@@ -1625,30 +1673,20 @@ static int render_image(sp_plan *plan, const char *who, const uint8_t *bytes, si
     // (a peak request with M >= 2 sub-frames per column reads more than half of the capture: the contiguous upload, chunked by columns)
     HostFeed feed{who, bytes, shape.g, shape.peak.m, request_kernel(plan, shape.peak.m) == kKernelFrames,
                   im.device_out || im.host, im.device_out ? 0 : image_bytes, !im.device_out, nullptr};
-    const auto copies_failed = [&](hipError_t e) { return hip_fail(ctx, e, (std::string(who) + " copies").c_str()); };
     // (nothing to clear: the kernels overwrite every histogram count, both range values and every gauge byte)
     auto launch = [&](int32_t x0, int32_t x1, bool first, bool last, const uint8_t *d_in, const PackedSource *src) {
         return plan_execute_range(plan, d_in, shape, x0, x1, first, last, &d, pic, src);
     };
-    rc = stream_chunks(ctx, plan->fmt, feed, launch, [&](int k, int32_t x0, int32_t x1) {
-        hipError_t e = hipSuccess;
-        if (im.device_out) return (int)SP_OK;
-        if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
-        if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
-        if (e == hipSuccess && im.host && x1 > x0)
-            e = download_band(im.host, im.host_pitch, pic.image, width, n, req->waterfall, x0, x1, feed.out_s, im.px);
-        return e == hipSuccess ? (int)SP_OK : copies_failed(e);
-    });
-    if (rc || im.device_out) return rc;
-    // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
-    // (separate copies into pageable memory cost more than the kernels of a small request)
-    hipError_t e = hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
-    if (e != hipSuccess) {
-        drain_streams(ctx);
-        return copies_failed(e);
-    }
+    if (im.device_out) return stream_chunks(ctx, plan->fmt, feed, launch, [](int, int32_t, int32_t) { return (int)SP_OK; });
+    rc = download_chunks(
+        ctx, plan->fmt, feed, launch,
+        [&](int32_t x0, int32_t x1, hipStream_t out_s) {
+            return im.host ? download_band(im.host, im.host_pitch, pic.image, width, n, req->waterfall, x0, x1, out_s, im.px) : hipSuccess;
+        },
+        // the small outputs sit side by side on the device: one copy into the context's page-locked block, handed out from there
+        // (separate copies into pageable memory cost more than the kernels of a small request)
+        [&] { return hipMemcpyAsync(ctx->host_small.p, ctx->render_small.p, rec.bytes(), hipMemcpyDeviceToHost, ctx->stream); });
+    if (rc) return rc;
     rec.unpack_side(ctx->host_small.p, *reply);
     rec.unpack_gauges(ctx->host_small.p, *reply);
     return SP_OK;
@@ -1907,15 +1945,10 @@ extern "C" int sp_density_from_index(sp_context *ctx, const uint8_t *d_index, in
     if (n < 1 || width < 0 || (width > 0 && !d_index)) return fail(ctx, SP_ERR_INVALID_ARG, "n >= 1, width >= 0 and an index image are needed");
     if ((double)width * (double)n > 4e12) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large");
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (!accumulate) SP_HIP(ctx, hipMemsetAsync(d_density, 0, (size_t)n * (size_t)lut_len * sizeof(uint32_t), ctx->stream));
-    rc = density_count(ctx, d_index, n, width, waterfall != 0, lut_len, 0, width, d_density);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&]() -> int {
+        if (!accumulate) SP_HIP(ctx, hipMemsetAsync(d_density, 0, (size_t)n * (size_t)lut_len * sizeof(uint32_t), ctx->stream));
+        return density_count(ctx, d_index, n, width, waterfall != 0, lut_len, 0, width, d_density);
+    });
 }
 
 // the index image and the reply record of a density request on device operands: both the context's, ordered on its stream
@@ -2018,19 +2051,78 @@ extern "C" int sp_debug_density_launch(int32_t n, int32_t width, int32_t waterfa
     return SP_OK;
 }
 
-// ------------------------------------------------------------------------------------------------- per-bin min / max traces
+// ------------------------------------------------------------------------------------------------- plain frame loops (traces, power planes)
 
-// k_frames_traces needs what k_frames needs of the transform - a finite taper (the (1, 0) butterflies skip their products on integer
-// samples) and the first-pass twiddle literals - and nothing of the picture: LUT length and edge ranges do not matter to a trace.
-static bool plan_traces_frames(const sp_plan *plan)
+// k_frames_traces and k_frames_power need what k_frames needs of the transform - a finite taper (the (1, 0) butterflies skip their
+// products on integer samples) and the first-pass twiddle literals - and nothing of the picture: LUT length and edge ranges do not
+// matter to a trace or a plane.
+static_assert(spk2::kTracesMaxLog2N == spk2::kPowerMaxLog2N, "plan_plain_frames asks frames_traces_supports for both kernels: their limits must agree");
+static bool plan_plain_frames(const sp_plan *plan)
 {
     return plan->force_kernel != kKernelScratch && spk2::frames_traces_supports(plan->req.n) && plan->taper_finite && plan->tw16_ok;
 }
 
+// The two kinds of plain_range: where the kernels write (Out), the slabs of a scratch workgroup, the LUT length the frame-loop launcher
+// asks for, that launcher, its refusal's text and the scratch kernel.
+struct TracesKind {
+    using Out = unsigned long long;   // the context's workspace (traces_clear)
+    static constexpr int kSlabs = 4;   // re, im, the bins' minima and maxima
+    static constexpr int kLutLen = spk2::kTracesLutLen;
+    static constexpr auto launch_frames = spk2::launch_frames_traces;
+    static constexpr const char *kRejected = "k_frames_traces launch rejected the configuration";
+    template <int FMT, bool WIDE>
+    static void launch_scratch(dim3 grid, dim3 block, hipStream_t s, const spk::FrameArgs &a, Out *out)
+    {
+        hipLaunchKernelGGL((spk::k_scratch_traces<FMT, WIDE>), grid, block, 0, s, a, out);
+    }
+};
+struct PowerKind {
+    using Out = double;   // the plane, frame x at out + x * n
+    static constexpr int kSlabs = 2;   // re, im
+    static constexpr int kLutLen = spk2::kPowerLutLen;
+    static constexpr auto launch_frames = spk2::launch_frames_power;
+    static constexpr const char *kRejected = "k_frames_power launch rejected the configuration";
+    template <int FMT, bool WIDE>
+    static void launch_scratch(dim3 grid, dim3 block, hipStream_t s, const spk::FrameArgs &a, Out *out)
+    {
+        hipLaunchKernelGGL((spk::k_scratch_power<FMT, WIDE>), grid, block, 0, s, a, out);
+    }
+};
+
+// The frame loop over frames [x_begin, x_end) of a traces or power request into `out` (`src`: as for plan_execute_range).  One launch.
+template <typename Kind>
+static int plain_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
+                       typename Kind::Out *out)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const bool frames = plan_plain_frames(plan);
+    if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
+    spk::FrameArgs a{};
+    plan_frame_args(plan, a);
+    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
+    hipStream_t s = ctx->stream;
+    if (frames) {
+        a.lut_len = Kind::kLutLen;   // (the shared prologue copies this many LUT and edge entries: the plan's tables hold them)
+        a.cells = 0;
+        const int rc = Kind::launch_frames(a, plan->req.format, plan->d_stage_tw, out, ctx->cu_count, ctx->device, s);
+        if (rc) return fail(ctx, rc, Kind::kRejected);
+    } else {
+        const int rc = scratch_launch(ctx, plan->req.format, a, Kind::kSlabs, x_end - x_begin, [&](auto F, auto WIDE, dim3 grid, dim3 block) {
+            Kind::template launch_scratch<decltype(F)::value, decltype(WIDE)::value>(grid, block, s, a, out);
+        });
+        if (rc) return rc;
+    }
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- per-bin min / max traces
+
 extern "C" const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
 {
     (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_traces_frames(plan) ? "frames_traces" : "scratch_traces";
+    return !plan ? "" : plan_plain_frames(plan) ? "frames_traces" : "scratch_traces";
 }
 
 // what every traces entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
@@ -2049,43 +2141,6 @@ static int traces_clear(sp_plan *plan)
     if (rc) return fail(ctx, rc, "traces workspace: out of device memory");
     hipLaunchKernelGGL(spk::k_traces_clear, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (unsigned long long *)ctx->traces_ws.p, n);
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
-}
-
-// The frame loop over frames [x_begin, x_end) of a traces request, into the context's workspace (`src`: as for plan_execute_range).
-static int traces_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src)
-{
-    sp_context *ctx = plan->ctx;
-    if (x_end <= x_begin) return SP_OK;
-    const int n = plan->req.n;
-    const bool frames = plan_traces_frames(plan);
-    if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    spk::FrameArgs a{};
-    plan_frame_args(plan, a);
-    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
-    unsigned long long *const ws = (unsigned long long *)ctx->traces_ws.p;
-    hipStream_t s = ctx->stream;
-    if (frames) {
-        a.lut_len = spk2::kTracesLutLen;   // (the shared prologue copies this many LUT and edge entries: the plan's tables hold them)
-        a.cells = 0;
-        const int rc = spk2::launch_frames_traces(a, plan->req.format, plan->d_stage_tw, ws, ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames_traces launch rejected the configuration");
-    } else {
-        // four slabs per workgroup (re, im, the bins' minima and maxima)
-        const long long blocks = scratch_blocks(4, n, x_end - x_begin, ctx->cu_count);
-        int rc = ctx->scratch.reserve((size_t)blocks * 4 * (size_t)n * sizeof(double));
-        if (rc) return fail(ctx, rc, "scratch: out of device memory");
-        a.scratch = (double *)ctx->scratch.p;
-        rc = dispatch_format(plan->req.format, [&](auto F) {
-            constexpr int FMT = decltype(F)::value;
-            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
-            if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_traces<FMT, true>), grid, block, 0, s, a, ws);
-            else hipLaunchKernelGGL((spk::k_scratch_traces<FMT, false>), grid, block, 0, s, a, ws);
-            return SP_OK;
-        });
-        if (rc) return fail(ctx, rc, "bad format");
-    }
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2111,16 +2166,11 @@ extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t
         return fail(ctx, SP_ERR_INVALID_ARG, "d_trace_min and d_trace_max must be 8-byte aligned");
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    rc = traces_clear(plan);
-    if (!rc) rc = traces_range(plan, d_bytes, g, 0, width, nullptr);
-    if (!rc) rc = traces_finish(plan, d_trace_min, d_trace_max);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&] {
+        int r = traces_clear(plan);
+        if (!r) r = plain_range<TracesKind>(plan, d_bytes, g, 0, width, nullptr, (unsigned long long *)ctx->traces_ws.p);
+        return r ? r : traces_finish(plan, d_trace_min, d_trace_max);
+    });
 }
 
 // A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
@@ -2140,10 +2190,12 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
     rc = ctx->render_small.reserve(2 * n * sizeof(double) + 16);
     if (rc) return fail(ctx, rc, "sp_render_traces: out of memory");
     double *const d_out = (double *)ctx->render_small.p;
-    HostFeed feed{"sp_render_traces", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_traces_frames(plan), true, 0, false, nullptr};
+    HostFeed feed{"sp_render_traces", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
     return render_result(
         ctx, plan->fmt, feed, [&] { return traces_clear(plan); },
-        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) { return traces_range(plan, d_in, feed.g, x0, x1, src); },
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
+            return plain_range<TracesKind>(plan, d_in, feed.g, x0, x1, src, (unsigned long long *)ctx->traces_ws.p);
+        },
         [&](bool, hipError_t &e) {
             const int r = traces_finish(plan, trace_min ? d_out : nullptr, trace_max ? d_out + n : nullptr);
             if (!r && trace_min) e = hipMemcpyAsync(trace_min, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
@@ -2154,16 +2206,10 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
 
 // ------------------------------------------------------------------------------------------------- power plane replies
 
-// k_frames_power needs what k_frames_traces needs of a plan (plan_traces_frames): nothing of the picture reaches a plane either.
-static bool plan_power_frames(const sp_plan *plan)
-{
-    return plan->force_kernel != kKernelScratch && spk2::frames_power_supports(plan->req.n) && plan->taper_finite && plan->tw16_ok;
-}
-
 extern "C" const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
 {
     (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_power_frames(plan) ? "frames_power" : "scratch_power";
+    return !plan ? "" : plan_plain_frames(plan) ? "frames_power" : "scratch_power";
 }
 
 // what every power entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
@@ -2172,44 +2218,6 @@ static int check_power(sp_context *ctx, int32_t detector, const spfmt::Format &f
     if (detector != SP_DETECTOR_SAMPLE)
         return fail(ctx, SP_ERR_UNSUPPORTED, "the power plane of a peak plan is not supported (the plane holds the sample detector's frames)");
     return check_capture(ctx, f, n, bytes, nbytes, width, nullptr, "");
-}
-
-// The frame loop over frames [x_begin, x_end) of a power request into the plane at d_power, frame x at d_power + x * n (`src`: as for
-// plan_execute_range).  One launch.
-static int power_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
-                       double *d_power)
-{
-    sp_context *ctx = plan->ctx;
-    if (x_end <= x_begin) return SP_OK;
-    const int n = plan->req.n;
-    const bool frames = plan_power_frames(plan);
-    if (src && !frames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
-    spk::FrameArgs a{};
-    plan_frame_args(plan, a);
-    frame_source_args(a, plan, d_bytes, g, x_begin, x_end, src);
-    hipStream_t s = ctx->stream;
-    if (frames) {
-        a.lut_len = spk2::kPowerLutLen;   // (the shared prologue copies this many LUT and edge entries: the plan's tables hold them)
-        a.cells = 0;
-        const int rc = spk2::launch_frames_power(a, plan->req.format, plan->d_stage_tw, d_power, ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames_power launch rejected the configuration");
-    } else {
-        // two slabs per workgroup (re, im)
-        const long long blocks = scratch_blocks(2, n, x_end - x_begin, ctx->cu_count);
-        int rc = ctx->scratch.reserve((size_t)blocks * 2 * (size_t)n * sizeof(double));
-        if (rc) return fail(ctx, rc, "scratch: out of device memory");
-        a.scratch = (double *)ctx->scratch.p;
-        rc = dispatch_format(plan->req.format, [&](auto F) {
-            constexpr int FMT = decltype(F)::value;
-            const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
-            if (n >= 4096) hipLaunchKernelGGL((spk::k_scratch_power<FMT, true>), grid, block, 0, s, a, d_power);
-            else hipLaunchKernelGGL((spk::k_scratch_power<FMT, false>), grid, block, 0, s, a, d_power);
-            return SP_OK;
-        });
-        if (rc) return fail(ctx, rc, "bad format");
-    }
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
 }
 
 // d_db[k] = d of d_power[k], k < count, on the context's stream (count > 0; in place where the pointers are equal)
@@ -2236,14 +2244,7 @@ extern "C" int sp_plan_execute_power(sp_plan *plan, const void *d_bytes, size_t 
     if (width == 0) return SP_OK;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    rc = power_range(plan, d_bytes, g, 0, width, nullptr, d_power);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&] { return plain_range<PowerKind>(plan, d_bytes, g, 0, width, nullptr, d_power); });
 }
 
 extern "C" int sp_plan_power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db)
@@ -2254,17 +2255,10 @@ extern "C" int sp_plan_power_to_db(sp_plan *plan, const double *d_power, size_t 
     if ((((uintptr_t)d_power | (uintptr_t)d_db) & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "d_power and d_db must be 8-byte aligned");
     if (!count) return SP_OK;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    const int rc = power_to_db(plan, d_power, count, d_db);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&] { return power_to_db(plan, d_power, count, d_db); });
 }
 
-// A request kind of stream_chunks - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
+// A request kind of download_chunks - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
 // plane comes back chunk by chunk: rows [x0, x1) of it are one contiguous copy.
 extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *power)
 {
@@ -2281,36 +2275,22 @@ extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uin
     if (rc) return rc;
 
     const size_t n = (size_t)req->n, plane_bytes = sizeof(double) * (size_t)width * n;
-    hipStream_t s = ctx->stream;
     rc = ctx->power_plane.reserve(plane_bytes + 16);
     if (rc) return fail(ctx, rc, "sp_render_power: out of memory");
     double *const d_plane = (double *)ctx->power_plane.p;
-    HostFeed feed{"sp_render_power", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_power_frames(plan), true, plane_bytes, true, nullptr};
-    const auto copies_failed = [&](hipError_t e) { return hip_fail(ctx, e, "sp_render_power copies"); };
-    rc = stream_chunks(
+    HostFeed feed{"sp_render_power", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, plane_bytes, true, nullptr};
+    return download_chunks(
         ctx, plan->fmt, feed,
         [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
-            int r = power_range(plan, d_in, feed.g, x0, x1, src, d_plane);
+            int r = plain_range<PowerKind>(plan, d_in, feed.g, x0, x1, src, d_plane);
             if (!r && db && x1 > x0) r = power_to_db(plan, d_plane + (size_t)x0 * n, (size_t)(x1 - x0) * n, d_plane + (size_t)x0 * n);
             return r;
         },
-        [&](int k, int32_t x0, int32_t x1) {
-            hipError_t e = hipSuccess;
-            if (feed.out_s != s) e = hipEventRecord(ctx->ev_rendered[k], s);
-            if (e == hipSuccess && feed.out_s != s) e = hipStreamWaitEvent(feed.out_s, ctx->ev_rendered[k], 0);
-            if (e == hipSuccess && x1 > x0)
-                e = hipMemcpyAsync(power + (size_t)x0 * n, d_plane + (size_t)x0 * n, sizeof(double) * (size_t)(x1 - x0) * n, hipMemcpyDeviceToHost,
-                                   feed.out_s);
-            return e == hipSuccess ? (int)SP_OK : copies_failed(e);
-        });
-    if (rc) return rc;
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess && feed.out_s != s) e = hipStreamSynchronize(feed.out_s);
-    if (e != hipSuccess) {
-        drain_streams(ctx);
-        return copies_failed(e);
-    }
-    return SP_OK;
+        [&](int32_t x0, int32_t x1, hipStream_t out_s) {
+            const size_t row0 = (size_t)x0 * n;
+            return hipMemcpyAsync(power + row0, d_plane + row0, sizeof(double) * (size_t)(x1 - x0) * n, hipMemcpyDeviceToHost, out_s);
+        },
+        [] { return hipSuccess; });
 }
 
 // ------------------------------------------------------------------------------------------------- exact mean-power trace
@@ -2321,7 +2301,7 @@ constexpr size_t kMeanWindowDefault = (size_t)64 << 20;
 extern "C" const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
 {
     (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_power_frames(plan) ? "frames_power+mean" : "scratch_power+mean";
+    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+mean" : "scratch_power+mean";
 }
 
 extern "C" int sp_context_set_mean_window(sp_context *ctx, size_t bytes)
@@ -2396,7 +2376,7 @@ static int mean_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry 
     for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
         const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
         double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
-        rc = power_range(plan, d_bytes, g, x0, x1, src, base);
+        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
         if (!rc) rc = mean_accumulate(ctx, d_win, n, x1 - x0);
     }
     return rc;
@@ -2409,16 +2389,11 @@ extern "C" int sp_power_mean(sp_context *ctx, const double *d_power, int32_t n, 
     if (!d_mean || (width > 0 && !d_power) || (((uintptr_t)d_power | (uintptr_t)d_mean) & 7) != 0)
         return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_mean: d_power and d_mean must be 8-byte aligned device pointers");
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    int rc = mean_clear(ctx, n);
-    if (!rc) rc = mean_accumulate(ctx, d_power, n, width);
-    if (!rc) rc = mean_finish(ctx, n, width, d_mean);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&] {
+        int r = mean_clear(ctx, n);
+        if (!r) r = mean_accumulate(ctx, d_power, n, width);
+        return r ? r : mean_finish(ctx, n, width, d_mean);
+    });
 }
 
 extern "C" int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_mean)
@@ -2430,16 +2405,11 @@ extern "C" int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t n
     if (!d_mean || ((uintptr_t)d_mean & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "d_mean must be an 8-byte aligned array of n doubles");
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    rc = mean_clear(ctx, plan->req.n);
-    if (!rc) rc = mean_range(plan, d_bytes, g, 0, width, nullptr);
-    if (!rc) rc = mean_finish(ctx, plan->req.n, width, d_mean);
-    if (rc) return rc;
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&] {
+        int r = mean_clear(ctx, plan->req.n);
+        if (!r) r = mean_range(plan, d_bytes, g, 0, width, nullptr);
+        return r ? r : mean_finish(ctx, plan->req.n, width, d_mean);
+    });
 }
 
 // A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
@@ -2461,7 +2431,7 @@ extern "C" int sp_render_mean(sp_context *ctx, const sp_request *req, const uint
     rc = ctx->render_small.reserve(n * sizeof(double) + 16);
     if (rc) return fail(ctx, rc, "sp_render_mean: out of memory");
     double *const d_out = (double *)ctx->render_small.p;
-    HostFeed feed{"sp_render_mean", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_power_frames(plan), true, 0, false, nullptr};
+    HostFeed feed{"sp_render_mean", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
     return render_result(
         ctx, plan->fmt, feed, [&] { return mean_clear(ctx, req->n); },
         [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) { return mean_range(plan, d_in, feed.g, x0, x1, src); },
@@ -2641,16 +2611,10 @@ static int batch_check_items(sp_context *ctx, const spfmt::Format &f, int n, con
     return SP_OK;
 }
 
-static int no_context(void)
-{
-    int32_t c = 0;
-    return sp_device_count(&c) == SP_OK ? SP_ERR_INVALID_ARG : SP_ERR_NO_DEVICE;
-}
-
 extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, int32_t count)
 {
     if (count < 0 || (!items && count > 0)) return SP_ERR_INVALID_ARG;
-    if (!plan) return no_context();
+    if (!plan) return no_object_status();
     if (count == 0) return SP_OK;
     sp_context *ctx = plan->ctx;
     if (plan->req.detector != SP_DETECTOR_SAMPLE)
@@ -2738,20 +2702,17 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
 
     spk::FrameArgs a{};
     plan_frame_args(plan, a);
-    if (ctx->timing) SP_HIP(ctx, hipEventRecord(ctx->ev0, s));
-    for (int l = 0; l < 2; l++) {
-        if (!w.groups[l]) continue;
-        rc = spk2::launch_frames_batch(a, plan->req.format, plan->d_stage_tw, w.gf, w.groups[l], l == 0 ? plan->fmt.width : 0,
-                                       d_rec + rec_first[l], d_map + (l ? w.groups[0] : 0), ctx->cu_count, ctx->device, s);
-        if (rc) return fail(ctx, rc, "k_frames_batch launch rejected the configuration");
-        SP_HIP(ctx, hipGetLastError());
-    }
-    SP_HIP(ctx, hipEventRecord(ctx->ev_batch_done, s));
-    if (ctx->timing) {
-        SP_HIP(ctx, hipEventRecord(ctx->ev1, s));
-        ctx->timed = true;
-    }
-    return SP_OK;
+    return timed(ctx, [&]() -> int {
+        for (int l = 0; l < 2; l++) {
+            if (!w.groups[l]) continue;
+            const int r = spk2::launch_frames_batch(a, plan->req.format, plan->d_stage_tw, w.gf, w.groups[l], l == 0 ? plan->fmt.width : 0,
+                                                    d_rec + rec_first[l], d_map + (l ? w.groups[0] : 0), ctx->cu_count, ctx->device, s);
+            if (r) return fail(ctx, r, "k_frames_batch launch rejected the configuration");
+            SP_HIP(ctx, hipGetLastError());
+        }
+        SP_HIP(ctx, hipEventRecord(ctx->ev_batch_done, s));
+        return SP_OK;
+    });
 }
 
 // sp_render_batch's device memory per sub-batch (captures, images and reply records together); a larger batch is rendered in several
@@ -2761,7 +2722,7 @@ static constexpr size_t kBatchBudget = (size_t)256 << 20;
 extern "C" int sp_render_batch(sp_context *ctx, const sp_request *req, const sp_batch_item *items, int32_t count)
 {
     if (count < 0 || (!items && count > 0)) return SP_ERR_INVALID_ARG;
-    if (!ctx) return no_context();
+    if (!ctx) return no_object_status();
     int rc = validate_request(ctx, req);
     if (rc) return rc;
     if (req->detector != SP_DETECTOR_SAMPLE)

@@ -18,6 +18,7 @@ PEAK_TARGETS = tuple("build/peak_%d.o" % lg for lg in range(6, 11))        # k_f
 INDEX_TARGETS = tuple("build/index_%d.o" % lg for lg in range(6, 14))      # k_frames_index
 TRACES_TARGETS = tuple("build/traces_%d.o" % lg for lg in range(6, 11))    # k_frames_traces
 POWER_TARGETS = tuple("build/power_%d.o" % lg for lg in range(6, 11))      # k_frames_power
+API_TARGETS = ("build/sp_api.o",)                                          # the scratch kernels and every small kernel
 
 
 def _built(pattern, at_least):
@@ -55,6 +56,12 @@ def traces_objs():
 def power_objs():
     objs = _built("power_*.o", 5)
     assert len(objs) == 5
+    return objs
+
+
+def api_objs():
+    objs = _built("sp_api.o", 1)
+    assert len(objs) == 1
     return objs
 
 
