@@ -3,6 +3,9 @@
 // One sp_context mirrors one reference Worker instance (lib/spectroplot.js:85-116): requests run in order on
 // its stream.  A plan holds everything the reference computes once per request before its frame loop
 // (lib/worker.js:30-62) plus the threshold tables that stand in for the per-pixel Math.log10.
+//
+// Host code only: the frame-loop kernels are reached through spk2::launch_frames* (sp_inst_frames.hip), every other kernel through the
+// launchers of sp_launch.h (sp_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,9 +24,8 @@
 #include "sp_kernel_frames_traces.h"
 #include "sp_kernel_frames_power.h"
 #include "sp_kernel_frames_index.h"
-#include "sp_kernel_scratch.h"
-#include "sp_kernel_mean.h"
-#include "sp_synth.h"
+#include "sp_launch.h"
+#include "sp_exact_sum.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -190,17 +192,6 @@ int hip_fail(sp_context *ctx, hipError_t e, const char *what)
         hipError_t e_ = (call);                                      \
         if (e_ != hipSuccess) return hip_fail((ctx), e_, #call);     \
     } while (0)
-
-template <typename F>
-int dispatch_format(int32_t fmt, F &&f)
-{
-    switch (fmt) {
-#define SP_CASE(X) case X: return f(std::integral_constant<int, X>{});
-        SP_FORMATS_BUT_CF64(SP_CASE) SP_CASE(SP_FMT_CF64)
-#undef SP_CASE
-    default: return SP_ERR_INVALID_ARG;
-    }
-}
 
 int validate_request(sp_context *ctx, const sp_request *r)
 {
@@ -457,8 +448,6 @@ extern "C" int sp_context_last_kernel_ms(sp_context *ctx, float *ms)
     return SP_OK;
 }
 
-__global__ void k_noop() {}
-
 extern "C" int sp_context_event_pair_overhead_ms(sp_context *ctx, float *ms)
 {
     if (!ctx || !ms) return SP_ERR_INVALID_ARG;
@@ -466,7 +455,7 @@ extern "C" int sp_context_event_pair_overhead_ms(sp_context *ctx, float *ms)
     float best = 1e30f;
     for (int i = 0; i < 8; i++) {
         SP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        hipLaunchKernelGGL(k_noop, dim3(1), dim3(64), 0, ctx->stream);
+        spk::launch_noop(ctx->stream);
         SP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         SP_HIP(ctx, hipEventSynchronize(ctx->ev1));
         float t = 0;
@@ -531,13 +520,8 @@ extern "C" int sp_synth_trinoise(sp_context *ctx, void *d_bytes, int32_t format,
     if (count == 0) return SP_OK;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const spk::SynthArgs a{(uint8_t *)d_bytes, t0, count, seed, step, gshift, amp, namp};
-    const uint64_t blocks = (count + 255) / 256;
-    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "synth: too many samples for one launch");
-    const int rc = dispatch_format(format, [&](auto F) {
-        hipLaunchKernelGGL(spk::k_synth_trinoise<decltype(F)::value>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
-        return SP_OK;
-    });
-    if (rc) return rc;
+    const int rc = spk::launch_synth_trinoise(a, format, ctx->stream);
+    if (rc) return rc == SP_ERR_UNSUPPORTED ? fail(ctx, rc, "synth: too many samples for one launch") : rc;
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -854,25 +838,18 @@ static long long scratch_blocks(int slabs_per_group, int n, int32_t frames, int 
     return blocks < 1 ? 1 : blocks;
 }
 
-// One scratch-kernel launch over `frames` frames: the workgroups, their `slabs` slabs each in the context's scratch buffer (a.scratch),
-// then launch(F, WIDE, grid, block) names the kernel - F: the format as an integral_constant, WIDE: std::true_type from n = 4096 on.
-template <typename Launch>
-static int scratch_launch(sp_context *ctx, int32_t format, spk::FrameArgs &a, int slabs, int32_t frames, Launch &&launch)
+// What a scratch-kernel launch over `frames` frames needs: its workgroups (*blocks), their `slabs` slabs each in the context's scratch
+// buffer (a.scratch).
+static int scratch_reserve(sp_context *ctx, spk::FrameArgs &a, int slabs, int32_t frames, unsigned *blocks)
 {
-    const long long blocks = scratch_blocks(slabs, a.n, frames, ctx->cu_count);
-    int rc = ctx->scratch.reserve((size_t)blocks * (size_t)slabs * (size_t)a.n * sizeof(double));
+    *blocks = (unsigned)scratch_blocks(slabs, a.n, frames, ctx->cu_count);
+    const int rc = ctx->scratch.reserve((size_t)*blocks * (size_t)slabs * (size_t)a.n * sizeof(double));
     if (rc) return fail(ctx, rc, "scratch: out of device memory");
     a.scratch = (double *)ctx->scratch.p;
-    rc = dispatch_format(format, [&](auto F) {
-        const dim3 grid((unsigned)blocks), block(spk::kScratchThreads);
-        if (a.n >= 4096) launch(F, std::true_type{}, grid, block);
-        else launch(F, std::false_type{}, grid, block);
-        return SP_OK;
-    });
-    return rc ? fail(ctx, rc, "bad format") : SP_OK;
+    return SP_OK;
 }
 
-// ------------------------------------------------------------------------------------------------- indexed images: small kernels
+// ------------------------------------------------------------------------------------------------- indexed images: the render_extract path
 
 // k_frames_index may store the index image in 16-byte pieces with 32-bit offsets: base, width, the launch's first frame and its end are
 // multiples of 16 (every row piece of 16 frames then lies aligned and is whole or absent), the image is below 4 GiB
@@ -880,25 +857,6 @@ static bool index_fast(const uint8_t *index, int32_t width, int n, int32_t x_beg
 {
     return index && ((uintptr_t)index & 15) == 0 && (width & 15) == 0 && ((x_begin | x_end) & 15) == 0 && width < (1 << 24)
            && (double)width * (double)n <= 4294967296.0;
-}
-
-// Byte 0 of every pixel of a band of an RGBA image: `rows` rows of row_px pixels, pitch_px pixels apart in both images.  A thread takes
-// the four pixels [4q, 4q + 4) of a row: one 16-byte load and one dword store where both lie aligned and the row has them, else pixel
-// by pixel (a row's ragged end, rows that start off 16 bytes).
-__global__ void k_extract_index(const uint8_t *__restrict__ rgba, uint8_t *__restrict__ index, size_t row_px, size_t rows, size_t pitch_px)
-{
-    const size_t quads = (row_px + 3) / 4;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= quads * rows) return;
-    const size_t r = i / quads, q = i % quads;
-    const uint8_t *const src = rgba + 4 * (r * pitch_px + 4 * q);
-    uint8_t *const dst = index + r * pitch_px + 4 * q;
-    if (4 * q + 4 <= row_px && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 3) == 0) {
-        const uint4 v = *(const uint4 *)src;
-        *(uint32_t *)dst = (v.x & 255u) | ((v.y & 255u) << 8) | ((v.z & 255u) << 16) | (v.w << 24);
-        return;
-    }
-    for (size_t k = 0; k < 4 && 4 * q + k < row_px; k++) dst[k] = src[4 * k];
 }
 
 // frames [x_begin, x_end) of the temporary RGBA image -> the same frames of the index image (both `width` frames wide)
@@ -909,220 +867,10 @@ static int extract_index_band(sp_context *ctx, const uint8_t *d_rgba, uint8_t *d
     // waterfall: rows width - x_end .. width - 1 - x_begin, contiguous; spectrogram: columns x_begin .. x_end - 1 of every row
     const size_t first = waterfall ? N * (W - (size_t)x_end) : (size_t)x_begin;
     const size_t row_px = waterfall ? N * band : band, rows = waterfall ? 1 : N, pitch = waterfall ? N * band : W;
-    const size_t blocks = (((row_px + 3) / 4) * rows + 255) / 256;
-    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one extraction launch");
-    hipLaunchKernelGGL(k_extract_index, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_rgba + 4 * first, d_index + first, row_px, rows, pitch);
+    const int rc = spk::launch_extract_index(d_rgba + 4 * first, d_index + first, row_px, rows, pitch, ctx->stream);
+    if (rc) return fail(ctx, rc, "image too large for one extraction launch");
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
-}
-
-// sp_index_to_rgba's table travels in the kernel arguments (1 KiB): nothing to copy, nothing of the caller's to keep alive
-struct IndexLut {
-    uint32_t v[256];
-};
-
-// index -> RGBA through a LUT.  The index image is read in 16-byte units from its first aligned byte on, one unit per thread: a 16-byte
-// load and four 16-byte stores where the unit's pixels lie aligned in the RGBA image, dword or byte stores where they do not; the
-// pixels in front of the first unit and behind the last one (at most 15 each) are taken byte-wise by workgroup 0's first threads.
-__global__ void k_index_to_rgba(const uint8_t *__restrict__ index, size_t pixels, const IndexLut lut, uint8_t *__restrict__ rgba)
-{
-    __shared__ uint32_t s_lut[256];
-    s_lut[threadIdx.x] = lut.v[threadIdx.x];
-    __syncthreads();
-    const auto put = [&](size_t i, uint32_t c) {
-        uint8_t *const d = rgba + 4 * i;
-        if (((uintptr_t)d & 3) == 0) {
-            *(uint32_t *)d = c;
-        } else {
-            for (int k = 0; k < 4; k++) d[k] = (uint8_t)(c >> (8 * k));
-        }
-    };
-    size_t head = (size_t)(-(intptr_t)(uintptr_t)index) & 15;
-    if (head > pixels) head = pixels;
-    const size_t units = (pixels - head) / 16, tail0 = head + 16 * units;
-    if (blockIdx.x == 0) {
-        const size_t t = threadIdx.x;
-        if (t < head) put(t, s_lut[index[t]]);
-        else if (t - head < pixels - tail0) put(tail0 + (t - head), s_lut[index[tail0 + (t - head)]]);
-    }
-    const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= units) return;
-    const size_t i0 = head + 16 * u;
-    const uint4 v = *(const uint4 *)(index + i0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    const bool wide = ((uintptr_t)(rgba + 4 * i0) & 15) == 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t c0 = s_lut[w[k] & 255u], c1 = s_lut[(w[k] >> 8) & 255u], c2 = s_lut[(w[k] >> 16) & 255u], c3 = s_lut[w[k] >> 24];
-        if (wide) {
-            *(uint4 *)(rgba + 4 * (i0 + 4 * k)) = make_uint4(c0, c1, c2, c3);
-        } else {
-            put(i0 + 4 * k, c0);
-            put(i0 + 4 * k + 1, c1);
-            put(i0 + 4 * k + 2, c2);
-            put(i0 + 4 * k + 3, c3);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------- persistence spectrum: the count
-
-// k_density_count's decomposition: a workgroup counts a rectangle of the index image - `rows` image rows x `frames` frames - into one
-// u32[256] histogram per row in LDS and then adds its non-zero cells to the caller's array.  It depends on n, the layout and the frame
-// range only.  Spectrogram layout (a row's frames are consecutive bytes): 8 rows x 2048 frames, 8 KiB of LDS, 16 Ki pixels against at
-// most 2048 global atomics.  Waterfall layout (a frame's bins are consecutive bytes, so a workgroup wants many bins for whole
-// cache lines): 64 rows x 512 frames, 64 KiB of LDS, 32 Ki pixels against at most 16 Ki global atomics.
-constexpr int kDensityThreads = 256;
-constexpr int kDensityRowsSpectrogram = 8, kDensityFramesSpectrogram = 2048;
-constexpr int kDensityRowsWaterfall = 64, kDensityFramesWaterfall = 512;
-constexpr int kDensityAhead = 4;   // loads a lane has in flight before it counts the first
-
-struct DensityShape {
-    int rows, frames;          // of one workgroup's rectangle
-    long long bands, pieces;   // ceil(n / rows) bands of rows x ceil(range / frames) pieces of frames: workgroup = band * pieces + piece
-};
-
-__host__ __device__ inline DensityShape density_shape(int n, bool waterfall, int x_begin, int x_end)
-{
-    DensityShape d;
-    d.rows = waterfall ? kDensityRowsWaterfall : kDensityRowsSpectrogram;
-    d.frames = waterfall ? kDensityFramesWaterfall : kDensityFramesSpectrogram;
-    d.bands = ((long long)n + d.rows - 1) / d.rows;
-    d.pieces = ((long long)x_end - x_begin + d.frames - 1) / d.frames;
-    return d;
-}
-
-// the rectangle of workgroup wg: rows [y0, y1) x frames [x0, x1), inside [0, n) x [x_begin, x_end)
-__host__ __device__ inline void density_rect(const DensityShape &d, int n, int x_begin, int x_end, long long wg, int &y0, int &y1, int &x0,
-                                             int &x1)
-{
-    const long long band = wg / d.pieces, piece = wg % d.pieces;
-    const long long ya = band * d.rows, yb = ya + d.rows, xa = x_begin + piece * d.frames, xb = xa + d.frames;
-    y0 = (int)ya;
-    y1 = (int)(yb < n ? yb : n);
-    x0 = (int)xa;
-    x1 = (int)(xb < x_end ? xb : x_end);
-}
-
-// The frames [x_begin, x_end) of an index image (n rows, `width` frames, either layout) counted per image row.  Slot s of the workgroup
-// keeps row y0 + s; the cell of index g is s * 256 + ((g + s) & 255): a histogram is 256 wide whatever lut_len is, so no byte can
-// index past it, and rotated by its slot, so that one index in neighbouring rows (a waterfall wave's lanes) lies in different banks.
-// Equal neighbours are merged before the LDS add - a lane's 16 frames of one row (spectrogram), a lane's successive frames of its four
-// bins (waterfall) - so a flat row costs one add per 16 pixels instead of 16 to one address.
-template <bool WATERFALL>
-__global__ void __launch_bounds__(kDensityThreads)
-k_density_count(const uint8_t *__restrict__ index, int n, int width, int x_begin, int x_end, int lut_len, uint32_t *__restrict__ density)
-{
-    constexpr int ROWS = WATERFALL ? kDensityRowsWaterfall : kDensityRowsSpectrogram;
-    __shared__ uint32_t s_h[ROWS * 256];
-    const int t = threadIdx.x;
-    for (int i = t; i < ROWS * 256; i += kDensityThreads) s_h[i] = 0;
-    __syncthreads();
-    const DensityShape d = density_shape(n, WATERFALL, x_begin, x_end);
-    int y0, y1, x0, x1;
-    density_rect(d, n, x_begin, x_end, (long long)blockIdx.x, y0, y1, x0, x1);
-    const auto add = [&](int slot, uint32_t g, uint32_t count) { atomicAdd(&s_h[slot * 256 + (int)((g + (uint32_t)slot) & 255u)], count); };
-
-    if (!WATERFALL) {
-        // image: n rows x width columns; 32 lanes per row, a lane takes 16 consecutive frames of its row per pass (512 frames a pass):
-        // one 16-byte load where the piece is whole and lies aligned, four dwords where it lies 4-byte aligned, else byte by byte.
-        // The loads of kDensityAhead passes are issued before the first of them is counted (a pass is a load and the LDS adds that
-        // wait for it; one after the other, a workgroup's time is its passes' memory latencies added up).
-        const int slot = t >> 5, y = y0 + slot;
-        if (y < y1) {
-            const uint8_t *const row = index + (size_t)y * (size_t)width;
-            const auto fetch = [&](long long xa, uint32_t (&w)[4]) -> int {   // -> the piece's pixels (0: it lies behind the range)
-                w[0] = w[1] = w[2] = w[3] = 0;
-                if (xa >= x1) return 0;
-                const uint8_t *const p = row + xa;
-                const int cnt = x1 - xa < 16 ? (int)(x1 - xa) : 16;
-                if (cnt == 16 && ((uintptr_t)p & 15) == 0) {
-                    const uint4 v = *(const uint4 *)p;
-                    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-                } else if (cnt == 16 && ((uintptr_t)p & 3) == 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) w[k] = ((const uint32_t *)p)[k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 16; k++)
-                        if (k < cnt) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
-                }
-                return cnt;
-            };
-            const auto count = [&](const uint32_t (&w)[4], int cnt) {
-                if (cnt < 1) return;
-                uint32_t cur = w[0] & 255u, run = 1;
-#pragma unroll
-                for (int k = 1; k < 16; k++) {
-                    const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-                    if (k < cnt) {
-                        if (b == cur) {
-                            run++;
-                        } else {
-                            add(slot, cur, run);
-                            cur = b;
-                            run = 1;
-                        }
-                    }
-                }
-                add(slot, cur, run);
-            };
-            for (long long xa = (long long)x0 + 16 * (t & 31); xa < x1; xa += 512 * kDensityAhead) {
-                uint32_t w[kDensityAhead][4];
-                int cnt[kDensityAhead];
-#pragma unroll
-                for (int u = 0; u < kDensityAhead; u++) cnt[u] = fetch(xa + 512 * u, w[u]);
-#pragma unroll
-                for (int u = 0; u < kDensityAhead; u++) count(w[u], cnt[u]);
-            }
-        }
-    } else {
-        // image: width rows x n columns, frame x in row width - 1 - x, image row y in column n - 1 - y: the band's rows are the
-        // columns [n - y1, n - y0).  16 lanes per frame, a lane takes four consecutive columns (one dword where they exist and lie
-        // aligned, else bytes) of every 16th frame, kDensityAhead loads ahead as above; byte j of its word belongs to slot top - j.
-        const int cols = y1 - y0, q = t & 15, valid = cols - 4 * q < 4 ? cols - 4 * q : 4, top = cols - 1 - 4 * q;
-        if (valid > 0) {
-            const auto flush = [&](uint32_t word, uint32_t count) {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (j < valid) add(top - j, (word >> (8 * j)) & 255u, count);
-            };
-            const auto fetch = [&](long long x) -> uint32_t {   // (x < x1)
-                const uint8_t *const p = index + (size_t)((long long)width - 1 - x) * (size_t)n + (size_t)(n - y1 + 4 * q);
-                if (valid == 4 && ((uintptr_t)p & 3) == 0) return *(const uint32_t *)p;
-                uint32_t word = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (j < valid) word |= (uint32_t)p[j] << (8 * j);
-                return word;
-            };
-            uint32_t held = 0, run = 0;
-            for (long long xa = (long long)x0 + (t >> 4); xa < x1; xa += 16 * kDensityAhead) {
-                uint32_t word[kDensityAhead];
-#pragma unroll
-                for (int u = 0; u < kDensityAhead; u++) word[u] = xa + 16 * u < x1 ? fetch(xa + 16 * u) : 0u;
-#pragma unroll
-                for (int u = 0; u < kDensityAhead; u++) {
-                    if (xa + 16 * u >= x1) continue;
-                    if (run && word[u] == held) {
-                        run++;
-                    } else {
-                        if (run) flush(held, run);
-                        held = word[u];
-                        run = 1;
-                    }
-                }
-            }
-            if (run) flush(held, run);
-        }
-    }
-    __syncthreads();
-    // the workgroup's share: its non-zero cells of indices the map has, one no-return atomic each (consecutive lanes, consecutive cells)
-    for (int i = t; i < ROWS * 256; i += kDensityThreads) {
-        const int slot = i >> 8, y = y0 + slot, g = (i - slot) & 255;
-        const uint32_t v = s_h[i];
-        if (v && y < y1 && g < lut_len) atomicAdd(&density[(size_t)y * (size_t)lut_len + (size_t)g], v);
-    }
 }
 
 // frames [x_begin, x_end) of the index image at d_index ADDED to d_density, on the context's stream
@@ -1130,15 +878,8 @@ static int density_count(sp_context *ctx, const uint8_t *d_index, int n, int32_t
                          int32_t x_end, uint32_t *d_density)
 {
     if (x_end <= x_begin) return SP_OK;
-    const DensityShape d = density_shape(n, waterfall, x_begin, x_end);
-    const long long grid = d.bands * d.pieces;
-    if (grid > 0x7fffffffll) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one counting launch");
-    if (waterfall)
-        hipLaunchKernelGGL(k_density_count<true>, dim3((unsigned)grid), dim3(kDensityThreads), 0, ctx->stream, d_index, n, width, x_begin, x_end,
-                           lut_len, d_density);
-    else
-        hipLaunchKernelGGL(k_density_count<false>, dim3((unsigned)grid), dim3(kDensityThreads), 0, ctx->stream, d_index, n, width, x_begin, x_end,
-                           lut_len, d_density);
+    const int rc = spk::launch_density_count(d_index, n, width, waterfall, x_begin, x_end, lut_len, d_density, ctx->stream);
+    if (rc) return fail(ctx, rc, "image too large for one counting launch");
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -1186,13 +927,6 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     if (src && which != kKernelFrames) return fail(ctx, SP_ERR_INVALID_ARG, "a packed source is for the frame-loop kernel only");
     rc = finishes_request(which) ? SP_OK : ctx->frame_minmax.reserve(2 * (size_t)width * sizeof(double));
     if (rc) return fail(ctx, rc, "workspace: out of device memory");
-    int finish_blocks = 3 * ((width + spk::kFinishThreads - 1) / spk::kFinishThreads);   // three roles per 256 frames
-    {
-        const int bins = plan->req.lut_len > SP_CB_HIST_SIZE ? plan->req.lut_len : SP_CB_HIST_SIZE;   // it also moves the histograms
-        const int hb = (bins + spk::kFinishThreads - 1) / spk::kFinishThreads;
-        if (finish_blocks < hb) finish_blocks = hb;
-        finish_blocks += 1;          // the dBfs range: a workgroup of its own, behind neither the histograms nor a gauge
-    }
     // [0,4) k_frames: the number of the last request whose reply workgroup 0 has cleared; scratch kernel: [16,32) bit patterns of the
     // extreme |X|^2 of a request, [64, ...) colour and centi-bel histogram accumulators, back at their initial values when a request ends
     const size_t acc_bytes = 64 + (SP_MAX_LUT + SP_CB_HIST_SIZE) * sizeof(unsigned long long);
@@ -1249,13 +983,11 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
         } else {
             // two slabs per workgroup (re, im), and for a held peak a third: the largest |X|^2 per bin over the column's sub-frames
             const bool hold = peak.m >= 2;
-            r = scratch_launch(ctx, plan->req.format, a, hold ? 3 : 2, x_end - x_begin, [&](auto F, auto WIDE, dim3 grid, dim3 block) {
-                constexpr int FMT = decltype(F)::value;
-                constexpr bool W = decltype(WIDE)::value;
-                if (hold) hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, W, true>), grid, block, 0, s, a, peak.m, peak_nsamp);
-                else hipLaunchKernelGGL((spk::k_scratch_radix2<FMT, W, false>), grid, block, 0, s, a, 1, peak_nsamp);
-            });
+            unsigned blocks;
+            r = scratch_reserve(ctx, a, hold ? 3 : 2, x_end - x_begin, &blocks);
             if (r) return r;
+            r = spk::launch_scratch_radix2(a, plan->req.format, blocks, hold, peak.m, peak_nsamp, s);
+            if (r) return fail(ctx, r, "bad format");
         }
         SP_HIP(ctx, hipGetLastError());
         if (extract && x_end > x_begin) return extract_index_band(ctx, a.rgba, pic.image, width, n, plan->req.waterfall != 0, x_begin, x_end);
@@ -1292,7 +1024,7 @@ static int plan_execute_range(sp_plan *plan, const void *d_bytes, const RequestS
     fa.acc_cb = a.cb_hist;
     fa.out_c = (unsigned long long *)out->c_hist;
     fa.out_cb = (unsigned long long *)out->cb_hist;
-    hipLaunchKernelGGL(spk::k_finish_frames, dim3((unsigned)finish_blocks), dim3(spk::kFinishThreads), 0, s, fa);
+    spk::launch_finish_frames(fa, s);
     SP_HIP(ctx, hipGetLastError());
     ctx->acc_dirty = false;
     return SP_OK;
@@ -1348,43 +1080,13 @@ extern "C" int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count,
 
 // ------------------------------------------------------------------------------------------------- merge of slice replies
 
-// `rank_stride`: 64-bit words between two ranks' records of the same render; blockIdx.y: the render of a batch (its records start
-// blockIdx.y * record_len words into every rank's block, its merged record blockIdx.y * record_len words into the outputs)
-__global__ void k_merge_replies(const unsigned long long *rec, int count, int lut_len, size_t rank_stride, unsigned long long *c_hist,
-                                unsigned long long *cb_hist, double *minmax)
-{
-    const int stride = lut_len + SP_CB_HIST_SIZE + 2;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t shift = (size_t)blockIdx.y * (size_t)stride;
-    rec += shift;
-    if (i < lut_len + SP_CB_HIST_SIZE) {
-        unsigned long long s = 0;
-        for (int r = 0; r < count; r++) s += rec[(size_t)r * rank_stride + i];                      // spectroplot.js:1232-1238
-        if (i < lut_len) {
-            if (c_hist) c_hist[shift + i] = s;
-        } else if (cb_hist) {
-            cb_hist[shift + i - lut_len] = s;
-        }
-    } else if (i < stride && minmax) {
-        const int k = i - (lut_len + SP_CB_HIST_SIZE);                                              // 0: min, 1: max
-        double v = __longlong_as_double((long long)rec[i]);
-        for (int r = 1; r < count; r++) {
-            const double w = __longlong_as_double((long long)rec[(size_t)r * rank_stride + i]);
-            v = k == 0 ? (w < v ? w : v) : (w > v ? w : v);                                         // the `<` / `>` updates of :1230-1231
-        }
-        minmax[shift + k] = v;
-    }
-}
-
 extern "C" int sp_merge_replies(sp_context *ctx, const void *d_records, int32_t count, int32_t lut_len, uint64_t *d_c_hist,
                                 uint64_t *d_cb_hist, double *d_dbfs_minmax)
 {
     if (!ctx || !d_records || count < 1 || lut_len < 1 || lut_len > SP_MAX_LUT) return SP_ERR_INVALID_ARG;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    const int total = (int)sphost::ReplyRecord{(size_t)lut_len, 0}.words();
-    hipLaunchKernelGGL(k_merge_replies, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)d_records, (int)count, (int)lut_len, (size_t)total, (unsigned long long *)d_c_hist,
-                       (unsigned long long *)d_cb_hist, d_dbfs_minmax);
+    spk::launch_merge_replies((const unsigned long long *)d_records, count, lut_len, sphost::ReplyRecord{(size_t)lut_len, 0}.words(), 1,
+                              (unsigned long long *)d_c_hist, (unsigned long long *)d_cb_hist, d_dbfs_minmax, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -1395,43 +1097,15 @@ extern "C" int sp_merge_replies_batch(sp_context *ctx, const void *d_gathered, i
         return SP_ERR_INVALID_ARG;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const sphost::ReplyRecord rec{(size_t)lut_len, 0};
-    const int total = (int)rec.words();
-    // the merged records keep the record layout [c_hist | cB_hist | min, max]: the three outputs are one block, `total` words per render
+    // the merged records keep the record layout [c_hist | cB_hist | min, max]: the three outputs are one block, rec.words() per render
     const sp_reply m = rec.view(d_merged);
-    hipLaunchKernelGGL(k_merge_replies, dim3((unsigned)((total + 255) / 256), (unsigned)renders), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)d_gathered, (int)ranks, (int)lut_len, (size_t)renders * (size_t)total,
-                       (unsigned long long *)m.c_hist, (unsigned long long *)m.cb_hist, m.dbfs_minmax);
+    spk::launch_merge_replies((const unsigned long long *)d_gathered, ranks, lut_len, (size_t)renders * rec.words(), renders,
+                              (unsigned long long *)m.c_hist, (unsigned long long *)m.cb_hist, m.dbfs_minmax, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- strip placement
-
-// putImageData(strip, offset, 0) for every gathered strip at once (lib/spectroplot.js:1241-1244): strip r of `count`, laid end to end in
-// `strips` as an all-gather / gather delivers them, goes to columns [r * slice_width, (r + 1) * slice_width) of the n x width image
-// (spectrogram), or to rows [width - slice_width - r * slice_width, ...) of the width x n image (waterfall: row bands in reverse order).
-// One thread moves one V (16 bytes = 4 pixels where the widths allow, else one pixel); reads and writes are whole row pieces.
-// (spgeo::SliceLayout in sp_geometry.h is the host-side twin of this arithmetic.)
-template <typename V>
-__global__ void k_place_strips(uint8_t *__restrict__ image, const uint8_t *__restrict__ strips, int count, int n, int width, int slice_width,
-                               int waterfall)
-{
-    constexpr int PX = (int)sizeof(V) / 4;
-    const size_t units_per_strip = (size_t)slice_width * (size_t)n / PX;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= units_per_strip * (size_t)count) return;
-    const int r = (int)(i / units_per_strip);
-    const size_t u = i % units_per_strip;
-    size_t dst;
-    if (waterfall) {
-        dst = ((size_t)(width - slice_width - r * slice_width) * (size_t)n) / PX + u;        // one contiguous band of rows
-    } else {
-        const size_t row_units = (size_t)slice_width / PX;
-        const size_t y = u / row_units, x = u % row_units;
-        dst = (y * (size_t)width + (size_t)r * (size_t)slice_width) / PX + x;
-    }
-    ((V *)image)[dst] = ((const V *)strips)[i];
-}
 
 extern "C" int sp_place_strips(sp_context *ctx, uint8_t *d_image, const uint8_t *d_strips, int32_t count, int32_t n, int32_t width,
                                int32_t slice_width, int32_t waterfall)
@@ -1442,11 +1116,8 @@ extern "C" int sp_place_strips(sp_context *ctx, uint8_t *d_image, const uint8_t 
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const bool wide = (slice_width & 3) == 0 && (width & 3) == 0 && (((uintptr_t)d_image | (uintptr_t)d_strips) & 15) == 0
                       && (!waterfall || (n & 3) == 0);
-    const size_t units = (size_t)slice_width * (size_t)n * (size_t)count / (wide ? 4 : 1);
-    const size_t blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one placement launch");
-    if (wide) hipLaunchKernelGGL(k_place_strips<uint4>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_image, d_strips, count, n, width, slice_width, waterfall);
-    else hipLaunchKernelGGL(k_place_strips<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_image, d_strips, count, n, width, slice_width, waterfall);
+    const int rc = spk::launch_place_strips(wide, d_image, d_strips, count, n, width, slice_width, waterfall, ctx->stream);
+    if (rc) return fail(ctx, rc, "image too large for one placement launch");
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -1903,9 +1574,8 @@ extern "C" int sp_index_to_rgba(sp_context *ctx, const uint8_t *d_index, size_t 
     for (int i = 0; i < 256; i++)
         lut.v[i] = i < lut_len ? (uint32_t)lut_rgb[3 * i] | ((uint32_t)lut_rgb[3 * i + 1] << 8) | ((uint32_t)lut_rgb[3 * i + 2] << 16) | 0xff000000u
                                : 0xff000000u;   // an index the map does not have: opaque black
-    const size_t blocks = (pixels / 16 + 255) / 256 + 1;
-    if (blocks > 0x7fffffffull) return fail(ctx, SP_ERR_UNSUPPORTED, "image too large for one recolouring launch");
-    hipLaunchKernelGGL(k_index_to_rgba, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_index, pixels, lut, d_rgba);
+    const int rc = spk::launch_index_to_rgba(d_index, pixels, lut, d_rgba, ctx->stream);
+    if (rc) return fail(ctx, rc, "image too large for one recolouring launch");
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2063,18 +1733,14 @@ static bool plan_plain_frames(const sp_plan *plan)
 }
 
 // The two kinds of plain_range: where the kernels write (Out), the slabs of a scratch workgroup, the LUT length the frame-loop launcher
-// asks for, that launcher, its refusal's text and the scratch kernel.
+// asks for, that launcher, its refusal's text and the scratch kernel's launcher.
 struct TracesKind {
     using Out = unsigned long long;   // the context's workspace (traces_clear)
     static constexpr int kSlabs = 4;   // re, im, the bins' minima and maxima
     static constexpr int kLutLen = spk2::kTracesLutLen;
     static constexpr auto launch_frames = spk2::launch_frames_traces;
     static constexpr const char *kRejected = "k_frames_traces launch rejected the configuration";
-    template <int FMT, bool WIDE>
-    static void launch_scratch(dim3 grid, dim3 block, hipStream_t s, const spk::FrameArgs &a, Out *out)
-    {
-        hipLaunchKernelGGL((spk::k_scratch_traces<FMT, WIDE>), grid, block, 0, s, a, out);
-    }
+    static constexpr auto launch_scratch = spk::launch_scratch_traces;
 };
 struct PowerKind {
     using Out = double;   // the plane, frame x at out + x * n
@@ -2082,11 +1748,7 @@ struct PowerKind {
     static constexpr int kLutLen = spk2::kPowerLutLen;
     static constexpr auto launch_frames = spk2::launch_frames_power;
     static constexpr const char *kRejected = "k_frames_power launch rejected the configuration";
-    template <int FMT, bool WIDE>
-    static void launch_scratch(dim3 grid, dim3 block, hipStream_t s, const spk::FrameArgs &a, Out *out)
-    {
-        hipLaunchKernelGGL((spk::k_scratch_power<FMT, WIDE>), grid, block, 0, s, a, out);
-    }
+    static constexpr auto launch_scratch = spk::launch_scratch_power;
 };
 
 // The frame loop over frames [x_begin, x_end) of a traces or power request into `out` (`src`: as for plan_execute_range).  One launch.
@@ -2108,10 +1770,11 @@ static int plain_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry
         const int rc = Kind::launch_frames(a, plan->req.format, plan->d_stage_tw, out, ctx->cu_count, ctx->device, s);
         if (rc) return fail(ctx, rc, Kind::kRejected);
     } else {
-        const int rc = scratch_launch(ctx, plan->req.format, a, Kind::kSlabs, x_end - x_begin, [&](auto F, auto WIDE, dim3 grid, dim3 block) {
-            Kind::template launch_scratch<decltype(F)::value, decltype(WIDE)::value>(grid, block, s, a, out);
-        });
+        unsigned blocks;
+        int rc = scratch_reserve(ctx, a, Kind::kSlabs, x_end - x_begin, &blocks);
         if (rc) return rc;
+        rc = Kind::launch_scratch(a, plan->req.format, blocks, out, s);
+        if (rc) return fail(ctx, rc, "bad format");
     }
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
@@ -2139,8 +1802,7 @@ static int traces_clear(sp_plan *plan)
     const int n = plan->req.n;
     const int rc = ctx->traces_ws.reserve(2 * (size_t)n * sizeof(unsigned long long));
     if (rc) return fail(ctx, rc, "traces workspace: out of device memory");
-    hipLaunchKernelGGL(spk::k_traces_clear, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (unsigned long long *)ctx->traces_ws.p, n);
+    spk::launch_traces_clear((unsigned long long *)ctx->traces_ws.p, n, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2148,9 +1810,8 @@ static int traces_clear(sp_plan *plan)
 static int traces_finish(sp_plan *plan, double *d_trace_min, double *d_trace_max)
 {
     sp_context *ctx = plan->ctx;
-    const int n = plan->req.n;
-    hipLaunchKernelGGL(spk::k_traces_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)ctx->traces_ws.p, n, plan->block_norm_db, plan->req.gain, d_trace_min, d_trace_max);
+    spk::launch_traces_finish((const unsigned long long *)ctx->traces_ws.p, plan->req.n, plan->block_norm_db, plan->req.gain, d_trace_min, d_trace_max,
+                              ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2224,11 +1885,7 @@ static int check_power(sp_context *ctx, int32_t detector, const spfmt::Format &f
 static int power_to_db(sp_plan *plan, const double *d_power, size_t count, double *d_db)
 {
     sp_context *ctx = plan->ctx;
-    size_t blocks = (count + 255) / 256;
-    const size_t most = 16 * (size_t)ctx->cu_count;   // (a grid-stride loop: enough workgroups to fill the chip)
-    if (blocks > most) blocks = most;
-    hipLaunchKernelGGL(spk::k_power_to_db, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_power, count, plan->block_norm_db, plan->req.gain,
-                       d_db);
+    spk::launch_power_to_db(d_power, count, plan->block_norm_db, plan->req.gain, d_db, ctx->cu_count, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2345,18 +2002,14 @@ static int mean_clear(sp_context *ctx, int n)
 static int mean_accumulate(sp_context *ctx, const double *d_plane, int n, long long frames)
 {
     if (frames <= 0) return SP_OK;
-    const int pieces = spk::mean_pieces(n, frames, ctx->cu_count);
-    const long long per = (frames + pieces - 1) / pieces;
-    hipLaunchKernelGGL(spk::k_mean_accumulate, dim3((unsigned)spk::mean_bands(n), (unsigned)pieces), dim3(spk::kMeanThreads), 0, ctx->stream,
-                       d_plane, n, frames, per, (unsigned long long *)ctx->mean_ws.p);
+    spk::launch_mean_accumulate(d_plane, n, frames, (unsigned long long *)ctx->mean_ws.p, ctx->cu_count, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
 
 static int mean_finish(sp_context *ctx, int n, int32_t width, double *d_mean)
 {
-    hipLaunchKernelGGL(spk::k_mean_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)ctx->mean_ws.p, n, (int)width, d_mean);
+    spk::launch_mean_finish((const unsigned long long *)ctx->mean_ws.p, n, width, d_mean, ctx->stream);
     SP_HIP(ctx, hipGetLastError());
     return SP_OK;
 }
@@ -2587,21 +2240,6 @@ extern "C" int sp_debug_batch_plan(int32_t format, int32_t n, int32_t lut_len, i
     return SP_OK;
 }
 
-// Clears the replies of a batch's items before its launches: histograms 0, dBfs range (0, -200) (worker.js:35-41).  One workgroup per item.
-__global__ void k_batch_clear(const spk2::BatchItem *items, int lut_len)
-{
-    const spk2::BatchItem &it = items[blockIdx.x];
-    for (int i = threadIdx.x; i < lut_len + SP_CB_HIST_SIZE + 2; i += blockDim.x) {
-        if (i < lut_len) {
-            if (it.out_c) it.out_c[i] = 0;
-        } else if (i < lut_len + SP_CB_HIST_SIZE) {
-            if (it.out_cb) it.out_cb[i - lut_len] = 0;
-        } else if (it.out_minmax) {
-            it.out_minmax[i - lut_len - SP_CB_HIST_SIZE] = i == lut_len + SP_CB_HIST_SIZE ? 0.0 : -200.0;
-        }
-    }
-}
-
 static int batch_check_items(sp_context *ctx, const spfmt::Format &f, int n, const sp_batch_item *items, int32_t count, bool device)
 {
     for (int i = 0; i < count; i++) {
@@ -2697,7 +2335,7 @@ extern "C" int sp_plan_execute_batch(sp_plan *plan, const sp_batch_item *items, 
     SP_HIP(ctx, hipEventRecord(ctx->ev_batch, s));
     const spk2::BatchItem *d_rec = (const spk2::BatchItem *)d;
     const int32_t *d_map = (const int32_t *)(d + map_off);
-    hipLaunchKernelGGL(k_batch_clear, dim3((unsigned)nrec), dim3(256), 0, s, d_rec, plan->req.lut_len);
+    spk::launch_batch_clear(d_rec, (unsigned)nrec, plan->req.lut_len, s);
     SP_HIP(ctx, hipGetLastError());
 
     spk::FrameArgs a{};

@@ -6,7 +6,7 @@
 // with run-time loops and none of that kernel's templates - not the fast path.
 #pragma once
 
-#include "sp_kernels_common.h"
+#include "sp_kernel_args.h"
 
 namespace spk {
 
@@ -227,23 +227,6 @@ __global__ __launch_bounds__(kScratchThreads) void k_scratch_radix2(const FrameA
 }
 
 // ---- per-frame side outputs (worker.js:124-136) and the global dBfs range (worker.js:124-125) -----------
-
-struct FinishArgs {
-    const uint8_t *bytes;
-    int64_t nbytes, nelem;
-    double stride;
-    int32_t n, width, format;
-    double block_norm_db, gain, range;
-    const double *frame_min, *frame_max;
-    uint8_t *gauge_mins, *gauge_maxs, *gauge_amps;
-    unsigned long long *mm_acc;   // [2] bit patterns of min / max |X|^2 over all frames; reset to {+inf, 0} here
-    double *out_minmax;       // [2] or nullptr
-    // histograms: the scratch kernel adds into context-owned accumulators (zero before and after every request);
-    // this kernel moves them to the caller's arrays, so a reply always holds the counts of its own request
-    int32_t lut_len;
-    unsigned long long *acc_c, *acc_cb;
-    unsigned long long *out_c, *out_cb;   // or nullptr
-};
 
 __device__ inline double centre_sample(int fmt, const spfmt::View &v, int64_t pos, int c)
 {

@@ -1,0 +1,52 @@
+// sp_launch.h — the launchers of every kernel outside the frame-loop objects (sp_kernels.hip): the scratch kernels, the synthesiser and
+// the small kernels around the frame loops.  Plain functions, as spk2::launch_frames* are for the frame loops: arguments and a stream
+// in, a status out where a launch can be refused - SP_ERR_INVALID_ARG for an unknown format, SP_ERR_UNSUPPORTED for work that does not
+// fit one grid - and nothing is launched then.  The grid and block arithmetic that follows from a kernel's constants is the launcher's.
+// The caller asks hipGetLastError() behind every launch.
+#pragma once
+
+#include "sp_kernel_args.h"
+
+namespace spk2 {
+struct BatchItem;   // sp_kernel_frames_batch.h
+}
+
+namespace spk {
+
+// The scratch kernels over `blocks` workgroups (a.scratch holds their slabs); the four-stage variants from n = 4096 on.
+// k_scratch_radix2 holds the peak over peak_m sub-frames per column where `hold`.
+int launch_scratch_radix2(const FrameArgs &a, int format, unsigned blocks, bool hold, int peak_m, int peak_nsamp, hipStream_t stream);
+int launch_scratch_traces(const FrameArgs &a, int format, unsigned blocks, unsigned long long *ws, hipStream_t stream);
+int launch_scratch_power(const FrameArgs &a, int format, unsigned blocks, double *power, hipStream_t stream);
+// k_finish_frames behind a request's last scratch launch: three roles per 256 frames (at least enough threads to move the histograms)
+// and the dBfs range's workgroup
+void launch_finish_frames(const FinishArgs &a, hipStream_t stream);
+
+void launch_traces_clear(unsigned long long *ws, int n, hipStream_t stream);
+void launch_traces_finish(const unsigned long long *ws, int n, double block_norm_db, double gain, double *trace_min, double *trace_max,
+                          hipStream_t stream);
+// d_db[k] = dB of d_power[k], k < count (a grid-stride loop: no more workgroups than fill the chip)
+void launch_power_to_db(const double *d_power, size_t count, double block_norm_db, double gain, double *d_db, int cu_count, hipStream_t stream);
+
+// the `frames` > 0 frames of the frame-major plane (n rows each) added into the exact-sum workspace; the workspace into the mean
+void launch_mean_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream);
+void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream);
+
+int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
+
+void launch_noop(hipStream_t stream);
+int launch_extract_index(const uint8_t *rgba, uint8_t *index, size_t row_px, size_t rows, size_t pitch_px, hipStream_t stream);
+int launch_index_to_rgba(const uint8_t *index, size_t pixels, const IndexLut &lut, uint8_t *rgba, hipStream_t stream);
+// the frames [x_begin, x_end), x_begin < x_end, of an index image ADDED to `density`
+int launch_density_count(const uint8_t *index, int n, int width, bool waterfall, int x_begin, int x_end, int lut_len, uint32_t *density,
+                         hipStream_t stream);
+
+// `renders` records of lut_len + SP_CB_HIST_SIZE + 2 words per rank, merged one by one (sp_merge_replies: one)
+void launch_merge_replies(const unsigned long long *rec, int count, int lut_len, size_t rank_stride, int renders, unsigned long long *c_hist,
+                          unsigned long long *cb_hist, double *minmax, hipStream_t stream);
+// `wide`: 16-byte units (the caller has checked widths and alignment), else one pixel per thread
+int launch_place_strips(bool wide, uint8_t *image, const uint8_t *strips, int count, int n, int width, int slice_width, int waterfall,
+                        hipStream_t stream);
+void launch_batch_clear(const spk2::BatchItem *items, unsigned count, int lut_len, hipStream_t stream);
+
+}  // namespace spk

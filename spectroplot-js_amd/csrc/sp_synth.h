@@ -5,16 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "sp_formats.h"
+#include "sp_kernel_args.h"
 
 namespace spk {
-
-struct SynthArgs {
-    uint8_t *out;
-    uint64_t t0, count;
-    uint32_t seed, step, gshift;
-    double amp, namp;
-};
 
 __device__ inline uint32_t fmix32(uint32_t h)
 {

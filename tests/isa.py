@@ -18,7 +18,8 @@ PEAK_TARGETS = tuple("build/peak_%d.o" % lg for lg in range(6, 11))        # k_f
 INDEX_TARGETS = tuple("build/index_%d.o" % lg for lg in range(6, 14))      # k_frames_index
 TRACES_TARGETS = tuple("build/traces_%d.o" % lg for lg in range(6, 11))    # k_frames_traces
 POWER_TARGETS = tuple("build/power_%d.o" % lg for lg in range(6, 11))      # k_frames_power
-API_TARGETS = ("build/sp_api.o",)                                          # the scratch kernels and every small kernel
+API_TARGETS = ("build/sp_api.o",)                                          # what held the scratch kernels and every small kernel in the
+#                                                                            reference commit; now build/sp_kernels.o does (api_objs)
 
 
 def _built(pattern, at_least):
@@ -60,7 +61,8 @@ def power_objs():
 
 
 def api_objs():
-    objs = _built("sp_api.o", 1)
+    """The object of the scratch kernels and every small kernel (csrc/sp_kernels.hip); sp_api.o and sp_group.o are host code only."""
+    objs = _built("sp_kernels.o", 1)
     assert len(objs) == 1
     return objs
 

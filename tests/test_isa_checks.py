@@ -199,8 +199,9 @@ STREAM_FAMILIES = {
     "k_frames_index": ("_ZN4spk214k_frames_indexI", _INDEX_H, "", isa.INDEX_TARGETS, isa.index_objs, 93),
     "k_frames_traces": ("_ZN4spk215k_frames_tracesI", _TRACES_H, "", isa.TRACES_TARGETS, isa.traces_objs, 60),
     "k_frames_power": ("_ZN4spk214k_frames_powerI", _POWER_H, "", isa.POWER_TARGETS, isa.power_objs, 60),
-    # every kernel of sp_api.o as the commit that added the mean kernels builds it, the last one before the host side of the scratch
-    # launches was folded: 56 k_scratch_radix2, 28 k_scratch_traces, 28 k_scratch_power, 14 k_synth_trinoise and 15 single kernels
+    # every kernel of sp_kernels.o against sp_api.o, which held them, as the commit that added the mean kernels builds it, the last one
+    # before the host side of the scratch launches was folded: 56 k_scratch_radix2, 28 k_scratch_traces, 28 k_scratch_power,
+    # 14 k_synth_trinoise and 15 single kernels
     "sp_api": ("", _MEAN_H, "", isa.API_TARGETS, isa.api_objs, 141),
 }
 
@@ -209,9 +210,9 @@ STREAM_FAMILIES = {
 def test_kernel_instruction_streams_match_their_reference_commit(family):
     """Every variant <L, C, P> of the six frame-loop kernels has the instruction stream (addresses stripped) of a reference build: k_frames
     of the commit before the batch kernel was added, each other kernel of the commit that added its header (sp_kernel_frames_batch.h,
-    _peak.h, _index.h, _traces.h, _power.h); so has every kernel of sp_api.o - the scratch kernels in all their formats, the synthesiser
-    and the small kernels around the frame loops - of the commit that added sp_kernel_mean.h, whatever the host code that names them in a
-    launch has become since.  What the frame-loop kernels share since - the sp_frames_*.inc.h fragments of the stages, of the
+    _peak.h, _index.h, _traces.h, _power.h); so has every kernel of sp_kernels.o - the scratch kernels in all their formats, the
+    synthesiser and the small kernels around the frame loops - of the commit that added sp_kernel_mean.h, which built them into sp_api.o
+    beside the host code that launched them (the "sp_api" family keeps that name).  What the frame-loop kernels share since - the sp_frames_*.inc.h fragments of the stages, of the
     prologue, of the loop's shell, the write-out lambdas, the finale and the two whole bodies - must not move any of them.  This guards those changes only: a later commit that
     changes a kernel on purpose replaces that family's reference with its own parent (HEAD^ of the commit that last touched the kernel's
     loop)."""
@@ -225,3 +226,13 @@ def test_kernel_instruction_streams_match_their_reference_commit(family):
     assert len(theirs) == count and set(mine) == set(theirs)
     differ = [k for k in theirs if mine[k] != theirs[k]]
     assert not differ, differ[:5]
+
+
+def test_the_host_units_hold_no_device_code():
+    """The C ABI (sp_api.hip) and the group render (sp_group.hip) are host code: every kernel they launch lies in another object and is
+    reached through a plain launcher (sp_launch.h, spk2::launch_frames*), so a change to them neither rebuilds nor moves a kernel."""
+    isa.api_objs()            # (builds the library where it is not built yet)
+    for unit in ("sp_api.o", "sp_group.o"):
+        obj = os.path.join(isa.PKG, "build", unit)
+        assert os.path.exists(obj), obj
+        assert isa.streams([obj], "") == {}, unit

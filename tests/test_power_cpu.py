@@ -106,7 +106,7 @@ def test_power_objects_hold_only_k_frames_power_and_nobody_else_does():
         assert kernels and all(k.startswith(MANGLED + "I") for k in kernels), (o, kernels[:3])
     others = _objs("frames_*.o") + _objs("peak_*.o") + _objs("traces_*.o") + _objs("index_*.o")
     assert len(others) == 8 + 5 + 5 + 8
-    for o in others + [os.path.join(isa.PKG, "build", "sp_api.o")]:
+    for o in others + [os.path.join(isa.PKG, "build", "sp_kernels.o")]:
         assert "k_frames_power" not in isa.notes(o), o
 
 

@@ -106,7 +106,7 @@ def test_traces_objects_hold_only_k_frames_traces_and_nobody_else_does():
         names = re.findall(r"\.name:\s*(\S+)", isa.notes(o))
         kernels = [k for k in names if not k.endswith(".kd")]
         assert kernels and all(k.startswith("_ZN4spk215k_frames_tracesI") for k in kernels), (o, kernels[:3])
-    others = isa.frame_objs() + isa.peak_objs() + [os.path.join(isa.PKG, "build", "sp_api.o")]      # every other object with kernels
+    others = isa.frame_objs() + isa.peak_objs() + [os.path.join(isa.PKG, "build", "sp_kernels.o")]      # every other object with kernels
     for o in others:
         assert "k_frames_traces" not in isa.notes(o), o
 
