@@ -548,6 +548,61 @@ int sp_debug_exact_sum(const double *values, size_t count, double *sum);
 const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
+ * Exact band-power series: the power of a band of image rows per frame - the zero-span / channel-power trace of a spectrum analyser,
+ * the envelope of one transmitter in a crowded capture - bit-exact like the mean.  The mean is the plane's marginal along x, this is
+ * its marginal along y.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y - the same geometry, limits, statuses, channel
+ * mode and row order y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90) - a band is a half-open range of image rows [y0, y1) with
+ * 0 <= y0 <= y1 <= n.  The bands are a HOST array int32_t bands[2 * count] = {y0_0, y1_0, y0_1, y1_1, ...}, read before the call
+ * returns; 0 <= count <= SP_MAX_BANDS; bands may overlap and may be empty.  The reply is double[count * width], BAND-MAJOR, so every
+ * band is one contiguous time series:
+ *     band[b * width + x] = RN( sum over y in [y0_b, y1_b) of power[x][y] )
+ * The sum is the EXACT real-number sum and RN is one IEEE-754 round-to-nearest-even to f64, as for the mean; a sum at or above
+ * 2^1024 - 2^970 gives +inf.  A band with a NaN addend is NaN, and A NaN IS ANY NaN; otherwise a band with a +inf addend is +inf.  An
+ * empty band gives +0.0.  The value is a SUM, not a mean: the power of a channel is the sum of its bins.  In Python:
+ * math.fsum(plane[x, y0:y1]) with OverflowError read as +inf; a band of one row therefore equals the plane's column bit for bit.
+ * width == 0 or count == 0 writes nothing and returns SP_OK.  The array is the same for both layouts and does not depend on gain,
+ * range, LUT or block_norm, NOR ON THE CU COUNT, THE WINDOW OR THE CHUNKING OF A HOST-FED REQUEST (integer adds commute).  Only plans of
+ * the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED, as for the plane and the mean.  The dB form is
+ * sp_plan_power_to_db applied to the count * width sums.
+ * SP_ERR_INVALID_ARG: a band outside 0 <= y0 <= y1 <= n, count outside 0 .. SP_MAX_BANDS, bands == NULL with count > 0, a NULL or
+ * misaligned (8 bytes) output when count * width > 0.
+ * How: the mean's accumulator (66 64-bit cells and two counters, integer adds only, rounded once) per FRAME instead of per row.  A
+ * frame's rows are summed inside one workgroup, in LDS, and finished there: no workspace of the context, no clear and no finishing
+ * launch.
+ *
+ * sp_band_rows: (pure host arithmetic, no device needed) the rows whose centre frequency lies in [f_lo, f_hi], in cycles per sample:
+ *   row y is centred on f(y) = (n/2 - y) / n, so row 0 is +1/2, row n/2 is DC and row n - 1 is -1/2 + 1/n.
+ *     *y0 = clamp(ceil(n/2 - f_hi * n), 0, n)        *y1 = clamp(floor(n/2 - f_lo * n) + 1, 0, n), raised to *y0 if below it
+ *   computed in f64 in exactly that order.  SP_ERR_INVALID_ARG for a NaN, for f_lo > f_hi, for n < 2 and for a NULL output;
+ *   SP_ERR_NOT_POW2 as elsewhere.  In channel mode the rows are the L/R split's (L above R), not one frequency axis: the helper is
+ *   for I/Q plans.
+ * sp_power_bands: the sums over a frame-major plane double[width * n] the caller holds on the device; the companion of sp_power_mean.
+ *   Asynchronous on the context's stream, ONE launch, no workspace of the context and no request number: a stream that is being
+ *   captured is not refused.  n >= 1 (any n, not only powers of two), width >= 0; d_power (non-NULL when count * width > 0) and d_band
+ *   8-byte aligned device pointers.  The values must not be negative: the sign bit of a value is not looked at.
+ * sp_plan_execute_bandpower: device operands, asynchronous.  The plane is never held whole: it passes block by block through the
+ *   mean's window (sp_context_set_mean_window applies) and the sums of the block's frames, columns [x0, x1) of every band, are made
+ *   behind each block.  The checks are sp_plan_execute_power's, then the bands'.  No request number: the call may be interleaved with
+ *   sp_plan_execute / _index / _power / _mean on one context without a synchronisation.
+ * sp_render_bandpower: host buffers, synchronous, the plan cached as by sp_render.  The samples are the only bulk transfer and travel
+ *   as for sp_render_mean - a packed upload where stride > n, chunks of frames where the request is large - and count * width doubles
+ *   come back in one copy, converted to dB on the device first when db != 0.  sp_context_last_upload_bytes / sp_context_last_chunks
+ *   report as before.
+ * sp_plan_bandpower_kernel_name_for: "frames_power+bands" or "scratch_power+bands", following sp_plan_power_kernel_name_for.
+ * Out of scope: peak plans, batches, groups and sharding.py (a shard's frames are a run of columns of every band), the sum fused into
+ * the frame loop, and weighted bands.
+ */
+#define SP_MAX_BANDS 64
+int sp_band_rows(int32_t n, double f_lo, double f_hi, int32_t *y0, int32_t *y1);
+int sp_power_bands(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count, double *d_band);
+int sp_plan_execute_bandpower(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                              double *d_band);
+int sp_render_bandpower(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                        int32_t count, int32_t db, double *band);
+const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

@@ -177,6 +177,12 @@ class Library:
         L.sp_debug_exact_sum.argtypes = [vp, sz, C.POINTER(dbl)]
         L.sp_plan_mean_kernel_name_for.restype = C.c_char_p
         L.sp_plan_mean_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_band_rows.argtypes = [i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32)]
+        L.sp_power_bands.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+        L.sp_plan_execute_bandpower.argtypes = [vp, vp, sz, i32, vp, i32, vp]
+        L.sp_render_bandpower.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, vp]
+        L.sp_plan_bandpower_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_bandpower_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -228,6 +234,24 @@ def exact_sum(values):
     lib = Library.get()
     lib.check(lib.L.sp_debug_exact_sum(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, C.byref(out)))
     return out.value
+
+
+SP_MAX_BANDS = 64
+
+
+def band_rows(n, f_lo, f_hi):
+    """sp_band_rows: the image rows (y0, y1) - a half-open range - whose centre frequency f(y) = (n/2 - y) / n lies in [f_lo, f_hi],
+    in cycles per sample (row 0 is +1/2, row n/2 is DC).  For I/Q plans; pure host arithmetic, no device needed."""
+    y0, y1 = C.c_int32(), C.c_int32()
+    lib = Library.get()
+    lib.check(lib.L.sp_band_rows(int(n), float(f_lo), float(f_hi), C.byref(y0), C.byref(y1)))
+    return y0.value, y1.value
+
+
+def _band_array(bands):
+    """(int32 [count, 2] host array, count) of a sequence of (y0, y1) rows ranges; nothing is checked here - the library refuses."""
+    b = np.ascontiguousarray(np.asarray(bands, dtype=np.int64).reshape(-1, 2).astype(np.int32))
+    return b, b.shape[0]
 
 
 def parse_format(name):
@@ -556,6 +580,30 @@ class Context:
         Asynchronous on the context's stream."""
         self._chk(self.lib.L.sp_power_mean(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_mean or None)))
 
+    def render_bandpower(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, channel_mode=False, db=False, lut=None,
+                         fill=None):
+        """sp_render_bandpower: the exact band-power series of the request, f64 [count, width]: per band (y0, y1) of image rows and
+        per frame the correctly rounded sum of |X|^2 over the band's rows, or with db=True the dB of it.  No image is rendered; `lut`
+        only takes part in the plan-cache key (default: two grey entries).  fill: a byte the output array holds before the call
+        (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
+        b, count = _band_array(bands)
+        out = np.zeros((count, max(int(width), 0)), np.float64)
+        if fill is not None:
+            out.view(np.uint8)[...] = fill
+        self._chk(self.lib.L.sp_render_bandpower(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                                 1 if db else 0, _p(out) if out.size else None))
+        return out
+
+    def power_bands(self, d_power, n, width, bands, d_band):
+        """sp_power_bands: the exact sums over the bands (y0, y1) of rows of every frame of the f64 [width, n] plane at device address
+        d_power into f64 [count, width] at d_band.  Asynchronous on the context's stream; the bands are read before it returns."""
+        b, count = _band_array(bands)
+        self._chk(self.lib.L.sp_power_bands(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                            C.c_void_p(d_band or None)))
+
     def set_mean_window(self, nbytes=0):
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
@@ -690,6 +738,17 @@ class Plan:
         (image row order).  Asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_mean(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                           C.c_void_p(d_mean or None)))
+
+    def bandpower_kernel_name_for(self, nbytes, width):
+        """What execute_bandpower() launches for a request of this shape: "frames_power+bands" or "scratch_power+bands"."""
+        return self.ctx.lib.L.sp_plan_bandpower_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def execute_bandpower(self, d_bytes, nbytes, width, bands, d_band):
+        """sp_plan_execute_bandpower: the exact sums of |X|^2 over the bands (y0, y1) of image rows, per frame, into the f64
+        [count, width] device array at address d_band.  Asynchronous on the context's stream; the bands are read before it returns."""
+        b, count = _band_array(bands)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_bandpower(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                               _p(b) if count else None, count, C.c_void_p(d_band or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -2097,6 +2097,114 @@ extern "C" int sp_render_mean(sp_context *ctx, const sp_request *req, const uint
         });
 }
 
+// ------------------------------------------------------------------------------------------------- exact band-power series
+
+extern "C" const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
+    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+bands" : "scratch_power+bands";
+}
+
+// what every band-power entry point refuses of its bands and its output (`out`: count * width doubles) before it touches the device
+static int check_band_args(sp_context *ctx, int n, int32_t width, const int32_t *bands, int32_t count, const double *out)
+{
+    if (const char *why = spgeo::check_bands(n, bands, count)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (count > 0 && width > 0 && (!out || ((uintptr_t)out & 7) != 0))
+        return fail(ctx, SP_ERR_INVALID_ARG, "the band series must be an 8-byte aligned array of count * width doubles");
+    return SP_OK;
+}
+
+// Columns [x_base, x_base + frames) of every band's series (`width` doubles apart) from the `frames` frames of the frame-major plane
+// at d_plane: one launch.
+static int band_sums(sp_context *ctx, const double *d_plane, int n, long long frames, const int32_t *bands, int32_t count, double *d_band,
+                     int32_t width, long long x_base)
+{
+    if (frames <= 0 || count <= 0) return SP_OK;
+    spk::launch_band_sum(d_plane, n, frames, bands, count, d_band, width, x_base, ctx->stream);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// The frames [x_begin, x_end) of a band-power request: rendered block by block into the mean's window, as mean_range does, with the
+// sums of the block's frames made behind each block.
+static int band_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
+                      const int32_t *bands, int32_t count, double *d_band)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = plan->req.n;
+    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
+    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
+    if (rc) return fail(ctx, rc, "mean window: out of device memory");
+    double *const d_win = (double *)ctx->mean_window.p;
+    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
+        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
+        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
+        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
+        if (!rc) rc = band_sums(ctx, d_win, n, x1 - x0, bands, count, d_band, g.width, x0);
+    }
+    return rc;
+}
+
+extern "C" int sp_power_bands(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                              double *d_band)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_bands: n >= 1 and width >= 0 are required");
+    const int rc = check_band_args(ctx, n, width, bands, count, d_band);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+    if (!d_power || ((uintptr_t)d_power & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_bands: d_power must be an 8-byte aligned device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] { return band_sums(ctx, d_power, n, width, bands, count, d_band, width, 0); });
+}
+
+extern "C" int sp_plan_execute_bandpower(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                         double *d_band)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    if (!rc) rc = check_band_args(ctx, plan->req.n, width, bands, count, d_band);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    return timed(ctx, [&] { return band_range(plan, d_bytes, g, 0, width, nullptr, bands, count, d_band); });
+}
+
+// A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
+// series fill column by column over the chunks (nothing to clear: every column is written once); count * width doubles come back.
+extern "C" int sp_render_bandpower(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                                   int32_t count, int32_t db, double *band)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    sp_plan *plan = nullptr;
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width, [&] { return check_band_args(ctx, req->n, width, bands, count, band); },
+        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+
+    const size_t total = (size_t)count * (size_t)width;
+    hipStream_t s = ctx->stream;
+    rc = ctx->render_small.reserve(total * sizeof(double) + 16);
+    if (rc) return fail(ctx, rc, "sp_render_bandpower: out of memory");
+    double *const d_out = (double *)ctx->render_small.p;
+    HostFeed feed{"sp_render_bandpower", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
+    return render_result(
+        ctx, plan->fmt, feed, no_check,
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
+            return band_range(plan, d_in, feed.g, x0, x1, src, bands, count, d_out);
+        },
+        [&](bool, hipError_t &e) {
+            const int r = db ? power_to_db(plan, d_out, total, d_out) : (int)SP_OK;
+            if (!r) e = hipMemcpyAsync(band, d_out, total * sizeof(double), hipMemcpyDeviceToHost, s);
+            return r;
+        });
+}
+
 // ------------------------------------------------------------------------------------------------- requests by name
 
 extern "C" int sp_named_resolve(const char *window, const char *cmap, const char **window_name, const char **cmap_key, int32_t *lut_len)

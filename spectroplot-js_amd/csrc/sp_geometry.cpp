@@ -166,7 +166,30 @@ void plan_upload(const Geometry &g, bool packable, bool chunkable, size_t out_by
     u.link_bytes = g.nbytes;
 }
 
+const char *check_bands(int32_t n, const int32_t *bands, int32_t count)
+{
+    if (count < 0 || count > SP_MAX_BANDS) return "count must be 0 .. SP_MAX_BANDS";
+    if (count > 0 && !bands) return "bands is null";
+    for (int32_t b = 0; b < count; b++) {
+        const int32_t y0 = bands[2 * b], y1 = bands[2 * b + 1];
+        if (y0 < 0 || y1 < y0 || y1 > n) return "a band must satisfy 0 <= y0 <= y1 <= n";
+    }
+    return nullptr;
+}
+
 }  // namespace spgeo
+
+extern "C" int sp_band_rows(int32_t n, double f_lo, double f_hi, int32_t *y0, int32_t *y1)
+{
+    if (!y0 || !y1 || f_lo != f_lo || f_hi != f_hi || f_lo > f_hi || n < 2) return SP_ERR_INVALID_ARG;
+    if (n & (n - 1)) return SP_ERR_NOT_POW2;
+    const double half = (double)(n / 2), dn = (double)n;
+    const auto clamp = [dn](double v) { return (int32_t)(v < 0.0 ? 0.0 : v > dn ? dn : v); };   // (an infinity clamps; no NaN comes here)
+    const int32_t a = clamp(std::ceil(half - f_hi * dn)), b = clamp(std::floor(half - f_lo * dn) + 1.0);
+    *y0 = a;
+    *y1 = b < a ? a : b;
+    return SP_OK;
+}
 
 extern "C" int sp_peak_subframes(int32_t format, int32_t n, size_t nbytes, int32_t width, int32_t *subframes, int32_t *last_column_count)
 {

@@ -78,6 +78,11 @@ struct UploadPlan {
 // back over the link.
 void plan_upload(const Geometry &g, bool packable, bool chunkable, size_t out_bytes, UploadPlan &u);
 
+// ---- band-power series: bands of image rows -----------------------------------------------------------------------------------------
+// What every band-power entry point refuses of its bands (include/spectroplot_hip.h): nullptr where they are in order - count within
+// 0 .. SP_MAX_BANDS, `bands` non-null where count > 0, every band within 0 <= y0 <= y1 <= n - else the refusal's text.
+const char *check_bands(int32_t n, const int32_t *bands, int32_t count);
+
 // ---- sliced renders: where the strips of `count` workers lie in the caller's image --------------------------------------------------
 // The caller's layout (lib/spectroplot.js:1206-1244), in bytes of the RGBA image: every worker renders sliceWidth = ~~(width / workers)
 // frames (:1208) and strip r is put at (r * sliceWidth, 0) of the width x n spectrogram - a band of columns - or at

@@ -31,6 +31,12 @@ void launch_power_to_db(const double *d_power, size_t count, double block_norm_d
 // the `frames` > 0 frames of the frame-major plane (n rows each) added into the exact-sum workspace; the workspace into the mean
 void launch_mean_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream);
 void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream);
+// band[b * stride + x_base + x] = the exact sum of the rows [bands[2 b], bands[2 b + 1]) of frame x of the frame-major plane, for its
+// `frames` > 0 frames and the `count` bands of the HOST array `bands` (1 .. SP_MAX_BANDS, each within 0 <= y0 <= y1 <= n: the caller
+// has checked them); they travel in the kernel's arguments.  One launch.  (k_band_sum and this launcher are sp_band.hip, a unit of
+// their own.)
+void launch_band_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, double *band, long long stride,
+                     long long x_base, hipStream_t stream);
 
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 

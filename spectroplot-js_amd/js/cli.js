@@ -8,6 +8,7 @@
  *        [--cmap cube1|viridis|plasma|inferno|magma|hot|afmhot|gist_heat|sox|naive|grayscale|roentgen|phosphor|parabola] [--gain 6] [--range 30] [--workers N] [--waterfall] [--lr] [--detector sample|peak]
  *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] [--power power.f64] [--power-db db.f64]
  *        [--mean mean.f64] [--mean-db mean_db.f64]
+ *        [--bandpower bands.f64] [--bandpower-db bands_db.f64] [--bands Y0:Y1,...] [--band-freqs LO:HI,...]
  *        --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
@@ -33,6 +34,12 @@
  * --mean FILE / --mean-db FILE (single-file runs, sample detector): the exact mean-power trace of the same request over the whole capture
  * (HipWorker.renderMean -> sp_render_mean) as raw little-endian f64, n values in image row order: per row the correctly rounded sum of
  * |X|^2 over the frames divided by width (or, for --mean-db, the dB of that mean).
+ *
+ * --bandpower FILE / --bandpower-db FILE (single-file runs, sample detector): the exact band-power series of the same request over the
+ * whole capture (HipWorker.renderBandPower -> sp_render_bandpower) as raw little-endian f64, count * width values, band-major: per band
+ * and frame the correctly rounded sum of |X|^2 over the band's image rows (or, for --bandpower-db, the dB of that sum).  The bands are
+ * --bands Y0:Y1,... (half-open ranges of image rows) followed by --band-freqs LO:HI,... (cycles per sample, -0.5 .. 0.5, turned into
+ * rows by sp_band_rows: row y is centred on (n/2 - y) / n); at most 64 in all.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -94,6 +101,32 @@ function writeMean(buffer, format, n, width, opt, db) {
         range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
         worker.terminate()
         fs.writeFileSync(db ? opt['mean-db'] : opt.mean, Buffer.from(r.mean.buffer, r.mean.byteOffset, r.mean.byteLength))
+    }, e => { worker.terminate(); throw e })
+}
+
+// the bands of --bands and --band-freqs, in that order, as [y0, y1] pairs
+function parseBands(opt, n) {
+    const pairs = (text, num) => String(text).split(',').filter(s => s.length).map(s => {
+        const p = s.split(':')
+        if (p.length !== 2 || !p.every(v => v.trim().length && Number.isFinite(num(v)))) throw new Error(`bad band '${s}': A:B expected`)
+        return p.map(num)
+    })
+    const bands = opt.bands === undefined ? [] : pairs(opt.bands, Number)
+    if (opt['band-freqs'] !== undefined) for (const [lo, hi] of pairs(opt['band-freqs'], Number)) bands.push(HipWorker.bandRows(n, lo, hi))
+    if (!bands.length) throw new Error('--bandpower needs --bands Y0:Y1,... and / or --band-freqs LO:HI,...')
+    return bands
+}
+
+// --bandpower / --bandpower-db: as --power, count * width values, band-major
+function writeBandPower(buffer, format, n, width, opt, db) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const bands = parseBands(opt, n)
+    const worker = new HipWorker()
+    return worker.renderBandPower({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db, bands }).then(r => {
+        worker.terminate()
+        fs.writeFileSync(db ? opt['bandpower-db'] : opt.bandpower, Buffer.from(r.bands.buffer, r.bands.byteOffset, r.bands.byteLength))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -205,6 +238,8 @@ function main(argv) {
         .then(() => opt['power-db'] === undefined ? null : writePower(buffer, format, n, width, opt, true))
         .then(() => opt.mean === undefined ? null : writeMean(buffer, format, n, width, opt, false))
         .then(() => opt['mean-db'] === undefined ? null : writeMean(buffer, format, n, width, opt, true))
+        .then(() => opt.bandpower === undefined ? null : writeBandPower(buffer, format, n, width, opt, false))
+        .then(() => opt['bandpower-db'] === undefined ? null : writeBandPower(buffer, format, n, width, opt, true))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

@@ -254,6 +254,52 @@ class HipWorker {
     renderMeanSync(m, opt) { return addon().renderMeanSync(this._ctx, this._meanRequest(m, opt)) }
 
     /**
+     * The exact band-power series of a request (sp_render_bandpower) - the zero-span / channel-power trace: the fields renderTraces
+     * reads in plus `{bands}` - an array of [y0, y1] pairs or a flat Int32Array of them, half-open ranges of image rows with
+     * 0 <= y0 <= y1 <= n, at most 64 (HipWorker.bandRows turns a frequency range into rows) - and one Float64Array(count * width) out,
+     * band-major: bands[b * width + x] is the correctly rounded sum of |X|^2 of frame x over the rows of band b, the same bits on every
+     * device and for every chunking - or, with `{db: true}`, the dB of that sum.  No image is rendered.  Only the sample detector has
+     * band sums (status -4) and bad bands are refused (status -1), both before anything is rendered.  Runs in the instance's request
+     * order; a malformed field rejects (and reports `onerror`) and never resolves to an array.
+     * @returns {Promise<{bands: Float64Array, count: number, width: number, n: number}>}
+     */
+    renderBandPower(m, opt) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            let req
+            try { req = this._bandRequest(m, opt) } catch (e) { reject(e); return }
+            try {
+                addon().renderBandPower(this._ctx, req,
+                    (err, r) => err ? reject(err) : resolve({ bands: r.bands, count: r.count, width: r.width, n: r.n }))
+            } catch (e) { reject(e) }
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
+        return p
+    }
+
+    _bandRequest(m, opt) {
+        if (!(m && m.buffer)) throw Object.assign(new Error('a band-power request needs a buffer'), { status: -1 })
+        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the band power of the peak detector is not supported'), { status: -4 })
+        const bad = why => Object.assign(new Error(why), { status: -1 })
+        const given = opt && opt.bands
+        if (!(Array.isArray(given) || ArrayBuffer.isView(given))) throw bad('a band-power request needs {bands}: [y0, y1] pairs')
+        const flat = Array.isArray(given) ? [].concat(...given) : Array.from(given)
+        if (flat.length % 2 !== 0 || flat.length > 128) throw bad('bands must be at most 64 [y0, y1] pairs')
+        for (let b = 0; b < flat.length; b += 2) {
+            const y0 = flat[b], y1 = flat[b + 1]
+            if (!Number.isInteger(y0) || !Number.isInteger(y1) || y0 < 0 || y1 < y0 || y1 > m.n) throw bad('a band must satisfy 0 <= y0 <= y1 <= n')
+        }
+        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db), bands: Int32Array.from(flat) })
+    }
+
+    /** Synchronous form of renderBandPower (tests). */
+    renderBandPowerSync(m, opt) { return addon().renderBandPowerSync(this._ctx, this._bandRequest(m, opt)) }
+
+    /** sp_band_rows: the image rows [y0, y1) whose centre frequency (n/2 - y) / n lies in [fLo, fHi] cycles per sample (I/Q plans). */
+    static bandRows(n, fLo, fHi) { return addon().bandRows(n, fLo, fHi) }
+
+    /**
      * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the
      * message's colour map pixel j of imageData.data shows, so the reply is a quarter of the size and js/consumers.js `recolour` redraws
      * it under another map without a render.  The message is a worker message (`detector: 'peak'` allowed; a colour map of more than 256

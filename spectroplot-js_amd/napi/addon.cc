@@ -26,6 +26,8 @@
 //   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
 //   renderPower(handle, req, cb) / renderPowerSync(handle, req) -> {power, width, n}: |X|^2 (or dB) per frame and bin as f64, no image
 //   renderMean(handle, req, cb) / renderMeanSync(handle, req) -> {mean, width, n}: the exact mean of |X|^2 over the frames per row (or its dB)
+//   renderBandPower(handle, req, cb) / renderBandPowerSync(handle, req) -> {bands, count, width, n}: the exact sum of |X|^2 over bands of
+//     rows per frame (or its dB)
 //   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
 //       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
@@ -1196,6 +1198,72 @@ napi_value MeanJob::result(napi_env env)
 napi_value RenderMeanSync(napi_env env, napi_callback_info info) { return checked_sync<MeanJob>(env, info, kMean); }
 napi_value RenderMean(napi_env env, napi_callback_info info) { return checked_async<MeanJob>(env, info, kMean); }
 
+// ---- exact band-power series: renderBandPower(handle, req, cb) / renderBandPowerSync(handle, req) -------------------------------------
+// req as for renderPower plus `bands`, an Int32Array of y0, y1 pairs (half-open ranges of image rows) -> {bands, count, width, n}:
+// bands a Float64Array(count * width), band-major - per band and frame the correctly rounded sum of |X|^2 over the band's rows, or the
+// dB of it with db (sp_render_bandpower).  The library refuses bad bands (status -1) before anything is rendered.
+const CheckedKind kBandPower{"renderBandPower", false, "renderBandPowerSync(handle, request)", "renderBandPower(handle, request, callback)",
+                             "spectroplot_hip.renderBandPower", "could not queue the band-power request"};
+
+struct BandPowerJob : PowerJob {
+    std::vector<int32_t> rows;   // y0, y1 per band
+    std::vector<double> out;
+    bool parse_own(napi_env env, napi_value r) override;
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+bool BandPowerJob::parse_own(napi_env env, napi_value r)
+{
+    if (!PowerJob::parse_own(env, r)) return false;
+    napi_value v, ab;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void *data = nullptr;
+    if (napi_get_named_property(env, r, "bands", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
+        || tt != napi_int32_array || len % 2 != 0) {
+        napi_throw_type_error(env, nullptr, "bands must be an Int32Array of y0, y1 pairs");
+        return false;
+    }
+    if (len) rows.assign((const int32_t *)data, (const int32_t *)data + len);
+    return true;
+}
+
+void BandPowerJob::run()
+{
+    const size_t count = rows.size() / 2;
+    if (count <= SP_MAX_BANDS) {   // (more bands than the library takes get no array: it refuses them)
+        try {
+            out.assign(count * (size_t)width, 0.0);
+        } catch (const std::bad_alloc &) {
+            status = SP_ERR_NOMEM;
+            error = "out of host memory";
+            return;
+        }
+    }
+    double none = 0;
+    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
+    status = sp_render_bandpower(ctx, &req, bytes, nbytes, width, rows.data(), c, db, out.empty() ? &none : out.data());
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value BandPowerJob::result(napi_env env)
+{
+    napi_value obj, ab, ta, v;
+    void *data = nullptr;
+    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, out.size() * 8, &data, &ab) != napi_ok) return nullptr;
+    if (!out.empty()) memcpy(data, out.data(), out.size() * 8);
+    if (napi_create_typedarray(env, napi_float64_array, out.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "bands", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
+    return obj;
+}
+
+napi_value RenderBandPowerSync(napi_env env, napi_callback_info info) { return checked_sync<BandPowerJob>(env, info, kBandPower); }
+napi_value RenderBandPower(napi_env env, napi_callback_info info) { return checked_async<BandPowerJob>(env, info, kBandPower); }
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1267,6 +1335,30 @@ napi_value SliceBounds(napi_env env, napi_callback_info info)
     napi_create_array_with_length(env, 2, &out);
     napi_create_double(env, (double)b, &v); napi_set_element(env, out, 0, v);
     napi_create_double(env, (double)e, &v); napi_set_element(env, out, 1, v);
+    return out;
+}
+
+// bandRows(n, fLo, fHi) -> [y0, y1]: sp_band_rows, the image rows whose centre frequency lies in [fLo, fHi] cycles per sample
+napi_value BandRows(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    int32_t n = 0, y0 = 0, y1 = 0;
+    double lo = 0, hi = 0;
+    if (argc < 3 || napi_get_value_int32(env, argv[0], &n) != napi_ok || napi_get_value_double(env, argv[1], &lo) != napi_ok
+        || napi_get_value_double(env, argv[2], &hi) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "bandRows(n, fLo, fHi): three numbers expected");
+        return nullptr;
+    }
+    const int rc = sp_band_rows(n, lo, hi, &y0, &y1);
+    if (rc) return throw_status(env, rc, "bandRows: n must be a power of two >= 2 and fLo <= fHi");
+    napi_value out, v;
+    NAPI_OK(env, napi_create_array_with_length(env, 2, &out));
+    NAPI_OK(env, napi_create_int32(env, y0, &v));
+    NAPI_OK(env, napi_set_element(env, out, 0, v));
+    NAPI_OK(env, napi_create_int32(env, y1, &v));
+    NAPI_OK(env, napi_set_element(env, out, 1, v));
     return out;
 }
 
@@ -1520,6 +1612,9 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderPowerSync", nullptr, RenderPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderMean", nullptr, RenderMean, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderMeanSync", nullptr, RenderMeanSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bandRows", nullptr, BandRows, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderBandPower", nullptr, RenderBandPower, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderBandPowerSync", nullptr, RenderBandPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -1,4 +1,5 @@
-"""The numeric spectrogram and its exact mean as torch tensors: sp_plan_execute_power / _mean on torch's current stream.
+"""The numeric spectrogram, its exact mean and its exact band sums as torch tensors: sp_plan_execute_power / _mean / _bandpower on
+torch's current stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
 library (include/spectroplot_hip.h, "Power plane replies"), resident on the capture's device and ordered on torch's current stream:
@@ -74,4 +75,19 @@ def mean(plan, capture, width):
     out = torch.empty((plan.n,), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_mean(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
+    return out
+
+
+def bandpower(plan, capture, width, bands):
+    """The exact band-power series of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [count, width] on the same
+    device: per band (y0, y1) of image rows - a half-open range - and per frame the correctly rounded sum of |X|^2 over the band's
+    rows (include/spectroplot_hip.h, "Exact band-power series"; binding.band_rows turns a frequency range into rows).  `plan` is a
+    binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the
+    plane itself is never held whole."""
+    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
+        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.bandpower: capture must be a contiguous uint8 CUDA tensor")
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    out = torch.empty((len(bands), max(int(width), 0)), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_bandpower(capture.data_ptr(), capture.numel(), int(width), bands, out.data_ptr())
     return out
