@@ -66,44 +66,6 @@ function readCapture(file) {
     return bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength)
 }
 
-// --traces: one request over the whole capture on one worker, with the taper and block_norm the image's request resolves to
-function writeTraces(buffer, format, n, width, opt) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const worker = new HipWorker()
-    return worker.renderTraces({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }).then(t => {
-        worker.terminate()
-        const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
-        fs.writeFileSync(opt.traces, JSON.stringify({ n, width, trace_min: plain(t.trace_min), trace_max: plain(t.trace_max) }))
-    }, e => { worker.terminate(); throw e })
-}
-
-// --power / --power-db: one request over the whole capture on one worker, resolved as --traces resolves its own; the plane's bytes as they
-// are (every host this runs on is little-endian)
-function writePower(buffer, format, n, width, opt, db) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const worker = new HipWorker()
-    return worker.renderPower({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
-        worker.terminate()
-        fs.writeFileSync(db ? opt['power-db'] : opt.power, Buffer.from(r.power.buffer, r.power.byteOffset, r.power.byteLength))
-    }, e => { worker.terminate(); throw e })
-}
-
-// --mean / --mean-db: as --power, n values
-function writeMean(buffer, format, n, width, opt, db) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const worker = new HipWorker()
-    return worker.renderMean({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db }).then(r => {
-        worker.terminate()
-        fs.writeFileSync(db ? opt['mean-db'] : opt.mean, Buffer.from(r.mean.buffer, r.mean.byteOffset, r.mean.byteLength))
-    }, e => { worker.terminate(); throw e })
-}
-
 // the bands of --bands and --band-freqs, in that order, as [y0, y1] pairs
 function parseBands(opt, n) {
     const pairs = (text, num) => String(text).split(',').filter(s => s.length).map(s => {
@@ -117,48 +79,48 @@ function parseBands(opt, n) {
     return bands
 }
 
-// --bandpower / --bandpower-db: as --power, count * width values, band-major
-function writeBandPower(buffer, format, n, width, opt, db) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const bands = parseBands(opt, n)
-    const worker = new HipWorker()
-    return worker.renderBandPower({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }, { db, bands }).then(r => {
-        worker.terminate()
-        fs.writeFileSync(db ? opt['bandpower-db'] : opt.bandpower, Buffer.from(r.bands.buffer, r.bands.byteOffset, r.bands.byteLength))
-    }, e => { worker.terminate(); throw e })
-}
+// a typed array's bytes as they are (every host this runs on is little-endian)
+const raw = a => Buffer.from(a.buffer, a.byteOffset, a.byteLength)
 
-// --index: one request over the whole capture on one worker, with the taper, block_norm and end-forced colour map the image's request
-// resolves to
-function writeIndex(buffer, format, n, width, opt) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())
-    cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
-    const worker = new HipWorker()
-    return worker.renderIndexed({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), cmap, channelMode: !!opt.channelMode, waterfall: !!opt.waterfall, detector: opt.detector }).then(r => {
-        worker.terminate()
-        fs.writeFileSync(opt.index, Buffer.concat([Buffer.from(`P5\n${r.width} ${r.height}\n255\n`),
-            Buffer.from(r.index.buffer, r.index.byteOffset, r.index.byteLength)]))
-    }, e => { worker.terminate(); throw e })
-}
+// --NAME FILE / --NAME-db FILE: raw f64 of the reply's `field`; `own(opt, n)`: the kind's options beside `db`
+const f64Outputs = (name, method, field, own) => [false, true].map(db => ({ option: db ? name + '-db' : name, method,
+    options: (opt, n) => Object.assign({ db }, own && own(opt, n)), bytes: r => raw(r[field]) }))
 
-// --density: one request over the whole capture on one worker, resolved as --index resolves its own; raw counts, saturated at 65535
-function writeDensity(buffer, format, n, width, opt) {
-    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
-    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
-    const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())
-    cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
-    const worker = new HipWorker()
-    return worker.renderDensity({ buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
-        range: parseFloat(opt.range), cmap, channelMode: !!opt.channelMode, waterfall: !!opt.waterfall, detector: opt.detector }).then(r => {
-        worker.terminate()
+// The side outputs of a single-file run, in the order they are written.  `picture`: the request carries the end-forced colour map and
+// `waterfall`, as the image's does; `method` of HipWorker gets the message and `options(opt, n)`; `bytes(reply, n, width)` is the file.
+const SIDE_OUTPUTS = [
+    { option: 'traces', method: 'renderTraces', bytes: (t, n, width) => {
+        const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
+        return JSON.stringify({ n, width, trace_min: plain(t.trace_min), trace_max: plain(t.trace_max) })
+    } },
+    { option: 'index', picture: true, method: 'renderIndexed',
+        bytes: r => Buffer.concat([Buffer.from(`P5\n${r.width} ${r.height}\n255\n`), raw(r.index)]) },
+    { option: 'density', picture: true, method: 'renderDensity', bytes: r => {                 // raw counts, saturated at 65535
         const body = Buffer.alloc(2 * r.density.length)
         for (let i = 0; i < r.density.length; i++) body.writeUInt16BE(r.density[i] < 65535 ? r.density[i] : 65535, 2 * i)
-        fs.writeFileSync(opt.density, Buffer.concat([Buffer.from(`P5\n${r.lutLen} ${r.n}\n65535\n`), body]))
+        return Buffer.concat([Buffer.from(`P5\n${r.lutLen} ${r.n}\n65535\n`), body])
+    } },
+    ...f64Outputs('power', 'renderPower', 'power'),                    // width * n values, frame-major
+    ...f64Outputs('mean', 'renderMean', 'mean'),                       // n values
+    ...f64Outputs('bandpower', 'renderBandPower', 'bands', (opt, n) => ({ bands: parseBands(opt, n) })),   // count * width values, band-major
+]
+
+// one side output: one request over the whole capture on one worker, with the taper and block_norm the image's request resolves to
+function writeSide(kind, buffer, format, n, width, opt) {
+    const native = require(path.join(__dirname, '..', 'lib', 'spectroplot_hip.node'))
+    const w = native.window(native.namedResolve(String(opt.window), String(opt.cmap)).window, n)
+    const message = { buffer, format, n, width, windowc: w.window, block_norm: 1.0 / w.weight, gain: parseFloat(opt.gain),
+        range: parseFloat(opt.range), channelMode: !!opt.channelMode, detector: opt.detector }
+    if (kind.picture) {
+        const cmap = cmapByName(String(opt.cmap)).map(c => c.slice())
+        cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
+        Object.assign(message, { cmap, waterfall: !!opt.waterfall })
+    }
+    const options = kind.options && kind.options(opt, n)
+    const worker = new HipWorker()
+    return worker[kind.method](message, options).then(r => {
+        worker.terminate()
+        fs.writeFileSync(opt[kind.option], kind.bytes(r, n, width))
     }, e => { worker.terminate(); throw e })
 }
 
@@ -231,15 +193,8 @@ function main(argv) {
             console.log(`${file}: ${format}, centre ${fr.freq} Hz, rate ${fr.rate} Hz -> ${opt.out} (${img.width} x ${img.height}), ` +
                 `dBfs ${img.dBfs_min.toFixed(2)} .. ${img.dBfs_max.toFixed(2)}, ${Date.now() - t0} ms`)
         })
-        .then(() => opt.traces === undefined ? null : writeTraces(buffer, format, n, width, opt))
-        .then(() => opt.index === undefined ? null : writeIndex(buffer, format, n, width, opt))
-        .then(() => opt.density === undefined ? null : writeDensity(buffer, format, n, width, opt))
-        .then(() => opt.power === undefined ? null : writePower(buffer, format, n, width, opt, false))
-        .then(() => opt['power-db'] === undefined ? null : writePower(buffer, format, n, width, opt, true))
-        .then(() => opt.mean === undefined ? null : writeMean(buffer, format, n, width, opt, false))
-        .then(() => opt['mean-db'] === undefined ? null : writeMean(buffer, format, n, width, opt, true))
-        .then(() => opt.bandpower === undefined ? null : writeBandPower(buffer, format, n, width, opt, false))
-        .then(() => opt['bandpower-db'] === undefined ? null : writeBandPower(buffer, format, n, width, opt, true))
+        .then(() => SIDE_OUTPUTS.reduce((done, kind) => done.then(() => opt[kind.option] === undefined ? null
+            : writeSide(kind, buffer, format, n, width, opt)), Promise.resolve()))
 }
 
 // (an explicit exit: Node 12 can crash while it tears its environment down when finalizers of collected reply buffers are

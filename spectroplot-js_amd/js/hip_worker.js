@@ -60,6 +60,17 @@ function detectorId(d) {
     throw Object.assign(new Error(`detector must be 'sample' or 'peak', not ${JSON.stringify(d) || String(d)}`), { status: -1 })
 }
 
+/** `buffer` of a message as the addon reads it: the bytes of a typed-array view copied out into an ArrayBuffer, anything else as it is. */
+function arrayBufferOf(buffer) {
+    return ArrayBuffer.isView(buffer) ? buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength) : buffer
+}
+
+const refusal = (message, status) => Object.assign(new Error(message), { status })
+
+// what `onerror` reports as the status of a rejected request (_queued): the error's own, or -1 where it has none
+const ownStatus = err => err.status
+const statusOrInvalid = err => err.status === undefined ? -1 : err.status
+
 class HipWorker {
     /** @param {{device?: number}} [options] — device index; default: round-robin over the visible GPUs. */
     constructor(options) {
@@ -103,9 +114,7 @@ class HipWorker {
         const n = m.n
         // (the typed-array constructor converts an Array in one go; Float64Array.from() walks its iterator)
         const windowc = m.windowc instanceof Float64Array ? m.windowc : new Float64Array(m.windowc)
-        let buffer = m.buffer
-        if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
-        return { format: fmt.id, buffer, n, windowc, block_norm: m.block_norm, gain: m.gain, range: m.range,
+        return { format: fmt.id, buffer: arrayBufferOf(m.buffer), n, windowc, block_norm: m.block_norm, gain: m.gain, range: m.range,
             lut: packLut(m.cmap), width: m.width, channelMode: !!m.channelMode, waterfall: !!m.waterfall, detector: detectorId(m.detector) }
     }
 
@@ -130,6 +139,25 @@ class HipWorker {
     }
 
     /**
+     * One request of the render* methods, in the instance's request order: `build()` makes the addon's request, `entry` names the
+     * addon's function, `wrap(r)` turns its reply into what the promise resolves to.  A terminated worker, a refusal of the builder and
+     * an error of the addon - thrown or called back - reject.  `report`: the status `onerror` is given for a rejection (ownStatus /
+     * statusOrInvalid), or null for a method whose rejected promise is the only report.
+     */
+    _queued(build, entry, wrap, report) {
+        const run = () => new Promise((resolve, reject) => {
+            if (this._closed) { reject(new Error('worker has been terminated')); return }
+            const req = build()                                         // (a throw in here is the promise's rejection)
+            addon()[entry](this._ctx, req, (err, r) => err ? reject(err) : resolve(wrap(r)))
+        })
+        const p = this._queue.then(run)
+        this._queue = p.then(() => null, err => {
+            if (report && !this._closed) this._emit('error', { message: err.message, status: report(err), error: err })
+        })
+        return p
+    }
+
+    /**
      * A request by option names instead of evaluated arrays - not part of the reference worker's wire contract (its messages carry the
      * evaluated taper and colour map, lib/spectroplot.js:1213-1226), but what the reference's caller starts from: the library resolves
      * `window` and `cmap` with the reference's lookup rules and defaults (lib/utils.js:25-40, lib/spectroplot.js:238-264), evaluates
@@ -138,21 +166,10 @@ class HipWorker {
      *          range?: number, channelMode?: boolean, waterfall?: boolean, offset?: number, detector?: 'sample'|'peak'}} o
      * @returns {Promise<object>} the reply, fields as in a worker reply; runs in the instance's request order
      */
-    renderNamed(o) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._namedRequest(o) } catch (e) { reject(e); return }
-            addon().renderNamed(this._ctx, req, (err, r) => err ? reject(err) : resolve(this._wrap(o, r)))
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, () => null)
-        return p
-    }
+    renderNamed(o) { return this._queued(() => this._namedRequest(o), 'renderNamed', r => this._wrap(o, r), null) }
 
     _namedRequest(o) {
-        let buffer = o.buffer
-        if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
+        const buffer = arrayBufferOf(o.buffer)
         return { format: String(o.format), window: String(o.window === undefined ? '' : o.window), cmap: String(o.cmap === undefined ? '' : o.cmap),
             buffer, n: o.n, width: o.width, gain: o.gain === undefined ? 6 : o.gain, range: o.range === undefined ? 30 : o.range,
             channelMode: !!o.channelMode, waterfall: !!o.waterfall, detector: detectorId(o.detector) }
@@ -167,28 +184,29 @@ class HipWorker {
      * @returns {Promise<{trace_min: Float64Array, trace_max: Float64Array}>}
      */
     renderTraces(m) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._tracesRequest(m) } catch (e) { reject(e); return }
-            try {
-                addon().renderTraces(this._ctx, req, (err, r) => err ? reject(err) : resolve({ trace_min: r.trace_min, trace_max: r.trace_max }))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
-        return p
+        return this._queued(() => this._tracesRequest(m), 'renderTraces', r => ({ trace_min: r.trace_min, trace_max: r.trace_max }), ownStatus)
     }
 
-    _tracesRequest(m) {
-        if (!(m && m.buffer)) throw Object.assign(new Error('a traces request needs a buffer'), { status: -1 })
-        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('traces of the peak detector are not supported'), { status: -4 })
+    _tracesRequest(m) { return this._plainRequest(m, 'a traces request needs a buffer', 'traces of the peak detector are not supported') }
+
+    /**
+     * A request without a picture - no colour map, no `waterfall`, the sample detector only - with the kind's two refusal texts: of a
+     * message without a buffer (status -1) and of the peak detector (status -4).  `own()` makes the kind's own fields, which follow the
+     * shared ones; what it refuses is refused before anything is built.
+     */
+    _plainRequest(m, noBuffer, noPeak, own) {
+        if (!(m && m.buffer)) throw refusal(noBuffer, -1)
+        if (detectorId(m.detector) !== 0) throw refusal(noPeak, -4)
+        const fields = own ? own() : null
         const fmt = addon().parseFormat(String(m.format))
         const windowc = m.windowc instanceof Float64Array ? m.windowc : new Float64Array(m.windowc)
-        let buffer = m.buffer
-        if (ArrayBuffer.isView(buffer)) buffer = buffer.buffer.slice(buffer.byteOffset, buffer.byteOffset + buffer.byteLength)
-        return { format: fmt.id, buffer, n: m.n, windowc, block_norm: m.block_norm, gain: m.gain, range: m.range, width: m.width,
-            channelMode: !!m.channelMode }
+        return Object.assign({ format: fmt.id, buffer: arrayBufferOf(m.buffer), n: m.n, windowc, block_norm: m.block_norm, gain: m.gain,
+            range: m.range, width: m.width, channelMode: !!m.channelMode }, fields)
+    }
+
+    /** ... plus `db` of the options (renderPower, renderMean, renderBandPower), the kind's own fields behind it. */
+    _dbRequest(m, opt, noBuffer, noPeak, own) {
+        return this._plainRequest(m, noBuffer, noPeak, () => Object.assign({ db: !!(opt && opt.db) }, own && own()))
     }
 
     /**
@@ -200,23 +218,11 @@ class HipWorker {
      * @returns {Promise<{power: Float64Array, width: number, n: number}>}
      */
     renderPower(m, opt) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._powerRequest(m, opt) } catch (e) { reject(e); return }
-            try {
-                addon().renderPower(this._ctx, req, (err, r) => err ? reject(err) : resolve({ power: r.power, width: r.width, n: r.n }))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
-        return p
+        return this._queued(() => this._powerRequest(m, opt), 'renderPower', r => ({ power: r.power, width: r.width, n: r.n }), ownStatus)
     }
 
     _powerRequest(m, opt) {
-        if (!(m && m.buffer)) throw Object.assign(new Error('a power request needs a buffer'), { status: -1 })
-        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the power plane of the peak detector is not supported'), { status: -4 })
-        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db) })
+        return this._dbRequest(m, opt, 'a power request needs a buffer', 'the power plane of the peak detector is not supported')
     }
 
     /** Synchronous form of renderPower (tests). */
@@ -231,23 +237,11 @@ class HipWorker {
      * @returns {Promise<{mean: Float64Array, width: number, n: number}>}
      */
     renderMean(m, opt) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._meanRequest(m, opt) } catch (e) { reject(e); return }
-            try {
-                addon().renderMean(this._ctx, req, (err, r) => err ? reject(err) : resolve({ mean: r.mean, width: r.width, n: r.n }))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
-        return p
+        return this._queued(() => this._meanRequest(m, opt), 'renderMean', r => ({ mean: r.mean, width: r.width, n: r.n }), ownStatus)
     }
 
     _meanRequest(m, opt) {
-        if (!(m && m.buffer)) throw Object.assign(new Error('a mean request needs a buffer'), { status: -1 })
-        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the mean power of the peak detector is not supported'), { status: -4 })
-        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db) })
+        return this._dbRequest(m, opt, 'a mean request needs a buffer', 'the mean power of the peak detector is not supported')
     }
 
     /** Synchronous form of renderMean (tests). */
@@ -264,33 +258,22 @@ class HipWorker {
      * @returns {Promise<{bands: Float64Array, count: number, width: number, n: number}>}
      */
     renderBandPower(m, opt) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._bandRequest(m, opt) } catch (e) { reject(e); return }
-            try {
-                addon().renderBandPower(this._ctx, req,
-                    (err, r) => err ? reject(err) : resolve({ bands: r.bands, count: r.count, width: r.width, n: r.n }))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => { if (!this._closed) this._emit('error', { message: err.message, status: err.status, error: err }) })
-        return p
+        return this._queued(() => this._bandRequest(m, opt), 'renderBandPower',
+            r => ({ bands: r.bands, count: r.count, width: r.width, n: r.n }), ownStatus)
     }
 
     _bandRequest(m, opt) {
-        if (!(m && m.buffer)) throw Object.assign(new Error('a band-power request needs a buffer'), { status: -1 })
-        if (detectorId(m.detector) !== 0) throw Object.assign(new Error('the band power of the peak detector is not supported'), { status: -4 })
-        const bad = why => Object.assign(new Error(why), { status: -1 })
-        const given = opt && opt.bands
-        if (!(Array.isArray(given) || ArrayBuffer.isView(given))) throw bad('a band-power request needs {bands}: [y0, y1] pairs')
-        const flat = Array.isArray(given) ? [].concat(...given) : Array.from(given)
-        if (flat.length % 2 !== 0 || flat.length > 128) throw bad('bands must be at most 64 [y0, y1] pairs')
-        for (let b = 0; b < flat.length; b += 2) {
-            const y0 = flat[b], y1 = flat[b + 1]
-            if (!Number.isInteger(y0) || !Number.isInteger(y1) || y0 < 0 || y1 < y0 || y1 > m.n) throw bad('a band must satisfy 0 <= y0 <= y1 <= n')
-        }
-        return Object.assign(this._tracesRequest(m), { db: !!(opt && opt.db), bands: Int32Array.from(flat) })
+        return this._dbRequest(m, opt, 'a band-power request needs a buffer', 'the band power of the peak detector is not supported', () => {
+            const given = opt && opt.bands
+            if (!(Array.isArray(given) || ArrayBuffer.isView(given))) throw refusal('a band-power request needs {bands}: [y0, y1] pairs', -1)
+            const flat = Array.isArray(given) ? [].concat(...given) : Array.from(given)
+            if (flat.length % 2 !== 0 || flat.length > 128) throw refusal('bands must be at most 64 [y0, y1] pairs', -1)
+            for (let b = 0; b < flat.length; b += 2) {
+                const y0 = flat[b], y1 = flat[b + 1]
+                if (!Number.isInteger(y0) || !Number.isInteger(y1) || y0 < 0 || y1 < y0 || y1 > m.n) throw refusal('a band must satisfy 0 <= y0 <= y1 <= n', -1)
+            }
+            return { bands: Int32Array.from(flat) }
+        })
     }
 
     /** Synchronous form of renderBandPower (tests). */
@@ -308,27 +291,13 @@ class HipWorker {
      * @returns {Promise<{index: Uint8Array, width: number, height: number, c_hist: number[], cB_hist: number[], dBfs_min: number,
      *          dBfs_max: number, gauge_mins: Uint8ClampedArray, gauge_maxs: Uint8ClampedArray, gauge_amps: Uint8ClampedArray}>}
      */
-    renderIndexed(m) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._indexRequest(m) } catch (e) { reject(e); return }
-            try {
-                addon().renderIndex(this._ctx, req, (err, r) => err ? reject(err) : resolve(this._wrapIndex(m, r)))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => {
-            if (!this._closed) this._emit('error', { message: err.message, status: err.status === undefined ? -1 : err.status, error: err })
-        })
-        return p
-    }
+    renderIndexed(m) { return this._queued(() => this._indexRequest(m), 'renderIndex', r => this._wrapIndex(m, r), statusOrInvalid) }
 
     _indexRequest(m) {
-        if (!(m && m.buffer)) throw Object.assign(new Error('an indexed request needs a buffer'), { status: -1 })
-        if (!Array.isArray(m.cmap)) throw Object.assign(new Error('an indexed request needs a colour map'), { status: -1 })
+        if (!(m && m.buffer)) throw refusal('an indexed request needs a buffer', -1)
+        if (!Array.isArray(m.cmap)) throw refusal('an indexed request needs a colour map', -1)
         for (const k of ['n', 'width', 'block_norm', 'gain', 'range'])
-            if (typeof m[k] !== 'number') throw Object.assign(new Error(`${k} must be a number, not ${JSON.stringify(m[k]) || String(m[k])}`), { status: -1 })
+            if (typeof m[k] !== 'number') throw refusal(`${k} must be a number, not ${JSON.stringify(m[k]) || String(m[k])}`, -1)
         return this._request(m)
     }
 
@@ -349,21 +318,7 @@ class HipWorker {
      * counts.
      * @returns {Promise<{density: Uint32Array, n: number, lutLen: number, width: number}>}
      */
-    renderDensity(m) {
-        const run = () => new Promise((resolve, reject) => {
-            if (this._closed) { reject(new Error('worker has been terminated')); return }
-            let req
-            try { req = this._indexRequest(m) } catch (e) { reject(e); return }
-            try {
-                addon().renderDensity(this._ctx, req, (err, r) => err ? reject(err) : resolve(this._wrapDensity(r)))
-            } catch (e) { reject(e) }
-        })
-        const p = this._queue.then(run)
-        this._queue = p.then(() => null, err => {
-            if (!this._closed) this._emit('error', { message: err.message, status: err.status === undefined ? -1 : err.status, error: err })
-        })
-        return p
-    }
+    renderDensity(m) { return this._queued(() => this._indexRequest(m), 'renderDensity', r => this._wrapDensity(r), statusOrInvalid) }
 
     _wrapDensity(r) { return { density: r.density, n: r.n, lutLen: r.lutLen, width: r.width } }
 

@@ -24,6 +24,15 @@ def test_addon_loads_and_host_helpers_match_reference_kats():
     assert "addon cpu checks ok" in out.stdout
 
 
+def test_request_builders_and_the_addons_export_table():
+    """Every request builder of HipWorker, called through HipWorker.prototype without an instance, on one well-formed message and on
+    that message with one field broken at a time, against what the builders made of them before they were folded into shared pieces;
+    every name of the addon's export table is a function."""
+    out = _node("check_requests_cpu.js")
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "request builders ok: 162 cases, 36 exports" in out.stdout
+
+
 def test_caller_side_parameter_helpers_match_reference():
     out = _node("check_params.js")
     assert out.returncode == 0, out.stdout + out.stderr
