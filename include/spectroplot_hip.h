@@ -603,6 +603,63 @@ int sp_render_bandpower(sp_context *ctx, const sp_request *req, const uint8_t *b
 const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
+ * Peak track: the strongest row of a band of image rows, and its power, per frame - the peak search of a spectrum analyser per sweep,
+ * over time the frequency-versus-time track of a transmitter (the two tones of an FSK burst, a drifting carrier, a chirp); the
+ * companion of the band-power series, which shows the same burst's amplitude.  gauge_maxs is no substitute: one clamped byte for the
+ * whole spectrum, which names no row and cannot be restricted to a band.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y (abs2 of lib/worker.js:85-92) - the same
+ * geometry, limits, statuses, channel mode and row order y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90) - the bands are exactly the
+ * band-power series' bands: a HOST array int32_t bands[2 * count] of half-open row ranges [y0, y1) with 0 <= y0 <= y1 <= n, read before
+ * the call returns; 0 <= count <= SP_MAX_BANDS; bands may overlap and may be empty.  The reply is two BAND-MAJOR arrays, so every band
+ * is one contiguous time series: int32_t row[count * width] and double peak[count * width].  For band b and frame x, over the rows y in
+ * [y0_b, y1_b) whose power[x][y] is not a NaN:
+ *     peak[b * width + x] = the largest such value, bit for bit as the plane holds it (+inf can win; an all-zero frame gives +0.0)
+ *     row[b * width + x]  = the row that holds it; among equal values THE SMALLEST y WINS
+ * and for an empty band, or a band whose rows are all NaN in that frame, row = -1 and peak = NaN.  A NaN IS ANY NaN, as everywhere
+ * else; a capture shorter than n therefore gives -1 / NaN throughout.  In numpy, per frame: p = plane[x, y0:y1]; (-1, nan) if p is
+ * empty or all NaN, else k = argmax(where(isnan(p), -1.0, p)) and (y0 + k, p[k]).  A band of one row gives that row's index and the
+ * plane's column bit for bit wherever the column is not NaN.
+ * width == 0 or count == 0 writes nothing and returns SP_OK.  Either output may be NULL and is not written then; both NULL with
+ * count * width > 0 is SP_ERR_INVALID_ARG, and so is a `row` that is not 4-byte aligned or a `peak` that is not 8-byte aligned, a band
+ * outside 0 <= y0 <= y1 <= n, count outside 0 .. SP_MAX_BANDS and bands == NULL with count > 0.  The arrays are the same for both
+ * layouts and do not depend on gain, range, LUT or block_norm, NOR ON THE CU COUNT, THE WINDOW OR THE CHUNKING OF A HOST-FED REQUEST (a
+ * maximum with a fixed tie rule commutes).  Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED, as
+ * for the plane, the mean and the bands.  The dB form is sp_plan_power_to_db applied to `peak`; NaN stays NaN.
+ * How: no floating-point compare anywhere.  The KEY of a value is its bit pattern with the sign bit cleared; non-negative doubles and
+ * +inf order as their keys do as unsigned integers, and a key above 0x7ff0000000000000 is a NaN.  The larger key wins and on an equal
+ * key the smaller row (csrc/sp_track_core.h, the one place the decision is made, for the kernel and for sp_debug_band_peak).  One
+ * launch behind every block of frames: no workspace of the context, no clear, no atomics, no second launch.
+ *
+ * sp_power_tracks: the track over a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_power_bands.  Asynchronous on the context's stream, ONE launch, no workspace of the context and no request number: a stream
+ *   that is being captured is not refused.  n >= 1 (any n, not only powers of two), width >= 0; d_power (non-NULL when
+ *   count * width > 0) an 8-byte aligned device pointer.  The values must not be negative: the sign bit of a value is not looked at,
+ *   and a NaN of either sign is a NaN; what comes back for a value whose sign bit is set is unspecified beyond that.
+ * sp_plan_execute_track: device operands, asynchronous.  The plane is never held whole: it passes block by block through the mean's
+ *   window (sp_context_set_mean_window applies) and the track of the block's frames, columns [x0, x1) of every band, is made behind
+ *   each block.  The checks are sp_plan_execute_power's, then the bands', then the outputs'.  No request number: the call may be
+ *   interleaved with sp_plan_execute / _power / _mean / _bandpower on one context without a synchronisation.
+ * sp_render_track: host buffers, synchronous, the plan cached as by sp_render.  The samples are the only bulk transfer and travel as
+ *   for sp_render_bandpower - a packed upload where stride > n, chunks of frames where the request is large - and `row` and `peak`
+ *   come back in one copy each, `peak` converted to dB on the device first when db != 0.  sp_context_last_upload_bytes /
+ *   sp_context_last_chunks report as before.
+ * sp_plan_track_kernel_name_for: "frames_power+track" or "scratch_power+track", following sp_plan_power_kernel_name_for.
+ * sp_debug_band_peak: (tests, no device needed) *row and *peak of the rows [y0, y1) of one frame's `n` values through the host side of
+ *   the code the kernel runs.  SP_ERR_INVALID_ARG for values == NULL, n < 1, a band outside 0 <= y0 <= y1 <= n, or both outputs NULL
+ *   (either one may be).
+ * Out of scope: peak plans, batches, groups and sharding.py (a shard's frames are a run of columns of every band, and their merge is
+ * trivial), the search fused into the frame loop, more than one peak per band, sub-bin interpolation, and a threshold.
+ */
+int sp_power_tracks(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                    int32_t *d_row, double *d_peak);
+int sp_plan_execute_track(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                          int32_t *d_row, double *d_peak);
+int sp_render_track(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                    int32_t count, int32_t db, int32_t *row, double *peak);
+const char *sp_plan_track_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_debug_band_peak(const double *values, int32_t n, int32_t y0, int32_t y1, int32_t *row, double *peak);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

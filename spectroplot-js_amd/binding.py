@@ -1,5 +1,6 @@
 """ctypes binding of include/spectroplot_hip.h.  No compute happens in Python."""
 import ctypes as C
+import math
 import os
 import weakref
 import subprocess
@@ -183,6 +184,12 @@ class Library:
         L.sp_render_bandpower.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, vp]
         L.sp_plan_bandpower_kernel_name_for.restype = C.c_char_p
         L.sp_plan_bandpower_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_power_tracks.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+        L.sp_plan_execute_track.argtypes = [vp, vp, sz, i32, vp, i32, vp, vp]
+        L.sp_render_track.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, vp, vp]
+        L.sp_plan_track_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_track_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_debug_band_peak.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -246,6 +253,25 @@ def band_rows(n, f_lo, f_hi):
     lib = Library.get()
     lib.check(lib.L.sp_band_rows(int(n), float(f_lo), float(f_hi), C.byref(y0), C.byref(y1)))
     return y0.value, y1.value
+
+
+def band_peak(values, y0, y1):
+    """sp_debug_band_peak: (row, peak) of the rows [y0, y1) of one frame's values - the strongest row that is not a NaN, the smallest
+    among equal ones, and its value bit for bit; (-1, nan) for an empty or all-NaN band - through the host side of the code the track
+    kernel runs.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    row, peak = C.c_int32(), C.c_double()
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_band_peak(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, int(y0), int(y1), C.byref(row),
+                                       C.byref(peak)))
+    return row.value, peak.value
+
+
+def row_freq(n, row):
+    """The centre frequency of image row `row` of an n-point spectrum in cycles per sample, (n/2 - row) / n: row 0 is +1/2, row n/2 is
+    DC; NaN for row -1, a track's "no value".  The inverse of band_rows for a single row, and like it for I/Q plans (in channel mode
+    the rows are the L/R split's, not one frequency axis).  Pure Python."""
+    return math.nan if row < 0 else (n // 2 - row) / n
 
 
 def _band_array(bands):
@@ -604,6 +630,33 @@ class Context:
         self._chk(self.lib.L.sp_power_bands(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
                                             C.c_void_p(d_band or None)))
 
+    def render_track(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, channel_mode=False, db=False, lut=None,
+                     fill=None):
+        """sp_render_track: the peak track of the request, (rows int32 [count, width], peaks f64 [count, width]): per band (y0, y1) of
+        image rows and per frame the strongest row that is not a NaN (the smallest among equal ones; -1 where there is none) and its
+        |X|^2 bit for bit (NaN where there is none), or with db=True the dB of it.  No image is rendered; `lut` only takes part in the
+        plan-cache key (default: two grey entries).  fill: a byte the output arrays hold before the call (tests)."""
+        fid, _ = parse_format(fmt)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
+        b, count = _band_array(bands)
+        rows = np.zeros((count, max(int(width), 0)), np.int32)
+        peaks = np.zeros((count, max(int(width), 0)), np.float64)
+        if fill is not None:
+            rows.view(np.uint8)[...] = fill
+            peaks.view(np.uint8)[...] = fill
+        self._chk(self.lib.L.sp_render_track(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                             1 if db else 0, _p(rows) if rows.size else None, _p(peaks) if peaks.size else None))
+        return rows, peaks
+
+    def power_tracks(self, d_power, n, width, bands, d_row, d_peak):
+        """sp_power_tracks: the strongest row of the bands (y0, y1) of rows of every frame of the f64 [width, n] plane at device address
+        d_power into int32 [count, width] at d_row, and its value into f64 [count, width] at d_peak (either address may be 0: not
+        written).  Asynchronous on the context's stream; the bands are read before it returns."""
+        b, count = _band_array(bands)
+        self._chk(self.lib.L.sp_power_tracks(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                             C.c_void_p(d_row or None), C.c_void_p(d_peak or None)))
+
     def set_mean_window(self, nbytes=0):
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
@@ -749,6 +802,19 @@ class Plan:
         b, count = _band_array(bands)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_bandpower(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                                _p(b) if count else None, count, C.c_void_p(d_band or None)))
+
+    def track_kernel_name_for(self, nbytes, width):
+        """What execute_track() launches for a request of this shape: "frames_power+track" or "scratch_power+track"."""
+        return self.ctx.lib.L.sp_plan_track_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+
+    def execute_track(self, d_bytes, nbytes, width, bands, d_row, d_peak):
+        """sp_plan_execute_track: per band (y0, y1) of image rows and per frame the strongest row into the int32 [count, width] device
+        array at address d_row and its |X|^2 into the f64 [count, width] device array at d_peak (either may be 0: not written).
+        Asynchronous on the context's stream; the bands are read before it returns."""
+        b, count = _band_array(bands)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_track(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                           _p(b) if count else None, count, C.c_void_p(d_row or None),
+                                                           C.c_void_p(d_peak or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -26,6 +26,7 @@
 #include "sp_kernel_frames_index.h"
 #include "sp_launch.h"
 #include "sp_exact_sum.h"
+#include "sp_track_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -2201,6 +2202,133 @@ extern "C" int sp_render_bandpower(sp_context *ctx, const sp_request *req, const
         [&](bool, hipError_t &e) {
             const int r = db ? power_to_db(plan, d_out, total, d_out) : (int)SP_OK;
             if (!r) e = hipMemcpyAsync(band, d_out, total * sizeof(double), hipMemcpyDeviceToHost, s);
+            return r;
+        });
+}
+
+// ------------------------------------------------------------------------------------------------- peak track
+
+extern "C" const char *sp_plan_track_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+{
+    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
+    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+track" : "scratch_power+track";
+}
+
+extern "C" int sp_debug_band_peak(const double *values, int32_t n, int32_t y0, int32_t y1, int32_t *row, double *peak)
+{
+    if (!values || n < 1 || y0 < 0 || y1 < y0 || y1 > n || (!row && !peak)) return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> bits((size_t)n);
+    memcpy(bits.data(), values, (size_t)n * sizeof(double));
+    const spt::Best best = spt::band_peak(bits.data(), y0, y1);
+    const uint64_t p = spt::peak_bits_of(best);
+    if (row) *row = spt::row_of(best);
+    if (peak) memcpy(peak, &p, sizeof p);
+    return SP_OK;
+}
+
+// what every track entry point refuses of its bands and its outputs (count * width elements each, either one may be null) before it
+// touches the device
+static int check_track_args(sp_context *ctx, int n, int32_t width, const int32_t *bands, int32_t count, const int32_t *row, const double *peak)
+{
+    if (const char *why = spgeo::check_bands(n, bands, count)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (count > 0 && width > 0) {
+        if (!row && !peak) return fail(ctx, SP_ERR_INVALID_ARG, "a track needs a row array or a peak array");
+        if (((uintptr_t)row & 3) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "the track's rows must be a 4-byte aligned array of count * width int32");
+        if (((uintptr_t)peak & 7) != 0)
+            return fail(ctx, SP_ERR_INVALID_ARG, "the track's peaks must be an 8-byte aligned array of count * width doubles");
+    }
+    return SP_OK;
+}
+
+// Columns [x_base, x_base + frames) of every band's track (`width` elements apart) from the `frames` frames of the frame-major plane
+// at d_plane: one launch.
+static int track_max(sp_context *ctx, const double *d_plane, int n, long long frames, const int32_t *bands, int32_t count, int32_t *d_row,
+                     double *d_peak, int32_t width, long long x_base)
+{
+    if (frames <= 0 || count <= 0) return SP_OK;
+    spk::launch_track_max(d_plane, n, frames, bands, count, d_row, d_peak, width, x_base, ctx->stream);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// The frames [x_begin, x_end) of a track request: rendered block by block into the mean's window, as band_range does, with the track
+// of the block's frames made behind each block.
+static int track_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
+                       const int32_t *bands, int32_t count, int32_t *d_row, double *d_peak)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = plan->req.n;
+    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
+    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
+    if (rc) return fail(ctx, rc, "mean window: out of device memory");
+    double *const d_win = (double *)ctx->mean_window.p;
+    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
+        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
+        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
+        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
+        if (!rc) rc = track_max(ctx, d_win, n, x1 - x0, bands, count, d_row, d_peak, g.width, x0);
+    }
+    return rc;
+}
+
+extern "C" int sp_power_tracks(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                               int32_t *d_row, double *d_peak)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_tracks: n >= 1 and width >= 0 are required");
+    const int rc = check_track_args(ctx, n, width, bands, count, d_row, d_peak);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+    if (!d_power || ((uintptr_t)d_power & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_tracks: d_power must be an 8-byte aligned device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] { return track_max(ctx, d_power, n, width, bands, count, d_row, d_peak, width, 0); });
+}
+
+extern "C" int sp_plan_execute_track(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                     int32_t *d_row, double *d_peak)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    if (!rc) rc = check_track_args(ctx, plan->req.n, width, bands, count, d_row, d_peak);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    return timed(ctx, [&] { return track_range(plan, d_bytes, g, 0, width, nullptr, bands, count, d_row, d_peak); });
+}
+
+// A request kind of render_result, exactly as sp_render_bandpower is: the two arrays fill column by column over the chunks (nothing to
+// clear: every column is written once); on the device the count * width doubles lie in front of the count * width rows.
+extern "C" int sp_render_track(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                               int32_t count, int32_t db, int32_t *row, double *peak)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    sp_plan *plan = nullptr;
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width, [&] { return check_track_args(ctx, req->n, width, bands, count, row, peak); },
+        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+    if (rc) return rc;
+    if (width == 0 || count == 0) return SP_OK;
+
+    const size_t total = (size_t)count * (size_t)width;
+    hipStream_t s = ctx->stream;
+    rc = ctx->render_small.reserve(total * (sizeof(double) + sizeof(int32_t)) + 16);
+    if (rc) return fail(ctx, rc, "sp_render_track: out of memory");
+    double *const d_peak = peak ? (double *)ctx->render_small.p : nullptr;
+    int32_t *const d_row = row ? (int32_t *)((double *)ctx->render_small.p + total) : nullptr;
+    HostFeed feed{"sp_render_track", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
+    return render_result(
+        ctx, plan->fmt, feed, no_check,
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
+            return track_range(plan, d_in, feed.g, x0, x1, src, bands, count, d_row, d_peak);
+        },
+        [&](bool, hipError_t &e) {
+            const int r = db && d_peak ? power_to_db(plan, d_peak, total, d_peak) : (int)SP_OK;
+            if (!r && row) e = hipMemcpyAsync(row, d_row, total * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+            if (!r && e == hipSuccess && peak) e = hipMemcpyAsync(peak, d_peak, total * sizeof(double), hipMemcpyDeviceToHost, s);
             return r;
         });
 }

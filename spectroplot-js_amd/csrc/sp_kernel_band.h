@@ -8,21 +8,16 @@
 
 #include <hip/hip_runtime.h>
 
+#include "sp_band_list.h"
 #include "sp_exact_sum.h"
 
 namespace spk {
 
-constexpr int kBandMax = 64;        // SP_MAX_BANDS (sp_band.hip asserts it)
 constexpr int kBandFrames = 8;      // frames of a workgroup: one LDS column each, and one finishing thread each.  (Few, so that a
                                     // screen-wide request still fills the chip: a band has width / 8 workgroups and no more.)
 constexpr int kBandWaves = 4;       // waves of a workgroup: wave w takes the frames w, w + 4, ... of its piece
 constexpr int kBandThreads = 64 * kBandWaves;
 constexpr int kBandUnroll = 4;      // loads of 64 rows a wave has in flight
-
-// The bands of a launch as a kernel argument, 512 bytes: band b is the rows [y[2 b], y[2 b + 1]), checked by the host.
-struct BandList {
-    int32_t y[2 * kBandMax];
-};
 
 // Lane 15 of every row of 16 lanes gets the row's sum (the other lanes a prefix of it); no overflow is looked after here.
 __device__ inline uint32_t band_row_sum(uint32_t x)

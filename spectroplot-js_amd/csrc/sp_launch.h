@@ -37,6 +37,11 @@ void launch_mean_finish(const unsigned long long *ws, int n, int width, double *
 // their own.)
 void launch_band_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, double *band, long long stride,
                      long long x_base, hipStream_t stream);
+// row[b * stride + x_base + x] and peak[b * stride + x_base + x] = the strongest row of the rows [bands[2 b], bands[2 b + 1]) of frame
+// x and its value (-1 and a NaN where the band holds no value), for the plane, frames and bands of launch_band_sum; a null `row` or
+// `peak` is not written.  One launch.  (k_track_max and this launcher are sp_track.hip, a unit of their own.)
+void launch_track_max(const double *plane, int n, long long frames, const int32_t *bands, int count, int32_t *row, double *peak,
+                      long long stride, long long x_base, hipStream_t stream);
 
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 

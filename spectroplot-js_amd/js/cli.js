@@ -9,6 +9,7 @@
  *        [--full] [--traces traces.json] [--index index.pgm] [--density density.pgm] [--power power.f64] [--power-db db.f64]
  *        [--mean mean.f64] [--mean-db mean_db.f64]
  *        [--bandpower bands.f64] [--bandpower-db bands_db.f64] [--bands Y0:Y1,...] [--band-freqs LO:HI,...]
+ *        [--track-rows rows.i32] [--track-power peaks.f64] [--track-db peaks_db.f64]
  *        --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
@@ -41,6 +42,11 @@
  * --bands Y0:Y1,... (half-open ranges of image rows) followed by --band-freqs LO:HI,... (cycles per sample, -0.5 .. 0.5, turned into
  * rows by sp_band_rows: row y is centred on (n/2 - y) / n); at most 64 in all.
  *
+ * --track-rows FILE / --track-power FILE / --track-db FILE (single-file runs, sample detector): the peak track of the same request over
+ * the whole capture (HipWorker.renderTrack -> sp_render_track) for the bands of --bands / --band-freqs, count * width values each,
+ * band-major: per band and frame the strongest image row that is not a NaN, the smallest among equal ones, as raw little-endian int32
+ * (-1 where the band holds no value), its |X|^2 as raw little-endian f64 (NaN there), or for --track-db the dB of it.
+ *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
  * --full composes the plot the reference shows around the spectrogram (js/raster.js): amplitude and min/max gauge strips above it, to
@@ -67,7 +73,7 @@ function readCapture(file) {
 }
 
 // the bands of --bands and --band-freqs, in that order, as [y0, y1] pairs
-function parseBands(opt, n) {
+function parseBands(opt, n, who = '--bandpower') {
     const pairs = (text, num) => String(text).split(',').filter(s => s.length).map(s => {
         const p = s.split(':')
         if (p.length !== 2 || !p.every(v => v.trim().length && Number.isFinite(num(v)))) throw new Error(`bad band '${s}': A:B expected`)
@@ -75,7 +81,7 @@ function parseBands(opt, n) {
     })
     const bands = opt.bands === undefined ? [] : pairs(opt.bands, Number)
     if (opt['band-freqs'] !== undefined) for (const [lo, hi] of pairs(opt['band-freqs'], Number)) bands.push(HipWorker.bandRows(n, lo, hi))
-    if (!bands.length) throw new Error('--bandpower needs --bands Y0:Y1,... and / or --band-freqs LO:HI,...')
+    if (!bands.length) throw new Error(who + ' needs --bands Y0:Y1,... and / or --band-freqs LO:HI,...')
     return bands
 }
 
@@ -103,6 +109,10 @@ const SIDE_OUTPUTS = [
     ...f64Outputs('power', 'renderPower', 'power'),                    // width * n values, frame-major
     ...f64Outputs('mean', 'renderMean', 'mean'),                       // n values
     ...f64Outputs('bandpower', 'renderBandPower', 'bands', (opt, n) => ({ bands: parseBands(opt, n) })),   // count * width values, band-major
+    // the peak track, count * width values each, band-major: the rows as int32, their power and its dB as f64
+    { option: 'track-rows', method: 'renderTrack', options: (opt, n) => ({ bands: parseBands(opt, n, '--track-rows') }), bytes: r => raw(r.rows) },
+    { option: 'track-power', method: 'renderTrack', options: (opt, n) => ({ bands: parseBands(opt, n, '--track-power') }), bytes: r => raw(r.peaks) },
+    { option: 'track-db', method: 'renderTrack', options: (opt, n) => ({ db: true, bands: parseBands(opt, n, '--track-db') }), bytes: r => raw(r.peaks) },
 ]
 
 // one side output: one request over the whole capture on one worker, with the taper and block_norm the image's request resolves to

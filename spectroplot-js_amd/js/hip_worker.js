@@ -204,7 +204,7 @@ class HipWorker {
             range: m.range, width: m.width, channelMode: !!m.channelMode }, fields)
     }
 
-    /** ... plus `db` of the options (renderPower, renderMean, renderBandPower), the kind's own fields behind it. */
+    /** ... plus `db` of the options (renderPower, renderMean, renderBandPower, renderTrack), the kind's own fields behind it. */
     _dbRequest(m, opt, noBuffer, noPeak, own) {
         return this._plainRequest(m, noBuffer, noPeak, () => Object.assign({ db: !!(opt && opt.db) }, own && own()))
     }
@@ -263,17 +263,21 @@ class HipWorker {
     }
 
     _bandRequest(m, opt) {
-        return this._dbRequest(m, opt, 'a band-power request needs a buffer', 'the band power of the peak detector is not supported', () => {
-            const given = opt && opt.bands
-            if (!(Array.isArray(given) || ArrayBuffer.isView(given))) throw refusal('a band-power request needs {bands}: [y0, y1] pairs', -1)
-            const flat = Array.isArray(given) ? [].concat(...given) : Array.from(given)
-            if (flat.length % 2 !== 0 || flat.length > 128) throw refusal('bands must be at most 64 [y0, y1] pairs', -1)
-            for (let b = 0; b < flat.length; b += 2) {
-                const y0 = flat[b], y1 = flat[b + 1]
-                if (!Number.isInteger(y0) || !Number.isInteger(y1) || y0 < 0 || y1 < y0 || y1 > m.n) throw refusal('a band must satisfy 0 <= y0 <= y1 <= n', -1)
-            }
-            return { bands: Int32Array.from(flat) }
-        })
+        return this._dbRequest(m, opt, 'a band-power request needs a buffer', 'the band power of the peak detector is not supported',
+            () => this._bandsField(m, opt, 'a band-power request'))
+    }
+
+    /** The `bands` field of a band-power or track request from `{bands}` of its options; what it refuses has status -1. */
+    _bandsField(m, opt, who) {
+        const given = opt && opt.bands
+        if (!(Array.isArray(given) || ArrayBuffer.isView(given))) throw refusal(who + ' needs {bands}: [y0, y1] pairs', -1)
+        const flat = Array.isArray(given) ? [].concat(...given) : Array.from(given)
+        if (flat.length % 2 !== 0 || flat.length > 128) throw refusal('bands must be at most 64 [y0, y1] pairs', -1)
+        for (let b = 0; b < flat.length; b += 2) {
+            const y0 = flat[b], y1 = flat[b + 1]
+            if (!Number.isInteger(y0) || !Number.isInteger(y1) || y0 < 0 || y1 < y0 || y1 > m.n) throw refusal('a band must satisfy 0 <= y0 <= y1 <= n', -1)
+        }
+        return { bands: Int32Array.from(flat) }
     }
 
     /** Synchronous form of renderBandPower (tests). */
@@ -281,6 +285,33 @@ class HipWorker {
 
     /** sp_band_rows: the image rows [y0, y1) whose centre frequency (n/2 - y) / n lies in [fLo, fHi] cycles per sample (I/Q plans). */
     static bandRows(n, fLo, fHi) { return addon().bandRows(n, fLo, fHi) }
+
+    /**
+     * The peak track of a request (sp_render_track) - the peak search of a spectrum analyser per sweep, over time the
+     * frequency-versus-time track of a transmitter: the fields renderTraces reads in plus `{bands}` as for renderBandPower, and two
+     * arrays out, band-major: rows[b * width + x] is the strongest image row of frame x among the rows of band b that are not NaN (the
+     * smallest among equal ones; -1 where there is none: an empty band, a capture shorter than n) and peaks[b * width + x] its |X|^2
+     * bit for bit (NaN where there is none) - or, with `{db: true}`, the dB of it.  HipWorker.rowFreq turns a row into a frequency.
+     * No image is rendered.  Only the sample detector has a track (status -4) and bad bands are refused (status -1), both before
+     * anything is rendered.  Runs in the instance's request order; a malformed field rejects (and reports `onerror`) and never
+     * resolves to arrays.
+     * @returns {Promise<{rows: Int32Array, peaks: Float64Array, count: number, width: number, n: number}>}
+     */
+    renderTrack(m, opt) {
+        return this._queued(() => this._trackRequest(m, opt), 'renderTrack',
+            r => ({ rows: r.rows, peaks: r.peaks, count: r.count, width: r.width, n: r.n }), ownStatus)
+    }
+
+    _trackRequest(m, opt) {
+        return this._dbRequest(m, opt, 'a track request needs a buffer', 'the peak track of the peak detector is not supported',
+            () => this._bandsField(m, opt, 'a track request'))
+    }
+
+    /** Synchronous form of renderTrack (tests). */
+    renderTrackSync(m, opt) { return addon().renderTrackSync(this._ctx, this._trackRequest(m, opt)) }
+
+    /** The centre frequency of image row `row` of an n-point spectrum, (n/2 - row) / n cycles per sample; NaN for row -1 (I/Q plans). */
+    static rowFreq(n, row) { return row < 0 ? NaN : (Math.floor(n / 2) - row) / n }
 
     /**
      * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the

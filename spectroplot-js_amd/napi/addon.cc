@@ -28,6 +28,8 @@
 //   renderMean(handle, req, cb) / renderMeanSync(handle, req) -> {mean, width, n}: the exact mean of |X|^2 over the frames per row (or its dB)
 //   renderBandPower(handle, req, cb) / renderBandPowerSync(handle, req) -> {bands, count, width, n}: the exact sum of |X|^2 over bands of
 //     rows per frame (or its dB)
+//   renderTrack(handle, req, cb) / renderTrackSync(handle, req) -> {rows, peaks, count, width, n}: the strongest row of bands of rows per
+//     frame and its |X|^2 (or its dB)
 //   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
 //       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
@@ -1264,6 +1266,61 @@ napi_value BandPowerJob::result(napi_env env)
 napi_value RenderBandPowerSync(napi_env env, napi_callback_info info) { return checked_sync<BandPowerJob>(env, info, kBandPower); }
 napi_value RenderBandPower(napi_env env, napi_callback_info info) { return checked_async<BandPowerJob>(env, info, kBandPower); }
 
+// ---- peak track: renderTrack(handle, req, cb) / renderTrackSync(handle, req) -------------------------------------------------------------
+// req as for renderBandPower -> {rows, peaks, count, width, n}: rows an Int32Array(count * width) and peaks a Float64Array(count * width),
+// band-major - per band and frame the strongest image row that is not a NaN (the smallest among equal ones, -1 where there is none) and
+// its |X|^2 (NaN where there is none), or the dB of it with db (sp_render_track).  The library refuses bad bands (status -1) before
+// anything is rendered.
+const CheckedKind kTrack{"renderTrack", false, "renderTrackSync(handle, request)", "renderTrack(handle, request, callback)",
+                         "spectroplot_hip.renderTrack", "could not queue the track request"};
+
+struct TrackJob : BandPowerJob {   // (`rows` are the bands, `out` the peaks)
+    std::vector<int32_t> best;     // the strongest row per band and frame
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+void TrackJob::run()
+{
+    const size_t count = rows.size() / 2;
+    if (count <= SP_MAX_BANDS) {   // (more bands than the library takes get no arrays: it refuses them)
+        try {
+            out.assign(count * (size_t)width, 0.0);
+            best.assign(count * (size_t)width, 0);
+        } catch (const std::bad_alloc &) {
+            status = SP_ERR_NOMEM;
+            error = "out of host memory";
+            return;
+        }
+    }
+    double none = 0;
+    int32_t no_row = 0;
+    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
+    status = sp_render_track(ctx, &req, bytes, nbytes, width, rows.data(), c, db, best.empty() ? &no_row : best.data(), out.empty() ? &none : out.data());
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value TrackJob::result(napi_env env)
+{
+    napi_value obj, ab, ta, v;
+    void *data = nullptr;
+    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, best.size() * 4, &data, &ab) != napi_ok) return nullptr;
+    if (!best.empty()) memcpy(data, best.data(), best.size() * 4);
+    if (napi_create_typedarray(env, napi_int32_array, best.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "rows", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_arraybuffer(env, out.size() * 8, &data, &ab) != napi_ok) return nullptr;
+    if (!out.empty()) memcpy(data, out.data(), out.size() * 8);
+    if (napi_create_typedarray(env, napi_float64_array, out.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "peaks", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
+    return obj;
+}
+
+napi_value RenderTrackSync(napi_env env, napi_callback_info info) { return checked_sync<TrackJob>(env, info, kTrack); }
+napi_value RenderTrack(napi_env env, napi_callback_info info) { return checked_async<TrackJob>(env, info, kTrack); }
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1615,6 +1672,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"bandRows", nullptr, BandRows, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderBandPower", nullptr, RenderBandPower, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderBandPowerSync", nullptr, RenderBandPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderTrack", nullptr, RenderTrack, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderTrackSync", nullptr, RenderTrackSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean and its exact band sums as torch tensors: sp_plan_execute_power / _mean / _bandpower on
-torch's current stream.
+"""The numeric spectrogram, its exact mean, its exact band sums and its peak track as torch tensors: sp_plan_execute_power / _mean /
+_bandpower / _track on torch's current stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
 library (include/spectroplot_hip.h, "Power plane replies"), resident on the capture's device and ordered on torch's current stream:
@@ -91,3 +91,21 @@ def bandpower(plan, capture, width, bands):
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_bandpower(capture.data_ptr(), capture.numel(), int(width), bands, out.data_ptr())
     return out
+
+
+def track(plan, capture, width, bands):
+    """The peak track of `capture` (a uint8 CUDA tensor: the raw bytes) as an int32 tensor [count, width] and a float64 tensor
+    [count, width] on the same device: per band (y0, y1) of image rows - a half-open range - and per frame the strongest row that is
+    not a NaN (the smallest among equal ones, -1 where there is none) and its |X|^2 bit for bit (NaN where there is none)
+    (include/spectroplot_hip.h, "Peak track"; binding.row_freq turns a row into a frequency).  `plan` is a binding.Plan of the sample
+    detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the plane itself is never held
+    whole."""
+    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
+        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.track: capture must be a contiguous uint8 CUDA tensor")
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    shape = (len(bands), max(int(width), 0))
+    rows = torch.empty(shape, dtype=torch.int32, device=capture.device)
+    peaks = torch.empty(shape, dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, rows, peaks)):
+        plan.execute_track(capture.data_ptr(), capture.numel(), int(width), bands, rows.data_ptr(), peaks.data_ptr())
+    return rows, peaks
