@@ -397,6 +397,22 @@ def _no_picture_lut(lut):
     return np.array([[0, 0, 0], [255, 255, 255]], np.uint8) if lut is None else lut
 
 
+def _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode):
+    """How a host-fed request that renders no picture begins: (the capture as contiguous bytes, the request, the arrays it points into)."""
+    fid, _ = parse_format(fmt)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
+    return data, req, keep
+
+
+def _filled(shape, dtype, fill, bytewise=True):
+    """An output array of zeros, or one that holds `fill` before the call (tests): in every byte, or as every element's value."""
+    out = np.zeros(shape, dtype)
+    if fill is not None:
+        (out.view(np.uint8) if bytewise else out)[...] = fill
+    return out
+
+
 def _launch_dict(words):
     """sp_plan_debug_launch's words as a dict of LAUNCH_FIELDS, "kernel" as a name (5: k_frames_index)."""
     d = dict(zip(LAUNCH_FIELDS, (int(v) for v in words)))
@@ -564,13 +580,8 @@ class Context:
         """sp_render_traces: the per-bin min-hold / max-hold traces of the request, {"trace_min": f64[n], "trace_max": f64[n]} in image
         row order.  No image is rendered; `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a value the
         output arrays hold before the call (tests)."""
-        fid, _ = parse_format(fmt)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
-        tmin, tmax = np.zeros(n), np.zeros(n)
-        if fill is not None:
-            tmin[:] = fill
-            tmax[:] = fill
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        tmin, tmax = _filled(n, np.float64, fill, False), _filled(n, np.float64, fill, False)
         self._chk(self.lib.L.sp_render_traces(self.h, C.byref(req), _p(data), data.size, int(width), _p(tmin), _p(tmax)))
         return {"trace_min": tmin, "trace_max": tmax}
 
@@ -578,13 +589,8 @@ class Context:
         """sp_render_power: the numeric spectrogram of the request, f64 [width, n]: |X|^2 of frame x at image row y in [x, y], or with
         db=True its dB plane.  No image is rendered; `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a
         byte the output array holds before the call (tests)."""
-        fid, _ = parse_format(fmt)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
-        W = max(int(width), 0)
-        power = np.zeros((W, int(n)), np.float64)
-        if fill is not None:
-            power.view(np.uint8)[...] = fill
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        power = _filled((max(int(width), 0), int(n)), np.float64, fill)
         self._chk(self.lib.L.sp_render_power(self.h, C.byref(req), _p(data), data.size, int(width), 1 if db else 0, _p(power)))
         return power
 
@@ -592,12 +598,8 @@ class Context:
         """sp_render_mean: the exact mean-power trace of the request, f64[n] in image row order: the correctly rounded sum of |X|^2 over
         the frames divided by width, or with db=True the dB of it.  No image is rendered; `lut` only takes part in the plan-cache key
         (default: two grey entries).  fill: a byte the output array holds before the call (tests)."""
-        fid, _ = parse_format(fmt)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
-        mean = np.zeros(int(n), np.float64)
-        if fill is not None:
-            mean.view(np.uint8)[...] = fill
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        mean = _filled(int(n), np.float64, fill)
         self._chk(self.lib.L.sp_render_mean(self.h, C.byref(req), _p(data), data.size, int(width), 1 if db else 0, _p(mean)))
         return mean
 
@@ -612,13 +614,9 @@ class Context:
         per frame the correctly rounded sum of |X|^2 over the band's rows, or with db=True the dB of it.  No image is rendered; `lut`
         only takes part in the plan-cache key (default: two grey entries).  fill: a byte the output array holds before the call
         (tests)."""
-        fid, _ = parse_format(fmt)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
         b, count = _band_array(bands)
-        out = np.zeros((count, max(int(width), 0)), np.float64)
-        if fill is not None:
-            out.view(np.uint8)[...] = fill
+        out = _filled((count, max(int(width), 0)), np.float64, fill)
         self._chk(self.lib.L.sp_render_bandpower(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
                                                  1 if db else 0, _p(out) if out.size else None))
         return out
@@ -636,15 +634,10 @@ class Context:
         image rows and per frame the strongest row that is not a NaN (the smallest among equal ones; -1 where there is none) and its
         |X|^2 bit for bit (NaN where there is none), or with db=True the dB of it.  No image is rendered; `lut` only takes part in the
         plan-cache key (default: two grey entries).  fill: a byte the output arrays hold before the call (tests)."""
-        fid, _ = parse_format(fmt)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        req, keep = _make_request(fid, n, windowc, block_norm, gain, rng, _no_picture_lut(lut), channel_mode, False)
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
         b, count = _band_array(bands)
-        rows = np.zeros((count, max(int(width), 0)), np.int32)
-        peaks = np.zeros((count, max(int(width), 0)), np.float64)
-        if fill is not None:
-            rows.view(np.uint8)[...] = fill
-            peaks.view(np.uint8)[...] = fill
+        rows = _filled((count, max(int(width), 0)), np.int32, fill)
+        peaks = _filled((count, max(int(width), 0)), np.float64, fill)
         self._chk(self.lib.L.sp_render_track(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
                                              1 if db else 0, _p(rows) if rows.size else None, _p(peaks) if peaks.size else None))
         return rows, peaks
@@ -762,9 +755,13 @@ class Plan:
         rep = _device_reply(rgba, gauge_mins, gauge_maxs, gauge_amps, c_hist, cb_hist, dbfs_minmax)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute(self.h, C.c_void_p(d_bytes), nbytes, int(width), C.byref(rep)))
 
+    def _kernel_name_for(self, kind, nbytes, width):
+        """sp_plan_<kind>_kernel_name_for: what that kind's execute runs for a request of this shape."""
+        return getattr(self.ctx.lib.L, "sp_plan_%s_kernel_name_for" % kind)(self.h, int(nbytes), int(width)).decode()
+
     def traces_kernel_name_for(self, nbytes, width):
         """The frame loop execute_traces() launches for a request of this shape: "frames_traces" or "scratch_traces"."""
-        return self.ctx.lib.L.sp_plan_traces_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("traces", nbytes, width)
 
     def execute_traces(self, d_bytes, nbytes, width, trace_min=0, trace_max=0):
         """sp_plan_execute_traces: the per-bin min / max traces of the request into two f64[n] device arrays (addresses; 0 skips one).
@@ -774,7 +771,7 @@ class Plan:
 
     def power_kernel_name_for(self, nbytes, width):
         """The frame loop execute_power() launches for a request of this shape: "frames_power" or "scratch_power"."""
-        return self.ctx.lib.L.sp_plan_power_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("power", nbytes, width)
 
     def execute_power(self, d_bytes, nbytes, width, d_power):
         """sp_plan_execute_power: |X|^2 of every frame and bin into the f64 [width, n] device array at address d_power (frame-major,
@@ -784,7 +781,7 @@ class Plan:
 
     def mean_kernel_name_for(self, nbytes, width):
         """What execute_mean() launches for a request of this shape: "frames_power+mean" or "scratch_power+mean"."""
-        return self.ctx.lib.L.sp_plan_mean_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("mean", nbytes, width)
 
     def execute_mean(self, d_bytes, nbytes, width, d_mean):
         """sp_plan_execute_mean: the exact mean of |X|^2 over the request's frames into the f64[n] device array at address d_mean
@@ -794,7 +791,7 @@ class Plan:
 
     def bandpower_kernel_name_for(self, nbytes, width):
         """What execute_bandpower() launches for a request of this shape: "frames_power+bands" or "scratch_power+bands"."""
-        return self.ctx.lib.L.sp_plan_bandpower_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("bandpower", nbytes, width)
 
     def execute_bandpower(self, d_bytes, nbytes, width, bands, d_band):
         """sp_plan_execute_bandpower: the exact sums of |X|^2 over the bands (y0, y1) of image rows, per frame, into the f64
@@ -805,7 +802,7 @@ class Plan:
 
     def track_kernel_name_for(self, nbytes, width):
         """What execute_track() launches for a request of this shape: "frames_power+track" or "scratch_power+track"."""
-        return self.ctx.lib.L.sp_plan_track_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("track", nbytes, width)
 
     def execute_track(self, d_bytes, nbytes, width, bands, d_row, d_peak):
         """sp_plan_execute_track: per band (y0, y1) of image rows and per frame the strongest row into the int32 [count, width] device
@@ -823,7 +820,7 @@ class Plan:
 
     def index_kernel_name_for(self, nbytes, width):
         """What execute_index() runs for a request of this shape: "frames_index" or "render_extract"."""
-        return self.ctx.lib.L.sp_plan_index_kernel_name_for(self.h, int(nbytes), int(width)).decode()
+        return self._kernel_name_for("index", nbytes, width)
 
     def debug_index_launch(self, nbytes, width, index=0):
         """debug_launch() for execute_index() with the index image at device address `index` (sp_plan_debug_index_launch); "kernel" is

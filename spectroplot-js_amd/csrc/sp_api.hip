@@ -112,8 +112,8 @@ struct sp_context {
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
     DeviceBuffer power_plane;    // sp_render_power: the request's plane on the device, 8 * width * n bytes (grown, never shrunk)
     DeviceBuffer mean_ws;        // a mean request's exact-sum cells, u64[spx::kSlots][n] (sp_kernel_mean.h; grown, never shrunk)
-    DeviceBuffer mean_window;    // ... and the block of frames of its plane that is being accumulated (mean_window_bytes at the most)
-    size_t mean_window_bytes = 0; // sp_context_set_mean_window: 0 is the default, kMeanWindowDefault
+    DeviceBuffer plane_window;   // a mean, band-power or track request: the block of frames of its plane that is being consumed (plane_blocks)
+    size_t mean_window_bytes = 0; // sp_context_set_mean_window: the window's size at the most; 0 is the default, kPlaneWindowDefault
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
     DeviceBuffer density_index;  // sp_plan_execute_density: the request's index image, width * n bytes (grown, never shrunk)
     DeviceBuffer density_reply;  // ... and the reply record its render's side outputs go to (sphost::ReplyRecord)
@@ -386,7 +386,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->traces_ws.release();
     ctx->power_plane.release();
     ctx->mean_ws.release();
-    ctx->mean_window.release();
+    ctx->plane_window.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
     ctx->density_reply.release();
@@ -1169,7 +1169,8 @@ static hipError_t download_band(uint8_t *host, size_t host_pitch, const uint8_t 
                             stream);
 }
 
-// sp_render / sp_render_strip / sp_plan_execute_from_host / sp_render_traces: the capture comes from HOST memory.  Large requests are
+// Every host-fed entry point (sp_render and its image kinds, sp_plan_execute_from_host, sp_render_density / _traces / _power and the
+// plane consumers sp_render_mean / _bandpower / _track): the capture comes from HOST memory.  Large requests are
 // rendered in chunks of frames: chunk k's samples travel to the device on copy_in while chunk k-1 is rendered and - where an image
 // comes back - chunk k-2's part of it travels back on copy_out (PCIe is full duplex; the kernels are a few per cent of the copies).
 // Chunks end on multiples of 32 frames (whole write-out groups); a chunk needs the samples up to the end of its last frame.  A request
@@ -1179,7 +1180,7 @@ struct HostFeed {
     const char *who;        // the entry point, for its error texts
     const uint8_t *bytes;   // the capture, g.nbytes bytes of host memory
     spgeo::Geometry g;
-    int32_t m;              // sub-frames per column: a contiguous chunk ends with its last column's last sub-frame (traces: 1)
+    int32_t m;              // sub-frames per column: a contiguous chunk ends with its last column's last sub-frame (a plain frame loop: 1)
     bool packable;          // the request's kernel can read a packed chunk (SPECTROPLOT_HIP_NO_PACKED_UPLOAD overrides)
     bool chunkable;         // plan_upload's: the request may be pipelined ...
     size_t out_bytes;       // ... and the image that comes back over the link
@@ -1373,8 +1374,8 @@ static int render_rgba(sp_plan *plan, const uint8_t *bytes, size_t nbytes, int32
     return render_image(plan, "sp_render", bytes, nbytes, width, reply, im);
 }
 
-// sp_render_density / sp_render_traces: a host-fed request without an image, whose one small result accumulates on the device over the
-// chunks.  The samples are the only transfer and nothing follows a chunk (stream_chunks as sp_plan_execute_from_host feeds it).  A kind
+// sp_render_density / sp_render_traces / plane_render (sp_render_mean, _bandpower, _track): a host-fed request without an image, whose
+// small result accumulates or fills on the device over the chunks.  The samples are the only transfer and nothing follows a chunk (stream_chunks as sp_plan_execute_from_host feeds it).  A kind
 // brings clear() (its result back at its initial value), launch (stream_chunks') and tail(cleared, e): what it queues on the context's
 // stream once every chunk has been launched - `cleared`: clear() has run - with a failed copy's error left in e.  The call returns
 // when the stream has ended.
@@ -1734,13 +1735,14 @@ static bool plan_plain_frames(const sp_plan *plan)
 }
 
 // The two kinds of plain_range: where the kernels write (Out), the slabs of a scratch workgroup, the LUT length the frame-loop launcher
-// asks for, that launcher, its refusal's text and the scratch kernel's launcher.
+// asks for, that launcher, its refusal's text, the scratch kernel's launcher and the refusal of a peak plan.
 struct TracesKind {
     using Out = unsigned long long;   // the context's workspace (traces_clear)
     static constexpr int kSlabs = 4;   // re, im, the bins' minima and maxima
     static constexpr int kLutLen = spk2::kTracesLutLen;
     static constexpr auto launch_frames = spk2::launch_frames_traces;
     static constexpr const char *kRejected = "k_frames_traces launch rejected the configuration";
+    static constexpr const char *kOfPeak = "traces of a peak plan are not supported (the traces fold the sample detector's frames)";
     static constexpr auto launch_scratch = spk::launch_scratch_traces;
 };
 struct PowerKind {
@@ -1749,6 +1751,7 @@ struct PowerKind {
     static constexpr int kLutLen = spk2::kPowerLutLen;
     static constexpr auto launch_frames = spk2::launch_frames_power;
     static constexpr const char *kRejected = "k_frames_power launch rejected the configuration";
+    static constexpr const char *kOfPeak = "the power plane of a peak plan is not supported (the plane holds the sample detector's frames)";
     static constexpr auto launch_scratch = spk::launch_scratch_power;
 };
 
@@ -1781,20 +1784,26 @@ static int plain_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry
     return SP_OK;
 }
 
-// ------------------------------------------------------------------------------------------------- per-bin min / max traces
-
-extern "C" const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+// What sp_plan_*_kernel_name_for tells of a plain frame loop and what runs behind it: one of two names (every shape of a plan takes the
+// same kernel today).
+static const char *plain_kernel_name(const sp_plan *plan, const char *frames, const char *scratch)
 {
-    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_plain_frames(plan) ? "frames_traces" : "scratch_traces";
+    return !plan ? "" : plan_plain_frames(plan) ? frames : scratch;
 }
 
-// what every traces entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
-static int check_traces(sp_context *ctx, int32_t detector, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width)
+// what every entry point of a kind refuses of a plan's or a request's detector, format and frame size before it touches the device
+template <typename Kind>
+static int check_plain(sp_context *ctx, int32_t detector, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width)
 {
-    if (detector != SP_DETECTOR_SAMPLE)
-        return fail(ctx, SP_ERR_UNSUPPORTED, "traces of a peak plan are not supported (the traces fold the sample detector's frames)");
+    if (detector != SP_DETECTOR_SAMPLE) return fail(ctx, SP_ERR_UNSUPPORTED, Kind::kOfPeak);
     return check_capture(ctx, f, n, bytes, nbytes, width, nullptr, "");
+}
+
+// ------------------------------------------------------------------------------------------------- per-bin min / max traces
+
+extern "C" const char *sp_plan_traces_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_traces", "scratch_traces");
 }
 
 static int traces_clear(sp_plan *plan)
@@ -1822,7 +1831,7 @@ extern "C" int sp_plan_execute_traces(sp_plan *plan, const void *d_bytes, size_t
 {
     if (!plan) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
-    int rc = check_traces(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    int rc = check_plain<TracesKind>(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
     if (rc) return rc;
     if ((((uintptr_t)d_trace_min | (uintptr_t)d_trace_max) & 7) != 0)
         return fail(ctx, SP_ERR_INVALID_ARG, "d_trace_min and d_trace_max must be 8-byte aligned");
@@ -1844,7 +1853,7 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
     sp_plan *plan = nullptr;
     int rc = host_request(
         ctx, req, bytes, nbytes, width, no_check,
-        [&] { return check_traces(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+        [&] { return check_plain<TracesKind>(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
     if (rc) return rc;
 
     const size_t n = (size_t)req->n;
@@ -1868,18 +1877,9 @@ extern "C" int sp_render_traces(sp_context *ctx, const sp_request *req, const ui
 
 // ------------------------------------------------------------------------------------------------- power plane replies
 
-extern "C" const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+extern "C" const char *sp_plan_power_kernel_name_for(const sp_plan *plan, size_t, int32_t)
 {
-    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_plain_frames(plan) ? "frames_power" : "scratch_power";
-}
-
-// what every power entry point refuses of a plan's or a request's detector, format and frame size before it touches the device
-static int check_power(sp_context *ctx, int32_t detector, const spfmt::Format &f, int n, const void *bytes, size_t nbytes, int32_t width)
-{
-    if (detector != SP_DETECTOR_SAMPLE)
-        return fail(ctx, SP_ERR_UNSUPPORTED, "the power plane of a peak plan is not supported (the plane holds the sample detector's frames)");
-    return check_capture(ctx, f, n, bytes, nbytes, width, nullptr, "");
+    return plain_kernel_name(plan, "frames_power", "scratch_power");
 }
 
 // d_db[k] = d of d_power[k], k < count, on the context's stream (count > 0; in place where the pointers are equal)
@@ -1895,7 +1895,7 @@ extern "C" int sp_plan_execute_power(sp_plan *plan, const void *d_bytes, size_t 
 {
     if (!plan) return SP_ERR_INVALID_ARG;
     sp_context *ctx = plan->ctx;
-    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    int rc = check_plain<PowerKind>(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
     if (rc) return rc;
     if (width > 0 && (!d_power || ((uintptr_t)d_power & 7) != 0))
         return fail(ctx, SP_ERR_INVALID_ARG, "d_power must be an 8-byte aligned array of width * n doubles");
@@ -1929,7 +1929,7 @@ extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uin
                        ? fail(ctx, SP_ERR_INVALID_ARG, "power must be an 8-byte aligned array of width * n doubles")
                        : (int)SP_OK;
         },
-        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+        [&] { return check_plain<PowerKind>(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
     if (rc) return rc;
 
     const size_t n = (size_t)req->n, plane_bytes = sizeof(double) * (size_t)width * n;
@@ -1951,22 +1951,143 @@ extern "C" int sp_render_power(sp_context *ctx, const sp_request *req, const uin
         [] { return hipSuccess; });
 }
 
-// ------------------------------------------------------------------------------------------------- exact mean-power trace
+// ------------------------------------------------------------------------------------------------- plane consumers (mean, band power, track)
 
-// The default size of the window a mean request's plane passes through, block of frames by block of frames.
-constexpr size_t kMeanWindowDefault = (size_t)64 << 20;
+// A plane consumer makes its reply from the f64 power plane without holding the plane whole: the power request's frame loop renders the
+// frames block by block into a window of the context and the kind's launch runs behind each block.  A kind is a struct of the caller's
+// arguments - its outputs are device arrays, or the host's arrays in what the host-fed entry point is given - with
+//   check(p)                              what it refuses of them before the device is touched
+//   empty(p)                              a request that writes nothing: SP_OK after the checks, before the device is touched
+//   clear(p), finish(p)                   what it queues in front of the first block and behind the last one
+//   consume(p, d_plane, frames, x_base)   its launch on the `frames` frames of the frame-major plane at d_plane, the request's frames
+//                                         from x_base on, followed by SP_HIP(ctx, hipGetLastError())
+// and for the host-fed form kRender (the entry point's name), small_bytes(p) of the context's render_small, on_device(p, small) - the
+// kind with its outputs there, null where the host's are - and tail(plan, p, db, host, e): the dB conversion and the copies back into
+// the kind `host`, a failed copy's error left in e.  Three drivers carry a kind out: plane_resident (sp_power_*), plane_capture
+// (sp_plan_execute_*) and plane_render (sp_render_*); kBadPlane is how sp_power_*'s refusal of its d_power ends.  (The kinds stand in
+// unnamed namespaces: their member functions are no symbols of the library.)
+struct PlaneShape {
+    sp_context *ctx;
+    int n;           // rows of a frame
+    int32_t width;   // frames of the whole request
+};
 
-extern "C" const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
-{
-    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+mean" : "scratch_power+mean";
-}
+// The default size of the window a request's plane passes through, block of frames by block of frames.
+constexpr size_t kPlaneWindowDefault = (size_t)64 << 20;
 
 extern "C" int sp_context_set_mean_window(sp_context *ctx, size_t bytes)
 {
     if (!ctx) return SP_ERR_INVALID_ARG;
     ctx->mean_window_bytes = bytes;
     return SP_OK;
+}
+
+// the frames of a plane of n rows that one block of the window holds: at least one
+static int32_t plane_block_frames(const sp_context *ctx, int n, int32_t width)
+{
+    const size_t window = ctx->mean_window_bytes ? ctx->mean_window_bytes : kPlaneWindowDefault;
+    size_t frames = window / (sizeof(double) * (size_t)n);
+    if (frames < 1) frames = 1;
+    return frames < (size_t)width ? (int32_t)frames : width;
+}
+
+// The frames [x_begin, x_end) of a plane consumer's request (`src`: as for plan_execute_range): rendered block by block into the
+// context's window by the power request's frame loop, with the kind's launch on the block's frames queued behind each block.  (The
+// frame loop puts frame x at base + x * n: the window stands in for the block's part of a whole plane.)
+template <typename Kind>
+static int plane_blocks(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
+                        const PlaneShape &p, const Kind &k)
+{
+    sp_context *ctx = plan->ctx;
+    if (x_end <= x_begin) return SP_OK;
+    const int n = p.n;
+    const int32_t block = plane_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
+    int rc = ctx->plane_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
+    if (rc) return fail(ctx, rc, "mean window: out of device memory");
+    double *const d_win = (double *)ctx->plane_window.p;
+    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
+        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
+        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
+        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
+        if (!rc) rc = k.consume(p, d_win, x1 - x0, x0);
+    }
+    return rc;
+}
+
+// sp_power_*: the plane is resident, `width` frames of n rows at d_power.  `who`: the entry point, for its error texts.
+template <typename Kind>
+static int plane_resident(sp_context *ctx, const char *who, const double *d_power, int32_t n, int32_t width, const Kind &k)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, std::string(who) + ": n >= 1 and width >= 0 are required");
+    const PlaneShape p{ctx, n, width};
+    const int rc = k.check(p);
+    if (rc) return rc;
+    if (k.empty(p)) return SP_OK;
+    if ((width > 0 && !d_power) || ((uintptr_t)d_power & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, std::string(who) + Kind::kBadPlane);
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] {
+        int r = k.clear(p);
+        if (!r) r = k.consume(p, d_power, width, 0);
+        return r ? r : k.finish(p);
+    });
+}
+
+// sp_plan_execute_*: the capture is resident and the plane passes through the window.
+template <typename Kind>
+static int plane_capture(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const Kind &k)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    const PlaneShape p{ctx, plan->req.n, width};
+    int rc = check_plain<PowerKind>(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
+    if (!rc) rc = k.check(p);
+    if (rc) return rc;
+    if (k.empty(p)) return SP_OK;
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
+    return timed(ctx, [&] {
+        int r = k.clear(p);
+        if (!r) r = plane_blocks(plan, d_bytes, g, 0, width, nullptr, p, k);
+        return r ? r : k.finish(p);
+    });
+}
+
+// sp_render_*: a request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large -
+// whose reply accumulates or fills on the device over the chunks and comes back behind the last one.
+template <typename Kind>
+static int plane_render(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, const Kind &host)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    sp_plan *plan = nullptr;
+    int rc = host_request(
+        ctx, req, bytes, nbytes, width, [&] { return host.check(PlaneShape{ctx, req->n, width}); },
+        [&] { return check_plain<PowerKind>(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
+    if (rc) return rc;
+    const PlaneShape p{ctx, req->n, width};
+    if (host.empty(p)) return SP_OK;
+
+    rc = ctx->render_small.reserve(host.small_bytes(p) + 16);
+    if (rc) return fail(ctx, rc, std::string(Kind::kRender) + ": out of memory");
+    const Kind k = host.on_device(p, ctx->render_small.p);
+    HostFeed feed{Kind::kRender, bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
+    return render_result(
+        ctx, plan->fmt, feed, [&] { return k.clear(p); },
+        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
+            return plane_blocks(plan, d_in, feed.g, x0, x1, src, p, k);
+        },
+        [&](bool cleared, hipError_t &e) {
+            int r = cleared ? (int)SP_OK : k.clear(p);   // (no chunk at all: the reply of no frames)
+            if (!r) r = k.finish(p);
+            return r ? r : k.tail(plan, p, db, host, e);
+        });
+}
+
+// ------------------------------------------------------------------------------------------------- exact mean-power trace
+
+extern "C" const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+mean", "scratch_power+mean");
 }
 
 extern "C" int sp_debug_exact_sum(const double *values, size_t count, double *sum)
@@ -1980,238 +2101,134 @@ extern "C" int sp_debug_exact_sum(const double *values, size_t count, double *su
     return SP_OK;
 }
 
-// the frames of a plane of n rows that one block of the window holds: at least one
-static int32_t mean_block_frames(const sp_context *ctx, int n, int32_t width)
-{
-    const size_t window = ctx->mean_window_bytes ? ctx->mean_window_bytes : kMeanWindowDefault;
-    size_t frames = window / (sizeof(double) * (size_t)n);
-    if (frames < 1) frames = 1;
-    return frames < (size_t)width ? (int32_t)frames : width;
-}
+namespace {
+// The exact sums accumulate in the context's workspace, (66 + 2) * 8 * n bytes that clear() zeroes on the stream, and finish() makes the
+// n means of them.  No request is empty: one of no frames still gives n NaNs.
+struct MeanKind {
+    static constexpr const char *kRender = "sp_render_mean";
+    static constexpr const char *kBadPlane = ": d_power and d_mean must be 8-byte aligned device pointers";
+    double *out;           // n doubles
+    const char *refusal;   // of a null or misaligned `out`: every entry point has its own sentence
 
-// The workspace of a request of n rows, zero on the stream: (66 + 2) * 8 * n bytes.
-static int mean_clear(sp_context *ctx, int n)
-{
-    const size_t bytes = (size_t)spx::kSlots * sizeof(unsigned long long) * (size_t)n;
-    const int rc = ctx->mean_ws.reserve(bytes);
-    if (rc) return fail(ctx, rc, "mean workspace: out of device memory");
-    SP_HIP(ctx, hipMemsetAsync(ctx->mean_ws.p, 0, bytes, ctx->stream));
-    return SP_OK;
-}
-
-// Adds the `frames` frames of the frame-major plane at d_plane (n rows each) into the workspace.
-static int mean_accumulate(sp_context *ctx, const double *d_plane, int n, long long frames)
-{
-    if (frames <= 0) return SP_OK;
-    spk::launch_mean_accumulate(d_plane, n, frames, (unsigned long long *)ctx->mean_ws.p, ctx->cu_count, ctx->stream);
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
-}
-
-static int mean_finish(sp_context *ctx, int n, int32_t width, double *d_mean)
-{
-    spk::launch_mean_finish((const unsigned long long *)ctx->mean_ws.p, n, width, d_mean, ctx->stream);
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
-}
-
-// The frames [x_begin, x_end) of a mean request: rendered block by block into the context's window by the power request's frame loop
-// and added to the workspace behind each block.  (The frame loop puts frame x at base + x * n: the window stands in for the block's
-// part of a whole plane.)
-static int mean_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src)
-{
-    sp_context *ctx = plan->ctx;
-    if (x_end <= x_begin) return SP_OK;
-    const int n = plan->req.n;
-    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
-    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
-    if (rc) return fail(ctx, rc, "mean window: out of device memory");
-    double *const d_win = (double *)ctx->mean_window.p;
-    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
-        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
-        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
-        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
-        if (!rc) rc = mean_accumulate(ctx, d_win, n, x1 - x0);
+    int check(const PlaneShape &p) const { return !out || ((uintptr_t)out & 7) != 0 ? fail(p.ctx, SP_ERR_INVALID_ARG, refusal) : (int)SP_OK; }
+    bool empty(const PlaneShape &) const { return false; }
+    int clear(const PlaneShape &p) const
+    {
+        const size_t bytes = (size_t)spx::kSlots * sizeof(unsigned long long) * (size_t)p.n;
+        const int rc = p.ctx->mean_ws.reserve(bytes);
+        if (rc) return fail(p.ctx, rc, "mean workspace: out of device memory");
+        SP_HIP(p.ctx, hipMemsetAsync(p.ctx->mean_ws.p, 0, bytes, p.ctx->stream));
+        return SP_OK;
     }
-    return rc;
-}
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long) const
+    {
+        if (frames <= 0) return SP_OK;
+        spk::launch_mean_accumulate(d_plane, p.n, frames, (unsigned long long *)p.ctx->mean_ws.p, p.ctx->cu_count, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &p) const
+    {
+        spk::launch_mean_finish((const unsigned long long *)p.ctx->mean_ws.p, p.n, p.width, out, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    size_t small_bytes(const PlaneShape &p) const { return (size_t)p.n * sizeof(double); }
+    MeanKind on_device(const PlaneShape &, void *small) const { return {(double *)small, refusal}; }
+    int tail(sp_plan *plan, const PlaneShape &p, int32_t db, const MeanKind &host, hipError_t &e) const
+    {
+        const int r = db ? power_to_db(plan, out, (size_t)p.n, out) : (int)SP_OK;
+        if (!r) e = hipMemcpyAsync(host.out, out, (size_t)p.n * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return r;
+    }
+};
+}  // namespace
 
 extern "C" int sp_power_mean(sp_context *ctx, const double *d_power, int32_t n, int32_t width, double *d_mean)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_mean: n >= 1 and width >= 0 are required");
-    if (!d_mean || (width > 0 && !d_power) || (((uintptr_t)d_power | (uintptr_t)d_mean) & 7) != 0)
-        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_mean: d_power and d_mean must be 8-byte aligned device pointers");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    return timed(ctx, [&] {
-        int r = mean_clear(ctx, n);
-        if (!r) r = mean_accumulate(ctx, d_power, n, width);
-        return r ? r : mean_finish(ctx, n, width, d_mean);
-    });
+    const MeanKind k{d_mean, "sp_power_mean: d_power and d_mean must be 8-byte aligned device pointers"};
+    return plane_resident(ctx, "sp_power_mean", d_power, n, width, k);
 }
 
 extern "C" int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_mean)
 {
-    if (!plan) return SP_ERR_INVALID_ARG;
-    sp_context *ctx = plan->ctx;
-    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
-    if (rc) return rc;
-    if (!d_mean || ((uintptr_t)d_mean & 7) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "d_mean must be an 8-byte aligned array of n doubles");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    return timed(ctx, [&] {
-        int r = mean_clear(ctx, plan->req.n);
-        if (!r) r = mean_range(plan, d_bytes, g, 0, width, nullptr);
-        return r ? r : mean_finish(ctx, plan->req.n, width, d_mean);
-    });
+    return plane_capture(plan, d_bytes, nbytes, width, MeanKind{d_mean, "d_mean must be an 8-byte aligned array of n doubles"});
 }
 
-// A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
-// exact sums accumulate in the workspace over the chunks; n doubles come back.
 extern "C" int sp_render_mean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *mean)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    sp_plan *plan = nullptr;
-    int rc = host_request(
-        ctx, req, bytes, nbytes, width,
-        [&] {
-            return !mean || ((uintptr_t)mean & 7) != 0 ? fail(ctx, SP_ERR_INVALID_ARG, "mean must be an 8-byte aligned array of n doubles") : (int)SP_OK;
-        },
-        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
-    if (rc) return rc;
-
-    const size_t n = (size_t)req->n;
-    hipStream_t s = ctx->stream;
-    rc = ctx->render_small.reserve(n * sizeof(double) + 16);
-    if (rc) return fail(ctx, rc, "sp_render_mean: out of memory");
-    double *const d_out = (double *)ctx->render_small.p;
-    HostFeed feed{"sp_render_mean", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
-    return render_result(
-        ctx, plan->fmt, feed, [&] { return mean_clear(ctx, req->n); },
-        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) { return mean_range(plan, d_in, feed.g, x0, x1, src); },
-        [&](bool cleared, hipError_t &e) {
-            int r = cleared ? (int)SP_OK : mean_clear(ctx, req->n);   // (no chunk at all: the sum of no frames)
-            if (!r) r = mean_finish(ctx, req->n, width, d_out);
-            if (!r && db) r = power_to_db(plan, d_out, n, d_out);
-            if (!r) e = hipMemcpyAsync(mean, d_out, n * sizeof(double), hipMemcpyDeviceToHost, s);
-            return r;
-        });
+    return plane_render(ctx, req, bytes, nbytes, width, db, MeanKind{mean, "mean must be an 8-byte aligned array of n doubles"});
 }
 
 // ------------------------------------------------------------------------------------------------- exact band-power series
 
-extern "C" const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+extern "C" const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t, int32_t)
 {
-    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+bands" : "scratch_power+bands";
+    return plain_kernel_name(plan, "frames_power+bands", "scratch_power+bands");
 }
 
-// what every band-power entry point refuses of its bands and its output (`out`: count * width doubles) before it touches the device
-static int check_band_args(sp_context *ctx, int n, int32_t width, const int32_t *bands, int32_t count, const double *out)
-{
-    if (const char *why = spgeo::check_bands(n, bands, count)) return fail(ctx, SP_ERR_INVALID_ARG, why);
-    if (count > 0 && width > 0 && (!out || ((uintptr_t)out & 7) != 0))
-        return fail(ctx, SP_ERR_INVALID_ARG, "the band series must be an 8-byte aligned array of count * width doubles");
-    return SP_OK;
-}
+namespace {
+// Every block's launch writes its columns of every band's series, `width` doubles apart: nothing to clear (every column is written
+// once) and nothing to finish.
+struct BandKind {
+    static constexpr const char *kRender = "sp_render_bandpower";
+    static constexpr const char *kBadPlane = ": d_power must be an 8-byte aligned device pointer";
+    const int32_t *bands;
+    int32_t count;
+    double *out;   // count * width doubles
 
-// Columns [x_base, x_base + frames) of every band's series (`width` doubles apart) from the `frames` frames of the frame-major plane
-// at d_plane: one launch.
-static int band_sums(sp_context *ctx, const double *d_plane, int n, long long frames, const int32_t *bands, int32_t count, double *d_band,
-                     int32_t width, long long x_base)
-{
-    if (frames <= 0 || count <= 0) return SP_OK;
-    spk::launch_band_sum(d_plane, n, frames, bands, count, d_band, width, x_base, ctx->stream);
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
-}
-
-// The frames [x_begin, x_end) of a band-power request: rendered block by block into the mean's window, as mean_range does, with the
-// sums of the block's frames made behind each block.
-static int band_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
-                      const int32_t *bands, int32_t count, double *d_band)
-{
-    sp_context *ctx = plan->ctx;
-    if (x_end <= x_begin) return SP_OK;
-    const int n = plan->req.n;
-    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
-    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
-    if (rc) return fail(ctx, rc, "mean window: out of device memory");
-    double *const d_win = (double *)ctx->mean_window.p;
-    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
-        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
-        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
-        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
-        if (!rc) rc = band_sums(ctx, d_win, n, x1 - x0, bands, count, d_band, g.width, x0);
+    int check(const PlaneShape &p) const
+    {
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (count > 0 && p.width > 0 && (!out || ((uintptr_t)out & 7) != 0))
+            return fail(p.ctx, SP_ERR_INVALID_ARG, "the band series must be an 8-byte aligned array of count * width doubles");
+        return SP_OK;
     }
-    return rc;
-}
+    bool empty(const PlaneShape &p) const { return p.width == 0 || count == 0; }
+    int clear(const PlaneShape &) const { return SP_OK; }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        if (frames <= 0 || count <= 0) return SP_OK;
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, out, p.width, x_base, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &) const { return SP_OK; }
+    size_t total(const PlaneShape &p) const { return (size_t)count * (size_t)p.width; }
+    size_t small_bytes(const PlaneShape &p) const { return total(p) * sizeof(double); }
+    BandKind on_device(const PlaneShape &, void *small) const { return {bands, count, (double *)small}; }
+    int tail(sp_plan *plan, const PlaneShape &p, int32_t db, const BandKind &host, hipError_t &e) const
+    {
+        const int r = db ? power_to_db(plan, out, total(p), out) : (int)SP_OK;
+        if (!r) e = hipMemcpyAsync(host.out, out, total(p) * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return r;
+    }
+};
+}  // namespace
 
 extern "C" int sp_power_bands(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
                               double *d_band)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_bands: n >= 1 and width >= 0 are required");
-    const int rc = check_band_args(ctx, n, width, bands, count, d_band);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-    if (!d_power || ((uintptr_t)d_power & 7) != 0)
-        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_bands: d_power must be an 8-byte aligned device pointer");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    return timed(ctx, [&] { return band_sums(ctx, d_power, n, width, bands, count, d_band, width, 0); });
+    return plane_resident(ctx, "sp_power_bands", d_power, n, width, BandKind{bands, count, d_band});
 }
 
 extern "C" int sp_plan_execute_bandpower(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
                                          double *d_band)
 {
-    if (!plan) return SP_ERR_INVALID_ARG;
-    sp_context *ctx = plan->ctx;
-    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
-    if (!rc) rc = check_band_args(ctx, plan->req.n, width, bands, count, d_band);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    return timed(ctx, [&] { return band_range(plan, d_bytes, g, 0, width, nullptr, bands, count, d_band); });
+    return plane_capture(plan, d_bytes, nbytes, width, BandKind{bands, count, d_band});
 }
 
-// A request kind of render_result - a packed sparse upload where stride > n, chunks of frames where the request is large - whose
-// series fill column by column over the chunks (nothing to clear: every column is written once); count * width doubles come back.
 extern "C" int sp_render_bandpower(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
                                    int32_t count, int32_t db, double *band)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    sp_plan *plan = nullptr;
-    int rc = host_request(
-        ctx, req, bytes, nbytes, width, [&] { return check_band_args(ctx, req->n, width, bands, count, band); },
-        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-
-    const size_t total = (size_t)count * (size_t)width;
-    hipStream_t s = ctx->stream;
-    rc = ctx->render_small.reserve(total * sizeof(double) + 16);
-    if (rc) return fail(ctx, rc, "sp_render_bandpower: out of memory");
-    double *const d_out = (double *)ctx->render_small.p;
-    HostFeed feed{"sp_render_bandpower", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
-    return render_result(
-        ctx, plan->fmt, feed, no_check,
-        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
-            return band_range(plan, d_in, feed.g, x0, x1, src, bands, count, d_out);
-        },
-        [&](bool, hipError_t &e) {
-            const int r = db ? power_to_db(plan, d_out, total, d_out) : (int)SP_OK;
-            if (!r) e = hipMemcpyAsync(band, d_out, total * sizeof(double), hipMemcpyDeviceToHost, s);
-            return r;
-        });
+    return plane_render(ctx, req, bytes, nbytes, width, db, BandKind{bands, count, band});
 }
 
 // ------------------------------------------------------------------------------------------------- peak track
 
-extern "C" const char *sp_plan_track_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width)
+extern "C" const char *sp_plan_track_kernel_name_for(const sp_plan *plan, size_t, int32_t)
 {
-    (void)nbytes, (void)width;   // (every shape of a plan takes the same kernel today)
-    return !plan ? "" : plan_plain_frames(plan) ? "frames_power+track" : "scratch_power+track";
+    return plain_kernel_name(plan, "frames_power+track", "scratch_power+track");
 }
 
 extern "C" int sp_debug_band_peak(const double *values, int32_t n, int32_t y0, int32_t y1, int32_t *row, double *peak)
@@ -2226,111 +2243,71 @@ extern "C" int sp_debug_band_peak(const double *values, int32_t n, int32_t y0, i
     return SP_OK;
 }
 
-// what every track entry point refuses of its bands and its outputs (count * width elements each, either one may be null) before it
-// touches the device
-static int check_track_args(sp_context *ctx, int n, int32_t width, const int32_t *bands, int32_t count, const int32_t *row, const double *peak)
-{
-    if (const char *why = spgeo::check_bands(n, bands, count)) return fail(ctx, SP_ERR_INVALID_ARG, why);
-    if (count > 0 && width > 0) {
-        if (!row && !peak) return fail(ctx, SP_ERR_INVALID_ARG, "a track needs a row array or a peak array");
-        if (((uintptr_t)row & 3) != 0) return fail(ctx, SP_ERR_INVALID_ARG, "the track's rows must be a 4-byte aligned array of count * width int32");
-        if (((uintptr_t)peak & 7) != 0)
-            return fail(ctx, SP_ERR_INVALID_ARG, "the track's peaks must be an 8-byte aligned array of count * width doubles");
-    }
-    return SP_OK;
-}
+namespace {
+// As BandKind, with two arrays of count * width elements, either of which may be null: not written.  In render_small the doubles lie in
+// front of the rows.
+struct TrackKind {
+    static constexpr const char *kRender = "sp_render_track";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    const int32_t *bands;
+    int32_t count;
+    int32_t *row;
+    double *peak;
 
-// Columns [x_base, x_base + frames) of every band's track (`width` elements apart) from the `frames` frames of the frame-major plane
-// at d_plane: one launch.
-static int track_max(sp_context *ctx, const double *d_plane, int n, long long frames, const int32_t *bands, int32_t count, int32_t *d_row,
-                     double *d_peak, int32_t width, long long x_base)
-{
-    if (frames <= 0 || count <= 0) return SP_OK;
-    spk::launch_track_max(d_plane, n, frames, bands, count, d_row, d_peak, width, x_base, ctx->stream);
-    SP_HIP(ctx, hipGetLastError());
-    return SP_OK;
-}
-
-// The frames [x_begin, x_end) of a track request: rendered block by block into the mean's window, as band_range does, with the track
-// of the block's frames made behind each block.
-static int track_range(sp_plan *plan, const void *d_bytes, const spgeo::Geometry &g, int32_t x_begin, int32_t x_end, const PackedSource *src,
-                       const int32_t *bands, int32_t count, int32_t *d_row, double *d_peak)
-{
-    sp_context *ctx = plan->ctx;
-    if (x_end <= x_begin) return SP_OK;
-    const int n = plan->req.n;
-    const int32_t block = mean_block_frames(ctx, n, g.width);   // (of the whole request: the window does not grow from chunk to chunk)
-    int rc = ctx->mean_window.reserve(sizeof(double) * (size_t)block * (size_t)n);
-    if (rc) return fail(ctx, rc, "mean window: out of device memory");
-    double *const d_win = (double *)ctx->mean_window.p;
-    for (int32_t x0 = x_begin; x0 < x_end && !rc; x0 += block) {
-        const int32_t x1 = x_end - x0 > block ? x0 + block : x_end;
-        double *const base = (double *)((uintptr_t)d_win - sizeof(double) * (size_t)x0 * (size_t)n);
-        rc = plain_range<PowerKind>(plan, d_bytes, g, x0, x1, src, base);
-        if (!rc) rc = track_max(ctx, d_win, n, x1 - x0, bands, count, d_row, d_peak, g.width, x0);
+    int check(const PlaneShape &p) const
+    {
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (count > 0 && p.width > 0) {
+            if (!row && !peak) return fail(p.ctx, SP_ERR_INVALID_ARG, "a track needs a row array or a peak array");
+            if (((uintptr_t)row & 3) != 0)
+                return fail(p.ctx, SP_ERR_INVALID_ARG, "the track's rows must be a 4-byte aligned array of count * width int32");
+            if (((uintptr_t)peak & 7) != 0)
+                return fail(p.ctx, SP_ERR_INVALID_ARG, "the track's peaks must be an 8-byte aligned array of count * width doubles");
+        }
+        return SP_OK;
     }
-    return rc;
-}
+    bool empty(const PlaneShape &p) const { return p.width == 0 || count == 0; }
+    int clear(const PlaneShape &) const { return SP_OK; }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        if (frames <= 0 || count <= 0) return SP_OK;
+        spk::launch_track_max(d_plane, p.n, frames, bands, count, row, peak, p.width, x_base, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &) const { return SP_OK; }
+    size_t total(const PlaneShape &p) const { return (size_t)count * (size_t)p.width; }
+    size_t small_bytes(const PlaneShape &p) const { return total(p) * (sizeof(double) + sizeof(int32_t)); }
+    TrackKind on_device(const PlaneShape &p, void *small) const
+    {
+        return {bands, count, row ? (int32_t *)((double *)small + total(p)) : nullptr, peak ? (double *)small : nullptr};
+    }
+    int tail(sp_plan *plan, const PlaneShape &p, int32_t db, const TrackKind &host, hipError_t &e) const
+    {
+        const int r = db && peak ? power_to_db(plan, peak, total(p), peak) : (int)SP_OK;
+        if (!r && row) e = hipMemcpyAsync(host.row, row, total(p) * sizeof(int32_t), hipMemcpyDeviceToHost, p.ctx->stream);
+        if (!r && e == hipSuccess && peak) e = hipMemcpyAsync(host.peak, peak, total(p) * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return r;
+    }
+};
+}  // namespace
 
 extern "C" int sp_power_tracks(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
                                int32_t *d_row, double *d_peak)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    if (n < 1 || width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_tracks: n >= 1 and width >= 0 are required");
-    const int rc = check_track_args(ctx, n, width, bands, count, d_row, d_peak);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-    if (!d_power || ((uintptr_t)d_power & 7) != 0)
-        return fail(ctx, SP_ERR_INVALID_ARG, "sp_power_tracks: d_power must be an 8-byte aligned device pointer");
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    return timed(ctx, [&] { return track_max(ctx, d_power, n, width, bands, count, d_row, d_peak, width, 0); });
+    return plane_resident(ctx, "sp_power_tracks", d_power, n, width, TrackKind{bands, count, d_row, d_peak});
 }
 
 extern "C" int sp_plan_execute_track(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
                                      int32_t *d_row, double *d_peak)
 {
-    if (!plan) return SP_ERR_INVALID_ARG;
-    sp_context *ctx = plan->ctx;
-    int rc = check_power(ctx, plan->req.detector, plan->fmt, plan->req.n, d_bytes, nbytes, width);
-    if (!rc) rc = check_track_args(ctx, plan->req.n, width, bands, count, d_row, d_peak);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    const spgeo::Geometry g = spgeo::geometry(plan->fmt, plan->req.n, nbytes, width);
-    return timed(ctx, [&] { return track_range(plan, d_bytes, g, 0, width, nullptr, bands, count, d_row, d_peak); });
+    return plane_capture(plan, d_bytes, nbytes, width, TrackKind{bands, count, d_row, d_peak});
 }
 
-// A request kind of render_result, exactly as sp_render_bandpower is: the two arrays fill column by column over the chunks (nothing to
-// clear: every column is written once); on the device the count * width doubles lie in front of the count * width rows.
 extern "C" int sp_render_track(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
                                int32_t count, int32_t db, int32_t *row, double *peak)
 {
-    if (!ctx) return SP_ERR_INVALID_ARG;
-    sp_plan *plan = nullptr;
-    int rc = host_request(
-        ctx, req, bytes, nbytes, width, [&] { return check_track_args(ctx, req->n, width, bands, count, row, peak); },
-        [&] { return check_power(ctx, req->detector, spfmt::describe(req->format), req->n, bytes, nbytes, width); }, &plan);
-    if (rc) return rc;
-    if (width == 0 || count == 0) return SP_OK;
-
-    const size_t total = (size_t)count * (size_t)width;
-    hipStream_t s = ctx->stream;
-    rc = ctx->render_small.reserve(total * (sizeof(double) + sizeof(int32_t)) + 16);
-    if (rc) return fail(ctx, rc, "sp_render_track: out of memory");
-    double *const d_peak = peak ? (double *)ctx->render_small.p : nullptr;
-    int32_t *const d_row = row ? (int32_t *)((double *)ctx->render_small.p + total) : nullptr;
-    HostFeed feed{"sp_render_track", bytes, spgeo::geometry(plan->fmt, req->n, nbytes, width), 1, plan_plain_frames(plan), true, 0, false, nullptr};
-    return render_result(
-        ctx, plan->fmt, feed, no_check,
-        [&](int32_t x0, int32_t x1, bool, bool, const uint8_t *d_in, const PackedSource *src) {
-            return track_range(plan, d_in, feed.g, x0, x1, src, bands, count, d_row, d_peak);
-        },
-        [&](bool, hipError_t &e) {
-            const int r = db && d_peak ? power_to_db(plan, d_peak, total, d_peak) : (int)SP_OK;
-            if (!r && row) e = hipMemcpyAsync(row, d_row, total * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-            if (!r && e == hipSuccess && peak) e = hipMemcpyAsync(peak, d_peak, total * sizeof(double), hipMemcpyDeviceToHost, s);
-            return r;
-        });
+    return plane_render(ctx, req, bytes, nbytes, width, db, TrackKind{bands, count, row, peak});
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

@@ -13,6 +13,11 @@ import torch
 from . import binding
 
 
+def _check_capture(name, capture):
+    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
+        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.%s: capture must be a contiguous uint8 CUDA tensor" % name)
+
+
 @contextlib.contextmanager
 def _on_current_stream(ctx, dev, operands):
     """Binds the context to torch's current stream of `dev` for the calls in the body (see power()), records the operands on it and puts
@@ -48,8 +53,7 @@ def power(plan, capture, width, db=False, out=None):
     recorded on it, and the context's previous binding put back on the way out.  The call does not wait for the plane: only where the
     context was bound to another stream is that stream's earlier work drained first (the context's workspaces rely on one stream's
     order)."""
-    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
-        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.power: capture must be a contiguous uint8 CUDA tensor")
+    _check_capture("power", capture)
     ctx, n = plan.ctx, plan.n
     dev = capture.device
     width = int(width)
@@ -70,8 +74,7 @@ def mean(plan, capture, width):
     correctly rounded sum of |X|^2 over the `width` frames divided by width, per image row (include/spectroplot_hip.h, "Exact
     mean-power trace").  `plan` is a binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as
     power() queues its plane; the plane itself is never held whole."""
-    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
-        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.mean: capture must be a contiguous uint8 CUDA tensor")
+    _check_capture("mean", capture)
     out = torch.empty((plan.n,), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_mean(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
@@ -84,8 +87,7 @@ def bandpower(plan, capture, width, bands):
     rows (include/spectroplot_hip.h, "Exact band-power series"; binding.band_rows turns a frequency range into rows).  `plan` is a
     binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the
     plane itself is never held whole."""
-    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
-        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.bandpower: capture must be a contiguous uint8 CUDA tensor")
+    _check_capture("bandpower", capture)
     bands = [(int(y0), int(y1)) for y0, y1 in bands]
     out = torch.empty((len(bands), max(int(width), 0)), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
@@ -100,8 +102,7 @@ def track(plan, capture, width, bands):
     (include/spectroplot_hip.h, "Peak track"; binding.row_freq turns a row into a frequency).  `plan` is a binding.Plan of the sample
     detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the plane itself is never held
     whole."""
-    if capture.dtype != torch.uint8 or not capture.is_cuda or not capture.is_contiguous():
-        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.track: capture must be a contiguous uint8 CUDA tensor")
+    _check_capture("track", capture)
     bands = [(int(y0), int(y1)) for y0, y1 in bands]
     shape = (len(bands), max(int(width), 0))
     rows = torch.empty(shape, dtype=torch.int32, device=capture.device)
