@@ -660,6 +660,59 @@ const char *sp_plan_track_kernel_name_for(const sp_plan *plan, size_t nbytes, in
 int sp_debug_band_peak(const double *values, int32_t n, int32_t y0, int32_t y1, int32_t *row, double *peak);
 
 /*
+ * Occupancy counts: how often a row reaches a threshold, and how many rows of a band reach theirs in a frame - per row the duty cycle
+ * or channel occupancy of a monitoring receiver (rows[y] / width), per frame and band the occupied-bandwidth trace of a burst.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y - the same geometry, limits, statuses, channel
+ * mode and row order as for the track above - and threshold[y] one double per image row:
+ *     hit(x, y)            = power[x][y] >= threshold[y]       numpy's >=: A NaN ON EITHER SIDE IS NO HIT
+ *     rows[y]              = the number of x in [0, width) with hit(x, y)            uint32_t rows[n]
+ *     frames[b * width + x] = the number of y in [y0_b, y1_b) with hit(x, y)         uint32_t frames[count * width], BAND-MAJOR
+ * The bands are exactly the band-power series' bands: a HOST array int32_t bands[2 * count] of half-open row ranges with 0 <= y0 <= y1
+ * <= n, read before the call returns; 0 <= count <= SP_MAX_BANDS; bands may overlap and may be empty (an empty band counts 0).  `rows`
+ * is over all n rows and needs no bands.  A threshold of -inf, or any negative one, is reached by every value that is not a NaN; one of
+ * +inf only by +inf; -0.0 is +0.0.
+ * Either output may be NULL and is not written then; both NULL is SP_ERR_INVALID_ARG.  A non-NULL `rows` is ALWAYS written: a request
+ * of no frames (width == 0, or a capture shorter than n, whose frames are NaN) gives n zeros.  `frames` is written when it is non-NULL
+ * and count > 0 && width > 0.  SP_ERR_INVALID_ARG also for: a NULL threshold or one that is not 8-byte aligned, an output that is not
+ * 4-byte aligned, a band outside 0 <= y0 <= y1 <= n, count outside 0 .. SP_MAX_BANDS, bands == NULL with count > 0.  width < 2^31 and n
+ * <= SP_MAX_N, so no count overflows 32 bits.  Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.
+ * The counts are the same for both layouts and do not depend on gain, range, LUT or block_norm, NOR ON THE CU COUNT, THE WINDOW OR THE
+ * CHUNKING OF A HOST-FED REQUEST: integer adds commute.
+ * How: no floating-point compare or add anywhere.  A threshold becomes a key once - all ones for a NaN, 0 for a negative one, else its
+ * bit pattern without the sign bit - and a value hits when its key is no NaN's and not below that (csrc/sp_occupancy_core.h, the one
+ * place the decision is made, for the kernel and for sp_debug_occupancy; the keys are the track's).  Both outputs are zeroed on the
+ * stream (two memsets) and ONE launch behind every block of frames reads the plane once for both: no workspace of the context.  The
+ * kernel's tile is SP_OCCUPANCY_TILE_ROWS rows: up to that n a frame count gets one add, beyond it one per tile its band touches.
+ *
+ * sp_power_occupancy: the counts over a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_power_tracks.  Asynchronous on the context's stream, no workspace of the context and no request number: a stream that is being
+ *   captured is not refused.  1 <= n <= SP_MAX_N (any n, not only powers of two), width >= 0; d_power (non-NULL when width > 0) and
+ *   d_threshold 8-byte aligned device pointers.  The values must not be negative: the sign bit of a value is not looked at.
+ * sp_plan_execute_occupancy: device operands (d_threshold too), asynchronous.  The plane is never held whole: it passes block by
+ *   block through the mean's window (sp_context_set_mean_window applies) and each block's hits are added behind it.  The checks are
+ *   sp_plan_execute_power's, then the bands', then the threshold's and the outputs'.  No request number: the call may be interleaved
+ *   with sp_plan_execute / _power / _mean / _bandpower / _track on one context without a synchronisation.
+ * sp_render_occupancy: host buffers (threshold: n doubles on the host), synchronous, the plan cached as by sp_render.  The samples
+ *   travel as for sp_render_track; the thresholds are uploaded in front of the first chunk and `rows` and `frames` come back in one
+ *   copy each.  There is no dB form: counts are not powers.
+ * sp_plan_occupancy_kernel_name_for: "frames_power+occupancy" or "scratch_power+occupancy", following sp_plan_power_kernel_name_for.
+ * sp_debug_occupancy: (tests, no device needed) *count = the hits among the rows [y0, y1) of one frame's `n` values against `n`
+ *   thresholds through the host side of the code the kernel runs.  SP_ERR_INVALID_ARG for a NULL argument, n < 1 or a band outside
+ *   0 <= y0 <= y1 <= n.
+ * Out of scope: thresholds in dB (the dB formula has no bit-exact inverse), hysteresis and burst lists, accumulation over successive
+ * captures, peak plans, batches, groups, sharding.py, and the count fused into the frame loop.
+ */
+#define SP_OCCUPANCY_TILE_ROWS 4096
+int sp_power_occupancy(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const double *d_threshold, const int32_t *bands,
+                       int32_t count, uint32_t *d_rows, uint32_t *d_frames);
+int sp_plan_execute_occupancy(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const double *d_threshold,
+                              const int32_t *bands, int32_t count, uint32_t *d_rows, uint32_t *d_frames);
+int sp_render_occupancy(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const double *threshold,
+                        const int32_t *bands, int32_t count, uint32_t *rows, uint32_t *frames);
+const char *sp_plan_occupancy_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_debug_occupancy(const double *values, const double *thresholds, int32_t n, int32_t y0, int32_t y1, uint32_t *count);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

@@ -190,6 +190,12 @@ class Library:
         L.sp_plan_track_kernel_name_for.restype = C.c_char_p
         L.sp_plan_track_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_debug_band_peak.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(dbl)]
+        L.sp_power_occupancy.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp]
+        L.sp_plan_execute_occupancy.argtypes = [vp, vp, sz, i32, vp, vp, i32, vp, vp]
+        L.sp_render_occupancy.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, vp, i32, vp, vp]
+        L.sp_plan_occupancy_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_occupancy_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_debug_occupancy.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_uint32)]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -265,6 +271,32 @@ def band_peak(values, y0, y1):
     lib.check(lib.L.sp_debug_band_peak(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, int(y0), int(y1), C.byref(row),
                                        C.byref(peak)))
     return row.value, peak.value
+
+
+def occupancy_count(values, thresholds, y0, y1):
+    """sp_debug_occupancy: the number of rows y in [y0, y1) of one frame's values with values[y] >= thresholds[y] (numpy's >=: a NaN
+    on either side is no hit; the values are not negative) through the host side of the code the occupancy kernel runs.  No device
+    needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if t.shape != v.shape:
+        raise ValueError("occupancy_count: one threshold per value")
+    count = C.c_uint32()
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_occupancy(v.ctypes.data_as(C.c_void_p) if v.size else None, t.ctypes.data_as(C.c_void_p) if t.size else None,
+                                       v.size, int(y0), int(y1), C.byref(count)))
+    return count.value
+
+
+def _threshold_array(threshold, n):
+    """f64[n] of a scalar (every row's threshold) or of n values; another length is refused here: the library cannot see it."""
+    t = np.asarray(threshold, dtype=np.float64)
+    if t.ndim == 0:
+        return np.full(int(n), float(t), np.float64)
+    t = np.ascontiguousarray(t.reshape(-1))
+    if t.size != int(n):
+        raise ValueError("threshold must be a number or %d values, one per image row" % int(n))
+    return t
 
 
 def row_freq(n, row):
@@ -650,6 +682,31 @@ class Context:
         self._chk(self.lib.L.sp_power_tracks(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
                                              C.c_void_p(d_row or None), C.c_void_p(d_peak or None)))
 
+    def render_occupancy(self, fmt, data, n, windowc, block_norm, gain, rng, width, threshold, bands=(), channel_mode=False, lut=None,
+                         fill=None):
+        """sp_render_occupancy: the occupancy counts of the request, (rows uint32 [n], frames uint32 [count, width]): rows[y] is the
+        number of frames whose |X|^2 at image row y is >= threshold[y], frames[b, x] the number of rows of band (y0, y1) that reach
+        theirs in frame x (a NaN on either side is no hit).  threshold: a number, for every row, or n values.  No image is rendered;
+        `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a byte the output arrays hold before the call
+        (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        b, count = _band_array(bands)
+        t = _threshold_array(threshold, n)
+        rows = _filled(int(n), np.uint32, fill)
+        frames = _filled((count, max(int(width), 0)), np.uint32, fill)
+        self._chk(self.lib.L.sp_render_occupancy(self.h, C.byref(req), _p(data), data.size, int(width), _p(t), _p(b) if count else None,
+                                                 count, _p(rows), _p(frames) if frames.size else None))
+        return rows, frames
+
+    def power_occupancy(self, d_power, n, width, d_threshold, bands, d_rows, d_frames):
+        """sp_power_occupancy: the threshold crossings of the f64 [width, n] plane at device address d_power against the f64[n]
+        thresholds at d_threshold: per row over the frames into uint32[n] at d_rows, per band (y0, y1) of rows and frame into uint32
+        [count, width] at d_frames (either address may be 0: not written).  Asynchronous on the context's stream; the bands are read
+        before it returns."""
+        b, count = _band_array(bands)
+        self._chk(self.lib.L.sp_power_occupancy(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_threshold or None),
+                                                _p(b) if count else None, count, C.c_void_p(d_rows or None), C.c_void_p(d_frames or None)))
+
     def set_mean_window(self, nbytes=0):
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
@@ -812,6 +869,20 @@ class Plan:
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_track(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                            _p(b) if count else None, count, C.c_void_p(d_row or None),
                                                            C.c_void_p(d_peak or None)))
+
+    def occupancy_kernel_name_for(self, nbytes, width):
+        """What execute_occupancy() launches for a request of this shape: "frames_power+occupancy" or "scratch_power+occupancy"."""
+        return self._kernel_name_for("occupancy", nbytes, width)
+
+    def execute_occupancy(self, d_bytes, nbytes, width, d_threshold, bands, d_rows, d_frames):
+        """sp_plan_execute_occupancy: the frames whose |X|^2 reaches the f64[n] thresholds at device address d_threshold, per image
+        row, into the uint32[n] device array at d_rows, and per band (y0, y1) of image rows and frame the rows that reach theirs into the
+        uint32 [count, width] device array at d_frames (either may be 0: not written).  Asynchronous on the context's stream; the
+        bands are read before it returns."""
+        b, count = _band_array(bands)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_occupancy(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                               C.c_void_p(d_threshold or None), _p(b) if count else None, count,
+                                                               C.c_void_p(d_rows or None), C.c_void_p(d_frames or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -27,6 +27,7 @@
 #include "sp_launch.h"
 #include "sp_exact_sum.h"
 #include "sp_track_core.h"
+#include "sp_occupancy_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -2308,6 +2309,104 @@ extern "C" int sp_render_track(sp_context *ctx, const sp_request *req, const uin
                                int32_t count, int32_t db, int32_t *row, double *peak)
 {
     return plane_render(ctx, req, bytes, nbytes, width, db, TrackKind{bands, count, row, peak});
+}
+
+// ------------------------------------------------------------------------------------------------- occupancy counts
+
+extern "C" const char *sp_plan_occupancy_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+occupancy", "scratch_power+occupancy");
+}
+
+extern "C" int sp_debug_occupancy(const double *values, const double *thresholds, int32_t n, int32_t y0, int32_t y1, uint32_t *count)
+{
+    if (!values || !thresholds || !count || n < 1 || y0 < 0 || y1 < y0 || y1 > n) return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> v((size_t)n), t((size_t)n);
+    memcpy(v.data(), values, (size_t)n * sizeof(double));
+    memcpy(t.data(), thresholds, (size_t)n * sizeof(double));
+    *count = spo::band_count(v.data(), t.data(), y0, y1);
+    return SP_OK;
+}
+
+namespace {
+// Two arrays of counts, rows (n words, over all frames) and frames (count * width words, band-major), either of which may be null: not
+// touched.  Every block's launch ADDS its hits, so clear() zeroes both on the stream.  A non-null `rows` makes a request of no frames one
+// that still writes (n zeros), as the mean's does.  The thresholds are n device doubles; the host-fed form holds its own in `upload`
+// and clear() sends them to render_small, where they lie in front of the rows and the rows in front of the frames.
+struct OccupancyKind {
+    static constexpr const char *kRender = "sp_render_occupancy";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    const double *threshold;
+    const int32_t *bands;
+    int32_t count;
+    uint32_t *rows;
+    uint32_t *frames;
+    const double *upload;   // the host's thresholds where `threshold` is render_small's copy of them, else null
+
+    bool fills_frames(const PlaneShape &p) const { return frames && count > 0 && p.width > 0; }
+    int check(const PlaneShape &p) const
+    {
+        if (p.n > SP_MAX_N) return fail(p.ctx, SP_ERR_INVALID_ARG, "occupancy counts need n <= SP_MAX_N");
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (!rows && !frames) return fail(p.ctx, SP_ERR_INVALID_ARG, "occupancy counts need a rows array or a frames array");
+        if (!threshold || ((uintptr_t)threshold & 7) != 0)
+            return fail(p.ctx, SP_ERR_INVALID_ARG, "the thresholds must be an 8-byte aligned array of n doubles");
+        if (((uintptr_t)rows & 3) != 0) return fail(p.ctx, SP_ERR_INVALID_ARG, "the row counts must be a 4-byte aligned array of n uint32");
+        if (((uintptr_t)frames & 3) != 0)
+            return fail(p.ctx, SP_ERR_INVALID_ARG, "the frame counts must be a 4-byte aligned array of count * width uint32");
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &p) const { return !rows && !fills_frames(p); }
+    int clear(const PlaneShape &p) const
+    {
+        if (upload)
+            SP_HIP(p.ctx, hipMemcpyAsync((void *)threshold, upload, (size_t)p.n * sizeof(double), hipMemcpyHostToDevice, p.ctx->stream));
+        if (rows) SP_HIP(p.ctx, hipMemsetAsync(rows, 0, (size_t)p.n * sizeof(uint32_t), p.ctx->stream));
+        if (fills_frames(p)) SP_HIP(p.ctx, hipMemsetAsync(frames, 0, total(p) * sizeof(uint32_t), p.ctx->stream));
+        return SP_OK;
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames_, long long x_base) const
+    {
+        if (frames_ <= 0) return SP_OK;
+        spk::launch_occupancy_count(d_plane, p.n, frames_, threshold, bands, count, rows, fills_frames(p) ? frames : nullptr, p.width, x_base,
+                                    p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &) const { return SP_OK; }
+    size_t total(const PlaneShape &p) const { return (size_t)count * (size_t)p.width; }
+    size_t small_bytes(const PlaneShape &p) const { return (size_t)p.n * (sizeof(double) + sizeof(uint32_t)) + total(p) * sizeof(uint32_t); }
+    OccupancyKind on_device(const PlaneShape &p, void *small) const
+    {
+        uint32_t *const words = (uint32_t *)((double *)small + p.n);
+        return {(const double *)small, bands, count, rows ? words : nullptr, frames ? words + p.n : nullptr, threshold};
+    }
+    int tail(sp_plan *, const PlaneShape &p, int32_t, const OccupancyKind &host, hipError_t &e) const
+    {
+        if (rows) e = hipMemcpyAsync(host.rows, rows, (size_t)p.n * sizeof(uint32_t), hipMemcpyDeviceToHost, p.ctx->stream);
+        if (e == hipSuccess && fills_frames(p))
+            e = hipMemcpyAsync(host.frames, frames, total(p) * sizeof(uint32_t), hipMemcpyDeviceToHost, p.ctx->stream);
+        return SP_OK;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_occupancy(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const double *d_threshold,
+                                  const int32_t *bands, int32_t count, uint32_t *d_rows, uint32_t *d_frames)
+{
+    return plane_resident(ctx, "sp_power_occupancy", d_power, n, width, OccupancyKind{d_threshold, bands, count, d_rows, d_frames, nullptr});
+}
+
+extern "C" int sp_plan_execute_occupancy(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const double *d_threshold,
+                                         const int32_t *bands, int32_t count, uint32_t *d_rows, uint32_t *d_frames)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, OccupancyKind{d_threshold, bands, count, d_rows, d_frames, nullptr});
+}
+
+extern "C" int sp_render_occupancy(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width,
+                                   const double *threshold, const int32_t *bands, int32_t count, uint32_t *rows, uint32_t *frames)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, 0, OccupancyKind{threshold, bands, count, rows, frames, nullptr});
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

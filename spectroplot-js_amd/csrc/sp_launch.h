@@ -42,6 +42,12 @@ void launch_band_sum(const double *plane, int n, long long frames, const int32_t
 // `peak` is not written.  One launch.  (k_track_max and this launcher are sp_track.hip, a unit of their own.)
 void launch_track_max(const double *plane, int n, long long frames, const int32_t *bands, int count, int32_t *row, double *peak,
                       long long stride, long long x_base, hipStream_t stream);
+// rows[y] += the frames of the plane whose row y reaches threshold[y] (n device doubles), and out[b * stride + x_base + x] += the rows
+// of [bands[2 b], bands[2 b + 1]) of frame x that reach theirs, for the plane, frames and bands of launch_band_sum (`count` may be 0);
+// a null `rows` or `out` is not touched, one of them is not null, and the caller has zeroed both.  One launch.  (k_occupancy_count and
+// this launcher are sp_occupancy.hip, a unit of their own.)
+void launch_occupancy_count(const double *plane, int n, long long frames, const double *threshold, const int32_t *bands, int count,
+                            uint32_t *rows, uint32_t *out, long long stride, long long x_base, hipStream_t stream);
 
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 

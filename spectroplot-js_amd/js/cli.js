@@ -10,6 +10,7 @@
  *        [--mean mean.f64] [--mean-db mean_db.f64]
  *        [--bandpower bands.f64] [--bandpower-db bands_db.f64] [--bands Y0:Y1,...] [--band-freqs LO:HI,...]
  *        [--track-rows rows.i32] [--track-power peaks.f64] [--track-db peaks_db.f64]
+ *        [--occupancy-rows rows.u32] [--occupancy-frames frames.u32] [--threshold P | --threshold-over-mean K]
  *        --out image.ppm
  *   node spectroplot-js_amd/js/cli.js a.cu8 b.cu8 c.cs16 ... --n 1024 --width 2048 [options] --out-dir DIR
  *
@@ -46,6 +47,12 @@
  * the whole capture (HipWorker.renderTrack -> sp_render_track) for the bands of --bands / --band-freqs, count * width values each,
  * band-major: per band and frame the strongest image row that is not a NaN, the smallest among equal ones, as raw little-endian int32
  * (-1 where the band holds no value), its |X|^2 as raw little-endian f64 (NaN there), or for --track-db the dB of it.
+ *
+ * --occupancy-rows FILE / --occupancy-frames FILE (single-file runs, sample detector): the occupancy counts of the same request over the
+ * whole capture (HipWorker.renderOccupancy -> sp_render_occupancy) as raw little-endian uint32: n values, per image row the frames whose
+ * |X|^2 is >= the row's threshold, or count * width values, band-major, per band of --bands / --band-freqs and frame the rows that reach
+ * theirs.  The threshold is --threshold P, one power for all rows, or --threshold-over-mean K: threshold[y] = K * mean[y], the exact
+ * mean-power trace of the same request (one HipWorker.renderMean first, one multiply per row) - the noise-relative form.
  *
  * The format defaults to the file extension (lib/parseFreqRate.js:58-70), the worker count to the number of visible GPUs.
  * Output: binary PPM (P6, alpha dropped) or, with --out *.rgba, the raw RGBA bytes exactly as the reference's canvas holds them.
@@ -85,6 +92,19 @@ function parseBands(opt, n, who = '--bandpower') {
     return bands
 }
 
+// {threshold} of an occupancy request: --threshold P, or K times the request's own mean trace (a promise then)
+function occupancyThreshold(opt, worker, message, who) {
+    const number = (name) => {
+        const v = Number(opt[name])
+        if (!String(opt[name]).trim().length || Number.isNaN(v)) throw new Error(`--${name} needs a number`)
+        return v
+    }
+    if ((opt.threshold === undefined) === (opt['threshold-over-mean'] === undefined)) throw new Error(who + ' needs either --threshold P or --threshold-over-mean K')
+    if (opt.threshold !== undefined) return { threshold: number('threshold') }
+    const k = number('threshold-over-mean')
+    return worker.renderMean(message).then(r => ({ threshold: r.mean.map(v => k * v) }))
+}
+
 // a typed array's bytes as they are (every host this runs on is little-endian)
 const raw = a => Buffer.from(a.buffer, a.byteOffset, a.byteLength)
 
@@ -93,7 +113,8 @@ const f64Outputs = (name, method, field, own) => [false, true].map(db => ({ opti
     options: (opt, n) => Object.assign({ db }, own && own(opt, n)), bytes: r => raw(r[field]) }))
 
 // The side outputs of a single-file run, in the order they are written.  `picture`: the request carries the end-forced colour map and
-// `waterfall`, as the image's does; `method` of HipWorker gets the message and `options(opt, n)`; `bytes(reply, n, width)` is the file.
+// `waterfall`, as the image's does; `method` of HipWorker gets the message and `options(opt, n, worker, message)` - or what that promises,
+// where the options take a request of their own -; `bytes(reply, n, width)` is the file.
 const SIDE_OUTPUTS = [
     { option: 'traces', method: 'renderTraces', bytes: (t, n, width) => {
         const plain = a => Array.from(a, v => Number.isFinite(v) ? v : String(v))
@@ -113,6 +134,13 @@ const SIDE_OUTPUTS = [
     { option: 'track-rows', method: 'renderTrack', options: (opt, n) => ({ bands: parseBands(opt, n, '--track-rows') }), bytes: r => raw(r.rows) },
     { option: 'track-power', method: 'renderTrack', options: (opt, n) => ({ bands: parseBands(opt, n, '--track-power') }), bytes: r => raw(r.peaks) },
     { option: 'track-db', method: 'renderTrack', options: (opt, n) => ({ db: true, bands: parseBands(opt, n, '--track-db') }), bytes: r => raw(r.peaks) },
+    // the occupancy counts as uint32: n values per row, and count * width values, band-major
+    { option: 'occupancy-rows', method: 'renderOccupancy', options: (opt, n, worker, message) =>
+        occupancyThreshold(opt, worker, message, '--occupancy-rows'), bytes: r => raw(r.rows) },
+    { option: 'occupancy-frames', method: 'renderOccupancy', options: (opt, n, worker, message) => {
+        const bands = parseBands(opt, n, '--occupancy-frames')
+        return Promise.resolve(occupancyThreshold(opt, worker, message, '--occupancy-frames')).then(t => Object.assign({ bands }, t))
+    }, bytes: r => raw(r.frames) },
 ]
 
 // one side output: one request over the whole capture on one worker, with the taper and block_norm the image's request resolves to
@@ -126,12 +154,12 @@ function writeSide(kind, buffer, format, n, width, opt) {
         cmap[0] = [0, 0, 0]; cmap[cmap.length - 1] = [255, 255, 255]                    // lib/spectroplot.js:1129-1130
         Object.assign(message, { cmap, waterfall: !!opt.waterfall })
     }
-    const options = kind.options && kind.options(opt, n)
     const worker = new HipWorker()
-    return worker[kind.method](message, options).then(r => {
-        worker.terminate()
-        fs.writeFileSync(opt[kind.option], kind.bytes(r, n, width))
-    }, e => { worker.terminate(); throw e })
+    return new Promise(resolve => resolve(kind.options && kind.options(opt, n, worker, message)))
+        .then(options => worker[kind.method](message, options)).then(r => {
+            worker.terminate()
+            fs.writeFileSync(opt[kind.option], kind.bytes(r, n, width))
+        }, e => { worker.terminate(); throw e })
 }
 
 // --out-dir: the captures grouped by format, each group in one batch; the option names resolve as the single-file run's do

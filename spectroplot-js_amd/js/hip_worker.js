@@ -314,6 +314,39 @@ class HipWorker {
     static rowFreq(n, row) { return row < 0 ? NaN : (Math.floor(n / 2) - row) / n }
 
     /**
+     * The occupancy counts of a request (sp_render_occupancy) - how often a frequency is in use and how much of a band is in use at a
+     * time: the fields renderTraces reads in plus `{threshold, bands}` - `threshold` a power (|X|^2) for every image row or a
+     * Float64Array(n) of one per row, `bands` as for renderBandPower (none: no frame counts) - and two Uint32Arrays out: rows[y] is the
+     * number of frames whose |X|^2 at image row y is >= threshold[y] (rows[y] / width is the row's duty cycle) and, band-major,
+     * frames[b * width + x] the number of rows of band b that reach theirs in frame x.  A NaN on either side is no hit, so a capture
+     * shorter than n counts nothing.  The same words on every device and for every chunking.  No image is rendered.  Only the sample
+     * detector has counts (status -4), and bad bands or a threshold that is neither a number nor n values are refused (status -1), all
+     * before anything is rendered.  Runs in the instance's request order; a malformed field rejects (and reports `onerror`) and never
+     * resolves to arrays.
+     * @returns {Promise<{rows: Uint32Array, frames: Uint32Array, count: number, width: number, n: number}>}
+     */
+    renderOccupancy(m, opt) {
+        return this._queued(() => this._occupancyRequest(m, opt), 'renderOccupancy',
+            r => ({ rows: r.rows, frames: r.frames, count: r.count, width: r.width, n: r.n }), ownStatus)
+    }
+
+    _occupancyRequest(m, opt) {
+        return this._plainRequest(m, 'an occupancy request needs a buffer', 'the occupancy counts of the peak detector are not supported', () => {
+            const bands = opt && opt.bands !== undefined ? this._bandsField(m, opt, 'an occupancy request') : { bands: new Int32Array(0) }
+            const given = opt && opt.threshold
+            let threshold
+            if (typeof given === 'number') threshold = new Float64Array(Number.isInteger(m.n) && m.n > 0 ? m.n : 0).fill(given)
+            else if (given instanceof Float64Array) threshold = given
+            else throw refusal('an occupancy request needs {threshold}: a power or a Float64Array of n powers', -1)
+            if (threshold.length !== m.n) throw refusal('threshold must hold n values, one per image row', -1)
+            return Object.assign({ threshold }, bands)
+        })
+    }
+
+    /** Synchronous form of renderOccupancy (tests). */
+    renderOccupancySync(m, opt) { return addon().renderOccupancySync(this._ctx, this._occupancyRequest(m, opt)) }
+
+    /**
      * The picture of a worker message as ONE colour-index byte per pixel instead of RGBA (sp_render_index): index[j] is the entry of the
      * message's colour map pixel j of imageData.data shows, so the reply is a quarter of the size and js/consumers.js `recolour` redraws
      * it under another map without a render.  The message is a worker message (`detector: 'peak'` allowed; a colour map of more than 256

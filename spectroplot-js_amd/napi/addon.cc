@@ -30,6 +30,8 @@
 //     rows per frame (or its dB)
 //   renderTrack(handle, req, cb) / renderTrackSync(handle, req) -> {rows, peaks, count, width, n}: the strongest row of bands of rows per
 //     frame and its |X|^2 (or its dB)
+//   renderOccupancy(handle, req, cb) / renderOccupancySync(handle, req) -> {rows, frames, count, width, n}: the frames per row, and the
+//     rows per band and frame, whose |X|^2 reaches the row's threshold
 //   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
 //       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
 //   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
@@ -1321,6 +1323,85 @@ napi_value TrackJob::result(napi_env env)
 napi_value RenderTrackSync(napi_env env, napi_callback_info info) { return checked_sync<TrackJob>(env, info, kTrack); }
 napi_value RenderTrack(napi_env env, napi_callback_info info) { return checked_async<TrackJob>(env, info, kTrack); }
 
+// ---- occupancy counts: renderOccupancy(handle, req, cb) / renderOccupancySync(handle, req) ------------------------------------------------
+// req as for renderBandPower (db is not looked at) plus `threshold`, a Float64Array(n): one power per image row -> {rows, frames, count,
+// width, n}: rows a Uint32Array(n) - per image row the frames whose |X|^2 is >= the row's threshold - and frames a
+// Uint32Array(count * width), band-major - per band and frame the rows of the band that reach theirs (sp_render_occupancy; a NaN on
+// either side is no hit).  The library refuses bad bands, and a threshold of another length is refused here (status -1), before
+// anything is rendered.
+const CheckedKind kOccupancy{"renderOccupancy", false, "renderOccupancySync(handle, request)", "renderOccupancy(handle, request, callback)",
+                             "spectroplot_hip.renderOccupancy", "could not queue the occupancy request"};
+
+struct OccupancyJob : BandPowerJob {   // (`rows` are the bands; `out` is not used)
+    std::vector<double> threshold;
+    std::vector<uint32_t> row_counts, frame_counts;
+    bool parse_own(napi_env env, napi_value r) override;
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+bool OccupancyJob::parse_own(napi_env env, napi_value r)
+{
+    if (!BandPowerJob::parse_own(env, r)) return false;
+    napi_value v, ab;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void *data = nullptr;
+    if (napi_get_named_property(env, r, "threshold", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
+        || tt != napi_float64_array) {
+        napi_throw_type_error(env, nullptr, "threshold must be a Float64Array of n powers");
+        return false;
+    }
+    if (len) threshold.assign((const double *)data, (const double *)data + len);
+    return true;
+}
+
+void OccupancyJob::run()
+{
+    const size_t count = rows.size() / 2;
+    if (req.n < 1 || threshold.size() != (size_t)req.n) {
+        status = SP_ERR_INVALID_ARG;
+        error = "threshold must hold n values, one per image row";
+        return;
+    }
+    try {
+        row_counts.assign((size_t)req.n, 0);
+        if (count <= SP_MAX_BANDS && width > 0) frame_counts.assign(count * (size_t)width, 0);   // (more bands than the library takes: it refuses)
+    } catch (const std::bad_alloc &) {
+        status = SP_ERR_NOMEM;
+        error = "out of host memory";
+        return;
+    }
+    uint32_t none = 0;
+    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
+    status = sp_render_occupancy(ctx, &req, bytes, nbytes, width, threshold.data(), rows.data(), c, row_counts.data(),
+                                 frame_counts.empty() ? &none : frame_counts.data());
+    if (status != SP_OK) error = sp_last_error(ctx);
+}
+
+napi_value OccupancyJob::result(napi_env env)
+{
+    napi_value obj, ab, ta, v;
+    void *data = nullptr;
+    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, row_counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
+    if (!row_counts.empty()) memcpy(data, row_counts.data(), row_counts.size() * 4);
+    if (napi_create_typedarray(env, napi_uint32_array, row_counts.size(), ab, 0, &ta) != napi_ok
+        || napi_set_named_property(env, obj, "rows", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_arraybuffer(env, frame_counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
+    if (!frame_counts.empty()) memcpy(data, frame_counts.data(), frame_counts.size() * 4);
+    if (napi_create_typedarray(env, napi_uint32_array, frame_counts.size(), ab, 0, &ta) != napi_ok
+        || napi_set_named_property(env, obj, "frames", ta) != napi_ok)
+        return nullptr;
+    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
+    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
+    return obj;
+}
+
+napi_value RenderOccupancySync(napi_env env, napi_callback_info info) { return checked_sync<OccupancyJob>(env, info, kOccupancy); }
+napi_value RenderOccupancy(napi_env env, napi_callback_info info) { return checked_async<OccupancyJob>(env, info, kOccupancy); }
+
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
     int32_t c = 0;
@@ -1674,6 +1755,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"renderBandPowerSync", nullptr, RenderBandPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTrack", nullptr, RenderTrack, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderTrackSync", nullptr, RenderTrackSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderOccupancy", nullptr, RenderOccupancy, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"renderOccupancySync", nullptr, RenderOccupancySync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},

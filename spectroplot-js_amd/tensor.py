@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean, its exact band sums and its peak track as torch tensors: sp_plan_execute_power / _mean /
-_bandpower / _track on torch's current stream.
+"""The numeric spectrogram, its exact mean, its exact band sums, its peak track and its occupancy counts as torch tensors:
+sp_plan_execute_power / _mean / _bandpower / _track / _occupancy on torch's current stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
 library (include/spectroplot_hip.h, "Power plane replies"), resident on the capture's device and ordered on torch's current stream:
@@ -110,3 +110,28 @@ def track(plan, capture, width, bands):
     with _on_current_stream(plan.ctx, capture.device, (capture, rows, peaks)):
         plan.execute_track(capture.data_ptr(), capture.numel(), int(width), bands, rows.data_ptr(), peaks.data_ptr())
     return rows, peaks
+
+
+def occupancy(plan, capture, width, threshold, bands=()):
+    """The occupancy counts of `capture` (a uint8 CUDA tensor: the raw bytes) as two int32 tensors on the same device, rows [n] and
+    frames [count, width]: rows[y] is the number of frames whose |X|^2 at image row y is >= threshold[y], frames[b, x] the number of rows
+    of band (y0, y1) - a half-open range of image rows - that reach theirs in frame x; a NaN on either side is no hit
+    (include/spectroplot_hip.h, "Occupancy counts").  The library's words are uint32; no count reaches 2^31, so they are int32 here.
+    threshold: a Python float, for every row, or a contiguous float64 tensor of n values on the capture's device.  `plan` is a
+    binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the plane
+    itself is never held whole."""
+    _check_capture("occupancy", capture)
+    dev, n = capture.device, plan.n
+    if isinstance(threshold, torch.Tensor):
+        if threshold.dtype != torch.float64 or threshold.device != dev or not threshold.is_contiguous() or threshold.numel() != n:
+            raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG,
+                                           "tensor.occupancy: threshold must be a number or a contiguous float64 tensor of n on the capture's device")
+    else:
+        threshold = torch.full((n,), float(threshold), dtype=torch.float64, device=dev)
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    rows = torch.empty((n,), dtype=torch.int32, device=dev)
+    frames = torch.empty((len(bands), max(int(width), 0)), dtype=torch.int32, device=dev)
+    with _on_current_stream(plan.ctx, dev, (capture, threshold, rows, frames)):
+        plan.execute_occupancy(capture.data_ptr(), capture.numel(), int(width), threshold.data_ptr(), bands, rows.data_ptr(),
+                               frames.data_ptr() if frames.numel() else 0)
+    return rows, frames
