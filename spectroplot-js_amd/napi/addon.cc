@@ -5,51 +5,48 @@
 // language boundary.  No compute happens here and there is no fallback: every entry point that needs a device
 // throws when the HIP library reports an error.
 //
-// Exports
+// Exports: every name of Init's table, once (the sections below have the detail)
 //   deviceCount()                                  -> number
-//   parseFormat(name)                              -> {id, sampleWidth}
+//   parseFormat(name)                              -> {id, sampleWidth, elementSize}
 //   window(name, n)                                -> {window: Float64Array, weight}
 //   sliceBounds(nbytes, sampleWidth, index, count) -> [begin, end]
-//   poolStats()                                    -> {fresh, recycled, recycledPinned, freeBytes, pinnedBytes, pinRefused, keepLimit,
-//                                                      pinnedLimit, replyWeightCap} of the reply-image pool
+//   bandRows(n, fLo, fHi)                          -> [y0, y1]: the image rows whose centre frequency lies in the band (sp_band_rows)
+//   peakSubframes(formatId, n, nbytes, width)      -> {subframes, lastColumnCount} (sp_peak_subframes)
 //   cmap(name)                                     -> Uint8Array of r,g,b triples (the reference's map under its lookup rules) or null
 //   cmapKeys()                                     -> the reference's colour-map keys in its table order
+//   namedResolve(window, cmap)                     -> {window, cmap, lutLength}: what the two option names resolve to (sp_named_resolve)
+//   poolStats()                                    -> {fresh, recycled, recycledPinned, freeBytes, pinnedBytes, pinRefused, keepLimit,
+//                                                      pinnedLimit, replyWeightCap} of the reply-image pool
 //   allocBuffer(nbytes)                            -> ArrayBuffer in page-locked host memory (sp_host_alloc): a request whose `buffer`
 //                                                     is one of these goes to the device at the full rate of the host link
 //   createContext(device)                          -> external handle
 //   destroyContext(handle)                         -> releases the device context as soon as no render is in flight on it
-//   render(handle, req, cb)   req = {format:int, buffer:ArrayBuffer, n, windowc:Float64Array, block_norm, gain, range,
-//                                    lut:Uint8Array, width, channelMode, waterfall}
-//       runs sp_render on a libuv worker thread and calls cb(err, {rgba, gauge_mins, gauge_maxs, gauge_amps: ArrayBuffer,
-//       c_hist, cB_hist: Float64Array, dBfs_min, dBfs_max}) on the main thread
-//   renderSync(handle, req)                        -> the same reply object, synchronously
-//   renderTraces(handle, req, cb) / renderTracesSync(handle, req) -> {trace_min, trace_max}: per-bin min / max traces, no image
-//   renderPower(handle, req, cb) / renderPowerSync(handle, req) -> {power, width, n}: |X|^2 (or dB) per frame and bin as f64, no image
-//   renderMean(handle, req, cb) / renderMeanSync(handle, req) -> {mean, width, n}: the exact mean of |X|^2 over the frames per row (or its dB)
-//   renderBandPower(handle, req, cb) / renderBandPowerSync(handle, req) -> {bands, count, width, n}: the exact sum of |X|^2 over bands of
-//     rows per frame (or its dB)
-//   renderTrack(handle, req, cb) / renderTrackSync(handle, req) -> {rows, peaks, count, width, n}: the strongest row of bands of rows per
-//     frame and its |X|^2 (or its dB)
-//   renderOccupancy(handle, req, cb) / renderOccupancySync(handle, req) -> {rows, frames, count, width, n}: the frames per row, and the
-//     rows per band and frame, whose |X|^2 reaches the row's threshold
-//   renderDensity(handle, req, cb) / renderDensitySync(handle, req) -> {density, n, lutLen, width}: the persistence spectrum, a
-//       Uint32Array(n * lutLen) of per-row colour-index counts (sp_render_density); the request is renderIndex's
-//   renderIndex(handle, req, cb) / renderIndexSync(handle, req)   -> render's reply with `index`, a Uint8Array(width * n) of colour
-//                                    indices, in place of `rgba` (sp_render_index); req as for render
-//   renderNamed(handle, req, cb) / renderNamedSync(handle, req)   req = {format, window, cmap: strings, buffer, n, gain, range, width,
-//                                    channelMode, waterfall}: sp_render_named - the library resolves the names as the reference's caller
-//                                    does (lib/spectroplot.js:238-264, 1113-1146) and keeps the plan while they repeat
-//   namedResolve(window, cmap)                     -> {window, cmap, lutLength}: what the two option names resolve to (sp_named_resolve)
 //   planCreations(handle)                          -> how many plans this context has built (sp_context_plan_creations)
 //   createGroup(devices: number[])                 -> external handle of an sp_group: one member context per listed device
 //   destroyGroup(handle)                           -> like destroyContext
-//   groupRender(handle, req, cb) / groupRenderSync(handle, req)   req as for render, `width` = frames of the WHOLE image, plus
-//       `gather`: 'device' (default) | 'host' (sp_group_render_ex); the result carries transport, transportNote and timings:
-//       sp_group_render - the caller's sliced render (lib/spectroplot.js:1206-1244) with the strips gathered device to device (RCCL or
-//       peer copies) and merged on the root; the reply is the merged result (rgba = the whole image, gauges [width]) plus
-//       {sliceWidth, members, transport: 'none' | 'rccl' | 'peer'}
-//   renderBatch(handle, req, items, cb) / renderBatchSync(handle, req, items)   req as for render without buffer and width; items =
-//       [{buffer: ArrayBuffer, width}]: sp_render_batch, one reply per item shaped as render's
+// The render entry points come in pairs: name(handle, req, cb) runs the library call on a libuv worker thread and calls cb(err, reply) on
+// the main thread; nameSync(handle, req) returns the same reply or throws.  An error of the library carries its `status`.
+//   render / renderSync              req = {format: int, buffer: ArrayBuffer, n, windowc: Float64Array, block_norm, gain, range,
+//                                    lut: Uint8Array, width, channelMode, waterfall, detector} -> {rgba, gauge_mins, gauge_maxs,
+//                                    gauge_amps: ArrayBuffer, c_hist, cB_hist: Float64Array, stages, dBfs_min, dBfs_max} (sp_render)
+//   renderNamed / renderNamedSync    req = {format, window, cmap: strings, buffer, n, gain, range, width, channelMode, waterfall,
+//                                    detector} -> render's reply (sp_render_named: the library resolves the names as the reference's
+//                                    caller does, lib/spectroplot.js:238-264, 1113-1146, and keeps the plan while they repeat)
+//   groupRender / groupRenderSync    a group handle; req as for render, `width` = frames of the WHOLE image, plus gather: 'device'
+//                                    (default) | 'host' -> render's reply for the merged image plus {members, sliceWidth, transport:
+//                                    'none' | 'rccl' | 'peer', transportNote, timings} (sp_group_render_ex: the caller's sliced render,
+//                                    lib/spectroplot.js:1206-1244, with the strips gathered device to device and merged on the root)
+//   renderBatch / renderBatchSync    (handle, req, items[, cb]): req as for render without buffer and width, items = [{buffer, width}]
+//                                    -> one reply per item shaped as render's (sp_render_batch)
+//   renderTraces / ...Sync           req without a picture -> {trace_min, trace_max}: per-bin min / max traces
+//   renderIndex / ...Sync            req as for render -> render's reply with `index`, a Uint8Array(width * n), in place of `rgba`
+//   renderDensity / ...Sync          req as for render -> {density: Uint32Array(n * lutLen), n, lutLen, width}: the persistence spectrum
+//   renderPower / ...Sync            req without a picture plus db -> {power: Float64Array(width * n), width, n}: |X|^2 or its dB
+//   renderMean / ...Sync             req as for renderPower -> {mean: Float64Array(n), width, n}: the exact mean of |X|^2 per row
+//   renderBandPower / ...Sync        req as for renderPower plus bands -> {bands: Float64Array(count * width), count, width, n}
+//   renderTrack / ...Sync            req as for renderBandPower -> {rows: Int32Array, peaks: Float64Array, count, width, n}
+//   renderOccupancy / ...Sync        req as for renderBandPower plus threshold -> {rows, frames: Uint32Array, count, width, n}
+// and `version`, the library's (sp_version), a number.
 // One render at a time per handle: a second render on a handle whose first is still in flight throws (HipWorker serialises its own).
 #include <node_api.h>
 
@@ -59,11 +56,13 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <initializer_list>
 #include <mutex>
 #include <new>
 #include <sys/mman.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/spectroplot_hip.h"
@@ -249,7 +248,8 @@ void pool_free_cb(napi_env env, void *data, void *hint)
 // What every request kind has: the context it runs on, its outcome, and - for an asynchronous one - the work item and the references
 // that keep its callback (refs[0]) and whatever the worker thread reads (the handle, the input buffers) alive until the callback.
 // A kind adds its parsed request, run() for the worker thread and result() for a job that ended with SP_OK; its destructor gives back
-// the buffers that did not go to JavaScript.
+// the buffers that did not go to JavaScript.  The ways a run() ends are here: refused before the library was asked, out of host memory,
+// and the library call's status with the context's error text.
 struct JobBase {
     Ctx *owner = nullptr;
     int status = SP_OK;
@@ -259,40 +259,26 @@ struct JobBase {
     virtual ~JobBase() = default;
     virtual void run() = 0;
     virtual napi_value result(napi_env env) = 0;
-};
 
-struct Job;
-void run_job(Job *j);
-napi_value make_reply(napi_env env, Job *j);
-
-struct Job : JobBase {
-    sp_context *ctx = nullptr;
-    sp_group *group = nullptr;   // a group handle's job
-    int32_t gather = SP_GROUP_GATHER_DEVICE;   // ... and where its strips meet (req.gather: 'device' | 'host')
-    std::string transport, note;
-    double t_render = 0, t_gather = 0, t_download = 0;
-    // where the job's time went on the worker thread (microseconds): reply buffers from the pool, the library call
-    double us_take = 0, us_native = 0;
-    sp_request req{};
-    std::vector<double> window;
-    std::vector<uint8_t> lut;
-    // a request by option names (renderNamed): the library evaluates taper and colour map itself
-    bool named = false;
-    std::string nformat, nwindow, ncmap;
-    const uint8_t *bytes = nullptr;
-    size_t nbytes = 0;
-    int32_t width = 0;
-    // outputs: the image in a recycled block, the gauges malloc'd; handed to JS as external ArrayBuffers
-    uint8_t *rgba = nullptr, *gmin = nullptr, *gmax = nullptr, *gamp = nullptr;
-    size_t rgba_size = 0;
-    int rgba_pin = kUnpinned;
-    std::vector<uint64_t> c_hist, cb_hist;
-    double minmax[2] = {0.0, -200.0};
-    void run() override { run_job(this); }
-    napi_value result(napi_env env) override { return make_reply(env, this); }
-    // a checked kind's own request fields, read behind the shared ones (parse_checked); false: it has thrown
-    virtual bool parse_own(napi_env, napi_value) { return true; }
-    ~Job() override;
+    void refuse(int code, const char *why) { status = code; error = why; }
+    void no_memory() { refuse(SP_ERR_NOMEM, "out of host memory"); }
+    // the job's reply arrays: false, and the job out of memory, if they cannot be had
+    template <typename F> bool allocated(F &&assign)
+    {
+        try {
+            assign();
+            return true;
+        } catch (const std::bad_alloc &) {
+            no_memory();
+            return false;
+        }
+    }
+    // (a job's context stays the owner's while the job is counted in `inflight`)
+    void finish(int rc)
+    {
+        status = rc;
+        if (status != SP_OK) error = sp_last_error(owner->c);
+    }
 };
 
 void free_cb(napi_env, void *data, void *) { free(data); }
@@ -335,207 +321,12 @@ bool read_detector(napi_env env, napi_value req, int32_t *out)
     return true;
 }
 
-bool parse_request(napi_env env, napi_value handle, napi_value req, Job *j, bool named = false)
-{
-    void *p = nullptr;
-    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
-        napi_throw_type_error(env, nullptr, "context handle expected");
-        return false;
-    }
-    j->owner = (Ctx *)p;
-    if (j->owner->closed || (!j->owner->c && !j->owner->g)) {
-        napi_throw_error(env, nullptr, "context has been destroyed");
-        return false;
-    }
-    j->ctx = j->owner->c;
-    j->group = j->owner->g;
-    napi_value v;
-    int32_t i32 = 0;
-    j->named = named;
-    if (named) {
-        j->nformat = get_string(env, req, "format");
-        j->nwindow = get_string(env, req, "window");
-        j->ncmap = get_string(env, req, "cmap");
-    } else {
-        get_named(env, req, "format", &v); napi_get_value_int32(env, v, &i32); j->req.format = i32;
-    }
-    get_named(env, req, "n", &v); napi_get_value_int32(env, v, &i32); j->req.n = i32;
-    get_named(env, req, "width", &v); napi_get_value_int32(env, v, &i32); j->width = i32;
-    if (j->group && get_string(env, req, "gather") == "host") j->gather = SP_GROUP_GATHER_HOST;
-    j->req.channel_mode = get_bool(env, req, "channelMode");
-    j->req.waterfall = get_bool(env, req, "waterfall");
-    if (!read_detector(env, req, &j->req.detector)) return false;
-    j->req.block_norm = get_double(env, req, "block_norm");
-    j->req.gain = get_double(env, req, "gain");
-    j->req.range = get_double(env, req, "range");
-
-    void *data = nullptr;
-    size_t len = 0;
-    get_named(env, req, "buffer", &v);
-    if (napi_get_arraybuffer_info(env, v, &data, &len) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
-        return false;
-    }
-    j->bytes = (const uint8_t *)data;
-    j->nbytes = len;
-    if (named) {
-        int32_t lut_len = 0;
-        sp_named_resolve(j->nwindow.c_str(), j->ncmap.c_str(), nullptr, nullptr, &lut_len);   // sizes the reply's c_hist
-        j->req.lut_len = lut_len;
-        return true;
-    }
-
-    napi_typedarray_type tt;
-    napi_value ab;
-    size_t off = 0;
-    get_named(env, req, "windowc", &v);
-    if (napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_float64_array) {
-        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
-        return false;
-    }
-    j->window.assign((const double *)data, (const double *)data + len);
-    get_named(env, req, "lut", &v);
-    if (napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
-        napi_throw_type_error(env, nullptr, "lut must be a Uint8Array");
-        return false;
-    }
-    j->lut.assign((const uint8_t *)data, (const uint8_t *)data + len);
-    j->req.lut_len = (int32_t)(len / 3);
-    if ((size_t)j->req.n != j->window.size() && j->req.n > 0 && j->window.size() < (size_t)j->req.n) {
-        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
-        return false;
-    }
-    j->req.windowc = j->window.data();
-    j->req.lut_rgb = j->lut.data();
-    return true;
-}
 
 inline double now_us()
 {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-void run_job_inner(Job *j);
-void run_job(Job *j)
-{
-    const double t0 = now_us();
-    run_job_inner(j);
-    j->us_native = now_us() - t0 - j->us_take;
-}
-
-void run_job_inner(Job *j)
-{
-    const double t_take0 = now_us();
-    const size_t W = j->width > 0 ? (size_t)j->width : 0, n = j->req.n > 0 ? (size_t)j->req.n : 0;
-    j->rgba_size = 4 * W * n + 1;
-    j->rgba = (uint8_t *)g_pool.take(j->rgba_size, &j->rgba_pin);
-    j->gmin = (uint8_t *)calloc(W + 1, 1);
-    j->gmax = (uint8_t *)calloc(W + 1, 1);
-    j->gamp = (uint8_t *)calloc(W + 1, 1);
-    j->c_hist.assign(j->req.lut_len > 0 ? (size_t)j->req.lut_len : 0, 0);
-    j->cb_hist.assign(SP_CB_HIST_SIZE, 0);
-    j->us_take = now_us() - t_take0;
-    if (!j->rgba || !j->gmin || !j->gmax || !j->gamp) {
-        j->status = SP_ERR_NOMEM;
-        j->error = "out of host memory";
-        return;
-    }
-    sp_reply r{};
-    r.rgba = j->rgba; r.gauge_mins = j->gmin; r.gauge_maxs = j->gmax; r.gauge_amps = j->gamp;
-    r.c_hist = j->c_hist.data(); r.cb_hist = j->cb_hist.data(); r.dbfs_minmax = j->minmax;
-    if (j->group) {
-        j->status = sp_group_render_ex(j->group, &j->req, j->bytes, j->nbytes, j->width, &r, j->gather);
-        if (j->status != SP_OK) j->error = sp_group_last_error(j->group);
-        // (read here, on the worker thread that owns the group for the duration of the job)
-        j->transport = sp_group_transport(j->group);
-        j->note = sp_group_transport_note(j->group);
-        sp_group_last_timings(j->group, &j->t_render, &j->t_gather, &j->t_download);
-        return;
-    }
-    if (j->named) {
-        sp_named_request nr{};
-        nr.format = j->nformat.c_str();
-        nr.window = j->nwindow.c_str();
-        nr.cmap = j->ncmap.c_str();
-        nr.n = j->req.n;
-        nr.channel_mode = j->req.channel_mode;
-        nr.waterfall = j->req.waterfall;
-        nr.gain = j->req.gain;
-        nr.range = j->req.range;
-        j->status = sp_render_named_ex(j->ctx, &nr, j->req.detector, j->bytes, j->nbytes, j->width, &r);
-    } else {
-        j->status = sp_render(j->ctx, &j->req, j->bytes, j->nbytes, j->width, &r);
-    }
-    if (j->status != SP_OK) j->error = sp_last_error(j->ctx);
-}
-
-napi_value make_reply(napi_env env, Job *j)
-{
-    const size_t W = j->width > 0 ? (size_t)j->width : 0, n = (size_t)j->req.n;
-    napi_value out, v;
-    NAPI_OK(env, napi_create_object(env, &out));
-    auto put_ab = [&](const char *name, uint8_t *&p, size_t len) {
-        napi_value ab;
-        if (napi_create_external_arraybuffer(env, p, len, free_cb, nullptr, &ab) == napi_ok) {
-            p = nullptr;   // owned by the ArrayBuffer now
-            napi_set_named_property(env, out, name, ab);
-        }
-    };
-    {
-        napi_value ab;
-        PoolTag *tag = new PoolTag{j->rgba_size, j->rgba_pin};
-        if (napi_create_external_arraybuffer(env, j->rgba, 4 * W * n, pool_free_cb, tag, &ab) == napi_ok) {
-            int64_t total = 0;
-            napi_adjust_external_memory(env, reply_weight(j->rgba_size), &total);
-            j->rgba = nullptr;
-            napi_set_named_property(env, out, "rgba", ab);
-        } else {
-            delete tag;
-        }
-    }
-    put_ab("gauge_mins", j->gmin, W);
-    put_ab("gauge_maxs", j->gmax, W);
-    put_ab("gauge_amps", j->gamp, W);
-    auto put_hist = [&](const char *name, const std::vector<uint64_t> &h) {
-        napi_value ab, ta;
-        void *data;
-        if (napi_create_arraybuffer(env, h.size() * 8, &data, &ab) != napi_ok) return;
-        for (size_t i = 0; i < h.size(); i++) ((double *)data)[i] = (double)h[i];
-        napi_create_typedarray(env, napi_float64_array, h.size(), ab, 0, &ta);
-        napi_set_named_property(env, out, name, ta);
-    };
-    put_hist("c_hist", j->c_hist);
-    put_hist("cB_hist", j->cb_hist);
-    {
-        napi_value st;
-        napi_create_object(env, &st);
-        napi_create_double(env, j->us_take, &v); napi_set_named_property(env, st, "take_us", v);
-        napi_create_double(env, j->us_native, &v); napi_set_named_property(env, st, "native_us", v);
-        napi_set_named_property(env, out, "stages", st);
-    }
-    napi_create_double(env, j->minmax[0], &v); napi_set_named_property(env, out, "dBfs_min", v);
-    napi_create_double(env, j->minmax[1], &v); napi_set_named_property(env, out, "dBfs_max", v);
-    if (j->group) {
-        const int members = sp_group_size(j->group);
-        napi_create_int32(env, members, &v); napi_set_named_property(env, out, "members", v);
-        napi_create_int32(env, members > 0 ? j->width / members : 0, &v); napi_set_named_property(env, out, "sliceWidth", v);
-        napi_create_string_utf8(env, j->transport.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, out, "transport", v);
-        napi_create_string_utf8(env, j->note.c_str(), NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, out, "transportNote", v);
-        napi_value t;
-        napi_create_object(env, &t);
-        napi_create_double(env, j->t_render, &v); napi_set_named_property(env, t, "render_ms", v);
-        napi_create_double(env, j->t_gather, &v); napi_set_named_property(env, t, "gather_ms", v);
-        napi_create_double(env, j->t_download, &v); napi_set_named_property(env, t, "download_ms", v);
-        napi_set_named_property(env, out, "timings", t);
-    }
-    return out;
-}
-
-Job::~Job()
-{
-    if (rgba) g_pool.give(rgba, rgba_size, rgba_pin);
-    free(gmin); free(gmax); free(gamp);
-}
 
 void free_job(napi_env env, JobBase *j)
 {
@@ -632,48 +423,6 @@ napi_value queue_async(napi_env env, JobBase *j, std::initializer_list<napi_valu
     return nullptr;
 }
 
-napi_value render_sync(napi_env env, napi_callback_info info, bool named)
-{
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Job *j = new Job;
-    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
-    return run_sync(env, j);
-}
-napi_value RenderSync(napi_env env, napi_callback_info info) { return render_sync(env, info, false); }
-napi_value RenderNamedSync(napi_env env, napi_callback_info info) { return render_sync(env, info, true); }
-
-napi_value render_async(napi_env env, napi_callback_info info, bool named)
-{
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Job *j = new Job;
-    if (!parse_request(env, argv[0], argv[1], j, named)) { free_job(env, j); return nullptr; }
-    napi_value buf = nullptr;   // (left null, it fails the queueing)
-    napi_get_named_property(env, argv[1], "buffer", &buf);
-    return queue_async(env, j, {argv[2], argv[0], buf}, "spectroplot_hip.render", "could not queue the render");
-}
-napi_value Render(napi_env env, napi_callback_info info) { return render_async(env, info, false); }
-napi_value RenderNamed(napi_env env, napi_callback_info info) { return render_async(env, info, true); }
-
-// ---- batches: renderBatch(handle, req, [{buffer, width}], cb) / renderBatchSync(handle, req, items) -------------------------------
-// req is render's request without buffer and width; every item gets its own reply, shaped as render's (sp_render_batch).  Every
-// value is read with its status checked: a missing or non-numeric field throws instead of leaving a stale value behind.
-struct BatchJob;
-void run_batch(BatchJob *b);
-napi_value batch_result(napi_env env, BatchJob *b);
-
-struct BatchJob : JobBase {
-    sp_request req{};
-    std::vector<double> window;
-    std::vector<uint8_t> lut;
-    std::vector<Job *> items;
-    void run() override { run_batch(this); }
-    napi_value result(napi_env env) override { return batch_result(env, this); }
-    ~BatchJob() override { for (Job *j : items) delete j; }
-};
 
 bool checked_number(napi_env env, napi_value obj, const char *name, double *out)
 {
@@ -712,48 +461,430 @@ bool checked_bool(napi_env env, napi_value obj, const char *name, int32_t *out)
     return true;
 }
 
-bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value items, BatchJob *b)
+// ---- readers: what the request parsers below share; each returns false (or null) once it has thrown --------------------------------
+// The Ctx behind a handle.  `who`: the entry point that takes contexts only, named in its refusal of a group; null: a group will do.
+Ctx *read_handle(napi_env env, napi_value handle, const char *who)
 {
     void *p = nullptr;
     if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
         napi_throw_type_error(env, nullptr, "context handle expected");
+        return nullptr;
+    }
+    Ctx *x = (Ctx *)p;
+    if (!x->closed && (x->c || (x->g && !who))) return x;
+    napi_throw_error(env, nullptr, who && x->g ? (std::string(who) + " takes a context handle, not a group").c_str() : "context has been destroyed");
+    return nullptr;
+}
+
+// The samples of one request and how many frames are wanted of them
+struct Capture {
+    const uint8_t *bytes = nullptr;
+    size_t nbytes = 0;
+    int32_t width = 0;
+};
+
+bool read_buffer(napi_env env, napi_value obj, Capture *c)
+{
+    napi_value v;
+    void *data = nullptr;
+    if (napi_get_named_property(env, obj, "buffer", &v) != napi_ok || napi_get_arraybuffer_info(env, v, &data, &c->nbytes) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
         return false;
     }
-    b->owner = (Ctx *)p;
-    if (b->owner->closed || !b->owner->c) {
-        napi_throw_error(env, nullptr, b->owner->g ? "renderBatch takes a context handle, not a group" : "context has been destroyed");
-        return false;
-    }
-    double d = 0;
-    if (!checked_int32(env, req, "format", &b->req.format) || !checked_int32(env, req, "n", &b->req.n)) return false;
-    if (!checked_bool(env, req, "channelMode", &b->req.channel_mode) || !checked_bool(env, req, "waterfall", &b->req.waterfall)) return false;
-    if (!read_detector(env, req, &b->req.detector)) return false;   // (a peak batch is refused by the library: SP_ERR_UNSUPPORTED)
-    if (!checked_number(env, req, "block_norm", &b->req.block_norm) || !checked_number(env, req, "gain", &b->req.gain)) return false;
-    if (!checked_number(env, req, "range", &d)) return false;
-    b->req.range = d;
+    c->bytes = (const uint8_t *)data;
+    return true;
+}
+
+// A typed-array property copied into `out`: of one of `types`, at least `min_len` elements and a multiple of `multiple`, or `refusal` is
+// thrown as a TypeError.
+template <typename T>
+bool read_array(napi_env env, napi_value obj, const char *name, std::initializer_list<napi_typedarray_type> types, const char *refusal,
+                std::vector<T> *out, size_t min_len = 0, size_t multiple = 1)
+{
     napi_value v, ab;
     napi_typedarray_type tt;
     size_t len = 0, off = 0;
     void *data = nullptr;
-    if (napi_get_named_property(env, req, "windowc", &v) != napi_ok
-        || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_float64_array) {
-        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
+    bool ok = napi_get_named_property(env, obj, name, &v) == napi_ok && napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) == napi_ok;
+    bool of_type = false;
+    for (napi_typedarray_type t : types) of_type = of_type || (ok && tt == t);
+    if (!of_type || len < min_len || len % multiple != 0) {
+        napi_throw_type_error(env, nullptr, refusal);
         return false;
     }
-    if (b->req.n > 0 && len < (size_t)b->req.n) {
-        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
-        return false;
+    out->assign((const T *)data, (const T *)data + len);
+    return true;
+}
+
+// What a request asks of the library, with the taper and the colour map it points into
+struct Settings {
+    sp_request req{};
+    std::vector<double> window;
+    std::vector<uint8_t> lut;
+    void bind()
+    {
+        req.lut_len = (int32_t)(lut.size() / 3);
+        req.windowc = window.data();
+        req.lut_rgb = lut.data();
     }
-    b->window.assign((const double *)data, (const double *)data + len);
-    if (napi_get_named_property(env, req, "lut", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
-        || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
-        napi_throw_type_error(env, nullptr, "lut must be a Uint8Array");
-        return false;
+};
+
+bool read_windowc(napi_env env, napi_value req, Settings *s)
+{
+    return read_array(env, req, "windowc", {napi_float64_array}, "windowc must be a Float64Array", &s->window);
+}
+
+bool window_covers_n(napi_env env, const Settings &s)
+{
+    if (s.req.n <= 0 || s.window.size() >= (size_t)s.req.n) return true;
+    napi_throw_range_error(env, nullptr, "windowc is shorter than n");
+    return false;
+}
+
+bool read_lut(napi_env env, napi_value req, Settings *s, size_t min_len, const char *refusal)
+{
+    return read_array(env, req, "lut", {napi_uint8_array, napi_uint8_clamped_array}, refusal, &s->lut, min_len);
+}
+
+// ... and the three that only some checked kinds have
+bool read_db(napi_env env, napi_value req, int32_t *db) { return checked_bool(env, req, "db", db); }
+
+// The bands of a request, y0 and y1 per band (half-open ranges of image rows), and what the library is given for them: a count beyond
+// SP_MAX_BANDS is refused there, so the kinds allocate no arrays for it and SP_MAX_BANDS + 1 stands for any such count.
+struct Bands {
+    std::vector<int32_t> rows;
+    size_t count() const { return rows.size() / 2; }
+    bool taken() const { return count() <= (size_t)SP_MAX_BANDS; }
+    int32_t for_library() const { return taken() ? (int32_t)count() : SP_MAX_BANDS + 1; }
+};
+// ... and an array that was deliberately not allocated, for a request the library refuses before it writes: one element to point at
+template <typename T> T *or_placeholder(std::vector<T> &v, T *none) { return v.empty() ? none : v.data(); }
+
+bool read_bands(napi_env env, napi_value req, Bands *b)
+{
+    return read_array(env, req, "bands", {napi_int32_array}, "bands must be an Int32Array of y0, y1 pairs", &b->rows, 0, 2);
+}
+
+bool read_threshold(napi_env env, napi_value req, std::vector<double> *t)
+{
+    return read_array(env, req, "threshold", {napi_float64_array}, "threshold must be a Float64Array of n powers", t);
+}
+
+// ---- reply buffers ---------------------------------------------------------------------------------------------------------------------
+// One block of the reply pool on its way into a reply: taken on the worker thread; handed to JavaScript by Reply::block, or given back
+// here if the job ended without a reply.
+struct PoolBlock {
+    uint8_t *p = nullptr;
+    size_t size = 0;
+    int pin = kUnpinned;
+    PoolBlock() = default;
+    PoolBlock(const PoolBlock &) = delete;
+    bool take(size_t bytes)
+    {
+        size = bytes;
+        p = (uint8_t *)g_pool.take(size, &pin);
+        return p != nullptr;
     }
-    b->lut.assign((const uint8_t *)data, (const uint8_t *)data + len);
-    b->req.lut_len = (int32_t)(len / 3);
-    b->req.windowc = b->window.data();
-    b->req.lut_rgb = b->lut.data();
+    ~PoolBlock() { if (p) g_pool.give(p, size, pin); }
+};
+
+// What the library writes of an image reply: the image in a pool block, the gauges malloc'd (external ArrayBuffers later), histograms
+// and dBfs range.
+struct ImageBuffers {
+    PoolBlock image;
+    uint8_t *gmin = nullptr, *gmax = nullptr, *gamp = nullptr;
+    std::vector<uint64_t> c_hist, cb_hist;
+    double minmax[2] = {0.0, -200.0};
+    ImageBuffers() = default;
+    ImageBuffers(const ImageBuffers &) = delete;
+    // an image of W x n pixels of `pixel_bytes` each; `r` gets everything but the image.  false: out of host memory
+    bool take(size_t pixel_bytes, size_t W, size_t n, size_t lut_len, sp_reply *r)
+    {
+        image.take(pixel_bytes * W * n + 1);
+        gmin = (uint8_t *)calloc(W + 1, 1);
+        gmax = (uint8_t *)calloc(W + 1, 1);
+        gamp = (uint8_t *)calloc(W + 1, 1);
+        c_hist.assign(lut_len, 0);
+        cb_hist.assign(SP_CB_HIST_SIZE, 0);
+        r->gauge_mins = gmin; r->gauge_maxs = gmax; r->gauge_amps = gamp;
+        r->c_hist = c_hist.data(); r->cb_hist = cb_hist.data(); r->dbfs_minmax = minmax;
+        return image.p && gmin && gmax && gamp;
+    }
+    ~ImageBuffers() { free(gmin); free(gmax); free(gamp); }
+};
+
+// ---- writers: a reply object under construction ----------------------------------------------------------------------------------------
+// Properties appear in the order of the calls.  After a failed N-API call the remaining calls do nothing and done() is null; a buffer
+// belongs to JavaScript only once its ArrayBuffer exists, so whatever did not get that far is still freed by the job.
+struct Reply {
+    napi_env env;
+    napi_value obj = nullptr;
+    bool ok;
+    explicit Reply(napi_env e) : env(e) { ok = napi_create_object(env, &obj) == napi_ok; }
+    napi_value done() const { return ok ? obj : nullptr; }
+
+    void set(const char *name, napi_value v) { ok = ok && napi_set_named_property(env, obj, name, v) == napi_ok; }
+    static size_t element_size(napi_typedarray_type type) { return type == napi_float64_array ? 8 : type == napi_uint8_array ? 1 : 4; }
+    // `count` elements of `ab` from byte `offset` on, as the typed array `name`
+    void view(const char *name, napi_typedarray_type type, napi_value ab, size_t offset, size_t count)
+    {
+        napi_value ta;
+        ok = ok && napi_create_typedarray(env, type, count, ab, offset, &ta) == napi_ok;
+        set(name, ta);
+    }
+    // a new ArrayBuffer of `bytes` bytes; `data`: where they are
+    napi_value buffer(size_t bytes, void **data)
+    {
+        napi_value ab = nullptr;
+        ok = ok && napi_create_arraybuffer(env, bytes, data, &ab) == napi_ok;
+        return ab;
+    }
+    napi_value copy_of(const void *from, size_t bytes)
+    {
+        void *data = nullptr;
+        napi_value ab = buffer(bytes, &data);
+        if (ok && bytes) memcpy(data, from, bytes);
+        return ab;
+    }
+    // these `count` elements, copied into a new typed array `name`
+    void array(const char *name, napi_typedarray_type type, const void *from, size_t count)
+    {
+        view(name, type, copy_of(from, count * element_size(type)), 0, count);
+    }
+    void ints(std::initializer_list<std::pair<const char *, int32_t>> props)
+    {
+        for (const auto &p : props) {
+            napi_value v = nullptr;
+            ok = ok && napi_create_int32(env, p.second, &v) == napi_ok;
+            set(p.first, v);
+        }
+    }
+    // ... and doubles, in an object of their own under `under` if that is given
+    void doubles(const char *under, std::initializer_list<std::pair<const char *, double>> props)
+    {
+        Reply to = under ? Reply(env) : *this;
+        to.ok = to.ok && ok;
+        for (const auto &p : props) {
+            napi_value v = nullptr;
+            to.ok = to.ok && napi_create_double(env, p.second, &v) == napi_ok;
+            to.set(p.first, v);
+        }
+        ok = to.ok;
+        if (under) set(under, to.obj);
+    }
+    void string(const char *name, const std::string &s)
+    {
+        napi_value v = nullptr;
+        ok = ok && napi_create_string_utf8(env, s.c_str(), NAPI_AUTO_LENGTH, &v) == napi_ok;
+        set(name, v);
+    }
+    // a histogram's counts as a Float64Array
+    void hist(const char *name, const std::vector<uint64_t> &h)
+    {
+        void *data = nullptr;
+        napi_value ab = buffer(h.size() * 8, &data);
+        for (size_t i = 0; ok && i < h.size(); i++) ((double *)data)[i] = (double)h[i];
+        view(name, napi_float64_array, ab, 0, h.size());
+    }
+    // `len` malloc'd bytes as an external ArrayBuffer that frees them
+    void external(const char *name, uint8_t *&p, size_t len)
+    {
+        napi_value ab = nullptr;
+        ok = ok && napi_create_external_arraybuffer(env, p, len, free_cb, nullptr, &ab) == napi_ok;
+        if (ok) p = nullptr;   // owned by the ArrayBuffer now
+        set(name, ab);
+    }
+    void gauges(ImageBuffers &b, size_t W)
+    {
+        external("gauge_mins", b.gmin, W);
+        external("gauge_maxs", b.gmax, W);
+        external("gauge_amps", b.gamp, W);
+    }
+    // The pool block's first `bytes` bytes as an external ArrayBuffer under `name` - or, with `view_as`, the typed array of `count`
+    // elements over it.  V8 is told the block's weight; the ArrayBuffer's finalizer takes the weight back and returns the block.
+    void block(const char *name, PoolBlock &b, size_t bytes, const napi_typedarray_type *view_as = nullptr, size_t count = 0)
+    {
+        if (!ok) return;
+        napi_value ab;
+        PoolTag *tag = new PoolTag{b.size, b.pin};
+        if (napi_create_external_arraybuffer(env, b.p, bytes, pool_free_cb, tag, &ab) != napi_ok) {
+            delete tag;
+            ok = false;
+            return;
+        }
+        int64_t total = 0;
+        napi_adjust_external_memory(env, reply_weight(b.size), &total);
+        b.p = nullptr;   // owned by the ArrayBuffer now
+        if (view_as) view(name, *view_as, ab, 0, count);
+        else set(name, ab);
+    }
+};
+const napi_typedarray_type kAsU8 = napi_uint8_array, kAsF64 = napi_float64_array;
+
+// render's reply, and renderIndex's: the W x n image under `name` (as `bytes` bytes, or the Uint8Array of them), the gauges, the
+// histograms, `stages` (take_us, native_us) if given, and the dBfs range
+Reply image_reply(napi_env env, ImageBuffers &b, const char *name, bool as_u8, size_t bytes, size_t W, const double *stages)
+{
+    Reply r(env);
+    r.block(name, b.image, bytes, as_u8 ? &kAsU8 : nullptr, bytes);
+    r.gauges(b, W);
+    r.hist("c_hist", b.c_hist);
+    r.hist("cB_hist", b.cb_hist);
+    if (stages) r.doubles("stages", {{"take_us", stages[0]}, {"native_us", stages[1]}});
+    r.doubles(nullptr, {{"dBfs_min", b.minmax[0]}, {"dBfs_max", b.minmax[1]}});
+    return r;
+}
+
+inline size_t at_least_0(int32_t v) { return v > 0 ? (size_t)v : 0; }
+
+// ---- render, renderNamed, groupRender: (handle, req, cb) / ...Sync(handle, req) ------------------------------------------------------------
+// req: {format: int, buffer, n, windowc, block_norm, gain, range, lut, width, channelMode, waterfall, detector} - or, named, {format,
+// window, cmap: strings, buffer, n, gain, range, width, channelMode, waterfall, detector} - plus `gather` on a group handle.  The
+// numbers are read unchecked: one that is no number keeps the value read before it, and the library refuses what it cannot render.
+struct RenderJob : JobBase {
+    Settings set;
+    Capture cap;
+    // a request by option names (renderNamed): the library evaluates taper and colour map itself
+    bool named = false;
+    std::string nformat, nwindow, ncmap;
+    sp_group *group = nullptr;                  // a group handle's job
+    int32_t gather = SP_GROUP_GATHER_DEVICE;    // ... and where its strips meet (req.gather: 'device' | 'host')
+    std::string transport, note;
+    double t_render = 0, t_gather = 0, t_download = 0;
+    // where the job's time went on the worker thread (microseconds): reply buffers from the pool, everything else
+    double stages[2] = {0, 0};
+    ImageBuffers out;
+    void run() override;
+    void call(sp_reply *r);
+    napi_value result(napi_env env) override;
+};
+
+bool parse_request(napi_env env, napi_value handle, napi_value req, RenderJob *j, bool named)
+{
+    if (!(j->owner = read_handle(env, handle, nullptr))) return false;
+    j->group = j->owner->g;
+    sp_request &q = j->set.req;
+    napi_value v;
+    int32_t i32 = 0;
+    j->named = named;
+    if (named) {
+        j->nformat = get_string(env, req, "format");
+        j->nwindow = get_string(env, req, "window");
+        j->ncmap = get_string(env, req, "cmap");
+    } else {
+        get_named(env, req, "format", &v); napi_get_value_int32(env, v, &i32); q.format = i32;
+    }
+    get_named(env, req, "n", &v); napi_get_value_int32(env, v, &i32); q.n = i32;
+    get_named(env, req, "width", &v); napi_get_value_int32(env, v, &i32); j->cap.width = i32;
+    if (j->group && get_string(env, req, "gather") == "host") j->gather = SP_GROUP_GATHER_HOST;
+    q.channel_mode = get_bool(env, req, "channelMode");
+    q.waterfall = get_bool(env, req, "waterfall");
+    if (!read_detector(env, req, &q.detector)) return false;
+    q.block_norm = get_double(env, req, "block_norm");
+    q.gain = get_double(env, req, "gain");
+    q.range = get_double(env, req, "range");
+    if (!read_buffer(env, req, &j->cap)) return false;
+    if (named) {
+        int32_t lut_len = 0;
+        sp_named_resolve(j->nwindow.c_str(), j->ncmap.c_str(), nullptr, nullptr, &lut_len);   // sizes the reply's c_hist
+        q.lut_len = lut_len;
+        return true;
+    }
+    if (!read_windowc(env, req, &j->set) || !read_lut(env, req, &j->set, 0, "lut must be a Uint8Array") || !window_covers_n(env, j->set)) return false;
+    j->set.bind();
+    return true;
+}
+
+void RenderJob::run()
+{
+    const double t0 = now_us();
+    sp_reply r{};
+    const bool taken = out.take(4, at_least_0(cap.width), at_least_0(set.req.n), at_least_0(set.req.lut_len), &r);
+    r.rgba = out.image.p;
+    stages[0] = now_us() - t0;
+    if (taken) call(&r);
+    else no_memory();
+    stages[1] = now_us() - t0 - stages[0];
+}
+
+void RenderJob::call(sp_reply *r)
+{
+    const sp_request &q = set.req;
+    if (group) {
+        status = sp_group_render_ex(group, &q, cap.bytes, cap.nbytes, cap.width, r, gather);
+        if (status != SP_OK) error = sp_group_last_error(group);
+        // (read here, on the worker thread that owns the group for the duration of the job)
+        transport = sp_group_transport(group);
+        note = sp_group_transport_note(group);
+        sp_group_last_timings(group, &t_render, &t_gather, &t_download);
+        return;
+    }
+    if (!named) return finish(sp_render(owner->c, &q, cap.bytes, cap.nbytes, cap.width, r));
+    sp_named_request nr{};
+    nr.format = nformat.c_str();
+    nr.window = nwindow.c_str();
+    nr.cmap = ncmap.c_str();
+    nr.n = q.n;
+    nr.channel_mode = q.channel_mode;
+    nr.waterfall = q.waterfall;
+    nr.gain = q.gain;
+    nr.range = q.range;
+    finish(sp_render_named_ex(owner->c, &nr, q.detector, cap.bytes, cap.nbytes, cap.width, r));
+}
+
+napi_value RenderJob::result(napi_env env)
+{
+    const size_t W = at_least_0(cap.width);
+    Reply r = image_reply(env, out, "rgba", false, 4 * W * (size_t)set.req.n, W, stages);
+    if (group) {
+        const int members = sp_group_size(group);
+        r.ints({{"members", members}, {"sliceWidth", members > 0 ? cap.width / members : 0}});
+        r.string("transport", transport);
+        r.string("transportNote", note);
+        r.doubles("timings", {{"render_ms", t_render}, {"gather_ms", t_gather}, {"download_ms", t_download}});
+    }
+    return r.done();
+}
+
+template <bool Named, bool Async>
+napi_value Render(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    RenderJob *j = new RenderJob;
+    if (!parse_request(env, argv[0], argv[1], j, Named)) { free_job(env, j); return nullptr; }
+    if (!Async) return run_sync(env, j);
+    napi_value buf = nullptr;   // (left null, it fails the queueing)
+    napi_get_named_property(env, argv[1], "buffer", &buf);
+    return queue_async(env, j, {argv[2], argv[0], buf}, "spectroplot_hip.render", "could not queue the render");
+}
+
+// ---- batches: renderBatch(handle, req, [{buffer, width}], cb) / renderBatchSync(handle, req, items) -------------------------------
+// req is render's request without buffer and width; every item gets its own reply, shaped as render's (sp_render_batch).  Every
+// value is read with its status checked: a missing or non-numeric field throws instead of leaving a stale value behind.
+struct BatchJob : JobBase {
+    Settings set;
+    struct Item {
+        Capture cap;
+        ImageBuffers out;
+    };
+    std::deque<Item> items;
+    void run() override;
+    napi_value result(napi_env env) override;
+};
+
+bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value items, BatchJob *b)
+{
+    if (!(b->owner = read_handle(env, handle, "renderBatch"))) return false;
+    sp_request &q = b->set.req;
+    if (!checked_int32(env, req, "format", &q.format) || !checked_int32(env, req, "n", &q.n)) return false;
+    if (!checked_bool(env, req, "channelMode", &q.channel_mode) || !checked_bool(env, req, "waterfall", &q.waterfall)) return false;
+    if (!read_detector(env, req, &q.detector)) return false;   // (a peak batch is refused by the library: SP_ERR_UNSUPPORTED)
+    if (!checked_number(env, req, "block_norm", &q.block_norm) || !checked_number(env, req, "gain", &q.gain)) return false;
+    if (!checked_number(env, req, "range", &q.range)) return false;
+    if (!read_windowc(env, req, &b->set) || !window_covers_n(env, b->set) || !read_lut(env, req, &b->set, 0, "lut must be a Uint8Array")) return false;
+    b->set.bind();
     bool is_array = false;
     uint32_t count = 0;
     if (napi_is_array(env, items, &is_array) != napi_ok || !is_array || napi_get_array_length(env, items, &count) != napi_ok) {
@@ -761,646 +892,343 @@ bool parse_batch(napi_env env, napi_value handle, napi_value req, napi_value ite
         return false;
     }
     for (uint32_t k = 0; k < count; k++) {
-        napi_value it, buf;
+        napi_value it;
         napi_valuetype t;
         if (napi_get_element(env, items, k, &it) != napi_ok || napi_typeof(env, it, &t) != napi_ok || t != napi_object) {
             napi_throw_type_error(env, nullptr, "items must be an array of {buffer, width}");
             return false;
         }
-        Job *j = new Job;
-        b->items.push_back(j);
-        j->owner = b->owner;
-        j->ctx = b->owner->c;
-        j->req = b->req;
-        if (!checked_int32(env, it, "width", &j->width)) return false;
-        if (j->width < 0) {
+        b->items.emplace_back();
+        Capture &c = b->items.back().cap;
+        if (!checked_int32(env, it, "width", &c.width)) return false;
+        if (c.width < 0) {
             napi_throw_range_error(env, nullptr, "width must not be negative");
             return false;
         }
-        if (napi_get_named_property(env, it, "buffer", &buf) != napi_ok || napi_get_arraybuffer_info(env, buf, &data, &len) != napi_ok) {
-            napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
-            return false;
-        }
-        j->bytes = (const uint8_t *)data;
-        j->nbytes = len;
+        if (!read_buffer(env, it, &c)) return false;
     }
     return true;
 }
 
-void run_batch(BatchJob *b)
+void BatchJob::run()
 {
-    std::vector<sp_batch_item> items(b->items.size());
-    for (size_t k = 0; k < b->items.size(); k++) {
-        Job *j = b->items[k];
-        const size_t W = (size_t)j->width, n = (size_t)j->req.n;
-        j->rgba_size = 4 * W * n + 1;
-        j->rgba = (uint8_t *)g_pool.take(j->rgba_size, &j->rgba_pin);
-        j->gmin = (uint8_t *)calloc(W + 1, 1);
-        j->gmax = (uint8_t *)calloc(W + 1, 1);
-        j->gamp = (uint8_t *)calloc(W + 1, 1);
-        j->c_hist.assign(j->req.lut_len > 0 ? (size_t)j->req.lut_len : 0, 0);
-        j->cb_hist.assign(SP_CB_HIST_SIZE, 0);
-        if (!j->rgba || !j->gmin || !j->gmax || !j->gamp) {
-            b->status = SP_ERR_NOMEM;
-            b->error = "out of host memory";
-            return;
-        }
-        sp_batch_item &it = items[k];
-        it.bytes = j->bytes;
-        it.nbytes = j->nbytes;
-        it.width = j->width;
-        it.reply.rgba = j->rgba; it.reply.gauge_mins = j->gmin; it.reply.gauge_maxs = j->gmax; it.reply.gauge_amps = j->gamp;
-        it.reply.c_hist = j->c_hist.data(); it.reply.cb_hist = j->cb_hist.data(); it.reply.dbfs_minmax = j->minmax;
+    std::vector<sp_batch_item> its(items.size());
+    for (size_t k = 0; k < items.size(); k++) {
+        Item &j = items[k];
+        sp_batch_item &it = its[k];
+        if (!j.out.take(4, (size_t)j.cap.width, (size_t)set.req.n, at_least_0(set.req.lut_len), &it.reply)) return no_memory();
+        it.reply.rgba = j.out.image.p;
+        it.bytes = j.cap.bytes;
+        it.nbytes = j.cap.nbytes;
+        it.width = j.cap.width;
     }
-    b->status = sp_render_batch(b->owner->c, &b->req, items.data(), (int32_t)items.size());
-    if (b->status != SP_OK) b->error = sp_last_error(b->owner->c);
+    finish(sp_render_batch(owner->c, &set.req, its.data(), (int32_t)its.size()));
 }
 
-napi_value batch_result(napi_env env, BatchJob *b)
+napi_value BatchJob::result(napi_env env)
 {
     napi_value arr;
-    if (napi_create_array_with_length(env, b->items.size(), &arr) != napi_ok) return nullptr;
-    for (size_t k = 0; k < b->items.size(); k++) {
-        napi_value r = make_reply(env, b->items[k]);
+    if (napi_create_array_with_length(env, items.size(), &arr) != napi_ok) return nullptr;
+    const double no_stages[2] = {0, 0};   // (an item's reply has render's properties)
+    for (size_t k = 0; k < items.size(); k++) {
+        const size_t W = (size_t)items[k].cap.width;
+        napi_value r = image_reply(env, items[k].out, "rgba", false, 4 * W * (size_t)set.req.n, W, no_stages).done();
         if (!r || napi_set_element(env, arr, (uint32_t)k, r) != napi_ok) return nullptr;
     }
     return arr;
 }
 
-napi_value RenderBatchSync(napi_env env, napi_callback_info info)
-{
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 3) {
-        napi_throw_type_error(env, nullptr, "renderBatchSync(handle, request, items)");
-        return nullptr;
-    }
-    BatchJob *b = new BatchJob;
-    if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_job(env, b); return nullptr; }
-    return run_sync(env, b);
-}
-
+template <bool Async>
 napi_value RenderBatch(napi_env env, napi_callback_info info)
 {
     size_t argc = 4;
     napi_value argv[4];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     napi_valuetype t = napi_undefined;
-    if (argc < 4 || napi_typeof(env, argv[3], &t) != napi_ok || t != napi_function) {
-        napi_throw_type_error(env, nullptr, "renderBatch(handle, request, items, callback)");
+    if (argc < (Async ? 4 : 3) || (Async && (napi_typeof(env, argv[3], &t) != napi_ok || t != napi_function))) {
+        napi_throw_type_error(env, nullptr, Async ? "renderBatch(handle, request, items, callback)" : "renderBatchSync(handle, request, items)");
         return nullptr;
     }
     BatchJob *b = new BatchJob;
     if (!parse_batch(env, argv[0], argv[1], argv[2], b)) { free_job(env, b); return nullptr; }
+    if (!Async) return run_sync(env, b);
     // (the items array keeps their buffers alive)
     return queue_async(env, b, {argv[3], argv[0], argv[2]}, "spectroplot_hip.renderBatch", "could not queue the batch");
 }
 
-// ---- checked requests: traces, indexed images, persistence spectrum ----------------------------------------------------------------------
+// ---- checked requests: every kind below -----------------------------------------------------------------------------------------------------
 // Every value of such a request is read into a variable of its own with its status checked, as for a batch: a request that cannot be
-// read throws and never renders.  What differs between the kinds: the names in their texts, and whether the request carries a picture
-// (`waterfall`, `detector`, `lut`); one without gets the sample detector and a 2-entry map (the plan wants one).
+// read throws and never renders.  The shared fields are {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} and,
+// if the kind carries a picture, {waterfall, detector, lut}; a kind without one gets the sample detector and a 2-entry map (the plan
+// wants one).  A kind is a struct with
+//   kind      its entry point's name (the usage lines, the async resource and the refusal of a group are built from it), the noun of
+//             "could not queue the ... request", and whether it carries a picture
+//   read()    the readers of its own request fields, behind the shared ones
+//   run()     its reply arrays and its library call, on the worker thread
+//   result()  the properties of its reply
+// and the members these use; its entry points are Checked<Kind, false> (sync) and Checked<Kind, true> in Init's table.
 struct CheckedKind {
-    const char *who;   // in "<who> takes a context handle, not a group"
+    const char *name, *noun;
     bool picture;
-    const char *sync_usage, *async_usage, *resource, *could_not_queue;
 };
 
-bool parse_checked(napi_env env, napi_value handle, napi_value req, Job *t, const CheckedKind &kind)
+struct CheckedRequest : JobBase {   // what parse_checked fills
+    Settings set;
+    Capture cap;
+};
+
+bool parse_checked(napi_env env, napi_value handle, napi_value req, CheckedRequest *t, const CheckedKind &kind)
 {
-    void *p = nullptr;
-    if (napi_get_value_external(env, handle, &p) != napi_ok || !p) {
-        napi_throw_type_error(env, nullptr, "context handle expected");
-        return false;
-    }
-    t->owner = (Ctx *)p;
-    if (t->owner->closed || !t->owner->c) {
-        napi_throw_error(env, nullptr, t->owner->g ? (std::string(kind.who) + " takes a context handle, not a group").c_str() : "context has been destroyed");
-        return false;
-    }
-    t->ctx = t->owner->c;
-    if (!checked_int32(env, req, "format", &t->req.format) || !checked_int32(env, req, "n", &t->req.n)) return false;
-    if (!checked_int32(env, req, "width", &t->width)) return false;
-    if (!checked_bool(env, req, "channelMode", &t->req.channel_mode)) return false;
-    t->req.detector = SP_DETECTOR_SAMPLE;
-    if (kind.picture && (!checked_bool(env, req, "waterfall", &t->req.waterfall) || !read_detector(env, req, &t->req.detector))) return false;
-    if (!checked_number(env, req, "block_norm", &t->req.block_norm) || !checked_number(env, req, "gain", &t->req.gain)) return false;
-    if (!checked_number(env, req, "range", &t->req.range)) return false;
-    if (t->req.n < 1 || t->width < 0) {
+    if (!(t->owner = read_handle(env, handle, kind.name))) return false;
+    sp_request &q = t->set.req;
+    if (!checked_int32(env, req, "format", &q.format) || !checked_int32(env, req, "n", &q.n)) return false;
+    if (!checked_int32(env, req, "width", &t->cap.width)) return false;
+    if (!checked_bool(env, req, "channelMode", &q.channel_mode)) return false;
+    q.detector = SP_DETECTOR_SAMPLE;
+    if (kind.picture && (!checked_bool(env, req, "waterfall", &q.waterfall) || !read_detector(env, req, &q.detector))) return false;
+    if (!checked_number(env, req, "block_norm", &q.block_norm) || !checked_number(env, req, "gain", &q.gain)) return false;
+    if (!checked_number(env, req, "range", &q.range)) return false;
+    if (q.n < 1 || t->cap.width < 0) {
         napi_throw_range_error(env, nullptr, "n must be positive and width must not be negative");
         return false;
     }
-    napi_value v_win, v_lut, v_buf, ab_win, ab_lut;
-    napi_typedarray_type tt_win, tt_lut;
-    size_t len_win = 0, off_win = 0, len_lut = 0, off_lut = 0, len_buf = 0;
-    void *data_win = nullptr, *data_lut = nullptr, *data_buf = nullptr;
-    if (napi_get_named_property(env, req, "windowc", &v_win) != napi_ok
-        || napi_get_typedarray_info(env, v_win, &tt_win, &len_win, &data_win, &ab_win, &off_win) != napi_ok || tt_win != napi_float64_array) {
-        napi_throw_type_error(env, nullptr, "windowc must be a Float64Array");
-        return false;
-    }
-    if (len_win < (size_t)t->req.n) {
-        napi_throw_range_error(env, nullptr, "windowc is shorter than n");
-        return false;
-    }
-    t->window.assign((const double *)data_win, (const double *)data_win + len_win);
-    t->lut = {0, 0, 0, 255, 255, 255};   // (a request without a picture has no colours; the plan wants a map)
-    if (kind.picture) {
-        if (napi_get_named_property(env, req, "lut", &v_lut) != napi_ok
-            || napi_get_typedarray_info(env, v_lut, &tt_lut, &len_lut, &data_lut, &ab_lut, &off_lut) != napi_ok
-            || (tt_lut != napi_uint8_array && tt_lut != napi_uint8_clamped_array) || len_lut < 3) {
-            napi_throw_type_error(env, nullptr, "lut must be a Uint8Array of r, g, b triples");
-            return false;
-        }
-        t->lut.assign((const uint8_t *)data_lut, (const uint8_t *)data_lut + len_lut);
-    }
-    if (napi_get_named_property(env, req, "buffer", &v_buf) != napi_ok || napi_get_arraybuffer_info(env, v_buf, &data_buf, &len_buf) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "buffer must be an ArrayBuffer");
-        return false;
-    }
-    t->bytes = (const uint8_t *)data_buf;
-    t->nbytes = len_buf;
-    t->req.lut_len = (int32_t)(t->lut.size() / 3);
-    t->req.windowc = t->window.data();
-    t->req.lut_rgb = t->lut.data();
+    if (!read_windowc(env, req, &t->set) || !window_covers_n(env, t->set)) return false;
+    t->set.lut = {0, 0, 0, 255, 255, 255};   // (a request without a picture has no colours; the plan wants a map)
+    if (kind.picture && !read_lut(env, req, &t->set, 3, "lut must be a Uint8Array of r, g, b triples")) return false;
+    if (!read_buffer(env, req, &t->cap)) return false;
+    t->set.bind();
     return true;
 }
 
-// The entry pair of a checked kind whose job is a J: <kind>Sync(handle, req) and <kind>(handle, req, cb).
-template <typename J>
-napi_value checked_sync(napi_env env, napi_callback_info info, const CheckedKind &kind)
-{
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 2) {
-        napi_throw_type_error(env, nullptr, kind.sync_usage);
-        return nullptr;
-    }
-    J *t = new J;
-    if (!parse_checked(env, argv[0], argv[1], t, kind) || !t->parse_own(env, argv[1])) { free_job(env, t); return nullptr; }
-    return run_sync(env, t);
-}
+template <typename K>
+struct CheckedJob : CheckedRequest {
+    K k;
+    void run() override { k.run(*this); }
+    napi_value result(napi_env env) override { return k.result(env, *this); }
+};
 
-template <typename J>
-napi_value checked_async(napi_env env, napi_callback_info info, const CheckedKind &kind)
+template <typename K, bool Async>
+napi_value Checked(napi_env env, napi_callback_info info)
 {
+    const std::string name = K::kind.name;
     size_t argc = 3;
     napi_value argv[3];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     napi_valuetype ty = napi_undefined;
-    if (argc < 3 || napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function) {
-        napi_throw_type_error(env, nullptr, kind.async_usage);
+    if (argc < (Async ? 3 : 2) || (Async && (napi_typeof(env, argv[2], &ty) != napi_ok || ty != napi_function))) {
+        napi_throw_type_error(env, nullptr, (Async ? name + "(handle, request, callback)" : name + "Sync(handle, request)").c_str());
         return nullptr;
     }
-    J *t = new J;
-    if (!parse_checked(env, argv[0], argv[1], t, kind) || !t->parse_own(env, argv[1])) { free_job(env, t); return nullptr; }
+    CheckedJob<K> *t = new CheckedJob<K>;
+    if (!parse_checked(env, argv[0], argv[1], t, K::kind) || !t->k.read(env, argv[1])) { free_job(env, t); return nullptr; }
+    if (!Async) return run_sync(env, t);
     napi_value buf = nullptr;   // (left null, it fails the queueing)
     napi_get_named_property(env, argv[1], "buffer", &buf);
-    return queue_async(env, t, {argv[2], argv[0], buf}, kind.resource, kind.could_not_queue);
+    return queue_async(env, t, {argv[2], argv[0], buf}, ("spectroplot_hip." + name).c_str(),
+                       ("could not queue the " + std::string(K::kind.noun) + " request").c_str());
 }
 
-// ---- traces: renderTraces(handle, req, cb) / renderTracesSync(handle, req) ---------------------------------------------------------
-// req: {format, n, width, channelMode, block_norm, gain, range, windowc, buffer} -> {trace_min, trace_max}, two Float64Array(n) in image
-// row order (sp_render_traces).
-const CheckedKind kTraces{"renderTraces", false, "renderTracesSync(handle, request)", "renderTraces(handle, request, callback)",
-                          "spectroplot_hip.renderTraces", "could not queue the traces request"};
+// The library call of every checked kind begins with these
+#define SP_CALL_HEAD(j) (j).owner->c, &(j).set.req, (j).cap.bytes, (j).cap.nbytes, (j).cap.width
 
-struct TracesJob : Job {
+// traces: the shared fields -> {trace_min, trace_max}, two Float64Array(n) in image row order over one ArrayBuffer (sp_render_traces)
+struct Traces {
+    static constexpr CheckedKind kind{"renderTraces", "traces", false};
     std::vector<double> out;   // trace_min, then trace_max
-    void run() override;
-    napi_value result(napi_env env) override;
+    bool read(napi_env, napi_value) { return true; }
+    void run(CheckedRequest &j)
+    {
+        const size_t n = (size_t)j.set.req.n;
+        out.assign(2 * n, 0.0);
+        j.finish(sp_render_traces(SP_CALL_HEAD(j), out.data(), out.data() + n));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        const size_t n = (size_t)j.set.req.n;
+        Reply r(env);
+        napi_value ab = r.copy_of(out.data(), 2 * n * 8);
+        r.view("trace_min", napi_float64_array, ab, 0, n);
+        r.view("trace_max", napi_float64_array, ab, n * 8, n);
+        return r.done();
+    }
 };
 
-void TracesJob::run()
-{
-    const size_t n = (size_t)req.n;
-    out.assign(2 * n, 0.0);
-    status = sp_render_traces(ctx, &req, bytes, nbytes, width, out.data(), out.data() + n);
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value TracesJob::result(napi_env env)
-{
-    const size_t n = (size_t)req.n;
-    napi_value obj, ab, ta;
-    void *data = nullptr;
-    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, 2 * n * 8, &data, &ab) != napi_ok) return nullptr;
-    memcpy(data, out.data(), 2 * n * 8);
-    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "trace_min", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_typedarray(env, napi_float64_array, n, ab, n * 8, &ta) != napi_ok || napi_set_named_property(env, obj, "trace_max", ta) != napi_ok)
-        return nullptr;
-    return obj;
-}
-
-napi_value RenderTracesSync(napi_env env, napi_callback_info info) { return checked_sync<TracesJob>(env, info, kTraces); }
-napi_value RenderTraces(napi_env env, napi_callback_info info) { return checked_async<TracesJob>(env, info, kTraces); }
-
-// ---- indexed images: renderIndex(handle, req, cb) / renderIndexSync(handle, req) -------------------------------------------------------
-// req as for render plus `detector` -> render's reply with `index` - a Uint8Array(width * n), one colour-index byte per pixel in the RGBA
-// image's pixel order, in a page-locked block of the reply pool - in place of `rgba` (sp_render_index).
-const CheckedKind kIndex{"renderIndex", true, "renderIndexSync(handle, request)", "renderIndex(handle, request, callback)",
-                         "spectroplot_hip.renderIndex", "could not queue the indexed request"};
-
-struct IndexJob : Job {
-    void run() override;
-    napi_value result(napi_env env) override;
+// indexed images: req as for render -> render's reply with `index` - a Uint8Array(width * n), one colour-index byte per pixel in the
+// RGBA image's pixel order, in a page-locked block of the reply pool - in place of `rgba`, and without `stages` (sp_render_index)
+struct Index {
+    static constexpr CheckedKind kind{"renderIndex", "indexed", true};
+    ImageBuffers out;
+    bool read(napi_env, napi_value) { return true; }
+    void run(CheckedRequest &j)
+    {
+        sp_reply r{};
+        if (!out.take(1, (size_t)j.cap.width, (size_t)j.set.req.n, (size_t)j.set.req.lut_len, &r)) return j.no_memory();
+        j.finish(sp_render_index(SP_CALL_HEAD(j), &r, out.image.p));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        const size_t W = (size_t)j.cap.width;
+        return image_reply(env, out, "index", true, W * (size_t)j.set.req.n, W, nullptr).done();
+    }
 };
 
-void IndexJob::run()
-{
-    const size_t W = (size_t)width, n = (size_t)req.n;
-    rgba_size = W * n + 1;                                   // (Job's image block: here one byte per pixel)
-    rgba = (uint8_t *)g_pool.take(rgba_size, &rgba_pin);
-    gmin = (uint8_t *)calloc(W + 1, 1);
-    gmax = (uint8_t *)calloc(W + 1, 1);
-    gamp = (uint8_t *)calloc(W + 1, 1);
-    c_hist.assign((size_t)req.lut_len, 0);
-    cb_hist.assign(SP_CB_HIST_SIZE, 0);
-    if (!rgba || !gmin || !gmax || !gamp) {
-        status = SP_ERR_NOMEM;
-        error = "out of host memory";
-        return;
-    }
-    sp_reply r{};
-    r.gauge_mins = gmin; r.gauge_maxs = gmax; r.gauge_amps = gamp;
-    r.c_hist = c_hist.data(); r.cb_hist = cb_hist.data(); r.dbfs_minmax = minmax;
-    status = sp_render_index(ctx, &req, bytes, nbytes, width, &r, rgba);
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value IndexJob::result(napi_env env)
-{
-    const size_t W = (size_t)width, n = (size_t)req.n;
-    napi_value out, ab, ta, v;
-    if (napi_create_object(env, &out) != napi_ok) return nullptr;
-    PoolTag *tag = new PoolTag{rgba_size, rgba_pin};
-    if (napi_create_external_arraybuffer(env, rgba, W * n, pool_free_cb, tag, &ab) != napi_ok) {
-        delete tag;
-        return nullptr;
-    }
-    int64_t total = 0;
-    napi_adjust_external_memory(env, reply_weight(rgba_size), &total);
-    rgba = nullptr;   // owned by the ArrayBuffer now
-    if (napi_create_typedarray(env, napi_uint8_array, W * n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "index", ta) != napi_ok)
-        return nullptr;
-    const auto put_gauge = [&](const char *name, uint8_t *&p) {
-        napi_value gab;
-        if (napi_create_external_arraybuffer(env, p, W, free_cb, nullptr, &gab) != napi_ok) return false;
-        p = nullptr;
-        return napi_set_named_property(env, out, name, gab) == napi_ok;
-    };
-    if (!put_gauge("gauge_mins", gmin) || !put_gauge("gauge_maxs", gmax) || !put_gauge("gauge_amps", gamp)) return nullptr;
-    const auto put_hist = [&](const char *name, const std::vector<uint64_t> &h) {
-        napi_value hab, hta;
-        void *data = nullptr;
-        if (napi_create_arraybuffer(env, h.size() * 8, &data, &hab) != napi_ok) return false;
-        for (size_t i = 0; i < h.size(); i++) ((double *)data)[i] = (double)h[i];
-        return napi_create_typedarray(env, napi_float64_array, h.size(), hab, 0, &hta) == napi_ok
-               && napi_set_named_property(env, out, name, hta) == napi_ok;
-    };
-    if (!put_hist("c_hist", c_hist) || !put_hist("cB_hist", cb_hist)) return nullptr;
-    if (napi_create_double(env, minmax[0], &v) != napi_ok || napi_set_named_property(env, out, "dBfs_min", v) != napi_ok) return nullptr;
-    if (napi_create_double(env, minmax[1], &v) != napi_ok || napi_set_named_property(env, out, "dBfs_max", v) != napi_ok) return nullptr;
-    return out;
-}
-
-napi_value RenderIndexSync(napi_env env, napi_callback_info info) { return checked_sync<IndexJob>(env, info, kIndex); }
-napi_value RenderIndex(napi_env env, napi_callback_info info) { return checked_async<IndexJob>(env, info, kIndex); }
-
-// ---- persistence spectrum: renderDensity(handle, req, cb) / renderDensitySync(handle, req) ----------------------------------------------
-// req as for renderIndex -> {density, n, lutLen, width}: density a Uint32Array(n * lutLen), row y at y * lutLen - how many of the
-// request's frames showed colour index g in image row y (sp_render_density).
-const CheckedKind kDensity{"renderDensity", true, "renderDensitySync(handle, request)", "renderDensity(handle, request, callback)",
-                           "spectroplot_hip.renderDensity", "could not queue the density request"};
-
-struct DensityJob : IndexJob {
+// persistence spectrum: req as for renderIndex -> {density, n, lutLen, width}: density a Uint32Array(n * lutLen), row y at y * lutLen -
+// how many of the request's frames showed colour index g in image row y (sp_render_density)
+struct Density {
+    static constexpr CheckedKind kind{"renderDensity", "density", true};
     std::vector<uint32_t> counts;
-    void run() override;
-    napi_value result(napi_env env) override;
+    bool read(napi_env, napi_value) { return true; }
+    void run(CheckedRequest &j)
+    {
+        const sp_request &q = j.set.req;
+        // (a map the library refuses gets no array: its n * lut_len could be anything)
+        if (q.lut_len >= 1 && q.lut_len <= 256 && !j.allocated([&] { counts.assign((size_t)q.n * (size_t)q.lut_len, 0u); })) return;
+        uint32_t none = 0;
+        j.finish(sp_render_density(SP_CALL_HEAD(j), or_placeholder(counts, &none)));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        Reply r(env);
+        r.array("density", napi_uint32_array, counts.data(), counts.size());
+        r.ints({{"n", j.set.req.n}, {"lutLen", j.set.req.lut_len}, {"width", j.cap.width}});
+        return r.done();
+    }
 };
 
-void DensityJob::run()
-{
-    // (a map the library refuses gets no array: its n * lut_len could be anything)
-    if (req.lut_len >= 1 && req.lut_len <= 256) {
-        try {
-            counts.assign((size_t)req.n * (size_t)req.lut_len, 0u);
-        } catch (const std::bad_alloc &) {
-            status = SP_ERR_NOMEM;
-            error = "out of host memory";
-            return;
-        }
-    }
-    uint32_t none = 0;
-    status = sp_render_density(ctx, &req, bytes, nbytes, width, counts.empty() ? &none : counts.data());
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value DensityJob::result(napi_env env)
-{
-    napi_value out, ab, ta, v;
-    void *data = nullptr;
-    if (napi_create_object(env, &out) != napi_ok || napi_create_arraybuffer(env, counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
-    memcpy(data, counts.data(), counts.size() * 4);
-    if (napi_create_typedarray(env, napi_uint32_array, counts.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "density", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, out, "n", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.lut_len, &v) != napi_ok || napi_set_named_property(env, out, "lutLen", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, out, "width", v) != napi_ok) return nullptr;
-    return out;
-}
-
-napi_value RenderDensitySync(napi_env env, napi_callback_info info) { return checked_sync<DensityJob>(env, info, kDensity); }
-napi_value RenderDensity(napi_env env, napi_callback_info info) { return checked_async<DensityJob>(env, info, kDensity); }
-
-// ---- power plane: renderPower(handle, req, cb) / renderPowerSync(handle, req) ----------------------------------------------------------
-// req as for renderTraces plus `db` (boolean) -> {power, width, n}: power a Float64Array(width * n), frame-major - |X|^2 of frame x at
-// image row y in power[x * n + y], or its dB plane with db - in a page-locked block of the reply pool (sp_render_power).
-const CheckedKind kPower{"renderPower", false, "renderPowerSync(handle, request)", "renderPower(handle, request, callback)",
-                         "spectroplot_hip.renderPower", "could not queue the power request"};
-
-struct PowerJob : Job {
+// power plane: the shared fields plus `db` (boolean) -> {power, width, n}: power a Float64Array(width * n), frame-major - |X|^2 of frame
+// x at image row y in power[x * n + y], or its dB plane with db - in a page-locked block of the reply pool (sp_render_power)
+struct Power {
+    static constexpr CheckedKind kind{"renderPower", "power", false};
     int32_t db = 0;
-    bool parse_own(napi_env env, napi_value r) override { return checked_bool(env, r, "db", &db); }
-    void run() override;
-    napi_value result(napi_env env) override;
+    PoolBlock out;
+    bool read(napi_env env, napi_value req) { return read_db(env, req, &db); }
+    void run(CheckedRequest &j)
+    {
+        if (!out.take((size_t)j.cap.width * (size_t)j.set.req.n * sizeof(double) + 8)) return j.no_memory();
+        j.finish(sp_render_power(SP_CALL_HEAD(j), db, (double *)out.p));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        const size_t count = (size_t)j.cap.width * (size_t)j.set.req.n;
+        Reply r(env);
+        r.block("power", out, count * sizeof(double), &kAsF64, count);
+        r.ints({{"width", j.cap.width}, {"n", j.set.req.n}});
+        return r.done();
+    }
 };
 
-void PowerJob::run()
-{
-    const size_t W = (size_t)width, n = (size_t)req.n;
-    rgba_size = W * n * sizeof(double) + 8;                  // (Job's image block: here one f64 per frame and bin)
-    rgba = (uint8_t *)g_pool.take(rgba_size, &rgba_pin);
-    if (!rgba) {
-        status = SP_ERR_NOMEM;
-        error = "out of host memory";
-        return;
-    }
-    status = sp_render_power(ctx, &req, bytes, nbytes, width, db, (double *)rgba);
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value PowerJob::result(napi_env env)
-{
-    const size_t W = (size_t)width, n = (size_t)req.n;
-    napi_value out, ab, ta, v;
-    if (napi_create_object(env, &out) != napi_ok) return nullptr;
-    PoolTag *tag = new PoolTag{rgba_size, rgba_pin};
-    if (napi_create_external_arraybuffer(env, rgba, W * n * sizeof(double), pool_free_cb, tag, &ab) != napi_ok) {
-        delete tag;
-        return nullptr;
-    }
-    int64_t total = 0;
-    napi_adjust_external_memory(env, reply_weight(rgba_size), &total);
-    rgba = nullptr;   // owned by the ArrayBuffer now
-    if (napi_create_typedarray(env, napi_float64_array, W * n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, out, "power", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, out, "width", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, out, "n", v) != napi_ok) return nullptr;
-    return out;
-}
-
-napi_value RenderPowerSync(napi_env env, napi_callback_info info) { return checked_sync<PowerJob>(env, info, kPower); }
-napi_value RenderPower(napi_env env, napi_callback_info info) { return checked_async<PowerJob>(env, info, kPower); }
-
-// ---- exact mean-power trace: renderMean(handle, req, cb) / renderMeanSync(handle, req) -------------------------------------------------
-// req as for renderPower -> {mean, width, n}: mean a Float64Array(n) in image row order - the correctly rounded sum of |X|^2 over the
-// request's frames divided by width, or the dB of it with db (sp_render_mean).
-const CheckedKind kMean{"renderMean", false, "renderMeanSync(handle, request)", "renderMean(handle, request, callback)",
-                        "spectroplot_hip.renderMean", "could not queue the mean request"};
-
-struct MeanJob : PowerJob {
+// exact mean-power trace: req as for renderPower -> {mean, width, n}: mean a Float64Array(n) in image row order - the correctly rounded
+// sum of |X|^2 over the request's frames divided by width, or the dB of it with db (sp_render_mean)
+struct Mean {
+    static constexpr CheckedKind kind{"renderMean", "mean", false};
+    int32_t db = 0;
     std::vector<double> out;
-    void run() override;
-    napi_value result(napi_env env) override;
+    bool read(napi_env env, napi_value req) { return read_db(env, req, &db); }
+    void run(CheckedRequest &j)
+    {
+        out.assign((size_t)j.set.req.n, 0.0);
+        j.finish(sp_render_mean(SP_CALL_HEAD(j), db, out.data()));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        Reply r(env);
+        r.array("mean", napi_float64_array, out.data(), out.size());
+        r.ints({{"width", j.cap.width}, {"n", j.set.req.n}});
+        return r.done();
+    }
 };
 
-void MeanJob::run()
-{
-    out.assign((size_t)req.n, 0.0);
-    status = sp_render_mean(ctx, &req, bytes, nbytes, width, db, out.data());
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value MeanJob::result(napi_env env)
-{
-    const size_t n = (size_t)req.n;
-    napi_value obj, ab, ta, v;
-    void *data = nullptr;
-    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, n * 8, &data, &ab) != napi_ok) return nullptr;
-    memcpy(data, out.data(), n * 8);
-    if (napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "mean", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
-    return obj;
-}
-
-napi_value RenderMeanSync(napi_env env, napi_callback_info info) { return checked_sync<MeanJob>(env, info, kMean); }
-napi_value RenderMean(napi_env env, napi_callback_info info) { return checked_async<MeanJob>(env, info, kMean); }
-
-// ---- exact band-power series: renderBandPower(handle, req, cb) / renderBandPowerSync(handle, req) -------------------------------------
-// req as for renderPower plus `bands`, an Int32Array of y0, y1 pairs (half-open ranges of image rows) -> {bands, count, width, n}:
-// bands a Float64Array(count * width), band-major - per band and frame the correctly rounded sum of |X|^2 over the band's rows, or the
-// dB of it with db (sp_render_bandpower).  The library refuses bad bands (status -1) before anything is rendered.
-const CheckedKind kBandPower{"renderBandPower", false, "renderBandPowerSync(handle, request)", "renderBandPower(handle, request, callback)",
-                             "spectroplot_hip.renderBandPower", "could not queue the band-power request"};
-
-struct BandPowerJob : PowerJob {
-    std::vector<int32_t> rows;   // y0, y1 per band
+// exact band-power series: req as for renderPower plus `bands`, an Int32Array of y0, y1 pairs (half-open ranges of image rows) ->
+// {bands, count, width, n}: bands a Float64Array(count * width), band-major - per band and frame the correctly rounded sum of |X|^2 over
+// the band's rows, or the dB of it with db (sp_render_bandpower).  The library refuses bad bands (status -1) before anything is rendered.
+struct BandPower {
+    static constexpr CheckedKind kind{"renderBandPower", "band-power", false};
+    int32_t db = 0;
+    Bands bands;
     std::vector<double> out;
-    bool parse_own(napi_env env, napi_value r) override;
-    void run() override;
-    napi_value result(napi_env env) override;
+    bool read(napi_env env, napi_value req) { return read_db(env, req, &db) && read_bands(env, req, &bands); }
+    void run(CheckedRequest &j)
+    {
+        if (bands.taken() && !j.allocated([&] { out.assign(bands.count() * (size_t)j.cap.width, 0.0); })) return;
+        double none = 0;
+        j.finish(sp_render_bandpower(SP_CALL_HEAD(j), bands.rows.data(), bands.for_library(), db, or_placeholder(out, &none)));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        Reply r(env);
+        r.array("bands", napi_float64_array, out.data(), out.size());
+        r.ints({{"count", (int32_t)bands.count()}, {"width", j.cap.width}, {"n", j.set.req.n}});
+        return r.done();
+    }
 };
 
-bool BandPowerJob::parse_own(napi_env env, napi_value r)
-{
-    if (!PowerJob::parse_own(env, r)) return false;
-    napi_value v, ab;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void *data = nullptr;
-    if (napi_get_named_property(env, r, "bands", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
-        || tt != napi_int32_array || len % 2 != 0) {
-        napi_throw_type_error(env, nullptr, "bands must be an Int32Array of y0, y1 pairs");
-        return false;
+// peak track: req as for renderBandPower -> {rows, peaks, count, width, n}: rows an Int32Array(count * width) and peaks a
+// Float64Array(count * width), band-major - per band and frame the strongest image row that is not a NaN (the smallest among equal ones,
+// -1 where there is none) and its |X|^2 (NaN where there is none), or the dB of it with db (sp_render_track).  The library refuses bad
+// bands (status -1) before anything is rendered.
+struct Track {
+    static constexpr CheckedKind kind{"renderTrack", "track", false};
+    int32_t db = 0;
+    Bands bands;
+    std::vector<int32_t> best;    // the strongest row per band and frame
+    std::vector<double> peaks;    // ... and its power
+    bool read(napi_env env, napi_value req) { return read_db(env, req, &db) && read_bands(env, req, &bands); }
+    void run(CheckedRequest &j)
+    {
+        const size_t count = bands.count() * (size_t)j.cap.width;
+        if (bands.taken() && !j.allocated([&] { peaks.assign(count, 0.0); best.assign(count, 0); })) return;
+        double none = 0;
+        int32_t no_row = 0;
+        j.finish(sp_render_track(SP_CALL_HEAD(j), bands.rows.data(), bands.for_library(), db, or_placeholder(best, &no_row), or_placeholder(peaks, &none)));
     }
-    if (len) rows.assign((const int32_t *)data, (const int32_t *)data + len);
-    return true;
-}
-
-void BandPowerJob::run()
-{
-    const size_t count = rows.size() / 2;
-    if (count <= SP_MAX_BANDS) {   // (more bands than the library takes get no array: it refuses them)
-        try {
-            out.assign(count * (size_t)width, 0.0);
-        } catch (const std::bad_alloc &) {
-            status = SP_ERR_NOMEM;
-            error = "out of host memory";
-            return;
-        }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        Reply r(env);
+        r.array("rows", napi_int32_array, best.data(), best.size());
+        r.array("peaks", napi_float64_array, peaks.data(), peaks.size());
+        r.ints({{"count", (int32_t)bands.count()}, {"width", j.cap.width}, {"n", j.set.req.n}});
+        return r.done();
     }
-    double none = 0;
-    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
-    status = sp_render_bandpower(ctx, &req, bytes, nbytes, width, rows.data(), c, db, out.empty() ? &none : out.data());
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value BandPowerJob::result(napi_env env)
-{
-    napi_value obj, ab, ta, v;
-    void *data = nullptr;
-    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, out.size() * 8, &data, &ab) != napi_ok) return nullptr;
-    if (!out.empty()) memcpy(data, out.data(), out.size() * 8);
-    if (napi_create_typedarray(env, napi_float64_array, out.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "bands", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
-    return obj;
-}
-
-napi_value RenderBandPowerSync(napi_env env, napi_callback_info info) { return checked_sync<BandPowerJob>(env, info, kBandPower); }
-napi_value RenderBandPower(napi_env env, napi_callback_info info) { return checked_async<BandPowerJob>(env, info, kBandPower); }
-
-// ---- peak track: renderTrack(handle, req, cb) / renderTrackSync(handle, req) -------------------------------------------------------------
-// req as for renderBandPower -> {rows, peaks, count, width, n}: rows an Int32Array(count * width) and peaks a Float64Array(count * width),
-// band-major - per band and frame the strongest image row that is not a NaN (the smallest among equal ones, -1 where there is none) and
-// its |X|^2 (NaN where there is none), or the dB of it with db (sp_render_track).  The library refuses bad bands (status -1) before
-// anything is rendered.
-const CheckedKind kTrack{"renderTrack", false, "renderTrackSync(handle, request)", "renderTrack(handle, request, callback)",
-                         "spectroplot_hip.renderTrack", "could not queue the track request"};
-
-struct TrackJob : BandPowerJob {   // (`rows` are the bands, `out` the peaks)
-    std::vector<int32_t> best;     // the strongest row per band and frame
-    void run() override;
-    napi_value result(napi_env env) override;
 };
 
-void TrackJob::run()
-{
-    const size_t count = rows.size() / 2;
-    if (count <= SP_MAX_BANDS) {   // (more bands than the library takes get no arrays: it refuses them)
-        try {
-            out.assign(count * (size_t)width, 0.0);
-            best.assign(count * (size_t)width, 0);
-        } catch (const std::bad_alloc &) {
-            status = SP_ERR_NOMEM;
-            error = "out of host memory";
-            return;
-        }
-    }
-    double none = 0;
-    int32_t no_row = 0;
-    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
-    status = sp_render_track(ctx, &req, bytes, nbytes, width, rows.data(), c, db, best.empty() ? &no_row : best.data(), out.empty() ? &none : out.data());
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value TrackJob::result(napi_env env)
-{
-    napi_value obj, ab, ta, v;
-    void *data = nullptr;
-    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, best.size() * 4, &data, &ab) != napi_ok) return nullptr;
-    if (!best.empty()) memcpy(data, best.data(), best.size() * 4);
-    if (napi_create_typedarray(env, napi_int32_array, best.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "rows", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_arraybuffer(env, out.size() * 8, &data, &ab) != napi_ok) return nullptr;
-    if (!out.empty()) memcpy(data, out.data(), out.size() * 8);
-    if (napi_create_typedarray(env, napi_float64_array, out.size(), ab, 0, &ta) != napi_ok || napi_set_named_property(env, obj, "peaks", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
-    return obj;
-}
-
-napi_value RenderTrackSync(napi_env env, napi_callback_info info) { return checked_sync<TrackJob>(env, info, kTrack); }
-napi_value RenderTrack(napi_env env, napi_callback_info info) { return checked_async<TrackJob>(env, info, kTrack); }
-
-// ---- occupancy counts: renderOccupancy(handle, req, cb) / renderOccupancySync(handle, req) ------------------------------------------------
-// req as for renderBandPower (db is not looked at) plus `threshold`, a Float64Array(n): one power per image row -> {rows, frames, count,
-// width, n}: rows a Uint32Array(n) - per image row the frames whose |X|^2 is >= the row's threshold - and frames a
-// Uint32Array(count * width), band-major - per band and frame the rows of the band that reach theirs (sp_render_occupancy; a NaN on
-// either side is no hit).  The library refuses bad bands, and a threshold of another length is refused here (status -1), before
+// occupancy counts: req as for renderBandPower (db is read and not looked at) plus `threshold`, a Float64Array(n): one power per image
+// row -> {rows, frames, count, width, n}: rows a Uint32Array(n) - per image row the frames whose |X|^2 is >= the row's threshold - and
+// frames a Uint32Array(count * width), band-major - per band and frame the rows of the band that reach theirs (sp_render_occupancy; a NaN
+// on either side is no hit).  The library refuses bad bands, and a threshold of another length is refused here (status -1), before
 // anything is rendered.
-const CheckedKind kOccupancy{"renderOccupancy", false, "renderOccupancySync(handle, request)", "renderOccupancy(handle, request, callback)",
-                             "spectroplot_hip.renderOccupancy", "could not queue the occupancy request"};
-
-struct OccupancyJob : BandPowerJob {   // (`rows` are the bands; `out` is not used)
+struct Occupancy {
+    static constexpr CheckedKind kind{"renderOccupancy", "occupancy", false};
+    Bands bands;
     std::vector<double> threshold;
     std::vector<uint32_t> row_counts, frame_counts;
-    bool parse_own(napi_env env, napi_value r) override;
-    void run() override;
-    napi_value result(napi_env env) override;
+    bool read(napi_env env, napi_value req)
+    {
+        int32_t db = 0;
+        return read_db(env, req, &db) && read_bands(env, req, &bands) && read_threshold(env, req, &threshold);
+    }
+    void run(CheckedRequest &j)
+    {
+        const int32_t n = j.set.req.n, width = j.cap.width;
+        if (n < 1 || threshold.size() != (size_t)n) return j.refuse(SP_ERR_INVALID_ARG, "threshold must hold n values, one per image row");
+        if (!j.allocated([&] {
+                row_counts.assign((size_t)n, 0);
+                if (bands.taken() && width > 0) frame_counts.assign(bands.count() * (size_t)width, 0);
+            }))
+            return;
+        uint32_t none = 0;
+        j.finish(sp_render_occupancy(SP_CALL_HEAD(j), threshold.data(), bands.rows.data(), bands.for_library(), row_counts.data(),
+                                     or_placeholder(frame_counts, &none)));
+    }
+    napi_value result(napi_env env, CheckedRequest &j)
+    {
+        Reply r(env);
+        r.array("rows", napi_uint32_array, row_counts.data(), row_counts.size());
+        r.array("frames", napi_uint32_array, frame_counts.data(), frame_counts.size());
+        r.ints({{"count", (int32_t)bands.count()}, {"width", j.cap.width}, {"n", j.set.req.n}});
+        return r.done();
+    }
 };
-
-bool OccupancyJob::parse_own(napi_env env, napi_value r)
-{
-    if (!BandPowerJob::parse_own(env, r)) return false;
-    napi_value v, ab;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void *data = nullptr;
-    if (napi_get_named_property(env, r, "threshold", &v) != napi_ok || napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off) != napi_ok
-        || tt != napi_float64_array) {
-        napi_throw_type_error(env, nullptr, "threshold must be a Float64Array of n powers");
-        return false;
-    }
-    if (len) threshold.assign((const double *)data, (const double *)data + len);
-    return true;
-}
-
-void OccupancyJob::run()
-{
-    const size_t count = rows.size() / 2;
-    if (req.n < 1 || threshold.size() != (size_t)req.n) {
-        status = SP_ERR_INVALID_ARG;
-        error = "threshold must hold n values, one per image row";
-        return;
-    }
-    try {
-        row_counts.assign((size_t)req.n, 0);
-        if (count <= SP_MAX_BANDS && width > 0) frame_counts.assign(count * (size_t)width, 0);   // (more bands than the library takes: it refuses)
-    } catch (const std::bad_alloc &) {
-        status = SP_ERR_NOMEM;
-        error = "out of host memory";
-        return;
-    }
-    uint32_t none = 0;
-    const int32_t c = count > (size_t)SP_MAX_BANDS ? SP_MAX_BANDS + 1 : (int32_t)count;
-    status = sp_render_occupancy(ctx, &req, bytes, nbytes, width, threshold.data(), rows.data(), c, row_counts.data(),
-                                 frame_counts.empty() ? &none : frame_counts.data());
-    if (status != SP_OK) error = sp_last_error(ctx);
-}
-
-napi_value OccupancyJob::result(napi_env env)
-{
-    napi_value obj, ab, ta, v;
-    void *data = nullptr;
-    if (napi_create_object(env, &obj) != napi_ok || napi_create_arraybuffer(env, row_counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
-    if (!row_counts.empty()) memcpy(data, row_counts.data(), row_counts.size() * 4);
-    if (napi_create_typedarray(env, napi_uint32_array, row_counts.size(), ab, 0, &ta) != napi_ok
-        || napi_set_named_property(env, obj, "rows", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_arraybuffer(env, frame_counts.size() * 4, &data, &ab) != napi_ok) return nullptr;
-    if (!frame_counts.empty()) memcpy(data, frame_counts.data(), frame_counts.size() * 4);
-    if (napi_create_typedarray(env, napi_uint32_array, frame_counts.size(), ab, 0, &ta) != napi_ok
-        || napi_set_named_property(env, obj, "frames", ta) != napi_ok)
-        return nullptr;
-    if (napi_create_int32(env, (int32_t)(rows.size() / 2), &v) != napi_ok || napi_set_named_property(env, obj, "count", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, width, &v) != napi_ok || napi_set_named_property(env, obj, "width", v) != napi_ok) return nullptr;
-    if (napi_create_int32(env, req.n, &v) != napi_ok || napi_set_named_property(env, obj, "n", v) != napi_ok) return nullptr;
-    return obj;
-}
-
-napi_value RenderOccupancySync(napi_env env, napi_callback_info info) { return checked_sync<OccupancyJob>(env, info, kOccupancy); }
-napi_value RenderOccupancy(napi_env env, napi_callback_info info) { return checked_async<OccupancyJob>(env, info, kOccupancy); }
+#undef SP_CALL_HEAD
 
 napi_value DeviceCount(napi_env env, napi_callback_info)
 {
@@ -1422,12 +1250,9 @@ napi_value ParseFormat(napi_env env, napi_callback_info info)
     napi_get_value_string_utf8(env, s, buf, sizeof buf, &len);
     int32_t id = 0, sw = 0;
     sp_format_parse(buf, &id, &sw);
-    napi_value out, v;
-    napi_create_object(env, &out);
-    napi_create_int32(env, id, &v); napi_set_named_property(env, out, "id", v);
-    napi_create_int32(env, sw, &v); napi_set_named_property(env, out, "sampleWidth", v);
-    napi_create_int32(env, sp_format_element_size(id), &v); napi_set_named_property(env, out, "elementSize", v);
-    return out;
+    Reply r(env);
+    r.ints({{"id", id}, {"sampleWidth", sw}, {"elementSize", sp_format_element_size(id)}});
+    return r.done();
 }
 
 napi_value Window(napi_env env, napi_callback_info info)
@@ -1589,19 +1414,14 @@ napi_value AllocBuffer(napi_env env, napi_callback_info info)
 
 napi_value PoolStats(napi_env env, napi_callback_info)
 {
-    napi_value out, v;
-    napi_create_object(env, &out);
+    Reply r(env);
     std::lock_guard<std::mutex> g(g_pool.m);
-    napi_create_double(env, (double)g_pool.n_fresh, &v); napi_set_named_property(env, out, "fresh", v);
-    napi_create_double(env, (double)g_pool.n_recycled, &v); napi_set_named_property(env, out, "recycled", v);
-    napi_create_double(env, (double)g_pool.n_recycled_pinned, &v); napi_set_named_property(env, out, "recycledPinned", v);
-    napi_create_double(env, (double)g_pool.free_bytes, &v); napi_set_named_property(env, out, "freeBytes", v);
-    napi_create_double(env, (double)g_pool.pinned_bytes, &v); napi_set_named_property(env, out, "pinnedBytes", v);
-    napi_create_double(env, (double)g_pool.n_pin_refused, &v); napi_set_named_property(env, out, "pinRefused", v);
-    napi_create_double(env, (double)g_pool.keep_bytes, &v); napi_set_named_property(env, out, "keepLimit", v);
-    napi_create_double(env, (double)g_pool.pinned_limit, &v); napi_set_named_property(env, out, "pinnedLimit", v);
-    napi_create_double(env, (double)g_reply_weight_cap, &v); napi_set_named_property(env, out, "replyWeightCap", v);
-    return out;
+    r.doubles(nullptr, {{"fresh", (double)g_pool.n_fresh}, {"recycled", (double)g_pool.n_recycled},
+                        {"recycledPinned", (double)g_pool.n_recycled_pinned}, {"freeBytes", (double)g_pool.free_bytes},
+                        {"pinnedBytes", (double)g_pool.pinned_bytes}, {"pinRefused", (double)g_pool.n_pin_refused},
+                        {"keepLimit", (double)g_pool.keep_bytes}, {"pinnedLimit", (double)g_pool.pinned_limit},
+                        {"replyWeightCap", (double)g_reply_weight_cap}});
+    return r.done();
 }
 
 napi_value Cmap(napi_env env, napi_callback_info info)
@@ -1642,7 +1462,7 @@ napi_value CmapKeys(napi_env env, napi_callback_info)
 napi_value NamedResolve(napi_env env, napi_callback_info info)
 {
     size_t argc = 2;
-    napi_value argv[2], out, v, sv;
+    napi_value argv[2], sv;
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     std::string names[2];
     for (int k = 0; k < 2; k++) {
@@ -1655,18 +1475,18 @@ napi_value NamedResolve(napi_env env, napi_callback_info info)
     const char *wname = "", *ckey = "";
     int32_t lut_len = 0;
     sp_named_resolve(names[0].c_str(), names[1].c_str(), &wname, &ckey, &lut_len);
-    NAPI_OK(env, napi_create_object(env, &out));
-    napi_create_string_utf8(env, wname, NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, out, "window", v);
-    napi_create_string_utf8(env, ckey, NAPI_AUTO_LENGTH, &v); napi_set_named_property(env, out, "cmap", v);
-    napi_create_int32(env, lut_len, &v); napi_set_named_property(env, out, "lutLength", v);
-    return out;
+    Reply r(env);
+    r.string("window", wname);
+    r.string("cmap", ckey);
+    r.ints({{"lutLength", lut_len}});
+    return r.done();
 }
 
 // peakSubframes(formatId, n, nbytes, width) -> {subframes, lastColumnCount}: sp_peak_subframes, every argument checked
 napi_value PeakSubframes(napi_env env, napi_callback_info info)
 {
     size_t argc = 4;
-    napi_value argv[4], out, v;
+    napi_value argv[4];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     double a[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; k++) {
@@ -1681,10 +1501,9 @@ napi_value PeakSubframes(napi_env env, napi_callback_info info)
     int32_t m = 1, last = 0;
     const int rc = sp_peak_subframes((int32_t)a[0], (int32_t)a[1], (size_t)a[2], (int32_t)a[3], &m, &last);
     if (rc) return throw_status(env, rc, nullptr);
-    NAPI_OK(env, napi_create_object(env, &out));
-    napi_create_int32(env, m, &v); napi_set_named_property(env, out, "subframes", v);
-    napi_create_int32(env, last, &v); napi_set_named_property(env, out, "lastColumnCount", v);
-    return out;
+    Reply r(env);
+    r.ints({{"subframes", m}, {"lastColumnCount", last}});
+    return r.done();
 }
 
 napi_value PlanCreations(napi_env env, napi_callback_info info)
@@ -1727,49 +1546,51 @@ napi_value CreateContext(napi_env env, napi_callback_info info)
 
 napi_value Init(napi_env env, napi_value exports)
 {
-    const napi_property_descriptor props[] = {
-        {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"parseFormat", nullptr, ParseFormat, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"window", nullptr, Window, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"sliceBounds", nullptr, SliceBounds, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"createContext", nullptr, CreateContext, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"destroyContext", nullptr, DestroyContext, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"allocBuffer", nullptr, AllocBuffer, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"poolStats", nullptr, PoolStats, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"cmap", nullptr, Cmap, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"cmapKeys", nullptr, CmapKeys, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"render", nullptr, Render, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderSync", nullptr, RenderSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderNamed", nullptr, RenderNamed, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderNamedSync", nullptr, RenderNamedSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderBatch", nullptr, RenderBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderBatchSync", nullptr, RenderBatchSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderTraces", nullptr, RenderTraces, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderTracesSync", nullptr, RenderTracesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderPower", nullptr, RenderPower, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderPowerSync", nullptr, RenderPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderMean", nullptr, RenderMean, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderMeanSync", nullptr, RenderMeanSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"bandRows", nullptr, BandRows, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderBandPower", nullptr, RenderBandPower, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderBandPowerSync", nullptr, RenderBandPowerSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderTrack", nullptr, RenderTrack, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderTrackSync", nullptr, RenderTrackSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderOccupancy", nullptr, RenderOccupancy, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderOccupancySync", nullptr, RenderOccupancySync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderIndex", nullptr, RenderIndex, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderIndexSync", nullptr, RenderIndexSync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderDensity", nullptr, RenderDensity, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"renderDensitySync", nullptr, RenderDensitySync, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"namedResolve", nullptr, NamedResolve, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"peakSubframes", nullptr, PeakSubframes, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"planCreations", nullptr, PlanCreations, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"createGroup", nullptr, CreateGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"destroyGroup", nullptr, DestroyContext, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"groupRender", nullptr, Render, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"groupRenderSync", nullptr, RenderSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+    const struct { const char *name; napi_callback fn; } table[] = {
+        {"deviceCount", DeviceCount},
+        {"parseFormat", ParseFormat},
+        {"window", Window},
+        {"sliceBounds", SliceBounds},
+        {"createContext", CreateContext},
+        {"destroyContext", DestroyContext},
+        {"allocBuffer", AllocBuffer},
+        {"poolStats", PoolStats},
+        {"cmap", Cmap},
+        {"cmapKeys", CmapKeys},
+        {"render", Render<false, true>},
+        {"renderSync", Render<false, false>},
+        {"renderNamed", Render<true, true>},
+        {"renderNamedSync", Render<true, false>},
+        {"renderBatch", RenderBatch<true>},
+        {"renderBatchSync", RenderBatch<false>},
+        {"renderTraces", Checked<Traces, true>},
+        {"renderTracesSync", Checked<Traces, false>},
+        {"renderPower", Checked<Power, true>},
+        {"renderPowerSync", Checked<Power, false>},
+        {"renderMean", Checked<Mean, true>},
+        {"renderMeanSync", Checked<Mean, false>},
+        {"bandRows", BandRows},
+        {"renderBandPower", Checked<BandPower, true>},
+        {"renderBandPowerSync", Checked<BandPower, false>},
+        {"renderTrack", Checked<Track, true>},
+        {"renderTrackSync", Checked<Track, false>},
+        {"renderOccupancy", Checked<Occupancy, true>},
+        {"renderOccupancySync", Checked<Occupancy, false>},
+        {"renderIndex", Checked<Index, true>},
+        {"renderIndexSync", Checked<Index, false>},
+        {"renderDensity", Checked<Density, true>},
+        {"renderDensitySync", Checked<Density, false>},
+        {"namedResolve", NamedResolve},
+        {"peakSubframes", PeakSubframes},
+        {"planCreations", PlanCreations},
+        {"createGroup", CreateGroup},
+        {"destroyGroup", DestroyContext},
+        {"groupRender", Render<false, true>},
+        {"groupRenderSync", Render<false, false>},
     };
-    napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
+    std::vector<napi_property_descriptor> props;
+    for (const auto &e : table) props.push_back({e.name, nullptr, e.fn, nullptr, nullptr, nullptr, napi_default, nullptr});
+    napi_define_properties(env, exports, props.size(), props.data());
     napi_value v;
     napi_create_int32(env, sp_version(), &v);
     napi_set_named_property(env, exports, "version", v);

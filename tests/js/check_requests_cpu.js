@@ -12,10 +12,10 @@ const { HipWorker } = require('../../spectroplot-js_amd/js')
 // every name of the addon's Init table
 const EXPORTS = ['deviceCount', 'parseFormat', 'window', 'sliceBounds', 'createContext', 'destroyContext', 'allocBuffer', 'poolStats', 'cmap',
     'cmapKeys', 'render', 'renderSync', 'renderNamed', 'renderNamedSync', 'renderBatch', 'renderBatchSync', 'renderTraces', 'renderTracesSync',
-    'renderPower', 'renderPowerSync', 'renderMean', 'renderMeanSync', 'bandRows', 'renderBandPower', 'renderBandPowerSync', 'renderIndex',
-    'renderIndexSync', 'renderDensity', 'renderDensitySync', 'namedResolve', 'peakSubframes', 'planCreations', 'createGroup', 'destroyGroup',
-    'groupRender', 'groupRenderSync']
-assert.strictEqual(EXPORTS.length, 36)
+    'renderPower', 'renderPowerSync', 'renderMean', 'renderMeanSync', 'bandRows', 'renderBandPower', 'renderBandPowerSync', 'renderTrack',
+    'renderTrackSync', 'renderOccupancy', 'renderOccupancySync', 'renderIndex', 'renderIndexSync', 'renderDensity', 'renderDensitySync',
+    'namedResolve', 'peakSubframes', 'planCreations', 'createGroup', 'destroyGroup', 'groupRender', 'groupRenderSync']
+assert.strictEqual(EXPORTS.length, 40)
 for (const k of EXPORTS) assert.strictEqual(typeof addon[k], 'function', k)
 
 function fnv(bytes) {

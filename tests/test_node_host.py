@@ -30,7 +30,16 @@ def test_request_builders_and_the_addons_export_table():
     every name of the addon's export table is a function."""
     out = _node("check_requests_cpu.js")
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "request builders ok: 162 cases, 36 exports" in out.stdout
+    assert "request builders ok: 162 cases, 40 exports" in out.stdout
+
+
+def test_addon_refusals_without_a_handle_and_its_export_table():
+    """Every render entry point of the addon, sync and callback form, called without arguments and with ({}, {}): the usage lines and
+    "context handle expected" as recorded before the addon's reply kinds were folded; the export list is every function the module has
+    (tests/js/check_addon_shapes.js cpu)."""
+    out = _node("check_addon_shapes.js", "cpu")
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "addon shapes ok (cpu): 52 cases, 40 exports" in out.stdout
 
 
 def test_caller_side_parameter_helpers_match_reference():
