@@ -766,6 +766,70 @@ int32_t sp_quantile_rank(int32_t width, double q);
 int sp_debug_quantile(const double *values, int32_t count, int32_t rank, double *out);
 
 /*
+ * Burst lists: hysteresis pulse edges per band - when a transmitter switches on and off and for how long, the pulse widths and gaps
+ * of an OOK or FSK capture that one otherwise reads off the spectrogram by eye.  With s[b][x] the value sp_plan_execute_bandpower
+ * writes for band b and frame x - the same bands (a HOST array of `count` pairs, 0 <= count <= SP_MAX_BANDS), geometry, limits,
+ * statuses, channel mode and bits as for the band-power series above - and two thresholds per band, hi[b] and lo[b], HOST arrays of
+ * `count` doubles read before the call returns, every frame of a band is one of
+ *     SET     s >= hi, as numpy compares
+ *     RESET   s < lo, as numpy compares
+ *     HOLD    anything else: lo <= s < hi, and EVERY NaN - a NaN is neither SET nor RESET
+ * and a Schmitt trigger per band runs along the frames.  It STARTS OFF in front of frame 0.  After frame x it is ON if the last frame
+ * at or before x that is not HOLD is a SET, and OFF if that frame is a RESET or there is none.  A burst is a maximal run of ON frames
+ * [start, end); a burst that is still ON behind the last frame has end = width.  The reply:
+ *     counts[b]           = the TOTAL number of bursts of band b                                      uint32_t counts[count]
+ *     edges[b][2 i]       = start, edges[b][2 i + 1] = end of burst i, ascending in time,
+ *                           for i < min(counts[b], max_bursts); EVERY SLOT BEHIND THAT IS -1          int32_t edges[count][2 * max_bursts]
+ * Either output may be NULL and is not touched then; `edges` is also absent with max_bursts == 0.  Both absent: SP_ERR_INVALID_ARG.
+ * Both are 4-byte aligned.  max_bursts >= 0 and 2 * max_bursts * count must fit 31 bits.  counts[b] > max_bursts says the list is cut.
+ * The thresholds become keys once (csrc/sp_occupancy_core.h, threshold_key): a negative one and -0.0 are key 0, so a negative lo
+ * never resets and a negative hi is reached by every value that is not a NaN.  A NaN hi or lo is SP_ERR_INVALID_ARG, and so is
+ * lo_key > hi_key, before the device is touched; lo == hi is a plain threshold.  Also SP_ERR_INVALID_ARG: what the band-power series
+ * refuses of its bands, a NULL hi or lo with count > 0, max_bursts < 0.  Only plans of the sample detector are accepted: a peak plan
+ * returns SP_ERR_UNSUPPORTED.  width == 0 or count == 0: a non-NULL counts gets `count` zeros and edges all -1.
+ * The same words come out for both layouts; they do not depend on gain, range, LUT or block_norm, NOR ON THE CU COUNT, THE WINDOW OR
+ * THE CHUNKING OF A HOST-FED REQUEST, although a Schmitt trigger is a recurrence along time: the series is written whole first, and a
+ * run of frames is known to what follows it by a summary that combines associatively (csrc/sp_burst_core.h, the one place the decision
+ * is made, for the kernels and for sp_debug_bursts; no floating-point compare).
+ * MEMORY: the context keeps the band series, 8 * count * width bytes, and 16 bytes per band and segment of SP_BURST_SEGMENT_FRAMES
+ *   frames in a workspace that grows to the largest request so far, is never shrunk and is freed with the context; SP_ERR_NOMEM
+ *   where it cannot be had.
+ * How: behind every block of frames the band-power series' launch writes the block's columns of the workspace series; behind the last
+ *   block three launches: a summary per segment and band, one wave per band that scans the summaries (the state in front of every
+ *   segment, the bursts started before it, the total), and the first grid again, which stores the edges with plain stores - every slot
+ *   has one writer.  No workgroup waits for another.  `edges` is filled with 0xFF bytes on the stream in front of all that.
+ *
+ * sp_plan_execute_bursts: device operands, asynchronous on the context's stream, capturable.  The checks are
+ *   sp_plan_execute_bandpower's, then the thresholds', then the outputs'.  No request number: the call may be interleaved with
+ *   sp_plan_execute / _power / _mean / _bandpower / _track / _occupancy / _quantile on one context without a synchronisation.
+ * sp_power_bursts: the bursts of a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_power_bands.  Asynchronous.  n >= 1 (any n), width >= 0; d_power (non-NULL when width > 0 and count > 0) 8-byte aligned.
+ * sp_series_bursts: the three launches alone on a band-major device series double[count * width] the caller holds, sp_power_bands'
+ *   reply for example: band b's frames at d_series + b * width.  0 <= count <= SP_MAX_BANDS, width >= 0, d_series 8-byte aligned and
+ *   non-NULL when count * width > 0.  The values are read by key: the sign bit of a value is not looked at.  Asynchronous.
+ * sp_render_bursts: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for sp_render_bandpower; the
+ *   reply comes back in two copies.  There is no dB form: the thresholds are powers.
+ * sp_plan_bursts_kernel_name_for: "frames_power+bursts" or "scratch_power+bursts", following sp_plan_power_kernel_name_for.
+ * sp_debug_bursts: (tests, no device needed) one band on the host through the host side of the code the kernels run: `width` >= 0
+ *   values, the thresholds hi and lo, *count_out = the total and edges_out[2 * max_bursts] the list.  Either output may be NULL, not
+ *   both; the refusals of the thresholds, of max_bursts and of the outputs' alignment are those above.
+ * Out of scope: the energy or the peak of a burst, a minimum burst width or gap, peak plans, batches, groups, sharding.py, a dB form.
+ */
+#ifndef SP_BURST_SEGMENT_FRAMES   /* (a compile-time knob for tools/burst_bench.py's variants only) */
+#define SP_BURST_SEGMENT_FRAMES 2048
+#endif
+int sp_plan_execute_bursts(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                           const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges);
+int sp_power_bursts(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count, const double *hi,
+                    const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges);
+int sp_series_bursts(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo,
+                     int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges);
+int sp_render_bursts(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                     int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts, int32_t *edges);
+const char *sp_plan_bursts_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_debug_bursts(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out, int32_t *edges_out);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

@@ -204,6 +204,13 @@ class Library:
         L.sp_quantile_rank.restype = i32
         L.sp_quantile_rank.argtypes = [i32, dbl]
         L.sp_debug_quantile.argtypes = [vp, i32, i32, C.POINTER(dbl)]
+        L.sp_plan_execute_bursts.argtypes = [vp, vp, sz, i32, vp, i32, vp, vp, i32, vp, vp]
+        L.sp_power_bursts.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]
+        L.sp_series_bursts.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp]
+        L.sp_render_bursts.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, vp, vp, i32, vp, vp]
+        L.sp_plan_bursts_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_bursts_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_debug_bursts.argtypes = [vp, i32, dbl, dbl, i32, C.POINTER(C.c_uint32), vp]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -338,6 +345,45 @@ def _rank_array(width, q, ranks):
     # (a rank that is no int32 becomes one the library refuses - -1, or 2^31 - 1, which no width is above - and never wraps into range)
     r = np.ascontiguousarray(np.clip(np.asarray(ranks, dtype=np.int64).reshape(-1), -1, 2 ** 31 - 1).astype(np.int32))
     return r, r.size
+
+
+SP_BURST_SEGMENT_FRAMES = 2048
+
+
+def burst_scan(values, hi, lo, max_bursts):
+    """sp_debug_bursts: the bursts of one series through the host side of the code the burst kernels run - a Schmitt trigger that
+    starts OFF, sets where values[x] >= hi, resets where values[x] < lo (numpy's compares: a NaN does neither) - as (the total,
+    edges int32 [max_bursts, 2]): start and end of the first max_bursts bursts, -1 behind them; a burst open at the end ends at
+    len(values).  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    m = int(max_bursts)
+    edges = np.zeros((max(m, 0), 2), np.int32)
+    total = C.c_uint32()
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_bursts(_p(v) if v.size else None, v.size, float(hi), float(lo), m, C.byref(total),
+                                    _p(edges) if edges.size else None))
+    return total.value, edges
+
+
+def burst_pulses(edges_row, total):
+    """What a pulse analyser prints of one band's burst list (edges int32 [max_bursts, 2] or flat, and the band's total count): (the
+    widths end - start of the listed bursts, the gaps start[i + 1] - end[i] between them), two int64 arrays in frames, the second one
+    shorter by one.  Only min(total, max_bursts) bursts are listed."""
+    e = np.asarray(edges_row, dtype=np.int64).reshape(-1, 2)
+    e = e[:min(int(total), e.shape[0])]
+    return e[:, 1] - e[:, 0], e[1:, 0] - e[:-1, 1]
+
+
+def _burst_thresholds(hi, lo, count):
+    """(hi, lo) as two float64 [count] host arrays: a number for every band, or count values; nothing else is checked here."""
+    out = []
+    for name, t in (("hi", hi), ("lo", lo)):
+        a = np.asarray(t, dtype=np.float64)
+        a = np.full(count, float(a), np.float64) if a.ndim == 0 else np.ascontiguousarray(a.reshape(-1))
+        if a.size != count:
+            raise SpectroplotError(SP_ERR_INVALID_ARG, "%s must be a number or one value per band" % name)
+        out.append(a)
+    return out
 
 
 def row_freq(n, row):
@@ -769,6 +815,42 @@ class Context:
         self._chk(self.lib.L.sp_power_quantile(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(r) if count else None, count,
                                                C.c_void_p(d_out or None)))
 
+    def render_bursts(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, hi, lo, max_bursts, channel_mode=False, lut=None,
+                      fill=None):
+        """sp_render_bursts: the burst lists of the request, (counts uint32 [count], edges int32 [count, max_bursts, 2]): per band
+        (y0, y1) of image rows a Schmitt trigger along the frames of its exact band sum - ON from a frame with sum >= hi, OFF from
+        one with sum < lo, OFF in front of frame 0 - the total number of its bursts and start and end of the first max_bursts of
+        them, -1 behind those.  hi, lo: a number for every band, or `count` values.  No image is rendered; `lut` only takes part in
+        the plan-cache key.  fill: a byte the output arrays hold before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        counts = _filled(count, np.uint32, fill)
+        edges = _filled((count, max(int(max_bursts), 0), 2), np.int32, fill)
+        self._chk(self.lib.L.sp_render_bursts(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                              _p(h) if count else None, _p(l) if count else None, int(max_bursts), _p(counts),
+                                              _p(edges) if edges.size else None))
+        return counts, edges
+
+    def power_bursts(self, d_power, n, width, bands, hi, lo, max_bursts, d_counts, d_edges):
+        """sp_power_bursts: the burst lists of the f64 [width, n] plane at device address d_power: per band the total into uint32
+        [count] at d_counts and the edges into int32 [count, max_bursts, 2] at d_edges (either address may be 0: not written).
+        Asynchronous on the context's stream; bands, hi and lo are read before it returns."""
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        self._chk(self.lib.L.sp_power_bursts(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                             _p(h) if count else None, _p(l) if count else None, int(max_bursts),
+                                             C.c_void_p(d_counts or None), C.c_void_p(d_edges or None)))
+
+    def series_bursts(self, d_series, count, width, hi, lo, max_bursts, d_counts, d_edges):
+        """sp_series_bursts: the burst lists of the band-major f64 [count, width] series at device address d_series - power_bands'
+        reply, for example - into d_counts and d_edges as for power_bursts.  Asynchronous on the context's stream."""
+        count = int(count)
+        h, l = _burst_thresholds(hi, lo, max(count, 0))
+        self._chk(self.lib.L.sp_series_bursts(self.h, C.c_void_p(d_series or None), count, int(width), _p(h) if count > 0 else None,
+                                              _p(l) if count > 0 else None, int(max_bursts), C.c_void_p(d_counts or None),
+                                              C.c_void_p(d_edges or None)))
+
     def set_mean_window(self, nbytes=0):
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
@@ -957,6 +1039,23 @@ class Plan:
         r, count = _rank_array(width, None, ranks)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_quantile(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                               _p(r) if count else None, count, C.c_void_p(d_out or None)))
+
+    def bursts_kernel_name_for(self, nbytes, width):
+        """What execute_bursts() launches for a request of this shape: "frames_power+bursts" or "scratch_power+bursts"."""
+        return self._kernel_name_for("bursts", nbytes, width)
+
+    def execute_bursts(self, d_bytes, nbytes, width, bands, hi, lo, max_bursts, d_counts, d_edges):
+        """sp_plan_execute_bursts: per band (y0, y1) of image rows the bursts of a Schmitt trigger along the frames of its exact band
+        sum (hi, lo: a number for every band, or `count` values): the total into the uint32 [count] device array at d_counts, start
+        and end of the first max_bursts into the int32 [count, max_bursts, 2] device array at d_edges, -1 behind them (either may be
+        0: not written).  Asynchronous on the context's stream; bands, hi and lo are read before it returns.  The context keeps the
+        band series, 8 * count * width bytes."""
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_bursts(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                            _p(b) if count else None, count, _p(h) if count else None,
+                                                            _p(l) if count else None, int(max_bursts), C.c_void_p(d_counts or None),
+                                                            C.c_void_p(d_edges or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -29,6 +29,7 @@
 #include "sp_track_core.h"
 #include "sp_occupancy_core.h"
 #include "sp_quantile_core.h"
+#include "sp_burst_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -115,6 +116,7 @@ struct sp_context {
     DeviceBuffer power_plane;    // sp_render_power: the request's plane on the device, 8 * width * n bytes (grown, never shrunk)
     DeviceBuffer mean_ws;        // a mean request's exact-sum cells, u64[spx::kSlots][n] (sp_kernel_mean.h; grown, never shrunk)
     DeviceBuffer quantile_ws;    // a percentile request's whole plane as keys, u64[n][width] (sp_kernel_quantile.h; grown, never shrunk)
+    DeviceBuffer burst_ws;       // a burst request's band series f64[count][width] and, behind it, its segments' summaries and carries (sp_kernel_burst.h; grown, never shrunk)
     DeviceBuffer plane_window;   // a mean, band-power or track request: the block of frames of its plane that is being consumed (plane_blocks)
     size_t mean_window_bytes = 0; // sp_context_set_mean_window: the window's size at the most; 0 is the default, kPlaneWindowDefault
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
@@ -390,6 +392,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->power_plane.release();
     ctx->mean_ws.release();
     ctx->quantile_ws.release();
+    ctx->burst_ws.release();
     ctx->plane_window.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
@@ -2504,6 +2507,165 @@ extern "C" int sp_render_quantile(sp_context *ctx, const sp_request *req, const 
                                   const int32_t *ranks, int32_t count, double *out)
 {
     return plane_render(ctx, req, bytes, nbytes, width, db, QuantileKind{ranks, count, out});
+}
+
+// ------------------------------------------------------------------------------------------------- burst lists
+
+extern "C" const char *sp_plan_bursts_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+bursts", "scratch_power+bursts");
+}
+
+namespace {
+// What every burst entry point refuses of its thresholds - nullptr where they are in order - and their keys into hi_key[count] and
+// lo_key[count] where those are not null.
+const char *burst_keys(const double *hi, const double *lo, int32_t count, uint64_t *hi_key, uint64_t *lo_key)
+{
+    if (count > 0 && (!hi || !lo)) return "burst lists need hi and lo, count doubles each";
+    for (int32_t b = 0; b < count; b++) {
+        uint64_t hb, lb;
+        memcpy(&hb, hi + b, sizeof hb);
+        memcpy(&lb, lo + b, sizeof lb);
+        const uint64_t hk = spo::threshold_key(hb), lk = spo::threshold_key(lb);
+        if (hk == spo::kNoHitKey || lk == spo::kNoHitKey) return "a burst threshold must not be a NaN";
+        if (lk > hk) return "burst lists need lo <= hi for every band";
+        if (hi_key) hi_key[b] = hk;
+        if (lo_key) lo_key[b] = lk;
+    }
+    return nullptr;
+}
+
+// ... and of its outputs
+const char *burst_outputs(int32_t count, int32_t max_bursts, const uint32_t *counts, const int32_t *edges)
+{
+    if (max_bursts < 0) return "max_bursts >= 0 is required";
+    if (2ll * (long long)max_bursts * (long long)(count > 0 ? count : 0) > 0x7fffffffll) return "2 * max_bursts * count must fit 31 bits";
+    if (!counts && !(edges && max_bursts > 0)) return "burst lists need a counts array or an edges array with max_bursts > 0";
+    if (((uintptr_t)counts & 3) != 0) return "the burst counts must be a 4-byte aligned array of count uint32";
+    if (((uintptr_t)edges & 3) != 0) return "the burst edges must be a 4-byte aligned array of count * 2 * max_bursts int32";
+    return nullptr;
+}
+
+// The three launches on a band-major series of the device and the 0xFF fill in front of them; `records`: spk::burst_record_bytes.
+int burst_scan(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo, int32_t max_bursts,
+               void *records, uint32_t *counts, int32_t *edges)
+{
+    uint64_t hi_key[SP_MAX_BANDS], lo_key[SP_MAX_BANDS];
+    (void)burst_keys(hi, lo, count, hi_key, lo_key);   // (checked before)
+    spk::launch_bursts(d_series, count, width, hi_key, lo_key, max_bursts, (unsigned long long *)records, counts, edges, ctx->stream);
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// The first consumer whose reply depends on the order of the frames: clear() reserves the context's workspace - the band series
+// f64[count][width] and the segments' records behind it - and fills `edges` with -1; every block's launch is the band-power series'
+// own, its columns at x_base of the workspace series, so that the series is the same whatever the window; finish() is the three
+// launches on it.  A request without a band writes nothing; one without a frame still writes (count zeros and the fill).
+struct BurstKind {
+    static constexpr const char *kRender = "sp_render_bursts";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    const int32_t *bands;
+    int32_t count;
+    const double *hi, *lo;   // host arrays
+    int32_t max_bursts;
+    uint32_t *counts;        // count words, or null
+    int32_t *edges;          // count * 2 * max_bursts words, or null
+
+    bool lists() const { return edges && max_bursts > 0; }
+    size_t series_bytes(const PlaneShape &p) const { return sizeof(double) * (size_t)count * (size_t)p.width; }
+    size_t edge_bytes() const { return sizeof(int32_t) * 2 * (size_t)max_bursts * (size_t)count; }
+    int check(const PlaneShape &p) const
+    {
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (const char *why = burst_keys(hi, lo, count, nullptr, nullptr)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (const char *why = burst_outputs(count, max_bursts, counts, edges)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &) const { return count == 0; }
+    int clear(const PlaneShape &p) const
+    {
+        const int rc = p.ctx->burst_ws.reserve(series_bytes(p) + spk::burst_record_bytes(count, p.width));
+        if (rc) return fail(p.ctx, rc, "burst workspace: out of device memory");
+        if (lists()) SP_HIP(p.ctx, hipMemsetAsync(edges, 0xFF, edge_bytes(), p.ctx->stream));
+        return SP_OK;
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        if (frames <= 0) return SP_OK;
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, (double *)p.ctx->burst_ws.p, p.width, x_base, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &p) const
+    {
+        return burst_scan(p.ctx, (const double *)p.ctx->burst_ws.p, count, p.width, hi, lo, max_bursts,
+                          (char *)p.ctx->burst_ws.p + series_bytes(p), counts, lists() ? edges : nullptr);
+    }
+    size_t small_bytes(const PlaneShape &) const { return sizeof(uint32_t) * (size_t)count + edge_bytes(); }
+    BurstKind on_device(const PlaneShape &, void *small) const
+    {
+        return {bands, count, hi, lo, max_bursts, counts ? (uint32_t *)small : nullptr, lists() ? (int32_t *)small + count : nullptr};
+    }
+    int tail(sp_plan *, const PlaneShape &p, int32_t, const BurstKind &host, hipError_t &e) const
+    {
+        if (counts) e = hipMemcpyAsync(host.counts, counts, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost, p.ctx->stream);
+        if (e == hipSuccess && lists()) e = hipMemcpyAsync(host.edges, edges, edge_bytes(), hipMemcpyDeviceToHost, p.ctx->stream);
+        return SP_OK;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_bursts(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                               const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges)
+{
+    return plane_resident(ctx, "sp_power_bursts", d_power, n, width, BurstKind{bands, count, hi, lo, max_bursts, d_counts, d_edges});
+}
+
+extern "C" int sp_plan_execute_bursts(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                      const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, BurstKind{bands, count, hi, lo, max_bursts, d_counts, d_edges});
+}
+
+extern "C" int sp_render_bursts(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                                int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts, int32_t *edges)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, 0, BurstKind{bands, count, hi, lo, max_bursts, counts, edges});
+}
+
+extern "C" int sp_series_bursts(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo,
+                                int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (count < 0 || count > SP_MAX_BANDS || width < 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_bursts: count within 0 .. SP_MAX_BANDS and width >= 0 are required");
+    if (const char *why = burst_keys(hi, lo, count, nullptr, nullptr)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (const char *why = burst_outputs(count, max_bursts, d_counts, d_edges)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (count == 0) return SP_OK;
+    if ((width > 0 && !d_series) || ((uintptr_t)d_series & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_bursts: d_series must be an 8-byte aligned device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    const bool lists = d_edges && max_bursts > 0;
+    return timed(ctx, [&] {
+        const int rc = ctx->burst_ws.reserve(spk::burst_record_bytes(count, width));
+        if (rc) return fail(ctx, rc, "burst workspace: out of device memory");
+        if (lists)
+            SP_HIP(ctx, hipMemsetAsync(d_edges, 0xFF, sizeof(int32_t) * 2 * (size_t)max_bursts * (size_t)count, ctx->stream));
+        return burst_scan(ctx, d_series, count, width, hi, lo, max_bursts, ctx->burst_ws.p, d_counts, lists ? d_edges : nullptr);
+    });
+}
+
+extern "C" int sp_debug_bursts(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out,
+                               int32_t *edges_out)
+{
+    if (width < 0 || (width > 0 && !values)) return SP_ERR_INVALID_ARG;
+    uint64_t hi_key = 0, lo_key = 0;
+    if (burst_keys(&hi, &lo, 1, &hi_key, &lo_key) || burst_outputs(1, max_bursts, count_out, edges_out)) return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> bits((size_t)width);
+    if (width) memcpy(bits.data(), values, (size_t)width * sizeof(double));
+    const uint32_t total = spb::scan(bits.data(), width, hi_key, lo_key, max_bursts, max_bursts > 0 ? edges_out : nullptr);
+    if (count_out) *count_out = total;
+    return SP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

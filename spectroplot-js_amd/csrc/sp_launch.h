@@ -56,6 +56,15 @@ void launch_quantile_gather(const double *plane, int n, long long frames, unsign
 // the HOST array `ranks` (1 .. SP_MAX_RANKS, each within 0 <= k < width: the caller has checked them); width == 0 gives NaNs.  One
 // launch of n workgroups.  (k_quantile_gather, k_quantile_select and these launchers are sp_quantile.hip, a unit of their own.)
 void launch_quantile_select(const unsigned long long *keys, int n, int width, const int32_t *ranks, int count, double *out, hipStream_t stream);
+// The burst lists of the band-major series f64[count][width] at `series` (0 <= count <= SP_MAX_BANDS, width >= 0): counts[b] = the
+// bursts of band b and edges[b][2 i], edges[b][2 i + 1] = the start and the end of burst i < max_bursts, against the HOST arrays
+// hi_key[count] and lo_key[count] (spo::threshold_key of the thresholds; the caller has checked them).  Either output may be null; the
+// caller has filled `edges` with -1.  `records`: burst_record_bytes(count, width) bytes of device memory, 8-byte aligned, for the
+// segments' summaries and carries.  Three launches - one where width == 0, two where edges is null or max_bursts == 0 - none where
+// count == 0.  (k_burst_summary, k_burst_carry, k_burst_emit and this launcher are sp_burst.hip, a unit of their own.)
+size_t burst_record_bytes(int count, int width);
+void launch_bursts(const double *series, int count, int width, const uint64_t *hi_key, const uint64_t *lo_key, int max_bursts,
+                   unsigned long long *records, uint32_t *counts, int32_t *edges, hipStream_t stream);
 
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 

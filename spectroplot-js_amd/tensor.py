@@ -1,5 +1,6 @@
-"""The numeric spectrogram, its exact mean, its exact band sums, its peak track, its occupancy counts and its percentile traces as torch
-tensors: sp_plan_execute_power / _mean / _bandpower / _track / _occupancy / _quantile on torch's current stream.
+"""The numeric spectrogram, its exact mean, its exact band sums, its peak track, its occupancy counts, its percentile traces and its
+burst lists as torch tensors: sp_plan_execute_power / _mean / _bandpower / _track / _occupancy / _quantile / _bursts on torch's current
+stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
 library (include/spectroplot_hip.h, "Power plane replies"), resident on the capture's device and ordered on torch's current stream:
@@ -149,3 +150,21 @@ def quantile(plan, capture, width, ranks):
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_quantile(capture.data_ptr(), capture.numel(), int(width), ranks, out.data_ptr() if out.numel() else 0)
     return out
+
+
+def bursts(plan, capture, width, bands, hi, lo, max_bursts):
+    """The burst lists of `capture` (a uint8 CUDA tensor: the raw bytes) as two int32 tensors on the same device, counts [count] and
+    edges [count, max_bursts, 2]: per band (y0, y1) of image rows a Schmitt trigger along the frames of its exact band sum - ON from a
+    frame with sum >= hi, OFF from one with sum < lo, OFF in front of frame 0 - the total number of its bursts and start and end of the
+    first max_bursts of them, -1 behind those (include/spectroplot_hip.h, "Burst lists").  The library's counts are uint32; none
+    reaches 2^31, so they are int32 here.  hi, lo: a Python float for every band, or `count` of them.  `plan` is a binding.Plan of the
+    sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane."""
+    _check_capture("bursts", capture)
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    m = max(int(max_bursts), 0)
+    counts = torch.empty((len(bands),), dtype=torch.int32, device=capture.device)
+    edges = torch.empty((len(bands), m, 2), dtype=torch.int32, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, counts, edges)):
+        plan.execute_bursts(capture.data_ptr(), capture.numel(), int(width), bands, hi, lo, int(max_bursts),
+                            counts.data_ptr() if counts.numel() else 0, edges.data_ptr() if edges.numel() else 0)
+    return counts, edges
