@@ -813,7 +813,8 @@ int sp_debug_quantile(const double *values, int32_t count, int32_t rank, double 
  * sp_debug_bursts: (tests, no device needed) one band on the host through the host side of the code the kernels run: `width` >= 0
  *   values, the thresholds hi and lo, *count_out = the total and edges_out[2 * max_bursts] the list.  Either output may be NULL, not
  *   both; the refusals of the thresholds, of max_bursts and of the outputs' alignment are those above.
- * Out of scope: the energy or the peak of a burst, a minimum burst width or gap, peak plans, batches, groups, sharding.py, a dB form.
+ * Out of scope: a minimum burst width or gap, peak plans, batches, groups, sharding.py, a dB form.  (The energy and the peak of a
+ *   burst: "Burst measurements", below.)
  */
 #ifndef SP_BURST_SEGMENT_FRAMES   /* (a compile-time knob for tools/burst_bench.py's variants only) */
 #define SP_BURST_SEGMENT_FRAMES 2048
@@ -828,6 +829,67 @@ int sp_render_bursts(sp_context *ctx, const sp_request *req, const uint8_t *byte
                      int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts, int32_t *edges);
 const char *sp_plan_bursts_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 int sp_debug_bursts(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out, int32_t *edges_out);
+
+/*
+ * Burst measurements: exact energy and peak per burst - how strong each pulse of the burst lists above is, the level and the peak a
+ * pulse analyser prints beside width and gap, without copying the band series to the host.  The inputs are those of the burst lists:
+ * bands, count, hi[], lo[], max_bursts; s[b][x] is the band-power series and the bursts [start, end) of band b are EXACTLY those of
+ * sp_plan_execute_bursts, the open burst with end = width included.  For every listed burst i < min(counts[b], max_bursts):
+ *     energy[b][i]  = RN(exact sum of s[b][x] for x in [start, end)): Python's math.fsum of the burst's frames, rounded ONCE.  The
+ *                     rule of the specials is spx::apply_specials': any NaN frame gives the NaN 0x7ff8000000000000 (a burst may
+ *                     hold NaN frames: a NaN is HOLD), otherwise any +inf frame gives +inf, and a finite sum beyond DBL_MAX gives
+ *                     +inf.  Values are read by key: the sign bit is not looked at.                   double energy[count][max_bursts]
+ *     peak[b][i]    = the largest s[b][x] of the burst that is not a NaN, as a key (the sign bit cleared).  Powers are ordered as
+ *                     unsigned integers; there is no floating-point compare.                           double peak[count][max_bursts]
+ *     peak_at[b][i] = the EARLIEST frame of the burst that holds peak[b][i].  A burst's first frame is a SET, so it is not a NaN:
+ *                     every burst has a peak.                                                          int32_t peak_at[count][max_bursts]
+ * beside counts[count] and edges[count][2 * max_bursts] as the burst lists reply them.  Any output may be NULL and is not touched
+ * then; a per-burst output (edges, energy, peak, peak_at) with max_bursts == 0 counts as absent; all absent: SP_ERR_INVALID_ARG.
+ * EVERY SLOT BEHIND min(counts[b], max_bursts) HOLDS 0xFF BYTES: -1 in the int arrays, the all-ones NaN pattern in the double arrays.
+ * Bursts cut off by max_bursts are not measured.  energy and peak are 8-byte aligned, the int arrays 4-byte aligned.  The refusals are
+ * those of the burst lists, in the same order; a peak plan returns SP_ERR_UNSUPPORTED.  width == 0 or count == 0: zeros in counts
+ * and the fill elsewhere.  The reply does not depend on the CU count, the window, the chunking of a host-fed request or
+ * SP_BURST_SEGMENT_FRAMES: the energy's cells are added with integer adds and the peak is folded in a strict total order - the
+ * larger key, of equal keys the smaller frame (csrc/sp_pulse_core.h, the one place the decision is made, for the kernels and for
+ * sp_debug_pulses) - so neither depends on the order of the frames.
+ * MEMORY: beside the burst lists' workspace the context keeps 8 * 68 * count * max_bursts bytes of cells (68 = spx::kSlots, csrc/
+ *   sp_exact_sum.h), 8 * count * max_bursts bytes of peak keys and 4 * count bytes of counts in a workspace of its own that grows to
+ *   the largest request so far, is never shrunk and is freed with the context; SP_ERR_NOMEM where it cannot be had.  max_bursts is
+ *   what sizes it, not the number of bursts found.
+ * How: the three burst launches run first, unchanged.  Behind them the workspace is zeroed and, on the burst kernels' grid (segments,
+ *   bands), one launch adds every ON frame's pieces to its burst's cells and folds its key into the burst's peak key with integer
+ *   atomics whose results are not used - the burst that enters a segment and the last one that starts in it gather in LDS first, so a
+ *   burst of a million frames does not hammer one address; a second launch on the same grid puts the earliest frame whose key is the
+ *   peak key into peak_at with an UNSIGNED atomic minimum (the -1 fill is the largest unsigned word); a third, a thread per listed
+ *   burst, rounds the cells once and stores energy and peak with plain stores.  No workgroup waits for another.  The per-burst
+ *   outputs are filled with 0xFF bytes on the stream in front of all that.
+ *
+ * sp_plan_execute_pulses: device operands, asynchronous on the context's stream, capturable once the workspaces have their sizes.  No
+ *   request number: the call may be interleaved with the other sp_plan_execute_* on one context without a synchronisation.
+ * sp_power_pulses: on a frame-major plane double[width * n] of the device, as sp_power_bursts.  Asynchronous.
+ * sp_series_pulses: the burst launches and the measurement alone on a band-major device series double[count * width], the companion of
+ *   sp_series_bursts with its limits.  Asynchronous.
+ * sp_render_pulses: host buffers, synchronous, as sp_render_bursts; the reply comes back in up to five copies.
+ * sp_plan_pulses_kernel_name_for: "frames_power+pulses" or "scratch_power+pulses", following sp_plan_power_kernel_name_for.
+ * sp_debug_pulses: (tests, no device needed) one band on the host through the host side of the code the kernels run; the outputs
+ *   are *count_out, edges_out[2 * max_bursts] and energy_out, peak_out, peak_at_out of max_bursts slots each, any of them NULL.
+ * Out of scope: the mean (energy / (end - start)) and the dB forms stay with the caller; the frequency of a burst is sp_*_track's
+ *   rows[b][peak_at], a gather the caller does; a minimum burst width or gap, peak plans, batches, groups, sharding.py, a per-burst row.
+ */
+int sp_plan_execute_pulses(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                           const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges, double *d_energy,
+                           double *d_peak, int32_t *d_peak_at);
+int sp_power_pulses(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count, const double *hi,
+                    const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges, double *d_energy, double *d_peak,
+                    int32_t *d_peak_at);
+int sp_series_pulses(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo,
+                     int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges, double *d_energy, double *d_peak, int32_t *d_peak_at);
+int sp_render_pulses(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                     int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts, int32_t *edges, double *energy,
+                     double *peak, int32_t *peak_at);
+const char *sp_plan_pulses_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_debug_pulses(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out, int32_t *edges_out,
+                    double *energy_out, double *peak_out, int32_t *peak_at_out);
 
 /*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.

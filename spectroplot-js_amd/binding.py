@@ -211,6 +211,13 @@ class Library:
         L.sp_plan_bursts_kernel_name_for.restype = C.c_char_p
         L.sp_plan_bursts_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_debug_bursts.argtypes = [vp, i32, dbl, dbl, i32, C.POINTER(C.c_uint32), vp]
+        L.sp_plan_execute_pulses.argtypes = [vp, vp, sz, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.sp_power_pulses.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.sp_series_pulses.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.sp_render_pulses.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.sp_plan_pulses_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_pulses_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_debug_pulses.argtypes = [vp, i32, dbl, dbl, i32, C.POINTER(C.c_uint32), vp, vp, vp, vp]
         L.sp_plan_execute_index.argtypes = [vp, vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_render_index.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, C.POINTER(_Reply), vp]
         L.sp_index_to_rgba.argtypes = [vp, vp, sz, vp, i32, vp]
@@ -363,6 +370,24 @@ def burst_scan(values, hi, lo, max_bursts):
     lib.check(lib.L.sp_debug_bursts(_p(v) if v.size else None, v.size, float(hi), float(lo), m, C.byref(total),
                                     _p(edges) if edges.size else None))
     return total.value, edges
+
+
+def pulse_scan(values, hi, lo, max_bursts):
+    """sp_debug_pulses: the bursts of one series as burst_scan() gives them and their measurements, through the host side of the code
+    the kernels run: (the total, edges int32 [max_bursts, 2], energy float64 [max_bursts], peak float64 [max_bursts], peak_at int32
+    [max_bursts]).  energy is math.fsum of the burst's frames (any NaN frame: NaN; otherwise any +inf: +inf), peak the largest frame
+    that is no NaN and peak_at the earliest frame that holds it; behind the listed bursts -1 and the all-ones NaN.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    m = int(max_bursts)
+    edges = np.zeros((max(m, 0), 2), np.int32)
+    energy, peak = np.zeros(max(m, 0), np.float64), np.zeros(max(m, 0), np.float64)
+    peak_at = np.zeros(max(m, 0), np.int32)
+    total = C.c_uint32()
+    lib = Library.get()
+    some = edges.size > 0
+    lib.check(lib.L.sp_debug_pulses(_p(v) if v.size else None, v.size, float(hi), float(lo), m, C.byref(total), _p(edges) if some else None,
+                                    _p(energy) if some else None, _p(peak) if some else None, _p(peak_at) if some else None))
+    return total.value, edges, energy, peak, peak_at
 
 
 def burst_pulses(edges_row, total):
@@ -851,6 +876,50 @@ class Context:
                                               _p(l) if count > 0 else None, int(max_bursts), C.c_void_p(d_counts or None),
                                               C.c_void_p(d_edges or None)))
 
+    def render_pulses(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, hi, lo, max_bursts, channel_mode=False, lut=None,
+                      fill=None):
+        """sp_render_pulses: the burst lists of the request as render_bursts() gives them and the measurements of every listed burst,
+        (counts uint32 [count], edges int32 [count, max_bursts, 2], energy float64 [count, max_bursts], peak float64 [count,
+        max_bursts], peak_at int32 [count, max_bursts]): energy is the exact sum of the burst's frames of the band sum rounded once
+        (math.fsum), peak the largest of them and peak_at the earliest frame that holds it; behind the listed bursts -1 and the
+        all-ones NaN.  fill: a byte the output arrays hold before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        m = max(int(max_bursts), 0)
+        counts = _filled(count, np.uint32, fill)
+        edges = _filled((count, m, 2), np.int32, fill)
+        energy, peak = _filled((count, m), np.float64, fill), _filled((count, m), np.float64, fill)
+        peak_at = _filled((count, m), np.int32, fill)
+        some = edges.size > 0
+        self._chk(self.lib.L.sp_render_pulses(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                              _p(h) if count else None, _p(l) if count else None, int(max_bursts), _p(counts),
+                                              _p(edges) if some else None, _p(energy) if some else None, _p(peak) if some else None,
+                                              _p(peak_at) if some else None))
+        return counts, edges, energy, peak, peak_at
+
+    def power_pulses(self, d_power, n, width, bands, hi, lo, max_bursts, d_counts, d_edges, d_energy, d_peak, d_peak_at):
+        """sp_power_pulses: power_bursts() and the measurements of the listed bursts of the f64 [width, n] plane at device address
+        d_power: energy and peak into f64 [count, max_bursts] at d_energy and d_peak, the peak's frame into int32 [count, max_bursts]
+        at d_peak_at (any address may be 0: not written).  Asynchronous on the context's stream."""
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        self._chk(self.lib.L.sp_power_pulses(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                             _p(h) if count else None, _p(l) if count else None, int(max_bursts),
+                                             C.c_void_p(d_counts or None), C.c_void_p(d_edges or None), C.c_void_p(d_energy or None),
+                                             C.c_void_p(d_peak or None), C.c_void_p(d_peak_at or None)))
+
+    def series_pulses(self, d_series, count, width, hi, lo, max_bursts, d_counts, d_edges, d_energy, d_peak, d_peak_at):
+        """sp_series_pulses: series_bursts() and the measurements of the listed bursts of the band-major f64 [count, width] series at
+        device address d_series, into the device arrays as for power_pulses.  Asynchronous on the context's stream.  The context
+        keeps 552 bytes per band and slot of max_bursts."""
+        count = int(count)
+        h, l = _burst_thresholds(hi, lo, max(count, 0))
+        self._chk(self.lib.L.sp_series_pulses(self.h, C.c_void_p(d_series or None), count, int(width), _p(h) if count > 0 else None,
+                                              _p(l) if count > 0 else None, int(max_bursts), C.c_void_p(d_counts or None),
+                                              C.c_void_p(d_edges or None), C.c_void_p(d_energy or None), C.c_void_p(d_peak or None),
+                                              C.c_void_p(d_peak_at or None)))
+
     def set_mean_window(self, nbytes=0):
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
@@ -1056,6 +1125,24 @@ class Plan:
                                                             _p(b) if count else None, count, _p(h) if count else None,
                                                             _p(l) if count else None, int(max_bursts), C.c_void_p(d_counts or None),
                                                             C.c_void_p(d_edges or None)))
+
+    def pulses_kernel_name_for(self, nbytes, width):
+        """What execute_pulses() launches for a request of this shape: "frames_power+pulses" or "scratch_power+pulses"."""
+        return self._kernel_name_for("pulses", nbytes, width)
+
+    def execute_pulses(self, d_bytes, nbytes, width, bands, hi, lo, max_bursts, d_counts, d_edges, d_energy, d_peak, d_peak_at):
+        """sp_plan_execute_pulses: execute_bursts() and, for every listed burst, its exact energy and its peak into the f64 [count,
+        max_bursts] device arrays at d_energy and d_peak and the earliest frame of the peak into the int32 [count, max_bursts] device
+        array at d_peak_at; -1 and the all-ones NaN behind the listed bursts (any address may be 0: not written).  Asynchronous on the
+        context's stream; bands, hi and lo are read before it returns.  Beside the band series the context keeps 552 bytes per band
+        and slot of max_bursts."""
+        b, count = _band_array(bands)
+        h, l = _burst_thresholds(hi, lo, count)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_pulses(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                            _p(b) if count else None, count, _p(h) if count else None,
+                                                            _p(l) if count else None, int(max_bursts), C.c_void_p(d_counts or None),
+                                                            C.c_void_p(d_edges or None), C.c_void_p(d_energy or None),
+                                                            C.c_void_p(d_peak or None), C.c_void_p(d_peak_at or None)))
 
     def power_to_db(self, d_power, count, d_db):
         """sp_plan_power_to_db: d_db[k] = (5 * log10(d_power[k]) + block_norm_db + gain) - gain for k < count (device addresses; in place

@@ -30,6 +30,7 @@
 #include "sp_occupancy_core.h"
 #include "sp_quantile_core.h"
 #include "sp_burst_core.h"
+#include "sp_pulse_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -117,6 +118,7 @@ struct sp_context {
     DeviceBuffer mean_ws;        // a mean request's exact-sum cells, u64[spx::kSlots][n] (sp_kernel_mean.h; grown, never shrunk)
     DeviceBuffer quantile_ws;    // a percentile request's whole plane as keys, u64[n][width] (sp_kernel_quantile.h; grown, never shrunk)
     DeviceBuffer burst_ws;       // a burst request's band series f64[count][width] and, behind it, its segments' summaries and carries (sp_kernel_burst.h; grown, never shrunk)
+    DeviceBuffer pulse_ws;       // a burst-measurement request's cells u64[count][max_bursts][spx::kSlots], peak keys u64[count][max_bursts] and, behind them, count uint32 for a request without a counts array (sp_kernel_pulse.h; grown, never shrunk)
     DeviceBuffer plane_window;   // a mean, band-power or track request: the block of frames of its plane that is being consumed (plane_blocks)
     size_t mean_window_bytes = 0; // sp_context_set_mean_window: the window's size at the most; 0 is the default, kPlaneWindowDefault
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
@@ -393,6 +395,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->mean_ws.release();
     ctx->quantile_ws.release();
     ctx->burst_ws.release();
+    ctx->pulse_ws.release();
     ctx->plane_window.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
@@ -2664,6 +2667,198 @@ extern "C" int sp_debug_bursts(const double *values, int32_t width, double hi, d
     std::vector<uint64_t> bits((size_t)width);
     if (width) memcpy(bits.data(), values, (size_t)width * sizeof(double));
     const uint32_t total = spb::scan(bits.data(), width, hi_key, lo_key, max_bursts, max_bursts > 0 ? edges_out : nullptr);
+    if (count_out) *count_out = total;
+    return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- burst measurements
+
+extern "C" const char *sp_plan_pulses_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+pulses", "scratch_power+pulses");
+}
+
+namespace {
+// The per-burst outputs of a measurement request, each count * max_bursts values, each may be null.
+struct PulseOut {
+    double *energy, *peak;
+    int32_t *peak_at;
+    bool any() const { return energy || peak || peak_at; }
+};
+
+// What every measurement entry point refuses of its outputs: burst_outputs' refusals in burst_outputs' order, with the three per-burst
+// arrays counted among what may be asked for, and their alignment behind.
+const char *pulse_outputs(int32_t count, int32_t max_bursts, const uint32_t *counts, const int32_t *edges, const PulseOut &o)
+{
+    if (max_bursts < 0) return "max_bursts >= 0 is required";
+    if (2ll * (long long)max_bursts * (long long)(count > 0 ? count : 0) > 0x7fffffffll) return "2 * max_bursts * count must fit 31 bits";
+    if (!counts && !((edges || o.any()) && max_bursts > 0))
+        return "burst measurements need a counts array or, with max_bursts > 0, an edges, energy, peak or peak_at array";
+    if (((uintptr_t)counts & 3) != 0) return "the burst counts must be a 4-byte aligned array of count uint32";
+    if (((uintptr_t)edges & 3) != 0) return "the burst edges must be a 4-byte aligned array of count * 2 * max_bursts int32";
+    if (((uintptr_t)o.energy & 7) != 0 || ((uintptr_t)o.peak & 7) != 0)
+        return "the burst energy and peak must be 8-byte aligned arrays of count * max_bursts doubles";
+    if (((uintptr_t)o.peak_at & 3) != 0) return "the burst peak_at must be a 4-byte aligned array of count * max_bursts int32";
+    return nullptr;
+}
+
+// The context's measurement workspace for `count` bands of max_bursts bursts: the launcher's work area and count uint32 behind it.
+int pulse_reserve(sp_context *ctx, int32_t count, int32_t max_bursts)
+{
+    const int rc = ctx->pulse_ws.reserve(spk::pulse_work_bytes(count, max_bursts) + sizeof(uint32_t) * (size_t)count);
+    return rc ? fail(ctx, rc, "burst measurement workspace: out of device memory") : (int)SP_OK;
+}
+
+// The 0xFF fill of the per-burst outputs, on the stream in front of the launches.
+int pulse_fill(sp_context *ctx, int32_t count, int32_t max_bursts, int32_t *edges, const PulseOut &o)
+{
+    const size_t bursts = (size_t)count * (size_t)max_bursts;
+    if (!bursts) return SP_OK;
+    if (edges) SP_HIP(ctx, hipMemsetAsync(edges, 0xFF, sizeof(int32_t) * 2 * bursts, ctx->stream));
+    if (o.energy) SP_HIP(ctx, hipMemsetAsync(o.energy, 0xFF, sizeof(double) * bursts, ctx->stream));
+    if (o.peak) SP_HIP(ctx, hipMemsetAsync(o.peak, 0xFF, sizeof(double) * bursts, ctx->stream));
+    if (o.peak_at) SP_HIP(ctx, hipMemsetAsync(o.peak_at, 0xFF, sizeof(int32_t) * bursts, ctx->stream));
+    return SP_OK;
+}
+
+// The burst launches (burst_scan, unchanged) and the measurement behind them on a band-major series of the device.  Where the caller
+// has no counts array the bursts are counted into the workspace: k_pulse_finish reads how many are listed.
+int pulse_scan(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo, int32_t max_bursts,
+               void *records, uint32_t *counts, int32_t *edges, const PulseOut &o)
+{
+    const bool measured = o.any() && max_bursts > 0;
+    uint32_t *const ws_counts = (uint32_t *)((char *)ctx->pulse_ws.p + spk::pulse_work_bytes(count, max_bursts));
+    uint32_t *const total = counts || !measured ? counts : ws_counts;
+    const int rc = burst_scan(ctx, d_series, count, width, hi, lo, max_bursts, records, total, max_bursts > 0 ? edges : nullptr);
+    if (rc || !measured) return rc;
+    uint64_t hi_key[SP_MAX_BANDS], lo_key[SP_MAX_BANDS];
+    (void)burst_keys(hi, lo, count, hi_key, lo_key);   // (checked before)
+    SP_HIP(ctx, spk::launch_pulses(d_series, count, width, hi_key, lo_key, max_bursts, (const unsigned long long *)records, total,
+                                   ctx->pulse_ws.p, o.energy, o.peak, o.peak_at, ctx->stream));
+    return SP_OK;
+}
+
+// The burst lists' kind with three more outputs: the series is made as BurstKind makes it, the workspace of the measurement is reserved
+// beside burst_ws, the fill covers the per-burst arrays, and finish() runs the measurement behind the three burst launches.
+struct PulseKind {
+    static constexpr const char *kRender = "sp_render_pulses";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    BurstKind b;
+    PulseOut o;
+
+    bool per_burst() const { return b.max_bursts > 0; }
+    size_t bursts() const { return (size_t)b.count * (size_t)b.max_bursts; }
+    int check(const PlaneShape &p) const
+    {
+        if (const char *why = spgeo::check_bands(p.n, b.bands, b.count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (const char *why = burst_keys(b.hi, b.lo, b.count, nullptr, nullptr)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (const char *why = pulse_outputs(b.count, b.max_bursts, b.counts, b.edges, o)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &p) const { return b.empty(p); }
+    int clear(const PlaneShape &p) const
+    {
+        int rc = p.ctx->burst_ws.reserve(b.series_bytes(p) + spk::burst_record_bytes(b.count, p.width));
+        if (rc) return fail(p.ctx, rc, "burst workspace: out of device memory");
+        rc = pulse_reserve(p.ctx, b.count, b.max_bursts);
+        return rc ? rc : pulse_fill(p.ctx, b.count, b.max_bursts, b.edges, o);
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const { return b.consume(p, d_plane, frames, x_base); }
+    int finish(const PlaneShape &p) const
+    {
+        return pulse_scan(p.ctx, (const double *)p.ctx->burst_ws.p, b.count, p.width, b.hi, b.lo, b.max_bursts,
+                          (char *)p.ctx->burst_ws.p + b.series_bytes(p), b.counts, b.edges, o);
+    }
+    // render_small: the doubles in front (8-byte aligned), then counts, edges and peak_at
+    size_t small_bytes(const PlaneShape &) const
+    {
+        return (2 * sizeof(double) + 3 * sizeof(int32_t)) * bursts() + sizeof(uint32_t) * (size_t)b.count;
+    }
+    PulseKind on_device(const PlaneShape &, void *small) const
+    {
+        double *const d = (double *)small;
+        int32_t *const w = (int32_t *)(d + 2 * bursts());
+        const bool per = per_burst();
+        return {{b.bands, b.count, b.hi, b.lo, b.max_bursts, b.counts ? (uint32_t *)w : nullptr, per && b.edges ? w + b.count : nullptr},
+                {per && o.energy ? d : nullptr, per && o.peak ? d + bursts() : nullptr,
+                 per && o.peak_at ? w + b.count + 2 * bursts() : nullptr}};
+    }
+    int tail(sp_plan *, const PlaneShape &p, int32_t, const PulseKind &host, hipError_t &e) const
+    {
+        hipStream_t st = p.ctx->stream;
+        if (b.counts) e = hipMemcpyAsync(host.b.counts, b.counts, sizeof(uint32_t) * (size_t)b.count, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && b.edges) e = hipMemcpyAsync(host.b.edges, b.edges, sizeof(int32_t) * 2 * bursts(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && o.energy) e = hipMemcpyAsync(host.o.energy, o.energy, sizeof(double) * bursts(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && o.peak) e = hipMemcpyAsync(host.o.peak, o.peak, sizeof(double) * bursts(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && o.peak_at) e = hipMemcpyAsync(host.o.peak_at, o.peak_at, sizeof(int32_t) * bursts(), hipMemcpyDeviceToHost, st);
+        return SP_OK;
+    }
+};
+
+// the kind of an entry point's arguments (a per-burst array with max_bursts == 0 counts as absent: pulse_fill, pulse_scan, on_device)
+PulseKind pulse_kind(const int32_t *bands, int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts,
+                     int32_t *edges, double *energy, double *peak, int32_t *peak_at)
+{
+    return {{bands, count, hi, lo, max_bursts, counts, edges}, {energy, peak, peak_at}};
+}
+}  // namespace
+
+extern "C" int sp_power_pulses(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                               const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges, double *d_energy,
+                               double *d_peak, int32_t *d_peak_at)
+{
+    return plane_resident(ctx, "sp_power_pulses", d_power, n, width,
+                          pulse_kind(bands, count, hi, lo, max_bursts, d_counts, d_edges, d_energy, d_peak, d_peak_at));
+}
+
+extern "C" int sp_plan_execute_pulses(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                      const double *hi, const double *lo, int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges,
+                                      double *d_energy, double *d_peak, int32_t *d_peak_at)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, pulse_kind(bands, count, hi, lo, max_bursts, d_counts, d_edges, d_energy, d_peak, d_peak_at));
+}
+
+extern "C" int sp_render_pulses(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                                int32_t count, const double *hi, const double *lo, int32_t max_bursts, uint32_t *counts, int32_t *edges,
+                                double *energy, double *peak, int32_t *peak_at)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, 0, pulse_kind(bands, count, hi, lo, max_bursts, counts, edges, energy, peak, peak_at));
+}
+
+extern "C" int sp_series_pulses(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const double *hi, const double *lo,
+                                int32_t max_bursts, uint32_t *d_counts, int32_t *d_edges, double *d_energy, double *d_peak, int32_t *d_peak_at)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (count < 0 || count > SP_MAX_BANDS || width < 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_pulses: count within 0 .. SP_MAX_BANDS and width >= 0 are required");
+    const PulseOut o{d_energy, d_peak, d_peak_at};
+    if (const char *why = burst_keys(hi, lo, count, nullptr, nullptr)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (const char *why = pulse_outputs(count, max_bursts, d_counts, d_edges, o)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (count == 0) return SP_OK;
+    if ((width > 0 && !d_series) || ((uintptr_t)d_series & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_pulses: d_series must be an 8-byte aligned device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] {
+        int rc = ctx->burst_ws.reserve(spk::burst_record_bytes(count, width));
+        if (rc) return fail(ctx, rc, "burst workspace: out of device memory");
+        rc = pulse_reserve(ctx, count, max_bursts);
+        if (!rc) rc = pulse_fill(ctx, count, max_bursts, d_edges, o);
+        return rc ? rc : pulse_scan(ctx, d_series, count, width, hi, lo, max_bursts, ctx->burst_ws.p, d_counts, d_edges, o);
+    });
+}
+
+extern "C" int sp_debug_pulses(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out,
+                               int32_t *edges_out, double *energy_out, double *peak_out, int32_t *peak_at_out)
+{
+    if (width < 0 || (width > 0 && !values)) return SP_ERR_INVALID_ARG;
+    uint64_t hi_key = 0, lo_key = 0;
+    if (burst_keys(&hi, &lo, 1, &hi_key, &lo_key) || pulse_outputs(1, max_bursts, count_out, edges_out, PulseOut{energy_out, peak_out, peak_at_out}))
+        return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> bits((size_t)width);
+    if (width) memcpy(bits.data(), values, (size_t)width * sizeof(double));
+    std::vector<int32_t> own_edges(edges_out ? 0 : 2 * (size_t)max_bursts);
+    const uint32_t total = spp::measure(bits.data(), width, hi_key, lo_key, max_bursts, edges_out ? edges_out : own_edges.data(),
+                                        (uint64_t *)energy_out, (uint64_t *)peak_out, peak_at_out);
     if (count_out) *count_out = total;
     return SP_OK;
 }

@@ -65,6 +65,17 @@ void launch_quantile_select(const unsigned long long *keys, int n, int width, co
 size_t burst_record_bytes(int count, int width);
 void launch_bursts(const double *series, int count, int width, const uint64_t *hi_key, const uint64_t *lo_key, int max_bursts,
                    unsigned long long *records, uint32_t *counts, int32_t *edges, hipStream_t stream);
+// The burst measurements behind launch_bursts on the same series, keys and `records` (the carries are read from them): for the listed
+// bursts i < min(counts[b], max_bursts) of band b energy[b][i], peak[b][i] and peak_at[b][i], each of which may be null - not all.
+// `counts` is NOT null here: launch_bursts' counts, the caller's or a workspace's.  The caller has filled the three outputs with 0xFF
+// bytes.  `work`: pulse_work_bytes(count, max_bursts) bytes of device memory, 8-byte aligned - the bursts' cells
+// u64[count][max_bursts][spx::kSlots] and their peak keys u64[count][max_bursts] - which this zeroes on the stream in front.  A memset
+// and up to three launches; none where count == 0, width == 0 or max_bursts == 0.  (k_pulse_accumulate, k_pulse_peak_frame,
+// k_pulse_finish and this launcher are sp_pulse.hip, a unit of their own.)
+size_t pulse_work_bytes(int count, int max_bursts);
+hipError_t launch_pulses(const double *series, int count, int width, const uint64_t *hi_key, const uint64_t *lo_key, int max_bursts,
+                         const unsigned long long *records, const uint32_t *counts, void *work, double *energy, double *peak,
+                         int32_t *peak_at, hipStream_t stream);
 
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 

@@ -168,3 +168,26 @@ def bursts(plan, capture, width, bands, hi, lo, max_bursts):
         plan.execute_bursts(capture.data_ptr(), capture.numel(), int(width), bands, hi, lo, int(max_bursts),
                             counts.data_ptr() if counts.numel() else 0, edges.data_ptr() if edges.numel() else 0)
     return counts, edges
+
+
+def pulses(plan, capture, width, bands, hi, lo, max_bursts):
+    """The burst lists of `capture` as bursts() gives them and the measurements of every listed burst, five tensors on the capture's
+    device: counts int32 [count], edges int32 [count, max_bursts, 2], energy float64 [count, max_bursts], peak float64 [count,
+    max_bursts] and peak_at int32 [count, max_bursts].  energy is the exact sum of the burst's frames of the band sum rounded once
+    (math.fsum), peak the largest of them and peak_at the earliest frame that holds it; behind the listed bursts -1 and the all-ones
+    NaN (include/spectroplot_hip.h, "Burst measurements").  Queued on torch's current stream exactly as bursts() queues its lists."""
+    _check_capture("pulses", capture)
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    m = max(int(max_bursts), 0)
+    dev = capture.device
+    counts = torch.empty((len(bands),), dtype=torch.int32, device=dev)
+    edges = torch.empty((len(bands), m, 2), dtype=torch.int32, device=dev)
+    energy = torch.empty((len(bands), m), dtype=torch.float64, device=dev)
+    peak = torch.empty((len(bands), m), dtype=torch.float64, device=dev)
+    peak_at = torch.empty((len(bands), m), dtype=torch.int32, device=dev)
+    some = edges.numel() > 0
+    with _on_current_stream(plan.ctx, dev, (capture, counts, edges, energy, peak, peak_at)):
+        plan.execute_pulses(capture.data_ptr(), capture.numel(), int(width), bands, hi, lo, int(max_bursts),
+                            counts.data_ptr() if counts.numel() else 0, edges.data_ptr() if some else 0, energy.data_ptr() if some else 0,
+                            peak.data_ptr() if some else 0, peak_at.data_ptr() if some else 0)
+    return counts, edges, energy, peak, peak_at
