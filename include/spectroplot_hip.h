@@ -28,6 +28,7 @@
  *   sp_debug_batch_plan      (none)                     (tests) the host's work list for a batch
  *   sp_plan_debug_launch     (none)                     (tests) the launch sp_plan_execute would make for a request
  *   sp_debug_frames_launch   (none)                     (tests) the frame-loop kernels' launch rule alone
+ *   sp_debug_scratch_launch  (none)                     (tests) the scratch kernels' launch shape alone
  *   sp_merge_replies(_batch) lib/spectroplot.js:1229-1238   the caller's merge of the slices' histograms and dBfs range, on the device
  *   sp_place_strips          lib/spectroplot.js:1241-1244   the caller's putImageData of every slice's strip, on the device
  *   sp_group_render          lib/spectroplot.js:1206-1244, lib/samples.js:253-258   the caller's sliced render: one slice per device, the
@@ -417,6 +418,14 @@ int sp_plan_debug_launch(const sp_plan *plan, size_t nbytes, int32_t width, cons
  */
 int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count, int32_t cu_count, int32_t gf_fixed, int64_t *out, size_t capacity,
                            size_t *used);
+/*
+ * (tests) The launch shape of the portable ("scratch") kernels alone (scratch_blocks in sp_api.hip, scratch_wide in sp_launch.h), without
+ * a plan or a device: one launch over `frames` frames - or columns of a peak request - at n = 2 ... SP_MAX_N on a part with cu_count
+ * CUs, whose workgroups own `slabs` slabs of n doubles each (2: image and power plane, 3: a held peak, 4: traces).  out[] receives 2
+ * int64 words: the workgroups - min(frames, 4 * cu_count, 256 MiB / (8 * slabs * n)), at least 1; workgroup b serves the frames
+ * b, b + workgroups, ... - and whether the kernel is the variant that runs four radix-2 stages per barrier (n >= 4096).
+ */
+int sp_debug_scratch_launch(int32_t n, int32_t slabs, int32_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
 
 /* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else).
  * A peak plan answers what its M >= 2 requests take: "frames_peak" (64 <= n <= 1024 and what "frames" asks for) or "scratch_radix2". */

@@ -14,6 +14,9 @@ const siggen = require('./siggen.js')
 const gdir = path.resolve(process.argv[2] || path.join(__dirname, '../../tests/golden'))
 const spec = JSON.parse(fs.readFileSync(path.join(gdir, 'cases.json'), 'utf8'))
 const expected = JSON.parse(fs.readFileSync(path.join(gdir, 'worker_expected.json'), 'utf8'))
+// the worker cases beyond n = 16384 and their vectors
+spec.worker_cases.push(...JSON.parse(fs.readFileSync(path.join(gdir, 'cases_large.json'), 'utf8')).worker_cases)
+expected.push(...JSON.parse(fs.readFileSync(path.join(gdir, 'worker_expected_large.json'), 'utf8')))
 const cmapIndex = JSON.parse(fs.readFileSync(path.join(gdir, 'cmaps.json'), 'utf8'))
 const cmapBin = fs.readFileSync(path.join(gdir, 'cmaps.bin'))
 

@@ -3,7 +3,7 @@
  *
  * TEST INFRASTRUCTURE (container-only).  This file is copied by oracle/gen_golden.js into a scratch directory
  * OUTSIDE the repo, next to a scratch copy of the reference's lib/ directory, and executed there with
- *   node --experimental-specifier-resolution=node ref_harness.mjs <repo> <cases.json> <outdir>
+ *   node --experimental-specifier-resolution=node ref_harness.mjs <repo> <cases.json> <outdir> [<cases_large.json>]
  * (recipe: SURVEY.md §8c).  Nothing from the reference is ever copied into the repo; only the outputs
  * (vectors) written here are committed under tests/golden/.
  *
@@ -16,7 +16,7 @@ import path from 'path'
 import crypto from 'crypto'
 
 const require = createRequire(import.meta.url)
-const [repo, casesFile, outdir] = process.argv.slice(2)
+const [repo, casesFile, outdir, largeFile] = process.argv.slice(2)
 const siggen = require(path.join(repo, 'oracle/js/siggen.js'))
 
 let captured = null
@@ -112,7 +112,9 @@ const run = async () => {
 
     // ---- worker cases ----------------------------------------------------------------------------------------
     const results = []
-    for (const c of spec.worker_cases) {
+    // (the cases of cases_large.json run behind those of cases.json; their results go to a file of their own)
+    const large = largeFile ? JSON.parse(fs.readFileSync(largeFile, 'utf8')).worker_cases : []
+    for (const c of spec.worker_cases.concat(large)) {
         const input = makeInput(c)
         const wf = windows[c.window + 'Window']
         const { window: windowc, weight } = wf(c.n)
@@ -175,7 +177,8 @@ const run = async () => {
         }
         results.push(out)
     }
-    fs.writeFileSync(path.join(outdir, 'worker_expected.json'), JSON.stringify(results, null, 0))
+    fs.writeFileSync(path.join(outdir, 'worker_expected.json'), JSON.stringify(results.slice(0, spec.worker_cases.length), null, 0))
+    if (largeFile) fs.writeFileSync(path.join(outdir, 'worker_expected_large.json'), JSON.stringify(results.slice(spec.worker_cases.length), null, 0))
 
     // ---- window KAT (lib/windows.js) -----------------------------------------------------------------------------
     {

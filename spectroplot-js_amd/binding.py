@@ -228,6 +228,7 @@ class Library:
         L.sp_plan_execute_density.argtypes = [vp, vp, sz, i32, vp, i32]
         L.sp_render_density.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp]
         L.sp_debug_density_launch.argtypes = [i32, i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
+        L.sp_debug_scratch_launch.argtypes = [i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -481,6 +482,16 @@ def debug_frames_launch(n, lut_len, count, cu_count, gf_fixed=0):
         return None
     lib.check(rc)
     return tuple(int(v) for v in out)
+
+
+def debug_scratch_launch(n, slabs, frames, cu_count):
+    """The scratch kernels' launch shape alone (sp_debug_scratch_launch): (workgroups, whether the kernel is the four-stage variant)
+    of one launch over `frames` frames whose workgroups own `slabs` slabs of n doubles each."""
+    lib = Library.get()
+    out = np.zeros(2, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_scratch_launch(int(n), int(slabs), int(frames), int(cu_count), out.ctypes.data_as(C.c_void_p), 2, C.byref(used)))
+    return int(out[0]), bool(out[1])
 
 
 DENSITY_LAUNCH_FIELDS = ("workgroups", "rows", "frames", "lds_bytes", "bands", "pieces")

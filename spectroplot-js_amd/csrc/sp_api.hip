@@ -1089,6 +1089,19 @@ extern "C" int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count,
     return SP_OK;
 }
 
+// (tests) The launch shape of the scratch kernels alone, without a plan or a device: scratch_blocks' answer for a launch over `frames`
+// frames whose workgroups own `slabs` slabs of n doubles each on a part with cu_count CUs, and spk::scratch_wide's, as dispatch_scratch
+// asks it.
+extern "C" int sp_debug_scratch_launch(int32_t n, int32_t slabs, int32_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used)
+{
+    if (n < 2 || n > SP_MAX_N || sphost::log2_exact(n) < 0 || slabs < 1 || frames < 1 || cu_count < 1 || !used) return SP_ERR_INVALID_ARG;
+    const int64_t v[] = {scratch_blocks(slabs, n, frames, cu_count), spk::scratch_wide(n) ? 1 : 0};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- merge of slice replies
 
 extern "C" int sp_merge_replies(sp_context *ctx, const void *d_records, int32_t count, int32_t lut_len, uint64_t *d_c_hist,

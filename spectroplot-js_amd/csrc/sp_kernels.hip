@@ -27,13 +27,13 @@ int dispatch_format(int32_t fmt, F &&f)
 }
 
 // A scratch kernel's format and WIDE variant: launch(F, WIDE, grid, block) - F: the format as an integral_constant, WIDE:
-// std::true_type from n = 4096 on.
+// std::true_type where spk::scratch_wide(n).
 template <typename Launch>
 int dispatch_scratch(int format, int n, unsigned blocks, Launch &&launch)
 {
     return dispatch_format(format, [&](auto F) {
         const dim3 grid(blocks), block(spk::kScratchThreads);
-        if (n >= 4096) launch(F, std::true_type{}, grid, block);
+        if (spk::scratch_wide(n)) launch(F, std::true_type{}, grid, block);
         else launch(F, std::false_type{}, grid, block);
     });
 }

@@ -13,7 +13,10 @@ struct BatchItem;   // sp_kernel_frames_batch.h
 
 namespace spk {
 
-// The scratch kernels over `blocks` workgroups (a.scratch holds their slabs); the four-stage variants from n = 4096 on.
+// Whether a scratch kernel runs as its four-stage (WIDE) variant: from n = 4096 on, where every thread still has a 16-point item.
+inline bool scratch_wide(int n) { return n >= 4096; }
+
+// The scratch kernels over `blocks` workgroups (a.scratch holds their slabs); the four-stage variants where scratch_wide(a.n).
 // k_scratch_radix2 holds the peak over peak_m sub-frames per column where `hold`.
 int launch_scratch_radix2(const FrameArgs &a, int format, unsigned blocks, bool hold, int peak_m, int peak_nsamp, hipStream_t stream);
 int launch_scratch_traces(const FrameArgs &a, int format, unsigned blocks, unsigned long long *ws, hipStream_t stream);

@@ -34,8 +34,12 @@ class Golden:
     def __init__(self):
         with open(os.path.join(GDIR, "cases.json")) as f:
             self.spec = json.load(f)
+        with open(os.path.join(GDIR, "cases_large.json")) as f:      # the worker cases beyond n = 16384
+            self.spec["worker_cases"] += json.load(f)["worker_cases"]
         with open(os.path.join(GDIR, "worker_expected.json")) as f:
             self.expected = {e["name"]: e for e in json.load(f)}
+        with open(os.path.join(GDIR, "worker_expected_large.json")) as f:
+            self.expected.update({e["name"]: e for e in json.load(f)})
         with open(os.path.join(GDIR, "cmaps.json")) as f:
             self.cmap_index = {e["name"]: e for e in json.load(f)}
         self.cmap_bin = np.fromfile(os.path.join(GDIR, "cmaps.bin"), dtype=np.uint8)

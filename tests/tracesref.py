@@ -27,15 +27,19 @@ def fold(db):
     return tmin, tmax
 
 
-def expected(fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False):
-    """{"trace_min": f64[n], "trace_max": f64[n]} in row order, and the oracle's "dBfs_min" / "dBfs_max" of the same request."""
+def expected(fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, columns=False):
+    """{"trace_min": f64[n], "trace_max": f64[n]} in row order, and the oracle's "dBfs_min" / "dBfs_max" of the same request.
+    columns: also "min_column" / "max_column", int [n] in bin order: the first frame that holds the bin's smallest / largest |X|^2."""
     ref = pyoracle.render(fmt, data, n, windowc, block_norm, gain, rng, _LUT, width, channel_mode, False, planes=True)
     tmin, tmax = fold(ref["db"])
     y = rows(n)
     out_min, out_max = np.empty(n), np.empty(n)
     out_min[y] = tmin
     out_max[y] = tmax
-    return {"trace_min": out_min, "trace_max": out_max, "dBfs_min": ref["dBfs_min"], "dBfs_max": ref["dBfs_max"]}
+    out = {"trace_min": out_min, "trace_max": out_max, "dBfs_min": ref["dBfs_min"], "dBfs_max": ref["dBfs_max"]}
+    if columns:
+        out["min_column"], out["max_column"] = np.argmin(ref["abs2"], axis=0), np.argmax(ref["abs2"], axis=0)
+    return out
 
 
 def same_bits(a, b):
