@@ -29,6 +29,7 @@
  *   sp_plan_debug_launch     (none)                     (tests) the launch sp_plan_execute would make for a request
  *   sp_debug_frames_launch   (none)                     (tests) the frame-loop kernels' launch rule alone
  *   sp_debug_scratch_launch  (none)                     (tests) the scratch kernels' launch shape alone
+ *   sp_context_debug_set_cu_count  (none)               (tests) the CU count a context's launches are shaped by
  *   sp_merge_replies(_batch) lib/spectroplot.js:1229-1238   the caller's merge of the slices' histograms and dBfs range, on the device
  *   sp_place_strips          lib/spectroplot.js:1241-1244   the caller's putImageData of every slice's strip, on the device
  *   sp_group_render          lib/spectroplot.js:1206-1244, lib/samples.js:253-258   the caller's sliced render: one slice per device, the
@@ -426,6 +427,16 @@ int sp_debug_frames_launch(int32_t n, int32_t lut_len, int64_t count, int32_t cu
  * b, b + workgroups, ... - and whether the kernel is the variant that runs four radix-2 stages per barrier (n >= 4096).
  */
 int sp_debug_scratch_launch(int32_t n, int32_t slabs, int32_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
+/*
+ * (tests) The CU count that shapes every launch on this context: the grids and frames per group of the six frame-loop kernels
+ * (frames_launch_rule), a batch's work list, the scratch kernels' workgroups (at most 4 per CU), the pieces of a mean's accumulation
+ * and the grid of sp_plan_power_to_db.  A context starts with its device's own count (hipGetDeviceProperties); cu_count = 1 ... that
+ * count replaces it - an MI355X in a partition mode reports 128, 64 or 32 - and 0 puts the device's own back.  Anything else returns
+ * SP_ERR_INVALID_ARG and changes nothing: no launch ever asks for more workgroups than the part at hand would be given without an
+ * override.  Plans read the count when they launch, so the setting holds from the next call on the context, and
+ * sp_plan_debug_launch reports it.  No reply depends on it, and the tests hold that.
+ */
+int sp_context_debug_set_cu_count(sp_context *ctx, int32_t cu_count);
 
 /* Name of the kernel sp_plan_execute launches: "frames" (64 <= n <= 8192, LUT <= 256 entries) or "scratch_radix2" (everything else).
  * A peak plan answers what its M >= 2 requests take: "frames_peak" (64 <= n <= 1024 and what "frames" asks for) or "scratch_radix2". */
@@ -553,6 +564,10 @@ int sp_power_mean(sp_context *ctx, const double *d_power, int32_t n, int32_t wid
 int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_mean);
 int sp_render_mean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *mean);
 int sp_context_set_mean_window(sp_context *ctx, size_t bytes);
+/* (tests, no device needed) The grid of the accumulation behind `frames` >= 1 frames of a plane of n rows on a part with cu_count CUs:
+ * out[] receives 3 int64 words - the bands of 64 rows, the pieces the frames are cut into (about 4 workgroups per CU, no piece below 32
+ * frames) and the frames per piece (the last piece may be shorter).  *used = words needed (SP_ERR_INVALID_ARG if capacity is smaller). */
+int sp_debug_mean_launch(int32_t n, int64_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
 int sp_debug_exact_sum(const double *values, size_t count, double *sum);
 const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 

@@ -229,6 +229,8 @@ class Library:
         L.sp_render_density.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp]
         L.sp_debug_density_launch.argtypes = [i32, i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
         L.sp_debug_scratch_launch.argtypes = [i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
+        L.sp_context_debug_set_cu_count.argtypes = [vp, i32]
+        L.sp_debug_mean_launch.argtypes = [i32, C.c_int64, i32, vp, sz, C.POINTER(sz)]
 
     @classmethod
     def get(cls):
@@ -492,6 +494,15 @@ def debug_scratch_launch(n, slabs, frames, cu_count):
     used = C.c_size_t()
     lib.check(lib.L.sp_debug_scratch_launch(int(n), int(slabs), int(frames), int(cu_count), out.ctypes.data_as(C.c_void_p), 2, C.byref(used)))
     return int(out[0]), bool(out[1])
+
+
+def debug_mean_launch(n, frames, cu_count):
+    """The grid of a mean's accumulation alone (sp_debug_mean_launch): (bands of 64 rows, pieces of the frames, frames per piece)."""
+    lib = Library.get()
+    out = np.zeros(3, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_mean_launch(int(n), int(frames), int(cu_count), out.ctypes.data_as(C.c_void_p), 3, C.byref(used)))
+    return tuple(int(v) for v in out)
 
 
 DENSITY_LAUNCH_FIELDS = ("workgroups", "rows", "frames", "lds_bytes", "bands", "pieces")
@@ -935,6 +946,11 @@ class Context:
         """sp_context_set_mean_window: the bytes of plane a mean request renders before it accumulates them (0: the default, 64 MiB).
         The result does not depend on it (tests)."""
         self._chk(self.lib.L.sp_context_set_mean_window(self.h, int(nbytes)))
+
+    def set_cu_count(self, cu=0):
+        """sp_context_debug_set_cu_count: the CU count every launch on this context is shaped by from the next call on, 1 ... the
+        device's own (0: the device's own again; anything else is refused).  The result does not depend on it (tests)."""
+        self._chk(self.lib.L.sp_context_debug_set_cu_count(self.h, int(cu)))
 
     def render_index(self, fmt, data, n, windowc, block_norm, gain, rng, lut, width, channel_mode=False, waterfall=False,
                      detector="sample", want_index=True, fill=None):

@@ -108,7 +108,8 @@ struct sp_context {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string error;
-    int cu_count = 256;
+    int cu_count = 256;          // what every launch is shaped by: the device's own count, or sp_context_debug_set_cu_count's
+    int device_cu_count = 256;   // hipGetDeviceProperties' multiProcessorCount (what an override of 0 puts back)
     // workspace of the frame loop
     DeviceBuffer frame_minmax;   // 2 * width doubles (the scratch kernel's frame extremes, read by k_finish_frames)
     DeviceBuffer partial;        // [0,4) the number of the last request k_frames has started; the scratch kernel's {min,max} and histogram accumulators
@@ -374,7 +375,7 @@ extern "C" int sp_context_create(int32_t device, sp_context **out)
     }
     ctx->stream = ctx->own_stream;
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = ctx->device_cu_count = prop.multiProcessorCount;
     (void)hipEventCreate(&ctx->ev0);
     (void)hipEventCreate(&ctx->ev1);
     *out = ctx;
@@ -1070,6 +1071,16 @@ extern "C" int sp_plan_debug_launch(const sp_plan *plan, size_t nbytes, int32_t 
     *used = sizeof v / sizeof v[0];
     if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
     memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+// (tests) The CU count the context's launches are shaped by: 1 ... the device's own, 0 puts the device's own back.  Never more than the
+// part has: the frame loop's bounded wait for workgroup 0 was reasoned for grids that are resident at once.  Plans read ctx->cu_count
+// when they launch, so the next call on the context sees it.
+extern "C" int sp_context_debug_set_cu_count(sp_context *ctx, int32_t cu_count)
+{
+    if (!ctx || cu_count < 0 || cu_count > ctx->device_cu_count) return SP_ERR_INVALID_ARG;
+    ctx->cu_count = cu_count ? cu_count : ctx->device_cu_count;
     return SP_OK;
 }
 
@@ -2002,6 +2013,19 @@ extern "C" int sp_context_set_mean_window(sp_context *ctx, size_t bytes)
 {
     if (!ctx) return SP_ERR_INVALID_ARG;
     ctx->mean_window_bytes = bytes;
+    return SP_OK;
+}
+
+// (tests) k_mean_accumulate's grid for `frames` frames of n rows on a part with cu_count CUs, from the function its launch calls.
+extern "C" int sp_debug_mean_launch(int32_t n, int64_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used)
+{
+    if (n < 1 || frames < 1 || cu_count < 1 || !used) return SP_ERR_INVALID_ARG;
+    long long shape[3];
+    spk::mean_launch_shape(n, frames, cu_count, shape);
+    const int64_t v[] = {shape[0], shape[1], shape[2]};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
     return SP_OK;
 }
 

@@ -103,11 +103,17 @@ void launch_power_to_db(const double *d_power, size_t count, double block_norm_d
     hipLaunchKernelGGL(k_power_to_db, dim3((unsigned)blocks), dim3(256), 0, stream, d_power, count, block_norm_db, gain, d_db);
 }
 
-void launch_mean_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream)
+void mean_launch_shape(int n, long long frames, int cu_count, long long shape[3])
 {
     const int pieces = mean_pieces(n, frames, cu_count);
-    const long long per = (frames + pieces - 1) / pieces;
-    hipLaunchKernelGGL(k_mean_accumulate, dim3((unsigned)mean_bands(n), (unsigned)pieces), dim3(kMeanThreads), 0, stream, plane, n, frames, per, ws);
+    shape[0] = mean_bands(n), shape[1] = pieces, shape[2] = (frames + pieces - 1) / pieces;
+}
+
+void launch_mean_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream)
+{
+    long long shape[3];
+    mean_launch_shape(n, frames, cu_count, shape);
+    hipLaunchKernelGGL(k_mean_accumulate, dim3((unsigned)shape[0], (unsigned)shape[1]), dim3(kMeanThreads), 0, stream, plane, n, frames, shape[2], ws);
 }
 
 void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream)

@@ -33,6 +33,8 @@ void launch_power_to_db(const double *d_power, size_t count, double block_norm_d
 
 // the `frames` > 0 frames of the frame-major plane (n rows each) added into the exact-sum workspace; the workspace into the mean
 void launch_mean_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream);
+// ... and the grid launch_mean_accumulate gives k_mean_accumulate: {bands of rows, pieces of the frames, frames per piece}
+void mean_launch_shape(int n, long long frames, int cu_count, long long shape[3]);
 void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream);
 // band[b * stride + x_base + x] = the exact sum of the rows [bands[2 b], bands[2 b + 1]) of frame x of the frame-major plane, for its
 // `frames` > 0 frames and the `count` bands of the HOST array `bands` (1 .. SP_MAX_BANDS, each within 0 <= y0 <= y1 <= n: the caller

@@ -130,17 +130,27 @@ def choose_width(n, cu, gf, regime, w4, ragged_group=True):
 
 
 def unreachable_by_rule(cu, sizes=SIZES):
-    """The (n, gf, regime) combinations no width reaches on a part whose CU count is a multiple of 8, from the rule alone.
-    * A gf above the smallest is only chosen once it gives 2 * cu groups or more: never fewer groups than workgroups, and with every
-      XCD chunk holding 2 * cu / 8 groups or more no workgroup is left with one group while none has three.
+    """The (n, gf, regime) combinations no width reaches on a part of 8 CUs or more, from the rule alone.  G = grid_for(cu, cu) is the
+    grid of every launch with cu groups or more: cu rounded up to the 8 XCDs.
+    * A gf above the smallest is only chosen once it gives 2 * cu groups or more: never fewer groups than workgroups.  Where G = cu
+      every XCD chunk then holds 2 * cu / 8 groups or more and no workgroup is left with one group while none has three; where G > cu
+      2 * G - 1 groups (2 * cu or more) give every workgroup two but the last one of the last XCD: `mixed` is in reach.
     * A gf below the largest is given up beyond 2 * (2 * cu - 1) groups.  With a group count that is no multiple of 8 the last XCD's
-      chunk is short, so three groups for every workgroup take 8 * (3 * cu / 8 + 1) - 1 = 3 * cu + 7 groups: out of reach while
-      4 * cu - 2 < 3 * cu + 7, i.e. on 8 CUs."""
-    assert cu % 8 == 0
-    out = [(n, gf, r) for n in sizes for gf in reachable_gf(n)[1:] for r in ("one", "mixed")]
-    if 4 * cu - 2 < 3 * cu + 7:
+      chunk is short, so three groups for every workgroup take 8 * (3 * G / 8 + 1) - 1 = 3 * G + 7 groups: out of reach while
+      4 * cu - 2 < 3 * G + 7, i.e. on 8 CUs, and on 12 or 20, whose grids are rounded up by 4."""
+    assert cu >= 8
+    grid_full = grid_for(cu, cu)
+    out = [(n, gf, r) for n in sizes for gf in reachable_gf(n)[1:] for r in (("one", "mixed") if grid_full == cu else ("one",))]
+    if 4 * cu - 2 < 3 * grid_full + 7:
         out += [(n, gf, "many") for n in sizes for gf in reachable_gf(n)[:-1]]
     return sorted(out)
+
+
+def reachable(cases, cu):
+    """The cases of a lattice whose (n, gf, regime) cell some width reaches on a cu-CU part: all of them but on 8 and 20 CUs (of the
+    counts the tests run), where the `many` cells of every gf below the largest are out of reach."""
+    out_of_reach = set(unreachable_by_rule(cu))
+    return [c for c in cases if (c["n"], c["gf"], c["regime"]) not in out_of_reach]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the lattice

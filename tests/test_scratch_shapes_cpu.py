@@ -12,7 +12,7 @@ from __graft_entry__ import build, load_package
 
 SIZES = [1 << k for k in range(1, 21)]                  # n = 2 .. SP_MAX_N
 FRAMES = (1, 2, 1023, 1024, 1025, 5000)
-CUS = (1, 64, 256, 304)
+CUS = (1, 8, 32, 64, 256, 304)
 
 
 @pytest.fixture(scope="module")
@@ -89,3 +89,17 @@ def test_what_the_gpu_cases_cover():
     assert any(c["oob"] and c["n"] == 1 << 19 for c in by_part["B2"])
     assert {(c["kind"], c["n"]) for c in by_part["B1"]} == {("image", 32), ("image", 4096), ("peak", 32), ("peak", 4096), ("traces", 2048),
                                                             ("traces", 4096), ("power", 2048), ("power", 4096)}
+
+
+def test_what_the_cu_count_cases_cover(pkg):
+    """tests/test_cu_counts_gpu.py, part D: on 8 CUs the part is the bound - 32 workgroups for 100 frames, three or four columns each -
+    for every kind at n = 32, 2048, 8192 and 16384, through both variants."""
+    import test_cu_counts_gpu as gpu
+    assert gpu.SCRATCH_CU == 8 and len({c["id"] for c in gpu.D_CASES}) == len(gpu.D_CASES) == 16
+    assert {(c["kind"], c["n"]) for c in gpu.D_CASES} == {(k, n) for k in scratchref.SLABS for n in (32, 2048, 8192, 16384)}
+    for c in gpu.D_CASES:
+        W, B = gpu.ss._shape(c, 8)
+        assert (W, B) == (100, 32) and pkg.binding.debug_scratch_launch(c["n"], scratchref.SLABS[c["kind"]], W, 8) == (32, c["n"] >= 4096)
+        assert sorted({len(scratchref.columns_of(b, W, B)) for b in range(B)}) == [3, 4]
+        assert c["force"] == (c["n"] in (2048, 8192))
+    assert {c["ch"] for c in gpu.D_CASES} == {False, True} and {c["fmt"] for c in gpu.D_CASES} == {"CS16", "CU8", "CF32", "CS12"}

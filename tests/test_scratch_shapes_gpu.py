@@ -201,11 +201,10 @@ def _assert_shape(pkg, c, cu, W, B, what):
         assert B == W == 3 and scratchref.stage_groups(n.bit_length() - 1)[-1] == {13: 1, 14: 2, 15: 3, 19: 3, 20: 4}[n.bit_length() - 1], what
 
 
-@pytest.mark.parametrize("k", range(len(CASES)), ids=[c["id"] for c in CASES])
-def test_scratch_whole_reply(pkg, ctx, cu, ahead, k):
-    c = CASES[k]
+def run_case(pkg, ctx, cu, c, made):
+    """One case - its capture and reference are `made` = _make(c, cu) - through its one launch, the shape confirmed first."""
     n, kind = c["n"], c["kind"]
-    W, B, data, win, bn, want, what = ahead.get(k)
+    W, B, data, win, bn, want, what = made
     lut = base._lut()
     plan = ctx.plan(c["fmt"], n, win, bn, GAIN, RANGE, lut, c["ch"], c["wf"], detector="peak" if kind == "peak" else "sample")
     d_in = ctx.alloc(data.size + 16)
@@ -250,7 +249,12 @@ def test_scratch_whole_reply(pkg, ctx, cu, ahead, k):
     finally:
         ctx.free(d_in)
         plan.close()
-    RAN.add(c["id"])
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=[c["id"] for c in CASES])
+def test_scratch_whole_reply(pkg, ctx, cu, ahead, k):
+    run_case(pkg, ctx, cu, CASES[k], ahead.get(k))
+    RAN.add(CASES[k]["id"])
 
 
 # ------------------------------------------------------------------------------------------------------ B4: the consumers at SP_MAX_N
