@@ -916,6 +916,93 @@ int sp_debug_pulses(const double *values, int32_t width, double hi, double lo, i
                     double *energy_out, double *peak_out, int32_t *peak_at_out);
 
 /*
+ * Averaged spectrogram: exact block means over frames - the average (RMS) detector of a spectrum analyser, the third beside the sample
+ * detector and the peak hold.  A column is the mean power of all the frames it stands for: noise averages down, a weak carrier comes out
+ * of it, and one glitch frame does not own the column.  It is the time-resolved Welch spectrogram between the two extremes the library
+ * already has: with group == 1 it is the power plane, with group >= width it is the mean-power trace.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y - the same geometry, limits, statuses, channel
+ * mode and row order y = i <= n/2 ? n/2 - i : n/2 + n - i (worker.js:90) - and `group` an int32_t >= 1, the frames per column:
+ *     columns = sp_blockmean_columns(width, group) = ceil(width / group), computed in 64 bits; 0 for width == 0
+ *     column c covers the frames [c * group, min((c + 1) * group, width)); count_c is their number: only the last column can be short
+ *     out[c * n + y] = RN( sum over the column's frames x of power[x][y] ) / (double)count_c
+ * The sum is the EXACT real-number sum, RN one IEEE-754 round-to-nearest-even to f64, the division one correctly rounded f64 division:
+ * the rule of the mean-power trace.  In Python: math.fsum(plane[c * group : (c + 1) * group, y]) / count_c, OverflowError read as +inf.
+ * A column and row with a NaN in any of its frames is the NaN 0x7ff8000000000000; otherwise one with +inf in any frame is +inf; a
+ * finite sum from 2^1024 - 2^970 up gives +inf; a column of zeros gives +0.0.
+ * `out` is double[columns][n], FRAME-MAJOR like the plane, 8-byte aligned: it is itself a power plane of `columns` frames, and every
+ * sp_power_* consumer runs on it unchanged.  It is the same for both layouts and does not depend on gain, range, LUT or block_norm.
+ * Refusals, in this order: a NULL or misaligned `out` with columns > 0 is SP_ERR_INVALID_ARG; group < 1 is SP_ERR_INVALID_ARG; a peak
+ * plan is SP_ERR_UNSUPPORTED.  width == 0 writes nothing and returns SP_OK.
+ * THE REPLY DOES NOT DEPEND ON THE CU COUNT, THE WINDOW, THE CHUNKING OF A HOST-FED REQUEST OR THE PATH SPLIT BELOW: every path adds the
+ * same integers into the mean's cells (csrc/sp_exact_sum.h) and rounds once.  Hence, bit for bit: group == 1 gives the power plane
+ * (every NaN as the one NaN above), and group >= width gives the n values of sp_*_mean.
+ * How: a plane consumer receives the request's frames in runs that end wherever a window block or a chunk ends.  A run is cut
+ * (csrc/sp_blockmean_core.h, the one place the decision is made) into a head that continues a column an earlier run began, a body of
+ * whole columns and a tail that begins a column a later run finishes.  Body columns of group <= direct_max frames are made by ONE
+ * launch of k_blockmean, the DIRECT path: a workgroup owns 64 rows and one column at a time, adds the column's frames into cells in LDS
+ * and finishes them there - no workspace, no global atomic.  Head, tail and larger columns are CARRIED: added by the mean's own launches
+ * into the context's mean workspace ((66 + 2) * 8 * n bytes), which is cleared on the stream where a column begins and finished where
+ * it ends; a column of group == width is the mean-power trace's launches, one for one.
+ *
+ * sp_blockmean_columns: (pure host arithmetic) ceil(width / group); 0 where width <= 0 or group < 1.
+ * sp_power_blockmean: the block means of a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_power_mean.  Asynchronous on the context's stream, no request number: a stream that is being captured is not refused once the
+ *   workspace has its size.  n >= 1 (any n), width >= 0; both pointers 8-byte aligned, d_power non-NULL when width > 0.  The values must
+ *   not be negative: the sign bit of a value is not looked at.
+ * sp_plan_execute_blockmean: device operands, asynchronous.  The plane is never held whole: it passes block by block through the mean's
+ *   window (sp_context_set_mean_window applies).  The checks are the output's and the group's, then sp_plan_execute_power's.  No
+ *   request number: the call may be interleaved with the other sp_plan_execute_* on one context without a synchronisation.
+ * sp_render_blockmean: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for sp_render_mean - a packed
+ *   upload where stride > n, chunks of frames where the request is large - and the columns * n doubles come back in ONE copy behind the
+ *   last chunk, converted on the device first when db != 0: sp_plan_power_to_db of the means, the dB of the mean and NOT the mean of the
+ *   dB values.  The reply waits on the device for that copy, 8 * columns * n bytes of the context's small-reply buffer: where they
+ *   cannot be had the call returns SP_ERR_NOMEM and the reply is not cut.  sp_context_last_upload_bytes / _last_chunks report as before.
+ * sp_plan_blockmean_kernel_name_for: "frames_power+blockmean" or "scratch_power+blockmean", following sp_plan_power_kernel_name_for.
+ * sp_context_set_blockmean_direct_max: (tests) direct_max in frames, 1 ... 2^31 - 1; 0 restores the built default,
+ *   SP_BLOCKMEAN_DIRECT_FRAMES.  It changes speed only, never a bit.
+ * sp_debug_blockmean: (tests, no device needed) the reply of `width` frames of n values through the host side of the code the kernels
+ *   run, one spx::Accumulator per column and row.  SP_ERR_INVALID_ARG for n < 1, width < 0, group < 1, a NULL array with width > 0 and
+ *   a negative value, -0.0 or -inf.
+ * sp_debug_blockmean_split: (tests, no device needed) what becomes of the run [x_base, x_base + frames) of a request of `width` frames,
+ *   from the function the consumer calls: out[] receives 6 int64 words - the frames of the head, of the body and of the tail (they sum to
+ *   `frames`), the body's first column, its number of columns, and 1 where the body goes to k_blockmean (direct_max 0: the built
+ *   default).  *used = words needed (SP_ERR_INVALID_ARG if capacity is smaller, or 0 <= x_base, 0 <= frames, x_base + frames <= width,
+ *   group >= 1 does not hold).
+ *
+ * sp_debug_blockmean_launch: (tests, no device needed) k_blockmean's grid for the whole columns of `frames` >= 1 frames of n rows on a
+ *   part with cu_count CUs: out[] receives 3 int64 words - the bands of 64 rows, the pieces the columns are cut into (about 8
+ *   workgroups per CU where there are columns enough, 65535 at the most) and the columns per piece.  *used as above.
+ *
+ * sp_plan_power_to_index: colours a plane as the frame loop colours its own pixels.  d_power is double[width * n], frame-major, n the
+ *   plan's: a power plane, a block-mean plane or anything else of that shape.  d_index[j] = gray of lib/worker.js:105-117 of the value,
+ *   with the plan's gain, range, block_norm and LUT length, at the pixel position "Indexed image replies" defines for frame x and row
+ *   y in the plan's layout; sp_index_to_rgba makes RGBA of it.  On a sample plan's own plane it is sp_plan_execute_index's image byte
+ *   for byte.  The index is decided against the plan's colour edges by integer comparison of bit patterns (csrc/sp_blockmean_core.h):
+ *   0 and NaN take index 0, +inf takes the last index.  The sign bit of a value is not looked at.  Asynchronous on the context's stream,
+ *   ONE launch, no workspace and no request number: capturable.  Peak plans are accepted: it only colours.  lut_len > 256 is
+ *   SP_ERR_UNSUPPORTED; with width > 0 a NULL pointer or a d_power that is not 8-byte aligned is SP_ERR_INVALID_ARG; width == 0 queues
+ *   nothing.
+ * sp_debug_gray_index: (tests, no device needed) out[k] = that index of values[k] for a plan of these four parameters, through the host
+ *   side of the code the kernel runs; 1 <= lut_len <= 256.
+ * Out of scope: the Node addon (its export table is pinned, as for the burst lists), peak plans, batches, groups, sharding.py,
+ * overlapping or exponentially weighted averages, and the accumulation fused into the frame loop.
+ */
+#define SP_BLOCKMEAN_DIRECT_FRAMES 1024
+int32_t sp_blockmean_columns(int32_t width, int32_t group);
+int sp_power_blockmean(sp_context *ctx, const double *d_power, int32_t n, int32_t width, int32_t group, double *d_out);
+int sp_plan_execute_blockmean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, int32_t group, double *d_out);
+int sp_render_blockmean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t group,
+                        int32_t db, double *out);
+const char *sp_plan_blockmean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_context_set_blockmean_direct_max(sp_context *ctx, int32_t frames);
+int sp_debug_blockmean(const double *values, int32_t n, int32_t width, int32_t group, double *out);
+int sp_debug_blockmean_split(int64_t x_base, int64_t frames, int32_t width, int32_t group, int32_t direct_max, int64_t *out, size_t capacity,
+                             size_t *used);
+int sp_debug_blockmean_launch(int32_t n, int64_t frames, int32_t group, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
+int sp_plan_power_to_index(sp_plan *plan, const double *d_power, int32_t width, uint8_t *d_index);
+int sp_debug_gray_index(double block_norm, double gain, double range, int32_t lut_len, const double *values, size_t count, uint8_t *out);
+
+/*
  * Indexed image replies: the picture as ONE colour-index byte per pixel instead of RGBA.
  *     index[j] = gray of lib/worker.js:105-117 (the value `c_hist[gray] += 1` counts), a uint8_t,
  * at the RGBA image's pixel position: j = x + width * y for the spectrogram layout (n rows x width columns) and

@@ -231,6 +231,19 @@ class Library:
         L.sp_debug_scratch_launch.argtypes = [i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
         L.sp_context_debug_set_cu_count.argtypes = [vp, i32]
         L.sp_debug_mean_launch.argtypes = [i32, C.c_int64, i32, vp, sz, C.POINTER(sz)]
+        L.sp_blockmean_columns.restype = i32
+        L.sp_blockmean_columns.argtypes = [i32, i32]
+        L.sp_power_blockmean.argtypes = [vp, vp, i32, i32, i32, vp]
+        L.sp_plan_execute_blockmean.argtypes = [vp, vp, sz, i32, i32, vp]
+        L.sp_render_blockmean.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, i32, i32, vp]
+        L.sp_plan_blockmean_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_blockmean_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_context_set_blockmean_direct_max.argtypes = [vp, i32]
+        L.sp_debug_blockmean.argtypes = [vp, i32, i32, i32, vp]
+        L.sp_debug_blockmean_split.argtypes = [C.c_int64, C.c_int64, i32, i32, i32, vp, sz, C.POINTER(sz)]
+        L.sp_plan_power_to_index.argtypes = [vp, vp, i32, vp]
+        L.sp_debug_blockmean_launch.argtypes = [i32, C.c_int64, i32, i32, vp, sz, C.POINTER(sz)]
+        L.sp_debug_gray_index.argtypes = [dbl, dbl, dbl, i32, vp, sz, vp]
 
     @classmethod
     def get(cls):
@@ -272,6 +285,63 @@ def exact_sum(values):
     lib = Library.get()
     lib.check(lib.L.sp_debug_exact_sum(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, C.byref(out)))
     return out.value
+
+
+def blockmean_columns(width, group):
+    """sp_blockmean_columns: the columns of an averaged spectrogram of `width` frames, `group` frames per column: ceil(width / group),
+    0 where width <= 0 or group < 1.  Pure host arithmetic."""
+    return int(Library.get().L.sp_blockmean_columns(int(width), int(group)))
+
+
+def blockmean(values, group):
+    """sp_debug_blockmean: the block means of a frame-major plane f64 [width, n] through the host side of the code the kernels run:
+    f64 [columns, n], per column of `group` frames and per row the correctly rounded sum divided by the column's frames, with the mean's
+    NaN and inf rule.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    width, n = v.shape
+    out = np.empty((blockmean_columns(width, group), n), np.float64)
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_blockmean(v.ctypes.data_as(C.c_void_p) if v.size else None, int(n), int(width), int(group),
+                                       out.ctypes.data_as(C.c_void_p) if out.size else None))
+    return out
+
+
+BLOCKMEAN_SPLIT_FIELDS = ("head", "body", "tail", "body_column", "body_columns", "direct")
+
+
+def blockmean_split(x_base, frames, width, group, direct_max=0):
+    """sp_debug_blockmean_split: what becomes of the run [x_base, x_base + frames) of a block-mean request of `width` frames: a dict of
+    BLOCKMEAN_SPLIT_FIELDS - the frames of the head (continues an open column), of the body (whole columns) and of the tail (opens a
+    column), the body's first column and its columns, and whether the body takes the direct kernel (direct_max 0: the built default).
+    No device needed."""
+    out = np.zeros(len(BLOCKMEAN_SPLIT_FIELDS), np.int64)
+    used = C.c_size_t()
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_blockmean_split(int(x_base), int(frames), int(width), int(group), int(direct_max),
+                                             out.ctypes.data_as(C.c_void_p), len(out), C.byref(used)))
+    return dict(zip(BLOCKMEAN_SPLIT_FIELDS, (int(x) for x in out)))
+
+
+def debug_blockmean_launch(n, frames, group, cu_count):
+    """The grid of the direct block-mean kernel alone (sp_debug_blockmean_launch): (bands of 64 rows, pieces of the columns, columns per
+    piece)."""
+    lib = Library.get()
+    out = np.zeros(3, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_blockmean_launch(int(n), int(frames), int(group), int(cu_count), out.ctypes.data_as(C.c_void_p), 3, C.byref(used)))
+    return tuple(int(v) for v in out)
+
+
+def gray_index(block_norm, gain, rng, lut_len, values):
+    """sp_debug_gray_index: the colour index Plan.power_to_index gives each of `values` under a plan of these parameters, u8 of the
+    values' shape, through the host side of the code the kernel runs.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.empty(v.shape, np.uint8)
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_gray_index(float(block_norm), float(gain), float(rng), int(lut_len),
+                                        v.ctypes.data_as(C.c_void_p) if v.size else None, v.size,
+                                        out.ctypes.data_as(C.c_void_p) if v.size else None))
+    return out
 
 
 SP_MAX_BANDS = 64
@@ -774,6 +844,29 @@ class Context:
         Asynchronous on the context's stream."""
         self._chk(self.lib.L.sp_power_mean(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_mean or None)))
 
+    def render_blockmean(self, fmt, data, n, windowc, block_norm, gain, rng, width, group, channel_mode=False, db=False, lut=None,
+                         fill=None):
+        """sp_render_blockmean: the averaged spectrogram of the request, f64 [columns, n]: per column of `group` frames and per image
+        row the correctly rounded sum of |X|^2 over the column's frames divided by their number, or with db=True the dB of it.  No
+        image is rendered; `lut` only takes part in the plan-cache key (default: two grey entries).  fill: a byte the output array holds
+        before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        out = _filled((blockmean_columns(width, group), int(n)), np.float64, fill)
+        self._chk(self.lib.L.sp_render_blockmean(self.h, C.byref(req), _p(data), data.size, int(width), int(group), 1 if db else 0,
+                                                 _p(out) if out.size else None))
+        return out
+
+    def power_blockmean(self, d_power, n, width, group, d_out):
+        """sp_power_blockmean: the block means over `group` frames at a time of the f64 [width, n] plane at device address d_power into
+        f64 [columns, n] at d_out.  Asynchronous on the context's stream."""
+        self._chk(self.lib.L.sp_power_blockmean(self.h, C.c_void_p(d_power or None), int(n), int(width), int(group),
+                                                C.c_void_p(d_out or None)))
+
+    def set_blockmean_direct_max(self, frames=0):
+        """sp_context_set_blockmean_direct_max: the largest group whose whole columns take the direct kernel (0: the built default).
+        The result does not depend on it (tests)."""
+        self._chk(self.lib.L.sp_context_set_blockmean_direct_max(self.h, int(frames)))
+
     def render_bandpower(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, channel_mode=False, db=False, lut=None,
                          fill=None):
         """sp_render_bandpower: the exact band-power series of the request, f64 [count, width]: per band (y0, y1) of image rows and
@@ -1009,6 +1102,7 @@ class Plan:
         self.ctx = ctx
         self.detector = detector
         self.n = int(n)
+        self.waterfall = bool(waterfall)
         self.fid, self.sample_width = parse_format(fmt)
         req, keep = _make_request(self.fid, n, windowc, block_norm, gain, rng, lut, channel_mode, waterfall, detector)
         self.lut_len = len(keep[1])
@@ -1085,6 +1179,21 @@ class Plan:
         (image row order).  Asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_mean(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                           C.c_void_p(d_mean or None)))
+
+    def blockmean_kernel_name_for(self, nbytes, width):
+        """What execute_blockmean() launches for a request of this shape: "frames_power+blockmean" or "scratch_power+blockmean"."""
+        return self._kernel_name_for("blockmean", nbytes, width)
+
+    def execute_blockmean(self, d_bytes, nbytes, width, group, d_out):
+        """sp_plan_execute_blockmean: the exact means of |X|^2 over `group` frames at a time into the f64 [columns, n] device array at
+        address d_out (frame-major, image row order).  Asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_blockmean(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width), int(group),
+                                                               C.c_void_p(d_out or None)))
+
+    def power_to_index(self, d_power, width, d_index):
+        """sp_plan_power_to_index: the colour index of every value of the f64 [width, n] plane at device address d_power, with the plan's
+        gain, range and LUT length, into the u8 index image at d_index in the plan's layout.  Asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_power_to_index(self.h, C.c_void_p(d_power or None), int(width), C.c_void_p(d_index or None)))
 
     def bandpower_kernel_name_for(self, nbytes, width):
         """What execute_bandpower() launches for a request of this shape: "frames_power+bands" or "scratch_power+bands"."""

@@ -31,6 +31,7 @@
 #include "sp_quantile_core.h"
 #include "sp_burst_core.h"
 #include "sp_pulse_core.h"
+#include "sp_blockmean_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -121,6 +122,8 @@ struct sp_context {
     DeviceBuffer burst_ws;       // a burst request's band series f64[count][width] and, behind it, its segments' summaries and carries (sp_kernel_burst.h; grown, never shrunk)
     DeviceBuffer pulse_ws;       // a burst-measurement request's cells u64[count][max_bursts][spx::kSlots], peak keys u64[count][max_bursts] and, behind them, count uint32 for a request without a counts array (sp_kernel_pulse.h; grown, never shrunk)
     DeviceBuffer plane_window;   // a mean, band-power or track request: the block of frames of its plane that is being consumed (plane_blocks)
+    int32_t blockmean_direct_max = 0;   // sp_context_set_blockmean_direct_max: the largest group k_blockmean takes; 0 is the built default, SP_BLOCKMEAN_DIRECT_FRAMES
+    int64_t blockmean_next = 0;         // a block-mean request: the frame its next run begins with (BlockMeanKind::consume)
     size_t mean_window_bytes = 0; // sp_context_set_mean_window: the window's size at the most; 0 is the default, kPlaneWindowDefault
     DeviceBuffer index_rgba;     // an indexed request's temporary RGBA image on the render_extract path (grown, never shrunk)
     DeviceBuffer density_index;  // sp_plan_execute_density: the request's index image, width * n bytes (grown, never shrunk)
@@ -2205,6 +2208,216 @@ extern "C" int sp_plan_execute_mean(sp_plan *plan, const void *d_bytes, size_t n
 extern "C" int sp_render_mean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t db, double *mean)
 {
     return plane_render(ctx, req, bytes, nbytes, width, db, MeanKind{mean, "mean must be an 8-byte aligned array of n doubles"});
+}
+
+// ------------------------------------------------------------------------------------------------- averaged spectrogram
+
+extern "C" const char *sp_plan_blockmean_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+blockmean", "scratch_power+blockmean");
+}
+
+extern "C" int32_t sp_blockmean_columns(int32_t width, int32_t group) { return (int32_t)spbm::columns(width, group); }
+
+extern "C" int sp_context_set_blockmean_direct_max(sp_context *ctx, int32_t frames)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (frames < 0) return fail(ctx, SP_ERR_INVALID_ARG, "sp_context_set_blockmean_direct_max: frames >= 0 is required");
+    ctx->blockmean_direct_max = frames;
+    return SP_OK;
+}
+
+extern "C" int sp_debug_blockmean(const double *values, int32_t n, int32_t width, int32_t group, double *out)
+{
+    if (n < 1 || width < 0 || group < 1 || (width > 0 && (!values || !out))) return SP_ERR_INVALID_ARG;
+    const int64_t columns = spbm::columns(width, group);
+    std::vector<uint64_t> bits((size_t)width * (size_t)n);
+    if (!bits.empty()) memcpy(bits.data(), values, bits.size() * sizeof(uint64_t));
+    for (uint64_t b : bits)
+        if ((b >> 63) && (b & 0x7fffffffffffffffull) <= spx::kInfBits) return SP_ERR_INVALID_ARG;   // (the accumulator has no subtraction)
+    for (int64_t c = 0; c < columns; c++) {
+        const int64_t first = c * group, end = first + group < width ? first + group : width;
+        for (int32_t y = 0; y < n; y++) {
+            spx::Accumulator acc;
+            for (int64_t x = first; x < end; x++) acc.add(bits[(size_t)x * (size_t)n + (size_t)y]);
+            const uint64_t r = acc.finish();
+            double sum;
+            memcpy(&sum, &r, sizeof sum);
+            out[(size_t)c * (size_t)n + (size_t)y] = sum / (double)(end - first);
+        }
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_debug_blockmean_split(int64_t x_base, int64_t frames, int32_t width, int32_t group, int32_t direct_max, int64_t *out,
+                                        size_t capacity, size_t *used)
+{
+    if (x_base < 0 || frames < 0 || width < 0 || x_base + frames > width || group < 1 || direct_max < 0 || !used) return SP_ERR_INVALID_ARG;
+    const spbm::Split s = spbm::split(x_base, frames, width, group, direct_max ? direct_max : SP_BLOCKMEAN_DIRECT_FRAMES);
+    const int64_t v[] = {s.head, s.body, s.tail, s.body_column, s.body_columns, s.direct};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+// (tests) k_blockmean's grid for the whole columns of `frames` frames of n rows on a part with cu_count CUs, from the function its launch
+// calls.
+extern "C" int sp_debug_blockmean_launch(int32_t n, int64_t frames, int32_t group, int32_t cu_count, int64_t *out, size_t capacity, size_t *used)
+{
+    if (n < 1 || frames < 1 || group < 1 || cu_count < 1 || !used) return SP_ERR_INVALID_ARG;
+    long long shape[3];
+    spk::blockmean_launch_shape(n, frames, group, cu_count, shape);
+    const int64_t v[] = {shape[0], shape[1], shape[2]};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+extern "C" int sp_debug_gray_index(double block_norm, double gain, double range, int32_t lut_len, const double *values, size_t count,
+                                   uint8_t *out)
+{
+    if (lut_len < 2 || lut_len > 256 || (count && (!values || !out))) return SP_ERR_INVALID_ARG;
+    const sphost::Thresholds th = sphost::build_thresholds(sphost::PixelMath(block_norm, gain, range, lut_len), lut_len);
+    std::vector<uint64_t> edges((size_t)lut_len);
+    memcpy(edges.data(), th.gray_edge.data(), edges.size() * sizeof(uint64_t));
+    for (size_t k = 0; k < count; k++) {
+        uint64_t b;
+        memcpy(&b, values + k, sizeof b);
+        out[k] = (uint8_t)spbm::gray_index(edges.data(), lut_len, b);
+    }
+    return SP_OK;
+}
+
+namespace {
+// The columns are made as their frames arrive (sp_blockmean_core.h): whole columns of a run by k_blockmean where the group is small,
+// everything else - a column that straddles two runs, a group beyond direct_max - through the mean's own launches into the context's
+// mean_ws, cleared where a column begins and finished where it ends.  mean_ws is the mean's workspace too: every request that uses it
+// clears it on the stream before it adds, and a context's requests run in order on one stream, so neither sees the other's cells.  The
+// frame the next run must begin with is the context's: the drivers hand a kind over by const reference.
+struct BlockMeanKind {
+    static constexpr const char *kRender = "sp_render_blockmean";
+    static constexpr const char *kBadPlane = ": d_power and d_out must be 8-byte aligned device pointers";
+    int32_t group;
+    double *out;           // columns * n doubles
+    const char *refusal;   // of a null or misaligned `out`: every entry point has its own sentence
+
+    int64_t columns(const PlaneShape &p) const { return spbm::columns(p.width, group); }
+    size_t total(const PlaneShape &p) const { return (size_t)columns(p) * (size_t)p.n; }
+    int check(const PlaneShape &p) const
+    {
+        if (columns(p) > 0 && (!out || ((uintptr_t)out & 7) != 0)) return fail(p.ctx, SP_ERR_INVALID_ARG, refusal);
+        if (group < 1) return fail(p.ctx, SP_ERR_INVALID_ARG, "group >= 1 is required");
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &p) const { return p.width == 0; }
+    size_t ws_bytes(const PlaneShape &p) const { return (size_t)spx::kSlots * sizeof(unsigned long long) * (size_t)p.n; }
+    int clear(const PlaneShape &p) const
+    {
+        const int rc = p.ctx->mean_ws.reserve(ws_bytes(p));
+        if (rc) return fail(p.ctx, rc, "mean workspace: out of device memory");
+        p.ctx->blockmean_next = 0;
+        return SP_OK;
+    }
+    // `frames` > 0 frames from x0 on, all of one column, at `src`: the column is opened where x0 begins it and closed where they end it
+    int carry(const PlaneShape &p, const double *src, int64_t x0, int64_t frames) const
+    {
+        sp_context *ctx = p.ctx;
+        unsigned long long *const ws = (unsigned long long *)ctx->mean_ws.p;
+        const int64_t c = x0 / group, first = c * (int64_t)group, end = first + group < p.width ? first + group : p.width;
+        if (x0 == first) SP_HIP(ctx, hipMemsetAsync(ws, 0, ws_bytes(p), ctx->stream));
+        spk::launch_mean_accumulate(src, p.n, frames, ws, ctx->cu_count, ctx->stream);
+        SP_HIP(ctx, hipGetLastError());
+        if (x0 + frames == end) {
+            spk::launch_mean_finish(ws, p.n, (int)(end - first), out + (size_t)c * (size_t)p.n, ctx->stream);
+            SP_HIP(ctx, hipGetLastError());
+        }
+        return SP_OK;
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        sp_context *ctx = p.ctx;
+        if (frames <= 0) return SP_OK;
+        if (x_base != ctx->blockmean_next || x_base + frames > p.width)
+            return fail(ctx, SP_ERR_INVALID_ARG, "block mean: a run of frames that does not continue the one before it");
+        const int64_t direct_max = ctx->blockmean_direct_max ? ctx->blockmean_direct_max : SP_BLOCKMEAN_DIRECT_FRAMES;
+        const spbm::Split s = spbm::split(x_base, frames, p.width, group, direct_max);
+        const size_t n = (size_t)p.n;
+        int rc = SP_OK;
+        if (s.head) rc = carry(p, d_plane, x_base, s.head);
+        const double *const body = d_plane + (size_t)s.head * n;
+        const int64_t body_x = x_base + s.head;
+        if (!rc && s.body) {
+            if (s.direct) {
+                spk::launch_blockmean(body, p.n, s.body, group, out + (size_t)s.body_column * n, ctx->cu_count, ctx->stream);
+                SP_HIP(ctx, hipGetLastError());
+            } else {
+                for (int64_t k = 0; k < s.body_columns && !rc; k++) {
+                    const int64_t at = k * (int64_t)group, count = s.body - at < group ? s.body - at : group;
+                    rc = carry(p, body + (size_t)at * n, body_x + at, count);
+                }
+            }
+        }
+        if (!rc && s.tail) rc = carry(p, body + (size_t)s.body * n, body_x + s.body, s.tail);
+        if (!rc) ctx->blockmean_next = x_base + frames;
+        return rc;
+    }
+    int finish(const PlaneShape &p) const
+    {
+        // (every run that reaches `width` has closed the last column, the short one too: nothing is left to finish)
+        return p.ctx->blockmean_next == p.width ? (int)SP_OK : fail(p.ctx, SP_ERR_INVALID_ARG, "block mean: the request's frames did not all arrive");
+    }
+    size_t small_bytes(const PlaneShape &p) const { return total(p) * sizeof(double); }
+    BlockMeanKind on_device(const PlaneShape &, void *small) const { return {group, (double *)small, refusal}; }
+    int tail(sp_plan *plan, const PlaneShape &p, int32_t db, const BlockMeanKind &host, hipError_t &e) const
+    {
+        const int r = db ? power_to_db(plan, out, total(p), out) : (int)SP_OK;
+        if (!r) e = hipMemcpyAsync(host.out, out, total(p) * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return r;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_blockmean(sp_context *ctx, const double *d_power, int32_t n, int32_t width, int32_t group, double *d_out)
+{
+    const BlockMeanKind k{group, d_out, "sp_power_blockmean: d_power and d_out must be 8-byte aligned device pointers"};
+    return plane_resident(ctx, "sp_power_blockmean", d_power, n, width, k);
+}
+
+extern "C" int sp_plan_execute_blockmean(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, int32_t group, double *d_out)
+{
+    const BlockMeanKind k{group, d_out, "d_out must be an 8-byte aligned array of columns * n doubles"};
+    if (plan && width >= 0) {   // (the output's and the group's refusals come before the plan's)
+        const int rc = k.check(PlaneShape{plan->ctx, plan->req.n, width});
+        if (rc) return rc;
+    }
+    return plane_capture(plan, d_bytes, nbytes, width, k);
+}
+
+extern "C" int sp_render_blockmean(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, int32_t group,
+                                   int32_t db, double *out)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, db, BlockMeanKind{group, out, "out must be an 8-byte aligned array of columns * n doubles"});
+}
+
+extern "C" int sp_plan_power_to_index(sp_plan *plan, const double *d_power, int32_t width, uint8_t *d_index)
+{
+    if (!plan) return SP_ERR_INVALID_ARG;
+    sp_context *ctx = plan->ctx;
+    if (plan->req.lut_len > 256) return fail(ctx, SP_ERR_UNSUPPORTED, "sp_plan_power_to_index: a colour map of more than 256 entries has no index byte");
+    if (width < 0) return fail(ctx, SP_ERR_INVALID_ARG, "width < 0");
+    if (width == 0) return SP_OK;
+    if (!d_power || ((uintptr_t)d_power & 7) != 0 || !d_index)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_plan_power_to_index: d_power must be an 8-byte aligned device pointer and d_index a device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] {
+        const int rc = spk::launch_power_to_index(d_power, plan->req.n, width, plan->req.waterfall != 0, plan->d_gray_edge, plan->req.lut_len,
+                                                  d_index, ctx->stream);
+        if (rc) return fail(ctx, rc, "sp_plan_power_to_index: n is beyond what one grid covers");
+        SP_HIP(ctx, hipGetLastError());
+        return (int)SP_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------- exact band-power series

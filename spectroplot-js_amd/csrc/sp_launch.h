@@ -82,6 +82,18 @@ hipError_t launch_pulses(const double *series, int count, int width, const uint6
                          const unsigned long long *records, const uint32_t *counts, void *work, double *energy, double *peak,
                          int32_t *peak_at, hipStream_t stream);
 
+// out[c * n + y] = RN(exact sum of the rows y of column c's frames) / the column's frames, for the columns of `group` >= 1 frames each
+// that the `frames` > 0 frames of the frame-major plane make: ceil(frames / group) of them, only the last one short.  One launch, no
+// workspace.  ... and the grid it gives k_blockmean: {bands of rows, pieces of the columns, columns per piece}.  (k_blockmean,
+// k_power_to_index and these launchers are sp_blockmean.hip, a unit of their own.)
+void launch_blockmean(const double *plane, int n, long long frames, long long group, double *out, int cu_count, hipStream_t stream);
+void blockmean_launch_shape(int n, long long frames, long long group, int cu_count, long long shape[3]);
+// index[pixel of (x, y)] = the colour index of power[x * n + y] against the lut_len <= 256 device doubles at gray_edge, for the `width`
+// > 0 frames of the plane, at the pixel positions of an index image in the layout `waterfall` names.  One launch;
+// SP_ERR_UNSUPPORTED for a LUT a byte cannot index or more than 65535 bands of 64 rows.
+int launch_power_to_index(const double *power, int n, int width, bool waterfall, const double *gray_edge, int lut_len, uint8_t *index,
+                          hipStream_t stream);
+
 int launch_synth_trinoise(const SynthArgs &a, int format, hipStream_t stream);
 
 void launch_noop(hipStream_t stream);

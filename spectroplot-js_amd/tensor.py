@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean, its exact band sums, its peak track, its occupancy counts, its percentile traces and its
-burst lists as torch tensors: sp_plan_execute_power / _mean / _bandpower / _track / _occupancy / _quantile / _bursts on torch's current
+"""The numeric spectrogram, its exact mean, its exact block means and their colouring, its exact band sums, its peak track, its occupancy counts, its percentile traces and its
+burst lists as torch tensors: sp_plan_execute_power / _mean / _blockmean / _bandpower / _track / _occupancy / _quantile / _bursts on torch's current
 stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
@@ -79,6 +79,34 @@ def mean(plan, capture, width):
     out = torch.empty((plan.n,), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_mean(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
+    return out
+
+
+def blockmean(plan, capture, width, group):
+    """The averaged spectrogram of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [columns, n] on the same device:
+    per column of `group` frames and per image row the correctly rounded sum of |X|^2 over the column's frames divided by their number
+    (include/spectroplot_hip.h, "Averaged spectrogram"); columns = ceil(width / group).  The result is itself a frame-major power plane.
+    `plan` is a binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as power() queues its
+    plane; the plane itself is never held whole."""
+    _check_capture("blockmean", capture)
+    columns = binding.blockmean_columns(width, group)
+    out = torch.empty((columns, plan.n), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_blockmean(capture.data_ptr(), capture.numel(), int(width), int(group), out.data_ptr() if out.numel() else 0)
+    return out
+
+
+def power_to_index(plan, plane):
+    """The colour-index image of `plane` (a contiguous float64 CUDA tensor [width, n]: a power plane, a block-mean plane) as a uint8
+    tensor on the same device, coloured with the plan's gain, range and LUT length exactly as the frame loop colours its own pixels
+    (include/spectroplot_hip.h, sp_plan_power_to_index): [n, width] for a spectrogram plan, [width, n] for a waterfall plan.  Queued on
+    torch's current stream exactly as power() queues its plane."""
+    if plane.dtype != torch.float64 or not plane.is_cuda or not plane.is_contiguous() or plane.dim() != 2 or plane.shape[1] != plan.n:
+        raise binding.SpectroplotError(binding.SP_ERR_INVALID_ARG, "tensor.power_to_index: plane must be a contiguous float64 CUDA tensor [width, n]")
+    width = plane.shape[0]
+    out = torch.empty((width, plan.n) if plan.waterfall else (plan.n, width), dtype=torch.uint8, device=plane.device)
+    with _on_current_stream(plan.ctx, plane.device, (plane, out)):
+        plan.power_to_index(plane.data_ptr(), width, out.data_ptr() if out.numel() else 0)
     return out
 
 
