@@ -627,6 +627,61 @@ int sp_render_bandpower(sp_context *ctx, const sp_request *req, const uint8_t *b
 const char *sp_plan_bandpower_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
+ * Exact spectral moments: where a band's power lies and how wide it is, per frame - the power-weighted sums from which the caller takes
+ * the centroid (the discriminator output of an FSK capture, a sub-bin frequency estimate that the peak track's argmax cannot give) and
+ * the RMS bandwidth of a burst (without the threshold the occupancy counts need).  Bit-exact like the band-power series.
+ * With power[x][y], the bands (a HOST array of `count` pairs [y0, y1), 0 <= count <= SP_MAX_BANDS, read before the call returns, bands
+ * may overlap and may be empty), the geometry, limits, statuses, channel mode and row order of sp_plan_execute_bandpower, and `order` 0,
+ * 1 or 2, the reply is double[(order + 1) * count * width], MOMENT-MAJOR, then band-major, so each moment of each band is one contiguous
+ * time series:
+ *     m[(k * count + b) * width + x] = RN( sum over y in [y0_b, y1_b) of (y - y0_b)^k * power[x][y] ),   k = 0 .. order,   0^0 = 1
+ * The weights count rows from the band's FIRST row, so they are small integers below 2^20 (squared: below 2^40).  The sum is the EXACT
+ * real-number sum and RN is one IEEE-754 round-to-nearest-even to f64; a sum at or above 2^1024 - 2^970 gives +inf.  m[0] is the
+ * band-power series bit for bit.  In Python: float(sum(Fraction(y - y0) ** k * Fraction(v))) with OverflowError read as +inf.
+ * SPECIAL VALUES ARE THE BAND'S, NOT THE TERM'S: if any row of the band in that frame is a NaN, every moment of that (band, frame) is
+ * NaN (A NaN IS ANY NaN); otherwise, if any row is +inf, every moment is +inf - also where the row's weight is 0, where an IEEE 0 * inf
+ * would be a NaN: a band that holds a special value has no centroid, and says so in every series.  An empty band gives +0.0 in every
+ * moment; a band of one row gives m[1] = m[2] = +0.0.  width == 0 or count == 0 writes nothing and returns SP_OK.  The arrays are the
+ * same for both layouts and do not depend on gain, range, LUT or block_norm, NOR ON THE CU COUNT, THE WINDOW OR THE CHUNKING OF A
+ * HOST-FED REQUEST (integer adds commute).  Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED, as
+ * for the band-power series.
+ * The derived quantities stay with the caller, one or two IEEE operations each on the reply:
+ *     centroid row y0 + m1 / m0;   centroid frequency (n/2 - y0 - m1 / m0) / n cycles per sample (I/Q plans);
+ *     RMS width in rows sqrt(m2 / m0 - (m1 / m0)^2) - which cancels on a wide band: measure a width with a tight band.
+ * SP_ERR_INVALID_ARG: an order outside 0 .. 2, a band outside 0 <= y0 <= y1 <= n, count outside 0 .. SP_MAX_BANDS, bands == NULL with
+ * count > 0, n > SP_MAX_N, a NULL or misaligned (8 bytes) output when count * width > 0 - all before the device is touched.
+ * How: the band-power kernel's shape with one accumulator of 68 64-bit cells per moment in LDS (csrc/sp_moment_core.h: the value's
+ * 53-bit integer times its weight, cut into four 32-bit pieces) and the NaN and +inf counters shared; integer adds only, rounded once,
+ * no workspace of the context, no clear and no finishing launch.  The kernel is compiled per order: order 1 does not pay for m2.
+ *
+ * sp_power_moments: the moments over a frame-major plane double[width * n] the caller holds on the device; the companion of
+ *   sp_power_bands.  Asynchronous on the context's stream, ONE launch, no workspace and no request number.  1 <= n <= SP_MAX_N (any n),
+ *   width >= 0; d_power (non-NULL when count * width > 0) and d_out 8-byte aligned device pointers.  The values must not be negative.
+ * sp_plan_execute_moments: device operands, asynchronous.  The plane passes block by block through the mean's window
+ *   (sp_context_set_mean_window applies) and the block's columns [x0, x1) of every series are made behind each block.  The checks are
+ *   sp_plan_execute_power's, then the order's, the bands' and the output's.  No request number: the call may be interleaved with
+ *   sp_plan_execute / _power / _mean / _bandpower on one context without a synchronisation.
+ * sp_render_moments: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for sp_render_bandpower and
+ *   (order + 1) * count * width doubles come back in one copy.  db != 0 converts m[0] ONLY, the first count * width values, as
+ *   sp_plan_power_to_db does; m[1] and m[2] have no dB form and come back as they are.
+ * sp_debug_moment_sum: (tests, no device needed) out[k] = RN(exact sum of r^k * values[r]), k = 0 .. order, of one column of `count` <=
+ *   SP_MAX_N non-negative values with the weights r = 0 .. count - 1, through the host side of the code the kernel runs, with the NaN
+ *   and inf rule; out holds order + 1 doubles.  A negative value, -0.0 or -inf, a bad order or a longer column returns
+ *   SP_ERR_INVALID_ARG and writes nothing.
+ * sp_plan_moments_kernel_name_for: "frames_power+moments" or "scratch_power+moments", following sp_plan_power_kernel_name_for.
+ * Out of scope: the Node addon (its export table is pinned), peak plans, batches, groups and sharding.py, per-burst centroids,
+ * arbitrary f64 weights, and the sums fused into the frame loop.
+ */
+int sp_power_moments(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count, int32_t order,
+                     double *d_out);
+int sp_plan_execute_moments(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                            int32_t order, double *d_out);
+int sp_render_moments(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                      int32_t count, int32_t order, int32_t db, double *out);
+int sp_debug_moment_sum(const double *values, size_t count, int32_t order, double *out);
+const char *sp_plan_moments_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
  * Peak track: the strongest row of a band of image rows, and its power, per frame - the peak search of a spectrum analyser per sweep,
  * over time the frequency-versus-time track of a transmitter (the two tones of an FSK burst, a drifting carrier, a chirp); the
  * companion of the band-power series, which shows the same burst's amplitude.  gauge_maxs is no substitute: one clamped byte for the

@@ -184,6 +184,12 @@ class Library:
         L.sp_render_bandpower.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, vp]
         L.sp_plan_bandpower_kernel_name_for.restype = C.c_char_p
         L.sp_plan_bandpower_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_power_moments.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp]
+        L.sp_plan_execute_moments.argtypes = [vp, vp, sz, i32, vp, i32, i32, vp]
+        L.sp_render_moments.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, i32, vp]
+        L.sp_debug_moment_sum.argtypes = [vp, sz, i32, vp]
+        L.sp_plan_moments_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_moments_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_power_tracks.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
         L.sp_plan_execute_track.argtypes = [vp, vp, sz, i32, vp, i32, vp, vp]
         L.sp_render_track.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, i32, vp, vp]
@@ -354,6 +360,27 @@ def band_rows(n, f_lo, f_hi):
     lib = Library.get()
     lib.check(lib.L.sp_band_rows(int(n), float(f_lo), float(f_hi), C.byref(y0), C.byref(y1)))
     return y0.value, y1.value
+
+
+def moment_sum(values, order=2):
+    """sp_debug_moment_sum: f64 [order + 1], out[k] = the correctly rounded sum of r**k * values[r] over one column of non-negative
+    doubles with the weights r = 0 .. len - 1 (0**0 = 1), through the host side of the code the moment kernel runs; any NaN gives NaN
+    in every moment, else any +inf gives +inf in every moment, a sum that rounds past DBL_MAX gives +inf.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    out = np.zeros(max(int(order), 0) + 1, np.float64)
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_moment_sum(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, int(order), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def centroid_freq(n, bands, m0, m1):
+    """The centroid frequency of every band and frame in cycles per sample, f64 [count, width], from the moments m0 and m1
+    ([count, width] each) of the bands (y0, y1) of an I/Q plan of n rows: (n/2 - y0 - m1 / m0) / n, row y being centred on
+    (n/2 - y) / n.  NaN where a band holds no power (0 / 0) or a special value.  Plain numpy, no device needed."""
+    b, count = _band_array(bands)
+    m0, m1 = np.asarray(m0, np.float64).reshape(count, -1), np.asarray(m1, np.float64).reshape(count, -1)
+    with np.errstate(all="ignore"):
+        return (float(n // 2) - b[:, :1].astype(np.float64) - m1 / m0) / float(n)
 
 
 def band_peak(values, y0, y1):
@@ -887,6 +914,27 @@ class Context:
         self._chk(self.lib.L.sp_power_bands(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
                                             C.c_void_p(d_band or None)))
 
+    def render_moments(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, order=1, channel_mode=False, db=False, lut=None,
+                       fill=None):
+        """sp_render_moments: the exact spectral moments of the request, f64 [order + 1, count, width]: per band (y0, y1) of image rows
+        and per frame the correctly rounded sums of (y - y0)**k * |X|^2 over the band's rows, k = 0 .. order.  db=True converts m[0]
+        only: the higher moments have no dB form.  No image is rendered; `lut` only takes part in the plan-cache key.  fill: a byte the
+        output array holds before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        b, count = _band_array(bands)
+        out = _filled((max(int(order), 0) + 1, count, max(int(width), 0)), np.float64, fill)
+        self._chk(self.lib.L.sp_render_moments(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                               int(order), 1 if db else 0, _p(out) if out.size else None))
+        return out
+
+    def power_moments(self, d_power, n, width, bands, order, d_out):
+        """sp_power_moments: the exact moments k = 0 .. order over the bands (y0, y1) of rows of every frame of the f64 [width, n] plane
+        at device address d_power into f64 [order + 1, count, width] at d_out.  Asynchronous on the context's stream; the bands are
+        read before it returns."""
+        b, count = _band_array(bands)
+        self._chk(self.lib.L.sp_power_moments(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                              int(order), C.c_void_p(d_out or None)))
+
     def render_track(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, channel_mode=False, db=False, lut=None,
                      fill=None):
         """sp_render_track: the peak track of the request, (rows int32 [count, width], peaks f64 [count, width]): per band (y0, y1) of
@@ -1205,6 +1253,18 @@ class Plan:
         b, count = _band_array(bands)
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_bandpower(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                                _p(b) if count else None, count, C.c_void_p(d_band or None)))
+
+    def moments_kernel_name_for(self, nbytes, width):
+        """What execute_moments() launches for a request of this shape: "frames_power+moments" or "scratch_power+moments"."""
+        return self._kernel_name_for("moments", nbytes, width)
+
+    def execute_moments(self, d_bytes, nbytes, width, bands, order, d_out):
+        """sp_plan_execute_moments: the exact sums of (y - y0)**k * |X|^2 over the bands (y0, y1) of image rows, per frame and for
+        k = 0 .. order, into the f64 [order + 1, count, width] device array at address d_out.  Asynchronous on the context's stream;
+        the bands are read before it returns."""
+        b, count = _band_array(bands)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_moments(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                             _p(b) if count else None, count, int(order), C.c_void_p(d_out or None)))
 
     def track_kernel_name_for(self, nbytes, width):
         """What execute_track() launches for a request of this shape: "frames_power+track" or "scratch_power+track"."""

@@ -32,6 +32,7 @@
 #include "sp_burst_core.h"
 #include "sp_pulse_core.h"
 #include "sp_blockmean_core.h"
+#include "sp_moment_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -2482,6 +2483,86 @@ extern "C" int sp_render_bandpower(sp_context *ctx, const sp_request *req, const
                                    int32_t count, int32_t db, double *band)
 {
     return plane_render(ctx, req, bytes, nbytes, width, db, BandKind{bands, count, band});
+}
+
+// ------------------------------------------------------------------------------------------------- exact spectral moments
+
+extern "C" const char *sp_plan_moments_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+moments", "scratch_power+moments");
+}
+
+extern "C" int sp_debug_moment_sum(const double *values, size_t count, int32_t order, double *out)
+{
+    if (!out || (count && !values)) return SP_ERR_INVALID_ARG;
+    if (count > spm::kMaxRows) return SP_ERR_INVALID_ARG;   // (before the copy: a weight stays below 2^40)
+    std::vector<uint64_t> bits(count);
+    if (count) memcpy(bits.data(), values, count * sizeof(double));
+    uint64_t r[spm::kMaxOrder + 1] = {};
+    if (!spm::moment_sum_bits(bits.data(), count, order, r)) return SP_ERR_INVALID_ARG;
+    memcpy(out, r, (size_t)(order + 1) * sizeof(uint64_t));
+    return SP_OK;
+}
+
+namespace {
+// As BandKind with order + 1 series per band, moment-major: every block's launch writes its columns of every series, nothing to clear
+// and nothing to finish.  The dB form converts m[0] alone.
+struct MomentKind {
+    static constexpr const char *kRender = "sp_render_moments";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    const int32_t *bands;
+    int32_t count;
+    int32_t order;
+    double *out;   // (order + 1) * count * width doubles
+
+    int check(const PlaneShape &p) const
+    {
+        if (order < 0 || order > spm::kMaxOrder) return fail(p.ctx, SP_ERR_INVALID_ARG, "a moment order of 0, 1 or 2 is required");
+        if (p.n > SP_MAX_N) return fail(p.ctx, SP_ERR_INVALID_ARG, "moments: n <= SP_MAX_N is required");
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (count > 0 && p.width > 0 && (!out || ((uintptr_t)out & 7) != 0))
+            return fail(p.ctx, SP_ERR_INVALID_ARG, "the moment series must be an 8-byte aligned array of (order + 1) * count * width doubles");
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &p) const { return p.width == 0 || count == 0; }
+    int clear(const PlaneShape &) const { return SP_OK; }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        if (frames <= 0 || count <= 0) return SP_OK;
+        spk::launch_moment_sum(d_plane, p.n, frames, bands, count, order, out, p.width, x_base, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &) const { return SP_OK; }
+    size_t series(const PlaneShape &p) const { return (size_t)count * (size_t)p.width; }   // the values of one moment
+    size_t total(const PlaneShape &p) const { return (size_t)(order + 1) * series(p); }
+    size_t small_bytes(const PlaneShape &p) const { return total(p) * sizeof(double); }
+    MomentKind on_device(const PlaneShape &, void *small) const { return {bands, count, order, (double *)small}; }
+    int tail(sp_plan *plan, const PlaneShape &p, int32_t db, const MomentKind &host, hipError_t &e) const
+    {
+        const int r = db ? power_to_db(plan, out, series(p), out) : (int)SP_OK;   // (m[0] only: a higher moment has no dB form)
+        if (!r) e = hipMemcpyAsync(host.out, out, total(p) * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return r;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_moments(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                                int32_t order, double *d_out)
+{
+    return plane_resident(ctx, "sp_power_moments", d_power, n, width, MomentKind{bands, count, order, d_out});
+}
+
+extern "C" int sp_plan_execute_moments(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                       int32_t order, double *d_out)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, MomentKind{bands, count, order, d_out});
+}
+
+extern "C" int sp_render_moments(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                                 int32_t count, int32_t order, int32_t db, double *out)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, db, MomentKind{bands, count, order, out});
 }
 
 // ------------------------------------------------------------------------------------------------- peak track

@@ -42,6 +42,11 @@ void launch_mean_finish(const unsigned long long *ws, int n, int width, double *
 // their own.)
 void launch_band_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, double *band, long long stride,
                      long long x_base, hipStream_t stream);
+// out[(k * count + b) * stride + x_base + x] = the exact sum of (y - y0_b)^k times the rows of band b of frame x, k = 0 .. order (0, 1
+// or 2: the caller has checked it, and n <= SP_MAX_N), for the plane, frames and bands of launch_band_sum.  One launch.  (k_moment_sum
+// and this launcher are sp_moment.hip, a unit of their own.)
+void launch_moment_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, int order, double *out, long long stride,
+                       long long x_base, hipStream_t stream);
 // row[b * stride + x_base + x] and peak[b * stride + x_base + x] = the strongest row of the rows [bands[2 b], bands[2 b + 1]) of frame
 // x and its value (-1 and a NaN where the band holds no value), for the plane, frames and bands of launch_band_sum; a null `row` or
 // `peak` is not written.  One launch.  (k_track_max and this launcher are sp_track.hip, a unit of their own.)

@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean, its exact block means and their colouring, its exact band sums, its peak track, its occupancy counts, its percentile traces and its
-burst lists as torch tensors: sp_plan_execute_power / _mean / _blockmean / _bandpower / _track / _occupancy / _quantile / _bursts on torch's current
+"""The numeric spectrogram, its exact mean, its exact block means and their colouring, its exact band sums, its exact spectral moments, its peak track, its occupancy counts, its percentile traces and its
+burst lists as torch tensors: sp_plan_execute_power / _mean / _blockmean / _bandpower / _moments / _track / _occupancy / _quantile / _bursts on torch's current
 stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
@@ -121,6 +121,22 @@ def bandpower(plan, capture, width, bands):
     out = torch.empty((len(bands), max(int(width), 0)), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_bandpower(capture.data_ptr(), capture.numel(), int(width), bands, out.data_ptr())
+    return out
+
+
+def moments(plan, capture, width, bands, order=1):
+    """The exact spectral moments of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [order + 1, count, width] on
+    the same device: per band (y0, y1) of image rows - a half-open range - and per frame the correctly rounded sums of
+    (y - y0)**k * |X|^2 over the band's rows, k = 0 .. order (include/spectroplot_hip.h, "Exact spectral moments").  out[0] is
+    bandpower()'s series bit for bit; the centroid row is y0 + out[1] / out[0] and the RMS width in rows
+    sqrt(out[2] / out[0] - (out[1] / out[0])**2), one or two tensor operations each on the same stream.  `plan` is a binding.Plan of
+    the sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the plane itself is
+    never held whole."""
+    _check_capture("moments", capture)
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    out = torch.empty((max(int(order), 0) + 1, len(bands), max(int(width), 0)), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_moments(capture.data_ptr(), capture.numel(), int(width), bands, int(order), out.data_ptr())
     return out
 
 
