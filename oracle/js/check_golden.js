@@ -132,10 +132,10 @@ for (const c of spec.worker_cases) {
     try { O.fftPlan(12) } catch (e) { thrown = { type: typeof e, value: String(e) } }
     if (JSON.stringify(thrown) !== JSON.stringify(F.non_pow2_throw)) fail('fft non-pow2', 'throw value')
 }
-// decode
-{
-    const D = JSON.parse(fs.readFileSync(path.join(gdir, 'decode.json'), 'utf8'))
-    for (const k of spec.decode_kat) {
+// decode: the KAT of cases.json against decode.json, then every format's capture tail (decode_tails.json holds cases and vectors)
+for (const tails of [false, true]) {
+    const D = JSON.parse(fs.readFileSync(path.join(gdir, tails ? 'decode_tails.json' : 'decode.json'), 'utf8'))
+    for (const k of tails ? D : spec.decode_kat) {
         const e = D.find(x => x.name === k.name)
         const sw = siggen.SAMPLE_WIDTH[k.gen_format] || 2
         const bytes = k.hex ? new Uint8Array(Buffer.from(k.hex, 'hex'))

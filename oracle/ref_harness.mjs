@@ -3,7 +3,7 @@
  *
  * TEST INFRASTRUCTURE (container-only).  This file is copied by oracle/gen_golden.js into a scratch directory
  * OUTSIDE the repo, next to a scratch copy of the reference's lib/ directory, and executed there with
- *   node --experimental-specifier-resolution=node ref_harness.mjs <repo> <cases.json> <outdir> [<cases_large.json>]
+ *   node --experimental-specifier-resolution=node ref_harness.mjs <repo> <cases.json> <outdir> [<cases_large.json> [<decode_tails.json>]]
  * (recipe: SURVEY.md §8c).  Nothing from the reference is ever copied into the repo; only the outputs
  * (vectors) written here are committed under tests/golden/.
  *
@@ -16,7 +16,7 @@ import path from 'path'
 import crypto from 'crypto'
 
 const require = createRequire(import.meta.url)
-const [repo, casesFile, outdir, largeFile] = process.argv.slice(2)
+const [repo, casesFile, outdir, largeFile, tailsFile] = process.argv.slice(2)
 const siggen = require(path.join(repo, 'oracle/js/siggen.js'))
 
 let captured = null
@@ -230,14 +230,14 @@ const run = async () => {
     }
 
     // ---- decode KAT (lib/samples.js) ---------------------------------------------------------------------------
-    {
+    const decodeVectors = (kat, keep) => {
         const out = []
-        for (const k of spec.decode_kat) {
+        for (const k of kat) {
             const sw = siggen.SAMPLE_WIDTH[k.gen_format] || 2
             const bytes = k.hex ? new Uint8Array(Buffer.from(k.hex, 'hex'))
                 : siggen.generate(k.gen_format, { kind: 'bytes', seed: k.seed }, Math.ceil(k.bytes / sw), 0).slice(0, k.bytes)
             let sv
-            const e = { name: k.name, format: k.format, bytes: bytes.length }
+            const e = keep ? Object.assign({}, k) : { name: k.name, format: k.format, bytes: bytes.length }
             try {
                 sv = new SampleView(k.format, bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength))
             } catch (err) {
@@ -251,8 +251,11 @@ const run = async () => {
             e.pos_lo = k.pos_lo; e.values = vals
             out.push(e)
         }
-        fs.writeFileSync(path.join(outdir, 'decode.json'), JSON.stringify(out, null, 0))
+        return out
     }
+    fs.writeFileSync(path.join(outdir, 'decode.json'), JSON.stringify(decodeVectors(spec.decode_kat, false), null, 0))
+    // every format's capture tail: the cases of decode_tails.json written back with their vectors (the file stands alone)
+    if (tailsFile) fs.writeFileSync(tailsFile, JSON.stringify(decodeVectors(JSON.parse(fs.readFileSync(tailsFile, 'utf8')), true), null, 0))
 
     // ---- engine math KAT: Math.log10 / Math.cos / Math.sin of this V8 (the arithmetic the reference runs on) ---
     {

@@ -26,11 +26,13 @@ import numpy as np
 import pytest
 
 import bandref
+import blockmeanref
 import burstref
 import densityref
 import indexref
 import launchref
 import meanref
+import momentref
 import occref
 import peakref
 import powerref
@@ -509,8 +511,10 @@ def test_power_to_db_at_one_cu(ctx, count, place):
 # ------------------------------------------------------------------------------------------------------------------- F: invariance
 F_N, F_W, F_FMT, F_M = 256, 300, "CS16", 4
 F_CUS = (1, 8, 20, 32, 0)                    # 0: the part's own
-F_KINDS = ("image", "peak", "traces", "index", "density", "power", "mean", "bandpower", "track", "occupancy", "quantile", "bursts", "pulses",
-           "batch")
+F_KINDS = ("image", "peak", "traces", "index", "density", "power", "mean", "blockmean", "bandpower", "moments", "track", "occupancy", "quantile",
+           "bursts", "pulses", "batch")
+F_GROUPS = (12, 7)                           # block means: a group that divides the width and one that leaves a last column of 6 frames
+F_ORDER = 2                                  # moments 0, 1, 2 on the standard bands
 F_BATCH = (1, 31, 0, 77, 300)
 FIRST = {}
 
@@ -519,6 +523,7 @@ FIRST = {}
 def _f_request():
     """The capture every kind renders (the peak plan: one of three sub-frames per column), the batch's captures, and every reference."""
     n, W, lut = F_N, F_W, base._lut()
+    assert W % F_GROUPS[0] == 0 and W % F_GROUPS[1] == 6
     win, weight = pyoracle.window("hann", n)
     bn = 1.0 / weight
     data = base._trinoise(F_FMT, n + (W - 1) * (n // 2 + 3) + 1, seed=6)
@@ -537,7 +542,8 @@ def _f_request():
     assert peak["M"] == 3
     want = {"image": image, "peak": {k: v for k, v in peak.items() if k not in ("jstar", "counts", "M")}, "index": image,
             "traces": tracesref.expected(F_FMT, data, n, win, bn, GAIN, RANGE, W), "density": densityref.expected(image, n, len(lut), W, False),
-            "power": plane, "mean": meanref.expected(plane), "bandpower": sums, "track": trackref.expected(plane, bands),
+            "power": plane, "mean": meanref.expected(plane), "blockmean": [blockmeanref.expected(plane, g) for g in F_GROUPS],
+            "bandpower": sums, "moments": momentref.expected(plane, bands, F_ORDER), "track": trackref.expected(plane, bands),
             "occupancy": occref.expected(plane, thr, bands), "quantile": quantileref.expected(plane, ranks),
             "bursts": burstref.expected(sums, hi, lo, F_M), "pulses": pulseref.expected(sums, hi, lo, F_M),
             "batch": [pyoracle.render(F_FMT, d, n, win, bn, GAIN, RANGE, lut, w) for d, w in zip(items, F_BATCH)]}
@@ -548,7 +554,9 @@ def _f_replies(ctx, cu, what):
     """Every kind's reply to the request on this context as it stands, each checked against its reference; -> {kind: arrays} for the
     comparison with the first count's."""
     from test_band_gpu import _execute_bandpower
+    from test_blockmean_gpu import _execute_blockmean
     from test_mean_gpu import _execute_mean
+    from test_moments_gpu import _execute_moments
     from test_occupancy_gpu import _execute_occupancy
     from test_quantile_gpu import _execute_quantile
     from test_track_gpu import _execute_track
@@ -596,8 +604,13 @@ def _f_replies(ctx, cu, what):
         powerref.assert_same(out["power"], want["power"], what + " power")
         out["mean"] = _execute_mean(ctx, plan, d_in, nbytes, W, n, what)
         meanref.assert_same(out["mean"], want["mean"], what + " mean")
+        out["blockmean"] = [_execute_blockmean(ctx, plan, d_in, nbytes, W, g, n, what) for g in F_GROUPS]
+        for g, got_g, want_g in zip(F_GROUPS, out["blockmean"], want["blockmean"]):
+            blockmeanref.assert_same(got_g, want_g, "%s blockmean of %d" % (what, g))
         out["bandpower"] = _execute_bandpower(ctx, plan, d_in, nbytes, W, r["bands"], what)
         bandref.assert_same(out["bandpower"], want["bandpower"], what + " bandpower")
+        out["moments"] = _execute_moments(ctx, plan, d_in, nbytes, W, r["bands"], F_ORDER, what)
+        momentref.assert_same(out["moments"], want["moments"], what + " moments")
         out["track"] = _execute_track(ctx, plan, d_in, nbytes, W, r["bands"], what)
         trackref.assert_same(out["track"], want["track"], what + " track")
         out["occupancy"] = _execute_occupancy(ctx, plan, d_in, nbytes, W, r["thr"], r["bands"], what)
