@@ -2450,7 +2450,7 @@ struct BandKind {
     int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
     {
         if (frames <= 0 || count <= 0) return SP_OK;
-        spk::launch_band_sum(d_plane, p.n, frames, bands, count, out, p.width, x_base, p.ctx->stream);
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, 0, out, p.width, x_base, p.ctx->stream);
         SP_HIP(p.ctx, hipGetLastError());
         return SP_OK;
     }
@@ -2529,7 +2529,7 @@ struct MomentKind {
     int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
     {
         if (frames <= 0 || count <= 0) return SP_OK;
-        spk::launch_moment_sum(d_plane, p.n, frames, bands, count, order, out, p.width, x_base, p.ctx->stream);
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, order, out, p.width, x_base, p.ctx->stream);   // (order 0: the band sum)
         SP_HIP(p.ctx, hipGetLastError());
         return SP_OK;
     }
@@ -2926,7 +2926,7 @@ struct BurstKind {
     int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
     {
         if (frames <= 0) return SP_OK;
-        spk::launch_band_sum(d_plane, p.n, frames, bands, count, (double *)p.ctx->burst_ws.p, p.width, x_base, p.ctx->stream);
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, 0, (double *)p.ctx->burst_ws.p, p.width, x_base, p.ctx->stream);
         SP_HIP(p.ctx, hipGetLastError());
         return SP_OK;
     }

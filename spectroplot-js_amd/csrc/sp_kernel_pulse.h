@@ -22,6 +22,7 @@
 
 #include "sp_burst_parts.h"   // the segment's shape, BurstKeys, burst_wave_summary
 #include "sp_pulse_core.h"
+#include "sp_wave_sum.h"
 
 namespace spk {
 
@@ -29,22 +30,12 @@ constexpr int kPulseRounds = 6;                // fold rounds of a word; a word 
 constexpr uint32_t kNoBurst = 0xffffffffu;     // the index of "no such burst": above every index (max_bursts < 2^30)
 constexpr int kPulseHead = 0, kPulseTail = 1, kPulseGlobal = 2;   // where a burst's accumulators are: LDS column 0 or 1, or the workspace
 
-// The sum of x over the wave's 64 lanes, exactly.  16 bits at a time, so that a row of 16 lanes stays below 2^20; lane 15 of a row
-// gets the row's sum (row_shr, as sp_kernel_band.h).  Every lane of the wave must be here.
-__device__ inline uint32_t pulse_row_sum(uint32_t x)
-{
-#define SP_DPP_ADD(ctrl) x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, 0xf, 0xf, false);
-    SP_DPP_ADD(0x111)   // row_shr:1
-    SP_DPP_ADD(0x112)   // row_shr:2
-    SP_DPP_ADD(0x114)   // row_shr:4
-    SP_DPP_ADD(0x118)   // row_shr:8
-#undef SP_DPP_ADD
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 15) + (uint32_t)__builtin_amdgcn_readlane((int)x, 31) +
-           (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
+// The sum of x over the wave's 64 lanes, exactly (sp_wave_sum.h).  16 bits at a time, so that a half's total stays below 2^22 and is
+// a 32-bit word.  Every lane of the wave must be here.
 __device__ inline unsigned long long pulse_wave_sum(uint32_t x)
 {
-    return (unsigned long long)pulse_row_sum(x & 0xffffu) + ((unsigned long long)pulse_row_sum(x >> 16) << 16);
+    return (unsigned long long)wave_rows_total<uint32_t>(wave_row_sums(x & 0xffffu)) +
+           ((unsigned long long)wave_rows_total<uint32_t>(wave_row_sums(x >> 16)) << 16);
 }
 
 // the largest k of the wave's 64 lanes, in every lane

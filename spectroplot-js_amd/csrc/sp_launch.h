@@ -36,17 +36,13 @@ void launch_mean_accumulate(const double *plane, int n, long long frames, unsign
 // ... and the grid launch_mean_accumulate gives k_mean_accumulate: {bands of rows, pieces of the frames, frames per piece}
 void mean_launch_shape(int n, long long frames, int cu_count, long long shape[3]);
 void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream);
-// band[b * stride + x_base + x] = the exact sum of the rows [bands[2 b], bands[2 b + 1]) of frame x of the frame-major plane, for its
-// `frames` > 0 frames and the `count` bands of the HOST array `bands` (1 .. SP_MAX_BANDS, each within 0 <= y0 <= y1 <= n: the caller
-// has checked them); they travel in the kernel's arguments.  One launch.  (k_band_sum and this launcher are sp_band.hip, a unit of
-// their own.)
-void launch_band_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, double *band, long long stride,
+// out[(k * count + b) * stride + x_base + x] = the exact sum of (y - y0_b)^k times the rows [y0_b, y1_b) = [bands[2 b], bands[2 b + 1])
+// of frame x of the frame-major plane, k = 0 .. order, for its `frames` > 0 frames and the `count` bands of the HOST array `bands`
+// (1 .. SP_MAX_BANDS, each within 0 <= y0 <= y1 <= n: the caller has checked them); they travel in the kernel's arguments.  Order 0 is
+// the band-power series, band[b * stride + x_base + x]; orders 1 and 2 are the moments (the caller has checked the order, and
+// n <= SP_MAX_N above order 0).  One launch.  (k_band_sum<order> and this launcher are sp_band.hip, a unit of their own.)
+void launch_band_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, int order, double *out, long long stride,
                      long long x_base, hipStream_t stream);
-// out[(k * count + b) * stride + x_base + x] = the exact sum of (y - y0_b)^k times the rows of band b of frame x, k = 0 .. order (0, 1
-// or 2: the caller has checked it, and n <= SP_MAX_N), for the plane, frames and bands of launch_band_sum.  One launch.  (k_moment_sum
-// and this launcher are sp_moment.hip, a unit of their own.)
-void launch_moment_sum(const double *plane, int n, long long frames, const int32_t *bands, int count, int order, double *out, long long stride,
-                       long long x_base, hipStream_t stream);
 // row[b * stride + x_base + x] and peak[b * stride + x_base + x] = the strongest row of the rows [bands[2 b], bands[2 b + 1]) of frame
 // x and its value (-1 and a NaN where the band holds no value), for the plane, frames and bands of launch_band_sum; a null `row` or
 // `peak` is not written.  One launch.  (k_track_max and this launcher are sp_track.hip, a unit of their own.)

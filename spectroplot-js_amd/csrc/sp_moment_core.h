@@ -2,7 +2,7 @@
 // (include/spectroplot_hip.h, sp_plan_execute_moments), m_k = RN(sum of (y - y0)^k * power[y]).  sp_exact_sum.h's arithmetic with one
 // step in front: the 53-bit integer m of a value is multiplied by its weight before it is cut into pieces.  Plain C++, no HIP: the host
 // compiler takes it alone (sp_debug_moment_sum, tests/cpp/moment_core_check.cpp), and under hipcc the same functions are the device's
-// (sp_kernel_moment.h).
+// (k_band_sum<1> and <2> of sp_kernel_band.h).
 //
 // The weight does not move a value's cell: with e the exponent field the value is m << (e - 1) in units of 2^-1074, the product is
 // (m * w) << (e - 1), and cell = (e - 1) / 32 and the shift s = (e - 1) % 32 are spx::decompose's.  w <= kMaxWeight < 2^40 (a row

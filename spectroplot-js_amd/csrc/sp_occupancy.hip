@@ -8,14 +8,12 @@
 
 namespace spk {
 
-static_assert(kBandMax == SP_MAX_BANDS, "BandList holds SP_MAX_BANDS bands");
 static_assert(kOccTileRows == SP_OCCUPANCY_TILE_ROWS, "the header names the kernel's tile");
 static_assert(kBandMax <= 64, "a lane is a band");
 void launch_occupancy_count(const double *plane, int n, long long frames, const double *threshold, const int32_t *bands, int count,
                             uint32_t *rows, uint32_t *out, long long stride, long long x_base, hipStream_t stream)
 {
-    BandList list{};
-    for (int k = 0; k < 2 * count; k++) list.y[k] = bands[k];
+    const BandList list = band_list(bands, count);
     const unsigned pieces = (unsigned)((frames + kOccFrames - 1) / kOccFrames);
     const unsigned tiles = (unsigned)((n + kOccTileRows - 1) / kOccTileRows);
     hipLaunchKernelGGL(k_occupancy_count, dim3(pieces, tiles), dim3(kOccThreads), 0, stream, plane, n, frames,

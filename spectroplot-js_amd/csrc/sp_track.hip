@@ -8,12 +8,10 @@
 
 namespace spk {
 
-static_assert(kBandMax == SP_MAX_BANDS, "BandList holds SP_MAX_BANDS bands");
 void launch_track_max(const double *plane, int n, long long frames, const int32_t *bands, int count, int32_t *row, double *peak,
                       long long stride, long long x_base, hipStream_t stream)
 {
-    BandList list{};
-    for (int k = 0; k < 2 * count; k++) list.y[k] = bands[k];
+    const BandList list = band_list(bands, count);
     const unsigned pieces = (unsigned)((frames + kTrackFrames - 1) / kTrackFrames);
     hipLaunchKernelGGL(k_track_max, dim3(pieces, (unsigned)count), dim3(kTrackThreads), 0, stream, plane, n, frames, list, row, peak, stride,
                        x_base);

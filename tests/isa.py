@@ -20,6 +20,9 @@ TRACES_TARGETS = tuple("build/traces_%d.o" % lg for lg in range(6, 11))    # k_f
 POWER_TARGETS = tuple("build/power_%d.o" % lg for lg in range(6, 11))      # k_frames_power
 API_TARGETS = ("build/sp_api.o",)                                          # what held the scratch kernels and every small kernel in the
 #                                                                            reference commit; now build/sp_kernels.o does (api_objs)
+CONSUMER_UNITS = ("band", "track", "occupancy", "quantile", "burst", "pulse", "blockmean")   # a plane consumer's kernels, a unit each
+# ... and the reference commit's, which had the moments in a unit of their own beside the band sums
+CONSUMER_TARGETS = tuple("build/sp_%s.o" % u for u in CONSUMER_UNITS + ("moment",))
 
 
 def _built(pattern, at_least):
@@ -64,6 +67,14 @@ def api_objs():
     """The object of the scratch kernels and every small kernel (csrc/sp_kernels.hip); sp_api.o and sp_group.o are host code only."""
     objs = _built("sp_kernels.o", 1)
     assert len(objs) == 1
+    return objs
+
+
+def consumer_objs():
+    """The objects of the plane consumers' kernels (csrc/sp_band.hip ... sp_blockmean.hip)."""
+    api_objs()            # (builds the library where it is not built yet)
+    objs = [os.path.join(PKG, "build", "sp_%s.o" % u) for u in CONSUMER_UNITS]
+    assert all(os.path.exists(o) for o in objs), objs
     return objs
 
 
@@ -154,4 +165,8 @@ def commit_streams(ref, targets, prefix):
     r = _git("rev-parse", "--verify", "-q", ref + "^{commit}")
     if r.returncode:
         raise NoReference("the reference commit is not in this clone's history")
+    # (a truncated history names its oldest commit as the one that added every file: that commit need not hold a unit removed since)
+    for unit in re.findall(r"build/(sp_\w+)\.o", " ".join(targets)):
+        if _git("cat-file", "-e", "%s:spectroplot-js_amd/csrc/%s.hip" % (r.stdout.strip(), unit)).returncode:
+            raise NoReference("the commit found for the reference does not hold csrc/%s.hip" % unit)
     return {k: v for k, v in _commit_streams(r.stdout.strip(), tuple(targets)).items() if k.startswith(prefix)}

@@ -133,6 +133,34 @@ def test_a_lower_order_is_the_same_series(ctx, order):
     momentref.assert_same(got, want[:order + 1], "order %d" % order)
 
 
+WALK_BANDS = [(0, 700), (3, 324), (255, 257), (256, 512), (699, 700), (5, 5)]
+
+
+@functools.lru_cache(maxsize=None)
+def _walk():
+    n, width = 700, 9
+    plane = bandref.synthetic_plane(7000 * n + width, n, width)
+    plane.setflags(write=False)
+    want = momentref.expected(plane, WALK_BANDS)
+    want.setflags(write=False)
+    return plane, want
+
+
+@pytest.mark.parametrize("order", [0, 1, 2])
+def test_the_walk_past_one_step_of_rows_at_every_order(ctx, order):
+    """The kernel of every order walks a band 64 x 4 rows at a time: n = 700 gives a band of three steps whose last load is partial, a
+    start off a multiple of 64, a band across a step's edge, one that begins at one, one row and no row; W = 9 leaves the last
+    workgroup one frame.  m[0] of every order is sp_power_bands' series bit for bit."""
+    plane, want = _walk()
+    what = "sp_power_moments n=700 W=9 order %d" % order
+    got = _power_moments(ctx, plane, WALK_BANDS, order, what)
+    assert got.shape == (order + 1, len(WALK_BANDS), 9)
+    momentref.assert_same(got, want[:order + 1], what)
+    sums = _power_bands(ctx, plane, WALK_BANDS)
+    nan = np.isnan(sums)
+    assert np.array_equal(np.isnan(got[0]), nan) and np.array_equal(_bits(got[0])[~nan], _bits(sums)[~nan])
+
+
 @functools.lru_cache(maxsize=None)
 def _largest():
     """n = 2^20, two frames: a dense spectrum-like frame (clustered exponents) and a frame of a few thousand values over a wide range

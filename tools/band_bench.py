@@ -5,8 +5,8 @@
 Legs, device-resident, in one process behind one spin-up, HIP events around each call's launches, best of 5 after a warm-up, interleaved:
   a   sp_plan_execute_power into a resident plane (k_frames_power: one launch, 8 bytes per bin)
   b   sp_plan_execute_bandpower of one full band with the default window (the same frame loop block by block into the window,
-      k_band_sum behind each block)
-  c1  sp_power_bands alone on the resident plane of leg a, one full band [0, n) (k_band_sum: one launch)
+      k_band_sum<0> behind each block)
+  c1  sp_power_bands alone on the resident plane of leg a, one full band [0, n) (k_band_sum<0>: one launch)
   c8  ... eight bands of n/8 rows (the same bytes, eight times the workgroups)
   d   sp_power_mean on the same plane: the mean's code reading the same bytes (clear, k_mean_accumulate, k_mean_finish) - the
       yardstick for c1

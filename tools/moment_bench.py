@@ -3,12 +3,12 @@
 (profiles/moment_bench.jsonl).
 
 Legs, device-resident, in one process behind one spin-up, HIP events around each call's launches, best of 5 after a warm-up, interleaved:
-  y1      sp_power_bands on a resident plane, one full band [0, n) (k_band_sum: one launch) - the yardstick of m*_1
+  y1      sp_power_bands on a resident plane, one full band [0, n) (k_band_sum<0>: one launch) - the yardstick of m*_1
   y8      ... eight bands of n/8 rows - the yardstick of m*_8
-  m0_1, m1_1, m2_1   sp_power_moments at the orders 0, 1, 2 on the same plane, one full band (k_moment_sum<order>: one launch)
+  m0_1, m1_1, m2_1   sp_power_moments at the orders 0, 1, 2 on the same plane, one full band (k_band_sum<order>: one launch; order 0 is y1's kernel)
   m0_8, m1_8, m2_8   ... eight bands of n/8 rows
   eb      sp_plan_execute_bandpower of one full band with the default window - the yardstick of e2
-  e2      sp_plan_execute_moments at order 2 of one full band (the same frame loop block by block, k_moment_sum<2> behind each block)
+  e2      sp_plan_execute_moments at order 2 of one full band (the same frame loop block by block, k_band_sum<2> behind each block)
 Shapes: tools/band_bench.py's.  Every ratio to its yardstick is reported, and m*_1 as plane bytes per second.
 Usage: tools/moment_bench.py [--out FILE] [--reps 5]
 """

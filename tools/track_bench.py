@@ -8,7 +8,7 @@ Legs, device-resident, in one process behind one spin-up, HIP events around each
       behind each block)
   c1  sp_power_tracks alone on the resident plane of leg a, one full band [0, n) (k_track_max: one launch)
   c8  ... eight bands of n/8 rows (the same bytes, eight times the workgroups)
-  d   sp_power_bands of [0, n) on the same plane: the band sum's code reading the same bytes (k_band_sum) - the yardstick for c1
+  d   sp_power_bands of [0, n) on the same plane: the band sum's code reading the same bytes (k_band_sum<0>) - the yardstick for c1
 Shapes: tools/mean_bench.py's.  c1 / d is reported; c1 as plane bytes per second.
 Usage: tools/track_bench.py [--out FILE] [--reps 5]
 """
