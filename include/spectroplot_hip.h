@@ -572,6 +572,63 @@ int sp_debug_exact_sum(const double *values, size_t count, double *sum);
 const char *sp_plan_mean_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
 
 /*
+ * Exact variance and spectral-kurtosis traces: the second-order statistics of every image row over the request's frames - the confidence
+ * band of the Welch PSD the mean trace gives, and the spectral-kurtosis detector SK = (W + 1) / (W - 1) * (W * S2 / S1^2 - 1), about 1
+ * for Gaussian noise, below 1 for a steady carrier, above 1 for bursts.  Bit-exact like the mean trace.
+ * With power[x][y] the value sp_plan_execute_power writes for frame x and image row y (`abs2` of lib/worker.js:70-92 in the image row
+ * order of worker.js:90; the reference has no such fold) - the geometry, limits, statuses, channel mode and row order of
+ * sp_plan_execute_mean - and W = width, the reply is double[3 * n], three arrays of n:
+ *     out[0 * n + y] = RN( S1 ),              S1 = sum over x in [0, W) of power[x][y]         out[0][y] / W is sp_*_mean's value, bit for bit
+ *     out[1 * n + y] = RN( S2 ),              S2 = sum over x in [0, W) of power[x][y]^2
+ *     out[2 * n + y] = RN( W * S2 - S1^2 )    W^2 times the population variance of the row
+ * Every sum, square, product and the difference is the EXACT real number - a square is a 106-bit product, nothing is rounded before
+ * the one RN - so out[2] never suffers the cancellation of W * S2 - S1^2: a row that is constant over the frames gives +0.0 exactly, a
+ * row that differs by one ulp in one frame gives the exact tiny positive value, and no result is ever negative (Cauchy-Schwarz).  RN is
+ * one IEEE-754 round-to-nearest-even to f64, INTO THE DENORMAL RANGE where the exact value lies there (a square goes down to 2^-2148),
+ * and +inf where it rounds past DBL_MAX: out[1] or out[2] may be +inf where out[0] is finite.  In Python, per row:
+ * float(sum(Fraction(v))), float(sum(Fraction(v) ** 2)), float(W * sum(Fraction(v) ** 2) - sum(Fraction(v)) ** 2), OverflowError read
+ * as +inf.
+ * SPECIAL VALUES follow the mean's rule and apply to all three arrays of the row: a NaN in any frame gives NaN (A NaN IS ANY NaN);
+ * otherwise +inf in any frame gives +inf.  width == 0 writes 3 * n times +0.0, the sums of nothing.  The arrays do not depend on gain,
+ * range, LUT or block_norm, NOR ON THE CU COUNT, THE DEAL OF FRAMES TO WORKGROUPS, THE WINDOW OR THE CHUNKING OF A HOST-FED REQUEST
+ * (integer adds commute).  Only plans of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.
+ * The derived quantities stay with the caller, and neither form contains a cancellation:
+ *     population variance out[2] / (W * W), sample variance out[2] / (W * (W - 1));     SK = (W + 1) / (W - 1) * out[2] / out[0]^2
+ * How: csrc/sp_variance_core.h.  Every value is read once; its three 32-bit pieces go to the 66 cells of S1 as for the mean, and its
+ * square m^2 << 2 (e - 1), in units of 2^-2148, is cut into five pieces for 132 cells of S2; integer adds only.  The finish forms
+ * W * S2 and S1^2 digit by digit, subtracts with a borrow and rounds the digit string once.
+ * Cost: a workspace of the context of its own, (66 + 132 + 2) * 8 * n bytes (1.6 MiB at n = 1024, 1.6 GiB at SP_MAX_N), grown and
+ * never shrunk, cleared on the stream by every request.
+ *
+ * sp_power_variance: over a frame-major plane double[width * n] the caller holds on the device; the companion of sp_power_mean.
+ *   Asynchronous on the context's stream, no request number.  1 <= n <= SP_MAX_N (any n), width >= 0, both pointers 8-byte aligned,
+ *   d_out non-NULL, d_power non-NULL when width > 0 (SP_ERR_INVALID_ARG otherwise, and nothing is written).  The values must not be
+ *   negative: the sign bit of a value is not looked at.
+ * sp_plan_execute_variance: device operands, asynchronous.  The plane passes block by block through the mean's window
+ *   (sp_context_set_mean_window applies) and is accumulated behind each block; then the rows are finished.  The checks are
+ *   sp_plan_execute_power's, then the output's.  No request number: the call may be interleaved with sp_plan_execute / _power / _mean
+ *   on one context without a synchronisation.
+ * sp_render_variance: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for sp_render_mean and 3 * n
+ *   doubles come back in one copy.  There is no db argument: a sum of squares has no dB form.
+ * sp_debug_variance_sums: (tests, no device needed) out3[0 .. 2] of one row of `count` < 2^31 non-negative values (W = count) through
+ *   the host side of the code the kernels run, with the NaN and inf rule; no values give three times +0.0.  A negative value, -0.0
+ *   or -inf returns SP_ERR_INVALID_ARG and writes nothing.
+ * sp_debug_variance_launch: (tests, no device needed) the grid of the accumulation behind `frames` >= 1 frames of a plane of n rows on
+ *   a part with cu_count CUs: out[] receives 3 int64 words - the bands of 32 rows, the pieces the frames are cut into (about 6
+ *   workgroups per CU, no piece below 32 frames) and the frames per piece (the last piece may be shorter).  *used = words needed
+ *   (SP_ERR_INVALID_ARG if capacity is smaller).
+ * sp_plan_variance_kernel_name_for: "frames_power+variance" or "scratch_power+variance", following sp_plan_power_kernel_name_for.
+ * Out of scope: the Node addon (its export table is pinned), peak plans, batches, groups and sharding.py, covariances between rows,
+ * higher moments (skewness), and the accumulation fused into the frame loop.
+ */
+int sp_power_variance(sp_context *ctx, const double *d_power, int32_t n, int32_t width, double *d_out);
+int sp_plan_execute_variance(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_out);
+int sp_render_variance(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *out);
+int sp_debug_variance_sums(const double *values, size_t count, double *out3);
+int sp_debug_variance_launch(int32_t n, int64_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
+const char *sp_plan_variance_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+
+/*
  * Exact band-power series: the power of a band of image rows per frame - the zero-span / channel-power trace of a spectrum analyser,
  * the envelope of one transmitter in a crowded capture - bit-exact like the mean.  The mean is the plane's marginal along x, this is
  * its marginal along y.

@@ -178,6 +178,13 @@ class Library:
         L.sp_debug_exact_sum.argtypes = [vp, sz, C.POINTER(dbl)]
         L.sp_plan_mean_kernel_name_for.restype = C.c_char_p
         L.sp_plan_mean_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_power_variance.argtypes = [vp, vp, i32, i32, vp]
+        L.sp_plan_execute_variance.argtypes = [vp, vp, sz, i32, vp]
+        L.sp_render_variance.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp]
+        L.sp_debug_variance_sums.argtypes = [vp, sz, vp]
+        L.sp_debug_variance_launch.argtypes = [i32, C.c_int64, i32, vp, sz, C.POINTER(sz)]
+        L.sp_plan_variance_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_variance_kernel_name_for.argtypes = [vp, sz, i32]
         L.sp_band_rows.argtypes = [i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32)]
         L.sp_power_bands.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         L.sp_plan_execute_bandpower.argtypes = [vp, vp, sz, i32, vp, i32, vp]
@@ -291,6 +298,38 @@ def exact_sum(values):
     lib = Library.get()
     lib.check(lib.L.sp_debug_exact_sum(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, C.byref(out)))
     return out.value
+
+
+def variance_sums(values):
+    """sp_debug_variance_sums: f64 [3] of one row of non-negative doubles over W = len(values) frames, through the host side of the code
+    the variance kernels run: the correctly rounded sum, the correctly rounded sum of the exact squares, and the correctly rounded
+    W * sum of squares - sum**2 (W**2 times the population variance; +0.0 exactly for a constant row, never negative).  Any NaN gives
+    NaN in all three, else any +inf gives +inf in all three; a result that rounds past DBL_MAX gives +inf.  No device needed."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    out = np.zeros(3, np.float64)
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_variance_sums(v.ctypes.data_as(C.c_void_p) if v.size else None, v.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def variance_of(sums, width, ddof=0):
+    """The variance of every row from a variance reply `sums` ([3, n]) over `width` frames: sums[2] / (width * (width - ddof)), the
+    population variance with ddof=0 and the sample variance with ddof=1.  The subtraction was done exactly on the device: this form
+    contains no cancellation.  NaN by 0 / 0 where width * (width - ddof) is 0.  Plain numpy, no device needed."""
+    sums = np.asarray(sums, np.float64)
+    with np.errstate(all="ignore"):
+        return sums[2] / np.float64(int(width) * (int(width) - int(ddof)))
+
+
+def spectral_kurtosis(sums, width):
+    """The spectral kurtosis of every row from a variance reply `sums` ([3, n]) over `width` frames:
+    (width + 1) / (width - 1) * sums[2] / sums[0]**2 - about 1 for Gaussian noise, below 1 (0 exactly for a constant row) for a steady
+    carrier, above 1 for bursts.  No cancellation.  NaN where a row holds no power or width is 0; width 1 divides by zero.  Plain
+    numpy, no device needed."""
+    sums = np.asarray(sums, np.float64)
+    w = np.float64(int(width))
+    with np.errstate(all="ignore"):
+        return (w + 1.0) / (w - 1.0) * sums[2] / (sums[0] * sums[0])
 
 
 def blockmean_columns(width, group):
@@ -602,6 +641,16 @@ def debug_mean_launch(n, frames, cu_count):
     return tuple(int(v) for v in out)
 
 
+def debug_variance_launch(n, frames, cu_count):
+    """The grid of a variance request's accumulation alone (sp_debug_variance_launch): (bands of 32 rows, pieces of the frames, frames
+    per piece)."""
+    lib = Library.get()
+    out = np.zeros(3, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_variance_launch(int(n), int(frames), int(cu_count), out.ctypes.data_as(C.c_void_p), 3, C.byref(used)))
+    return tuple(int(v) for v in out)
+
+
 DENSITY_LAUNCH_FIELDS = ("workgroups", "rows", "frames", "lds_bytes", "bands", "pieces")
 LAUNCH_FIELDS = ("kernel", "log2n", "channel_mode", "prefetch", "gf", "groups", "grid", "lds_bytes", "rgba_fast", "peak_m", "cu_count")
 KERNELS = {0: "none", 1: "scratch_radix2", 3: "frames", 4: "frames_peak"}      # enum Kernel (sp_api.hip)
@@ -870,6 +919,21 @@ class Context:
         """sp_power_mean: the exact mean over the frames of the f64 [width, n] plane at device address d_power into f64[n] at d_mean.
         Asynchronous on the context's stream."""
         self._chk(self.lib.L.sp_power_mean(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_mean or None)))
+
+    def render_variance(self, fmt, data, n, windowc, block_norm, gain, rng, width, channel_mode=False, lut=None, fill=None):
+        """sp_render_variance: the exact variance sums of the request, f64 [3, n] in image row order: per row the correctly rounded sum
+        of |X|^2 over the frames, the correctly rounded sum of its exact squares, and the correctly rounded width * sum of squares -
+        sum**2 (variance_of and spectral_kurtosis take it from there).  No dB form.  No image is rendered; `lut` only takes part in the
+        plan-cache key.  fill: a byte the output array holds before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        out = _filled((3, int(n)), np.float64, fill)
+        self._chk(self.lib.L.sp_render_variance(self.h, C.byref(req), _p(data), data.size, int(width), _p(out)))
+        return out
+
+    def power_variance(self, d_power, n, width, d_out):
+        """sp_power_variance: the exact variance sums over the frames of the f64 [width, n] plane at device address d_power into
+        f64 [3, n] at d_out.  Asynchronous on the context's stream."""
+        self._chk(self.lib.L.sp_power_variance(self.h, C.c_void_p(d_power or None), int(n), int(width), C.c_void_p(d_out or None)))
 
     def render_blockmean(self, fmt, data, n, windowc, block_norm, gain, rng, width, group, channel_mode=False, db=False, lut=None,
                          fill=None):
@@ -1227,6 +1291,17 @@ class Plan:
         (image row order).  Asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_mean(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                           C.c_void_p(d_mean or None)))
+
+    def variance_kernel_name_for(self, nbytes, width):
+        """What execute_variance() launches for a request of this shape: "frames_power+variance" or "scratch_power+variance"."""
+        return self._kernel_name_for("variance", nbytes, width)
+
+    def execute_variance(self, d_bytes, nbytes, width, d_out):
+        """sp_plan_execute_variance: per image row the exact sum of |X|^2 over the request's frames, the exact sum of its squares and
+        width * sum of squares - sum**2, each rounded once, into the f64 [3, n] device array at address d_out.  Asynchronous on the
+        context's stream."""
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_variance(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                              C.c_void_p(d_out or None)))
 
     def blockmean_kernel_name_for(self, nbytes, width):
         """What execute_blockmean() launches for a request of this shape: "frames_power+blockmean" or "scratch_power+blockmean"."""

@@ -33,6 +33,7 @@
 #include "sp_pulse_core.h"
 #include "sp_blockmean_core.h"
 #include "sp_moment_core.h"
+#include "sp_variance_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -119,6 +120,7 @@ struct sp_context {
     DeviceBuffer traces_ws;      // a traces request's extremes per bin, u64[2 n] (sp_kernel_scratch.h: k_traces_clear)
     DeviceBuffer power_plane;    // sp_render_power: the request's plane on the device, 8 * width * n bytes (grown, never shrunk)
     DeviceBuffer mean_ws;        // a mean request's exact-sum cells, u64[spx::kSlots][n] (sp_kernel_mean.h; grown, never shrunk)
+    DeviceBuffer variance_ws;    // a variance request's cells, u64[spv::kSlots][n] (sp_kernel_variance.h; grown, never shrunk)
     DeviceBuffer quantile_ws;    // a percentile request's whole plane as keys, u64[n][width] (sp_kernel_quantile.h; grown, never shrunk)
     DeviceBuffer burst_ws;       // a burst request's band series f64[count][width] and, behind it, its segments' summaries and carries (sp_kernel_burst.h; grown, never shrunk)
     DeviceBuffer pulse_ws;       // a burst-measurement request's cells u64[count][max_bursts][spx::kSlots], peak keys u64[count][max_bursts] and, behind them, count uint32 for a request without a counts array (sp_kernel_pulse.h; grown, never shrunk)
@@ -398,6 +400,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->traces_ws.release();
     ctx->power_plane.release();
     ctx->mean_ws.release();
+    ctx->variance_ws.release();
     ctx->quantile_ws.release();
     ctx->burst_ws.release();
     ctx->pulse_ws.release();
@@ -2419,6 +2422,100 @@ extern "C" int sp_plan_power_to_index(sp_plan *plan, const double *d_power, int3
         SP_HIP(ctx, hipGetLastError());
         return (int)SP_OK;
     });
+}
+
+// ------------------------------------------------------------------------------------------------- exact variance and spectral-kurtosis traces
+
+extern "C" const char *sp_plan_variance_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+variance", "scratch_power+variance");
+}
+
+extern "C" int sp_debug_variance_sums(const double *values, size_t count, double *out3)
+{
+    if (!out3 || (count && !values) || (count >> 31)) return SP_ERR_INVALID_ARG;   // (a request has fewer than 2^31 frames)
+    std::vector<uint64_t> bits(count);
+    if (count) memcpy(bits.data(), values, count * sizeof(double));
+    uint64_t r[3] = {};
+    if (!spv::variance_sums_bits(bits.data(), count, r)) return SP_ERR_INVALID_ARG;
+    memcpy(out3, r, sizeof r);
+    return SP_OK;
+}
+
+// (tests) k_variance_accumulate's grid for `frames` frames of n rows on a part with cu_count CUs, from the function its launch calls.
+extern "C" int sp_debug_variance_launch(int32_t n, int64_t frames, int32_t cu_count, int64_t *out, size_t capacity, size_t *used)
+{
+    if (n < 1 || frames < 1 || cu_count < 1 || !used) return SP_ERR_INVALID_ARG;
+    long long shape[3];
+    spk::variance_launch_shape(n, frames, cu_count, shape);
+    const int64_t v[] = {shape[0], shape[1], shape[2]};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+namespace {
+// The sums and the sums of squares accumulate in a workspace of the context of their own, (66 + 132 + 2) * 8 * n bytes that clear()
+// zeroes on the stream, and finish() makes the 3 * n results of them.  No request is empty: one of no frames still gives 3 * n zeros.
+struct VarianceKind {
+    static constexpr const char *kRender = "sp_render_variance";
+    static constexpr const char *kBadPlane = ": d_power and d_out must be 8-byte aligned device pointers";
+    double *out;           // 3 * n doubles
+    const char *refusal;   // of a null or misaligned `out`: every entry point has its own sentence
+
+    int check(const PlaneShape &p) const
+    {
+        if (p.n > SP_MAX_N) return fail(p.ctx, SP_ERR_INVALID_ARG, "variance traces need n <= SP_MAX_N");
+        return !out || ((uintptr_t)out & 7) != 0 ? fail(p.ctx, SP_ERR_INVALID_ARG, refusal) : (int)SP_OK;
+    }
+    bool empty(const PlaneShape &) const { return false; }
+    int clear(const PlaneShape &p) const
+    {
+        const size_t bytes = (size_t)spv::kSlots * sizeof(unsigned long long) * (size_t)p.n;
+        const int rc = p.ctx->variance_ws.reserve(bytes);
+        if (rc) return fail(p.ctx, rc, "variance workspace: out of device memory");
+        SP_HIP(p.ctx, hipMemsetAsync(p.ctx->variance_ws.p, 0, bytes, p.ctx->stream));
+        return SP_OK;
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long) const
+    {
+        if (frames <= 0) return SP_OK;
+        spk::launch_variance_accumulate(d_plane, p.n, frames, (unsigned long long *)p.ctx->variance_ws.p, p.ctx->cu_count, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &p) const
+    {
+        spk::launch_variance_finish((const unsigned long long *)p.ctx->variance_ws.p, p.n, p.width, out, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    size_t small_bytes(const PlaneShape &p) const { return 3 * (size_t)p.n * sizeof(double); }
+    VarianceKind on_device(const PlaneShape &, void *small) const { return {(double *)small, refusal}; }
+    // (no dB form: a sum of squares has none)
+    int tail(sp_plan *, const PlaneShape &p, int32_t, const VarianceKind &host, hipError_t &e) const
+    {
+        e = hipMemcpyAsync(host.out, out, 3 * (size_t)p.n * sizeof(double), hipMemcpyDeviceToHost, p.ctx->stream);
+        return SP_OK;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_variance(sp_context *ctx, const double *d_power, int32_t n, int32_t width, double *d_out)
+{
+    const VarianceKind k{d_out, "sp_power_variance: d_power and d_out must be 8-byte aligned device pointers"};
+    return plane_resident(ctx, "sp_power_variance", d_power, n, width, k);
+}
+
+extern "C" int sp_plan_execute_variance(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, double *d_out)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, VarianceKind{d_out, "d_out must be an 8-byte aligned array of 3 * n doubles"});
+}
+
+extern "C" int sp_render_variance(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, double *out)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, 0, VarianceKind{out, "out must be an 8-byte aligned array of 3 * n doubles"});
 }
 
 // ------------------------------------------------------------------------------------------------- exact band-power series

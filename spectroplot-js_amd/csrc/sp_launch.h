@@ -36,6 +36,13 @@ void launch_mean_accumulate(const double *plane, int n, long long frames, unsign
 // ... and the grid launch_mean_accumulate gives k_mean_accumulate: {bands of rows, pieces of the frames, frames per piece}
 void mean_launch_shape(int n, long long frames, int cu_count, long long shape[3]);
 void launch_mean_finish(const unsigned long long *ws, int n, int width, double *mean, hipStream_t stream);
+// the `frames` > 0 frames of the frame-major plane added into the variance workspace u64[spv::kSlots][n] (every value gives its pieces
+// and its square's); the grid that gives k_variance_accumulate, {bands of rows, pieces of the frames, frames per piece}; and the
+// workspace into out[3][n], the sum, the sum of squares and width * sum of squares - sum^2, each rounded once.  (The two kernels and
+// these launchers are sp_variance.hip, a unit of their own.)
+void launch_variance_accumulate(const double *plane, int n, long long frames, unsigned long long *ws, int cu_count, hipStream_t stream);
+void variance_launch_shape(int n, long long frames, int cu_count, long long shape[3]);
+void launch_variance_finish(const unsigned long long *ws, int n, int width, double *out, hipStream_t stream);
 // out[(k * count + b) * stride + x_base + x] = the exact sum of (y - y0_b)^k times the rows [y0_b, y1_b) = [bands[2 b], bands[2 b + 1])
 // of frame x of the frame-major plane, k = 0 .. order, for its `frames` > 0 frames and the `count` bands of the HOST array `bands`
 // (1 .. SP_MAX_BANDS, each within 0 <= y0 <= y1 <= n: the caller has checked them); they travel in the kernel's arguments.  Order 0 is

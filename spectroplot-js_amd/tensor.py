@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean, its exact block means and their colouring, its exact band sums, its exact spectral moments, its peak track, its occupancy counts, its percentile traces and its
-burst lists as torch tensors: sp_plan_execute_power / _mean / _blockmean / _bandpower / _moments / _track / _occupancy / _quantile / _bursts on torch's current
+"""The numeric spectrogram, its exact mean, its exact variance sums, its exact block means and their colouring, its exact band sums, its exact spectral moments, its peak track, its occupancy counts, its percentile traces and its
+burst lists as torch tensors: sp_plan_execute_power / _mean / _variance / _blockmean / _bandpower / _moments / _track / _occupancy / _quantile / _bursts on torch's current
 stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
@@ -79,6 +79,21 @@ def mean(plan, capture, width):
     out = torch.empty((plan.n,), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_mean(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
+    return out
+
+
+def variance(plan, capture, width):
+    """The exact variance sums of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [3, n] on the same device: per
+    image row the correctly rounded sum of |X|^2 over the `width` frames, the correctly rounded sum of its exact squares, and the
+    correctly rounded width * sum of squares - sum**2, the subtraction done exactly (include/spectroplot_hip.h, "Exact variance and
+    spectral-kurtosis traces").  out[0] / width is mean()'s trace bit for bit; the variance is out[2] / width**2 and the spectral
+    kurtosis (width + 1) / (width - 1) * out[2] / out[0]**2, tensor operations on the same stream without a cancellation.  `plan` is a
+    binding.Plan of the sample detector on that device.  Queued on torch's current stream exactly as power() queues its plane; the
+    plane itself is never held whole."""
+    _check_capture("variance", capture)
+    out = torch.empty((3, plan.n), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_variance(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
     return out
 
 
