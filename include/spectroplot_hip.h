@@ -967,6 +967,80 @@ const char *sp_plan_bursts_kernel_name_for(const sp_plan *plan, size_t nbytes, i
 int sp_debug_bursts(const double *values, int32_t width, double hi, double lo, int32_t max_bursts, uint32_t *count_out, int32_t *edges_out);
 
 /*
+ * Exact lagged covariances of band-power series: how a frame relates to another frame - the autocovariance of a channel over lag (its
+ * symbol or repetition period) and the cross-covariance of two channels (FSK mark against space, a hopper, a wide-band interferer).
+ * Bit-exact like the variance: a band-power series sits on a pedestal and N * sum(a b) - sum(a) * sum(b) is the small difference of two
+ * huge terms, noise in floating point and one integer here.
+ * With s[b][x] the value sp_plan_execute_bandpower writes for band b and frame x - the same bands (a HOST array of `count` pairs,
+ * 0 <= count <= SP_MAX_BANDS), geometry, limits, statuses, channel mode and bits as for the band-power series above - `pairs` is a HOST
+ * array of `npairs` index pairs (ia, ib) into the bands, read before the call returns, 0 <= npairs <= SP_MAX_LAG_PAIRS; ia == ib is an
+ * autocovariance.  1 <= lags <= SP_MAX_LAGS.  N = width - lags + 1 where that is at least 1, else N = 0: the number of terms, THE SAME
+ * FOR EVERY LAG (the fixed window: every lag sees equally many frames).  The reply is double[3][npairs][lags]; for pair p = (a, b) -
+ * a = s[ia], b = s[ib] - and lag l in [0, lags):
+ *     out[0][p][l] = RN( P ),               P = sum over x in [0, N) of a[x] * b[x + l]
+ *     out[1][p][l] = RN( N * P - A * B ),   A = sum over x in [0, N) of a[x],   B = sum over x in [0, N) of b[x + l]
+ *     out[2][p][l] = RN( B )
+ * Every product, sum and the difference is the EXACT real number; RN is one IEEE-754 round-to-nearest-even to f64, INTO THE DENORMAL
+ * RANGE where the value lies there and to +-inf past DBL_MAX.  out[1] is SIGNED: a negative value carries the sign bit (also where it rounds to zero), an exact
+ * zero is +0.0, never -0.0.  out[1] is N^2 times the lag-l covariance; the covariance itself is one IEEE divide and stays with the caller.  A is
+ * out[2][q][0] of any pair q whose second index is ia.  In Python, with Fractions (OverflowError read as the infinity of the value's
+ * sign): float(sum(fa[x] * fb[x + l] for x in range(N))), float(N * P - A * B), float(sum(fb[l:l + N])).
+ * SPECIAL VALUES follow the mean's rule per (p, l) on the frames the window touches, a[0 .. N) and b[l .. l + N): a NaN among them gives
+ * NaN in all three arrays of that (p, l) (A NaN IS ANY NaN); otherwise a +inf among them gives +inf in all three.  The rule goes by
+ * presence, not by arithmetic: 0 * inf is marked +inf.  A NaN at b[N + l0 - 1] marks exactly the lags l >= l0.
+ * N == 0 (width == 0 too) writes 3 * npairs * lags times +0.0.  npairs == 0 or count == 0 writes nothing and returns SP_OK.
+ * The values must not be negative: the sign bit of a value is not looked at.  The reply depends on nothing but the series: NOT ON gain,
+ * range, LUT or block_norm, NOR ON THE CU COUNT, THE DEAL OF TERMS TO WORKGROUPS, THE WINDOW OR THE CHUNKING OF A HOST-FED REQUEST
+ * (integer adds commute).
+ * SP_ERR_INVALID_ARG, before the device is touched: what the band-power series refuses of its bands, an index outside [0, count),
+ * npairs or lags outside their limits, pairs == NULL with npairs > 0, a NULL or misaligned (8 bytes) output with npairs > 0.  Only plans
+ * of the sample detector are accepted: a peak plan returns SP_ERR_UNSUPPORTED.
+ * MEMORY: the context keeps the band series, 8 * count * width bytes, and 1600 bytes per (pair, lag) plus 528 per pair (26 MB at 16
+ *   pairs of 1024 lags) in a workspace of its own that grows to the largest request so far, is never shrunk and is freed with the
+ *   context; SP_ERR_NOMEM where it cannot be had.  The cells are zeroed on the stream by every request.
+ * How: csrc/sp_lagcov_core.h.  Behind every block of frames the band-power series' launch writes the block's columns of the workspace
+ *   series (the burst lists' way: the series is whole and independent of the window before anything is correlated); behind the last
+ *   block k_lagcov_accumulate - a workgroup per pair, band of 32 lags and piece of the terms; b's three 32-bit pieces go to 66 cells and
+ *   the product's five to 132, integer adds only - and k_lagcov_finish, which forms N * P and A * B digit by digit, subtracts with a
+ *   borrow, takes the two's complement where the last borrow says the difference is negative, and rounds once.
+ *
+ * sp_plan_execute_lagcov: device operands, asynchronous on the context's stream.  The checks are sp_plan_execute_bandpower's, then the
+ *   pairs', the lags' and the output's.  No request number: the call may be interleaved with sp_plan_execute / _power / _mean /
+ *   _bandpower / _variance on one context without a synchronisation.
+ * sp_power_lagcov: of a frame-major plane double[width * n] the caller holds on the device; the companion of sp_power_bands.
+ *   Asynchronous.  n >= 1 (any n), width >= 0; d_power (non-NULL when width > 0) 8-byte aligned.
+ * sp_series_lagcov: the two launches alone on a band-major device series double[count * width] the caller holds, sp_power_bands' reply
+ *   for example: band b's frames at d_series + b * width.  0 <= count <= SP_MAX_BANDS, width >= 0, d_series 8-byte aligned and non-NULL
+ *   when count * width > 0.  Asynchronous.
+ * sp_render_lagcov: host buffers, synchronous, the plan cached as by sp_render.  The samples travel as for sp_render_bandpower and the
+ *   3 * npairs * lags doubles come back in one copy.  There is no dB form: a covariance has a sign.
+ * sp_plan_lagcov_kernel_name_for: "frames_power+lagcov" or "scratch_power+lagcov", following sp_plan_power_kernel_name_for.
+ * sp_debug_lagcov: (tests, no device needed) out[3][lags] of the series a and b of `width` >= 0 non-negative values each, through the
+ *   host side of the code the kernels run.  A negative value, -0.0 or -inf, lags outside 1 .. SP_MAX_LAGS or a NULL out returns
+ *   SP_ERR_INVALID_ARG and writes nothing.
+ * sp_debug_lagcov_launch: (tests, no device needed) the grid of the accumulation behind `terms` >= 1 terms of npairs >= 1 pairs and
+ *   `lags` lags on a part with cu_count CUs: out[] receives 3 int64 words - npairs * ceil(lags / 32) bands, the pieces the terms are cut
+ *   into (about 6 workgroups per CU, no piece below 32 terms) and the terms per piece (the last piece may be shorter).  *used = words
+ *   needed (SP_ERR_INVALID_ARG if capacity is smaller).
+ * Out of scope: the Node addon (its export table is pinned), peak plans, batches, groups and sharding.py, negative lags (swap the pair),
+ *   more than SP_MAX_LAGS lags or an FFT-based form, the per-window variance of b, a correlation coefficient computed on the device, and
+ *   the product fused into the band-sum launch.
+ */
+#define SP_MAX_LAG_PAIRS 16
+#define SP_MAX_LAGS 1024
+int sp_series_lagcov(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const int32_t *pairs, int32_t npairs,
+                     int32_t lags, double *d_out);
+int sp_power_lagcov(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                    const int32_t *pairs, int32_t npairs, int32_t lags, double *d_out);
+int sp_plan_execute_lagcov(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                           const int32_t *pairs, int32_t npairs, int32_t lags, double *d_out);
+int sp_render_lagcov(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                     int32_t count, const int32_t *pairs, int32_t npairs, int32_t lags, double *out);
+const char *sp_plan_lagcov_kernel_name_for(const sp_plan *plan, size_t nbytes, int32_t width);
+int sp_debug_lagcov(const double *a, const double *b, int32_t width, int32_t lags, double *out);
+int sp_debug_lagcov_launch(int32_t npairs, int32_t lags, int64_t terms, int32_t cu_count, int64_t *out, size_t capacity, size_t *used);
+
+/*
  * Burst measurements: exact energy and peak per burst - how strong each pulse of the burst lists above is, the level and the peak a
  * pulse analyser prints beside width and gap, without copying the band series to the host.  The inputs are those of the burst lists:
  * bands, count, hi[], lo[], max_bursts; s[b][x] is the band-power series and the bursts [start, end) of band b are EXACTLY those of

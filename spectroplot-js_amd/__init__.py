@@ -11,10 +11,10 @@ from . import binding  # noqa: F401
 from .binding import (Library, Context, Plan, Group, SpectroplotError, FORMATS, lib_path, build_library,  # noqa: F401
                       parse_format, slice_bounds, window, twiddles, peak_subframes, band_rows, band_peak, row_freq,
                       occupancy_count, quantile_rank, quantile_select, burst_scan, burst_pulses, pulse_scan, moment_sum, centroid_freq,
-                      variance_sums, variance_of, spectral_kurtosis)
+                      variance_sums, variance_of, spectral_kurtosis, lagcov_sums, lagcov_terms, lag_correlation)
 from .worker import HipWorker, render_sliced  # noqa: F401
 
 __all__ = ["Library", "Context", "Plan", "Group", "SpectroplotError", "FORMATS", "HipWorker", "render_sliced", "lib_path",
            "build_library", "parse_format", "slice_bounds", "window", "twiddles", "peak_subframes", "band_rows", "band_peak", "row_freq",
            "occupancy_count", "quantile_rank", "quantile_select", "burst_scan", "burst_pulses", "pulse_scan", "moment_sum", "centroid_freq",
-           "variance_sums", "variance_of", "spectral_kurtosis"]
+           "variance_sums", "variance_of", "spectral_kurtosis", "lagcov_sums", "lagcov_terms", "lag_correlation"]

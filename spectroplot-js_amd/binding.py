@@ -185,6 +185,14 @@ class Library:
         L.sp_debug_variance_launch.argtypes = [i32, C.c_int64, i32, vp, sz, C.POINTER(sz)]
         L.sp_plan_variance_kernel_name_for.restype = C.c_char_p
         L.sp_plan_variance_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_series_lagcov.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp]
+        L.sp_power_lagcov.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, i32, vp]
+        L.sp_plan_execute_lagcov.argtypes = [vp, vp, sz, i32, vp, i32, vp, i32, i32, vp]
+        L.sp_render_lagcov.argtypes = [vp, C.POINTER(_Request), vp, sz, i32, vp, i32, vp, i32, i32, vp]
+        L.sp_plan_lagcov_kernel_name_for.restype = C.c_char_p
+        L.sp_plan_lagcov_kernel_name_for.argtypes = [vp, sz, i32]
+        L.sp_debug_lagcov.argtypes = [vp, vp, i32, i32, vp]
+        L.sp_debug_lagcov_launch.argtypes = [i32, i32, C.c_int64, i32, vp, sz, C.POINTER(sz)]
         L.sp_band_rows.argtypes = [i32, dbl, dbl, C.POINTER(i32), C.POINTER(i32)]
         L.sp_power_bands.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         L.sp_plan_execute_bandpower.argtypes = [vp, vp, sz, i32, vp, i32, vp]
@@ -330,6 +338,43 @@ def spectral_kurtosis(sums, width):
     w = np.float64(int(width))
     with np.errstate(all="ignore"):
         return (w + 1.0) / (w - 1.0) * sums[2] / (sums[0] * sums[0])
+
+
+SP_MAX_LAG_PAIRS = 16
+SP_MAX_LAGS = 1024
+
+
+def lagcov_terms(width, lags):
+    """The terms N every lag of a lagged-covariance request over `width` frames and `lags` lags has: width - lags + 1, 0 where that is
+    below 1 (the fixed window: every lag sees equally many frames).  Pure host arithmetic."""
+    return max(int(width) - int(lags) + 1, 0)
+
+
+def lagcov_sums(a, b, lags):
+    """sp_debug_lagcov: f64 [3, lags] of two series of non-negative doubles, equally long, through the host side of the code the
+    lagged-covariance kernels run.  With N = lagcov_terms(len(a), lags) and per lag l: the correctly rounded sum of a[x] * b[x + l] over
+    x < N; the correctly rounded N * that sum - sum(a[:N]) * sum(b[l:l + N]), SIGNED, the subtraction done exactly (N**2 times the
+    covariance at lag l; +0.0 exactly for a constant series); and the correctly rounded sum(b[l:l + N]).  A NaN in either window gives
+    NaN in all three of that lag, else a +inf gives +inf.  No device needed."""
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    if a.size != b.size:
+        raise SpectroplotError(SP_ERR_INVALID_ARG, "lagcov_sums: a and b must be equally long")
+    out = np.zeros((3, max(int(lags), 0)), np.float64)
+    lib = Library.get()
+    lib.check(lib.L.sp_debug_lagcov(_p(a) if a.size else None, _p(b) if b.size else None, a.size, int(lags), _p(out) if out.size else None))
+    return out
+
+
+def lag_correlation(cov_ab, cov_aa0, cov_bb0):
+    """The usual correlation coefficient per lag from lagged-covariance replies: cov_ab / sqrt(cov_aa0 * cov_bb0), where cov_ab is
+    out[1] of the pair (a, b) over the lags and cov_aa0, cov_bb0 are out[1] at lag 0 of the auto pairs (a, a) and (b, b) of the same
+    request (the common factor N**2 cancels).  THE NORMALISATION IS BY THE LAG-0 AUTOCOVARIANCES, the variances of a[0 .. N) and
+    b[0 .. N); it is NOT the per-window one, which would take the variance of b[l .. l + N) for every lag, so a value may pass 1 in
+    magnitude where b's later frames vary more than its first N.  Where a variance is 0 the division is by zero: NaN for a covariance
+    of 0, an infinity otherwise.  Plain numpy, no device needed."""
+    with np.errstate(all="ignore"):
+        return np.asarray(cov_ab, np.float64) / np.sqrt(np.float64(cov_aa0) * np.float64(cov_bb0))
 
 
 def blockmean_columns(width, group):
@@ -557,6 +602,12 @@ def row_freq(n, row):
     return math.nan if row < 0 else (n // 2 - row) / n
 
 
+def _pair_array(pairs):
+    """(int32 [npairs, 2] host array, npairs) of a sequence of (ia, ib) band indices; nothing is checked here - the library refuses."""
+    p = np.ascontiguousarray(np.clip(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), -1, 2 ** 31 - 1).astype(np.int32))
+    return p, p.shape[0]
+
+
 def _band_array(bands):
     """(int32 [count, 2] host array, count) of a sequence of (y0, y1) rows ranges; nothing is checked here - the library refuses."""
     b = np.ascontiguousarray(np.asarray(bands, dtype=np.int64).reshape(-1, 2).astype(np.int32))
@@ -648,6 +699,17 @@ def debug_variance_launch(n, frames, cu_count):
     out = np.zeros(3, np.int64)
     used = C.c_size_t()
     lib.check(lib.L.sp_debug_variance_launch(int(n), int(frames), int(cu_count), out.ctypes.data_as(C.c_void_p), 3, C.byref(used)))
+    return tuple(int(v) for v in out)
+
+
+def debug_lagcov_launch(npairs, lags, terms, cu_count):
+    """The grid of a lagged-covariance request's accumulation alone (sp_debug_lagcov_launch): (pairs times bands of 32 lags, pieces of
+    the terms, terms per piece)."""
+    lib = Library.get()
+    out = np.zeros(3, np.int64)
+    used = C.c_size_t()
+    lib.check(lib.L.sp_debug_lagcov_launch(int(npairs), int(lags), int(terms), int(cu_count), out.ctypes.data_as(C.c_void_p), 3,
+                                           C.byref(used)))
     return tuple(int(v) for v in out)
 
 
@@ -1103,6 +1165,36 @@ class Context:
                                               _p(l) if count > 0 else None, int(max_bursts), C.c_void_p(d_counts or None),
                                               C.c_void_p(d_edges or None)))
 
+    def render_lagcov(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, pairs, lags, channel_mode=False, lut=None,
+                      fill=None):
+        """sp_render_lagcov: the exact lagged covariance sums of the request, f64 [3, npairs, lags]: per pair (ia, ib) of the bands
+        (y0, y1) of image rows and per lag l, over the N = lagcov_terms(width, lags) terms, the correctly rounded sum of
+        a[x] * b[x + l], the correctly rounded N * that sum - sum(a) * sum(b window) (signed; N**2 times the covariance) and the
+        correctly rounded sum of b's window, a and b the exact band sums per frame.  No dB form.  No image is rendered; `lut` only takes
+        part in the plan-cache key.  fill: a byte the output array holds before the call (tests)."""
+        data, req, keep = _no_picture_request(fmt, data, n, windowc, block_norm, gain, rng, lut, channel_mode)
+        b, count = _band_array(bands)
+        p, npairs = _pair_array(pairs)
+        out = _filled((3, npairs, max(int(lags), 0)), np.float64, fill)
+        self._chk(self.lib.L.sp_render_lagcov(self.h, C.byref(req), _p(data), data.size, int(width), _p(b) if count else None, count,
+                                              _p(p) if npairs else None, npairs, int(lags), _p(out) if out.size else None))
+        return out
+
+    def power_lagcov(self, d_power, n, width, bands, pairs, lags, d_out):
+        """sp_power_lagcov: the lagged covariance sums of the bands of the f64 [width, n] plane at device address d_power into f64
+        [3, npairs, lags] at d_out.  Asynchronous on the context's stream; bands and pairs are read before it returns."""
+        b, count = _band_array(bands)
+        p, npairs = _pair_array(pairs)
+        self._chk(self.lib.L.sp_power_lagcov(self.h, C.c_void_p(d_power or None), int(n), int(width), _p(b) if count else None, count,
+                                             _p(p) if npairs else None, npairs, int(lags), C.c_void_p(d_out or None)))
+
+    def series_lagcov(self, d_series, count, width, pairs, lags, d_out):
+        """sp_series_lagcov: the lagged covariance sums of the band-major f64 [count, width] series at device address d_series -
+        power_bands' reply, for example - into f64 [3, npairs, lags] at d_out.  Asynchronous on the context's stream."""
+        p, npairs = _pair_array(pairs)
+        self._chk(self.lib.L.sp_series_lagcov(self.h, C.c_void_p(d_series or None), int(count), int(width), _p(p) if npairs else None,
+                                              npairs, int(lags), C.c_void_p(d_out or None)))
+
     def render_pulses(self, fmt, data, n, windowc, block_norm, gain, rng, width, bands, hi, lo, max_bursts, channel_mode=False, lut=None,
                       fill=None):
         """sp_render_pulses: the burst lists of the request as render_bursts() gives them and the measurements of every listed burst,
@@ -1302,6 +1394,20 @@ class Plan:
         context's stream."""
         self.ctx._chk(self.ctx.lib.L.sp_plan_execute_variance(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
                                                               C.c_void_p(d_out or None)))
+
+    def lagcov_kernel_name_for(self, nbytes, width):
+        """What execute_lagcov() launches for a request of this shape: "frames_power+lagcov" or "scratch_power+lagcov"."""
+        return self._kernel_name_for("lagcov", nbytes, width)
+
+    def execute_lagcov(self, d_bytes, nbytes, width, bands, pairs, lags, d_out):
+        """sp_plan_execute_lagcov: per pair (ia, ib) of the bands (y0, y1) of image rows and per lag the exact lagged covariance sums of
+        their band-power series, each rounded once, into the f64 [3, npairs, lags] device array at address d_out.  Asynchronous on the
+        context's stream; bands and pairs are read before it returns."""
+        b, count = _band_array(bands)
+        p, npairs = _pair_array(pairs)
+        self.ctx._chk(self.ctx.lib.L.sp_plan_execute_lagcov(self.h, C.c_void_p(d_bytes or None), int(nbytes), int(width),
+                                                            _p(b) if count else None, count, _p(p) if npairs else None, npairs, int(lags),
+                                                            C.c_void_p(d_out or None)))
 
     def blockmean_kernel_name_for(self, nbytes, width):
         """What execute_blockmean() launches for a request of this shape: "frames_power+blockmean" or "scratch_power+blockmean"."""

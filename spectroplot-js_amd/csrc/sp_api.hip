@@ -34,6 +34,7 @@
 #include "sp_blockmean_core.h"
 #include "sp_moment_core.h"
 #include "sp_variance_core.h"
+#include "sp_lagcov_core.h"
 #include "sp_cmap_tables.h"
 
 namespace {
@@ -124,6 +125,7 @@ struct sp_context {
     DeviceBuffer quantile_ws;    // a percentile request's whole plane as keys, u64[n][width] (sp_kernel_quantile.h; grown, never shrunk)
     DeviceBuffer burst_ws;       // a burst request's band series f64[count][width] and, behind it, its segments' summaries and carries (sp_kernel_burst.h; grown, never shrunk)
     DeviceBuffer pulse_ws;       // a burst-measurement request's cells u64[count][max_bursts][spx::kSlots], peak keys u64[count][max_bursts] and, behind them, count uint32 for a request without a counts array (sp_kernel_pulse.h; grown, never shrunk)
+    DeviceBuffer lagcov_ws;      // a lagged-covariance request's band series f64[count][width] and, behind it, its cells u64[spv::kSlots][npairs * lags] and u64[npairs][66] (sp_kernel_lagcov.h; grown, never shrunk)
     DeviceBuffer plane_window;   // a mean, band-power or track request: the block of frames of its plane that is being consumed (plane_blocks)
     int32_t blockmean_direct_max = 0;   // sp_context_set_blockmean_direct_max: the largest group k_blockmean takes; 0 is the built default, SP_BLOCKMEAN_DIRECT_FRAMES
     int64_t blockmean_next = 0;         // a block-mean request: the frame its next run begins with (BlockMeanKind::consume)
@@ -404,6 +406,7 @@ extern "C" void sp_context_destroy(sp_context *ctx)
     ctx->quantile_ws.release();
     ctx->burst_ws.release();
     ctx->pulse_ws.release();
+    ctx->lagcov_ws.release();
     ctx->plane_window.release();
     ctx->index_rgba.release();
     ctx->density_index.release();
@@ -3289,6 +3292,149 @@ extern "C" int sp_debug_pulses(const double *values, int32_t width, double hi, d
                                         (uint64_t *)energy_out, (uint64_t *)peak_out, peak_at_out);
     if (count_out) *count_out = total;
     return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- exact lagged covariances
+
+extern "C" const char *sp_plan_lagcov_kernel_name_for(const sp_plan *plan, size_t, int32_t)
+{
+    return plain_kernel_name(plan, "frames_power+lagcov", "scratch_power+lagcov");
+}
+
+extern "C" int sp_debug_lagcov(const double *a, const double *b, int32_t width, int32_t lags, double *out)
+{
+    if (!out || width < 0 || (width > 0 && (!a || !b)) || lags < 1 || lags > SP_MAX_LAGS) return SP_ERR_INVALID_ARG;
+    std::vector<uint64_t> ba((size_t)width), bb((size_t)width), r(3 * (size_t)lags);
+    if (width) memcpy(ba.data(), a, (size_t)width * sizeof(double)), memcpy(bb.data(), b, (size_t)width * sizeof(double));
+    if (!spl::lagcov_bits(ba.data(), bb.data(), width, lags, r.data())) return SP_ERR_INVALID_ARG;
+    memcpy(out, r.data(), r.size() * sizeof(uint64_t));
+    return SP_OK;
+}
+
+// (tests) k_lagcov_accumulate's grid for `terms` terms of npairs pairs and `lags` lags on a part with cu_count CUs, from the function
+// its launch calls.
+extern "C" int sp_debug_lagcov_launch(int32_t npairs, int32_t lags, int64_t terms, int32_t cu_count, int64_t *out, size_t capacity,
+                                      size_t *used)
+{
+    if (npairs < 1 || npairs > SP_MAX_LAG_PAIRS || lags < 1 || lags > SP_MAX_LAGS || terms < 1 || cu_count < 1 || !used)
+        return SP_ERR_INVALID_ARG;
+    long long shape[3];
+    spk::lagcov_launch_shape(npairs, lags, terms, cu_count, shape);
+    const int64_t v[] = {shape[0], shape[1], shape[2]};
+    *used = sizeof v / sizeof v[0];
+    if (*used > capacity || !out) return SP_ERR_INVALID_ARG;
+    memcpy(out, v, sizeof v);
+    return SP_OK;
+}
+
+namespace {
+static_assert(SP_MAX_LAG_PAIRS == spl::kMaxPairs && SP_MAX_LAGS == spl::kMaxLags, "the limits of the header are the core's");
+
+// What every lagged-covariance entry point refuses of its pairs, lags and output - nullptr where they are in order.
+const char *lagcov_args(int32_t count, const int32_t *pairs, int32_t npairs, int32_t lags, const double *out)
+{
+    if (npairs < 0 || npairs > SP_MAX_LAG_PAIRS) return "npairs within 0 .. SP_MAX_LAG_PAIRS is required";
+    if (lags < 1 || lags > SP_MAX_LAGS) return "lags within 1 .. SP_MAX_LAGS is required";
+    if (npairs > 0 && !pairs) return "lagged covariances need pairs, 2 * npairs int32";
+    for (int32_t k = 0; k < 2 * npairs; k++)
+        if (pairs[k] < 0 || pairs[k] >= count) return "a pair's index must lie within [0, count)";
+    if (npairs > 0 && (!out || ((uintptr_t)out & 7) != 0)) return "the reply must be an 8-byte aligned array of 3 * npairs * lags doubles";
+    return nullptr;
+}
+
+// The memset and the two launches on a band-major series of the device; `work`: spk::lagcov_work_bytes.
+int lagcov_scan(sp_context *ctx, const double *d_series, int32_t width, const int32_t *pairs, int32_t npairs, int32_t lags, void *work,
+                double *out)
+{
+    SP_HIP(ctx, spk::launch_lagcov(d_series, width, pairs, npairs, lags, work, out, ctx->cu_count, ctx->stream));
+    SP_HIP(ctx, hipGetLastError());
+    return SP_OK;
+}
+
+// BurstKind's way to a whole series: clear() reserves the context's workspace of its own - the band series f64[count][width] and the
+// cells behind it - every block's launch is the band-power series' own, its columns at x_base of the workspace series, so that the
+// series is the same whatever the window; finish() zeroes the cells and runs the two launches on it.  A request without a pair or
+// without a band writes nothing.
+struct LagcovKind {
+    static constexpr const char *kRender = "sp_render_lagcov";
+    static constexpr const char *kBadPlane = BandKind::kBadPlane;
+    const int32_t *bands;
+    int32_t count;
+    const int32_t *pairs;   // host array
+    int32_t npairs, lags;
+    double *out;            // 3 * npairs * lags doubles
+
+    size_t series_bytes(const PlaneShape &p) const { return sizeof(double) * (size_t)count * (size_t)p.width; }
+    size_t reply_bytes() const { return sizeof(double) * 3 * (size_t)npairs * (size_t)lags; }
+    int check(const PlaneShape &p) const
+    {
+        if (const char *why = spgeo::check_bands(p.n, bands, count)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        if (const char *why = lagcov_args(count, pairs, npairs, lags, out)) return fail(p.ctx, SP_ERR_INVALID_ARG, why);
+        return SP_OK;
+    }
+    bool empty(const PlaneShape &) const { return npairs == 0 || count == 0; }
+    int clear(const PlaneShape &p) const
+    {
+        const int rc = p.ctx->lagcov_ws.reserve(series_bytes(p) + spk::lagcov_work_bytes(npairs, lags));
+        return rc ? fail(p.ctx, rc, "lagged covariance workspace: out of device memory") : (int)SP_OK;
+    }
+    int consume(const PlaneShape &p, const double *d_plane, long long frames, long long x_base) const
+    {
+        if (frames <= 0) return SP_OK;
+        spk::launch_band_sum(d_plane, p.n, frames, bands, count, 0, (double *)p.ctx->lagcov_ws.p, p.width, x_base, p.ctx->stream);
+        SP_HIP(p.ctx, hipGetLastError());
+        return SP_OK;
+    }
+    int finish(const PlaneShape &p) const
+    {
+        return lagcov_scan(p.ctx, (const double *)p.ctx->lagcov_ws.p, p.width, pairs, npairs, lags, (char *)p.ctx->lagcov_ws.p + series_bytes(p),
+                           out);
+    }
+    size_t small_bytes(const PlaneShape &) const { return reply_bytes(); }
+    LagcovKind on_device(const PlaneShape &, void *small) const { return {bands, count, pairs, npairs, lags, (double *)small}; }
+    // (no dB form: a covariance has a sign)
+    int tail(sp_plan *, const PlaneShape &p, int32_t, const LagcovKind &host, hipError_t &e) const
+    {
+        e = hipMemcpyAsync(host.out, out, reply_bytes(), hipMemcpyDeviceToHost, p.ctx->stream);
+        return SP_OK;
+    }
+};
+}  // namespace
+
+extern "C" int sp_power_lagcov(sp_context *ctx, const double *d_power, int32_t n, int32_t width, const int32_t *bands, int32_t count,
+                               const int32_t *pairs, int32_t npairs, int32_t lags, double *d_out)
+{
+    return plane_resident(ctx, "sp_power_lagcov", d_power, n, width, LagcovKind{bands, count, pairs, npairs, lags, d_out});
+}
+
+extern "C" int sp_plan_execute_lagcov(sp_plan *plan, const void *d_bytes, size_t nbytes, int32_t width, const int32_t *bands, int32_t count,
+                                      const int32_t *pairs, int32_t npairs, int32_t lags, double *d_out)
+{
+    return plane_capture(plan, d_bytes, nbytes, width, LagcovKind{bands, count, pairs, npairs, lags, d_out});
+}
+
+extern "C" int sp_render_lagcov(sp_context *ctx, const sp_request *req, const uint8_t *bytes, size_t nbytes, int32_t width, const int32_t *bands,
+                                int32_t count, const int32_t *pairs, int32_t npairs, int32_t lags, double *out)
+{
+    return plane_render(ctx, req, bytes, nbytes, width, 0, LagcovKind{bands, count, pairs, npairs, lags, out});
+}
+
+extern "C" int sp_series_lagcov(sp_context *ctx, const double *d_series, int32_t count, int32_t width, const int32_t *pairs, int32_t npairs,
+                                int32_t lags, double *d_out)
+{
+    if (!ctx) return SP_ERR_INVALID_ARG;
+    if (count < 0 || count > SP_MAX_BANDS || width < 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_lagcov: count within 0 .. SP_MAX_BANDS and width >= 0 are required");
+    if (const char *why = lagcov_args(count, pairs, npairs, lags, d_out)) return fail(ctx, SP_ERR_INVALID_ARG, why);
+    if (npairs == 0 || count == 0) return SP_OK;
+    if ((width > 0 && !d_series) || ((uintptr_t)d_series & 7) != 0)
+        return fail(ctx, SP_ERR_INVALID_ARG, "sp_series_lagcov: d_series must be an 8-byte aligned device pointer");
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    return timed(ctx, [&] {
+        const int rc = ctx->lagcov_ws.reserve(spk::lagcov_work_bytes(npairs, lags));
+        if (rc) return fail(ctx, rc, "lagged covariance workspace: out of device memory");
+        return lagcov_scan(ctx, d_series, width, pairs, npairs, lags, ctx->lagcov_ws.p, d_out);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------- requests by name

@@ -89,6 +89,17 @@ size_t pulse_work_bytes(int count, int max_bursts);
 hipError_t launch_pulses(const double *series, int count, int width, const uint64_t *hi_key, const uint64_t *lo_key, int max_bursts,
                          const unsigned long long *records, const uint32_t *counts, void *work, double *energy, double *peak,
                          int32_t *peak_at, hipStream_t stream);
+// The lagged covariance sums of the band-major series f64[count][width] at `series` (width >= 0): out[3][npairs][lags] for the HOST
+// array `pairs` of npairs index pairs (1 .. SP_MAX_LAG_PAIRS, each index within [0, count)) and the lags [0, lags), 1 <= lags <=
+// SP_MAX_LAGS (the caller has checked them); every lag has width - lags + 1 terms, none where that is below 1, and the reply is zeros
+// then.  `work`: lagcov_work_bytes(npairs, lags) bytes of device memory, 8-byte aligned - the (pair, lag)s' cells
+// u64[spv::kSlots][npairs * lags] and the pairs' u64[npairs][66] - which this zeroes on the stream in front.  A memset and two launches,
+// one where there is no term.  ... and the grid it gives k_lagcov_accumulate: {pairs times bands of 32 lags, pieces of the terms,
+// terms per piece}.  (k_lagcov_accumulate, k_lagcov_finish and this launcher are sp_lagcov.hip, a unit of their own.)
+size_t lagcov_work_bytes(int npairs, int lags);
+hipError_t launch_lagcov(const double *series, long long width, const int32_t *pairs, int npairs, int lags, void *work, double *out,
+                         int cu_count, hipStream_t stream);
+void lagcov_launch_shape(int npairs, int lags, long long terms, int cu_count, long long shape[3]);
 
 // out[c * n + y] = RN(exact sum of the rows y of column c's frames) / the column's frames, for the columns of `group` >= 1 frames each
 // that the `frames` > 0 frames of the frame-major plane make: ceil(frames / group) of them, only the last one short.  One launch, no

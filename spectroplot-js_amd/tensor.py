@@ -1,5 +1,5 @@
-"""The numeric spectrogram, its exact mean, its exact variance sums, its exact block means and their colouring, its exact band sums, its exact spectral moments, its peak track, its occupancy counts, its percentile traces and its
-burst lists as torch tensors: sp_plan_execute_power / _mean / _variance / _blockmean / _bandpower / _moments / _track / _occupancy / _quantile / _bursts on torch's current
+"""The numeric spectrogram, its exact mean, its exact variance sums, its exact lagged covariances, its exact block means and their colouring, its exact band sums, its exact spectral moments, its peak track, its occupancy counts, its percentile traces and its
+burst lists as torch tensors: sp_plan_execute_power / _mean / _variance / _lagcov / _blockmean / _bandpower / _moments / _track / _occupancy / _quantile / _bursts on torch's current
 stream.
 
 `power(plan, capture, width)` hands a detector, a model or a viewer the f64 plane |X|^2 [width, n] behind every other reply of the
@@ -94,6 +94,23 @@ def variance(plan, capture, width):
     out = torch.empty((3, plan.n), dtype=torch.float64, device=capture.device)
     with _on_current_stream(plan.ctx, capture.device, (capture, out)):
         plan.execute_variance(capture.data_ptr(), capture.numel(), int(width), out.data_ptr())
+    return out
+
+
+def lagcov(plan, capture, width, bands, pairs, lags):
+    """The exact lagged covariance sums of `capture` (a uint8 CUDA tensor: the raw bytes) as a float64 tensor [3, npairs, lags] on the
+    same device: per pair (ia, ib) of the bands (y0, y1) of image rows and per lag l, over the N = width - lags + 1 terms every lag
+    has, the correctly rounded sum of a[x] * b[x + l], the correctly rounded N * that sum - sum(a) * sum(b's window) - signed, the
+    subtraction done exactly - and the correctly rounded sum of b's window, a and b the band-power series bandpower() gives
+    (include/spectroplot_hip.h, "Exact lagged covariances").  The covariance at lag l is out[1] / N**2 and the correlation coefficient
+    binding.lag_correlation's form, tensor operations on the same stream.  `plan` is a binding.Plan of the sample detector on that
+    device.  Queued on torch's current stream exactly as power() queues its plane; the plane itself is never held whole."""
+    _check_capture("lagcov", capture)
+    bands = [(int(y0), int(y1)) for y0, y1 in bands]
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    out = torch.empty((3, len(pairs), max(int(lags), 0)), dtype=torch.float64, device=capture.device)
+    with _on_current_stream(plan.ctx, capture.device, (capture, out)):
+        plan.execute_lagcov(capture.data_ptr(), capture.numel(), int(width), bands, pairs, int(lags), out.data_ptr() if out.numel() else 0)
     return out
 
 
